@@ -72,6 +72,38 @@ CONFIGS = {
 }
 
 
+DUMP_BYTES = 60_000_000   # --dump-outputs: at most this many bytes of arrays (the .npy headers stay far below the remaining 4 MB of 64)
+DUMP_SEED = 0x5EED0D0
+
+
+def dump_sample(n, bytes_per_unit):
+    """The units of a step --dump-outputs writes: all n when they fit DUMP_BYTES, else a fixed seeded sample (sorted), the same in every run."""
+    import numpy as np
+    m = max(1, min(n, DUMP_BYTES // bytes_per_unit))
+    if m == n:
+        return np.arange(n, dtype=np.int64)
+    return np.sort(np.random.default_rng(DUMP_SEED).choice(n, m, replace=False)).astype(np.int64)
+
+
+def take_units(a, cols, dim):
+    """a[..., cols, ...] along `dim` as a host numpy array: a device tensor is gathered on the device first (only the sample crosses PCIe)."""
+    if hasattr(a, "index_select"):
+        import torch
+        return a.index_select(dim, torch.as_tensor(cols, device=a.device)).cpu().numpy()
+    return a.a.take(cols, axis=dim)      # (tests/mp_plumbing.py: host buffers)
+
+
+def write_outputs(w, out_dir):
+    """--dump-outputs: the workload's outputs of its last step (w.outputs(): name -> float32 / float64 array) as out_dir/<name>.npy."""
+    import numpy as np
+    outs = w.outputs()
+    assert all(a.dtype in (np.float32, np.float64) for a in outs.values()), {k: a.dtype for k, a in outs.items()}
+    assert sum(a.nbytes for a in outs.values()) <= DUMP_BYTES, {k: a.nbytes for k, a in outs.items()}
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in outs.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a))
+
+
 def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -121,6 +153,9 @@ def parse_args(argv=None):
                     help="TEST HOOK: a directory into which every rank writes rank<r>.json = the global index range (and model blocks) of every step it "
                          "launched + a digest of its last step's output (tests check the ranks' ranges are disjoint and the digests are what one "
                          "process computes for those ranges)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the timed path computed in its last step as DIR/<name>.npy (float32 / float64, a fixed "
+                         "seeded sample of the units when the whole output exceeds %d MB; DIR/rank<r>/ when --gpus > 1)" % (DUMP_BYTES // 1_000_000))
     ap.add_argument("--oversubscribe", action="store_true",
                     help="TEST ONLY: allow more ranks than GPUs (ranks share devices, gloo barrier); the line says so")
     return ap.parse_args(argv)
@@ -399,6 +434,20 @@ class DbnWorkload:
         return {"init_bin": int(self.init_bin[:, :n].long().sum()), "dyn_bin": int(self.dyn_bin[:, :, :n].long().sum()),
                 "init_val_bits": int(self.init_val[:, :n].contiguous().view(self.pl.torch.int32).long().sum())}
 
+    def outputs(self):
+        """The last step's dense trace in the shapes a caller receives (native.unpack_dyn_bin / unpack_dyn_val), for the units of
+        dump_sample: unit_index [m] (global sample index), init_bin / init_val [m, n_initial], dyn_bin / dyn_val [m, T, n_dyn]."""
+        import numpy as np
+        from em_model_manned_bayes_amd import native   # (host-side unpacking: the module itself, not the plumbing's launch interface)
+        T = self.T
+        cols = dump_sample(self.n, 8 + 8 * self.ni + 8 * T * self.nd)
+
+        def take(a, dim):
+            return take_units(a, cols, dim)
+        return {"unit_index": (self.ranges[-1]["first"] + cols).astype(np.float64),
+                "init_bin": take(self.init_bin, 1).T.astype(np.float32), "init_val": np.ascontiguousarray(take(self.init_val, 1).T),
+                "dyn_bin": native.unpack_dyn_bin(take(self.dyn_bin, 2), T).astype(np.float32), "dyn_val": native.unpack_dyn_val(take(self.dyn_val, 2), T)}
+
     def kernel_name(self):
         return self.ctx.last_kernel()
 
@@ -524,6 +573,24 @@ class TerminalWorkload:
         t = self.pl.torch
         return {"rows": int(self.rows.long().sum()), "model_of": int(self.mof.long().sum()), "geom_val_bits": int(self.geom_val.view(t.int32).long().sum()),
                 "attempts": int(self.att.long().sum())}
+
+    def outputs(self):
+        """The last step's outputs for the encounters of dump_sample: unit_index [m] (global encounter index), geom_val [m, n_initial],
+        geo [m, 12] (f64), model_of / rows [m, 4], attempts [m], and tracks [m, 4, cap, 6] = the four PropagateTrajectory results of
+        each encounter cut out of the joined tracks (native.split_joined_tracks: rows beyond a track's length are 0)."""
+        import numpy as np
+        from em_model_manned_bayes_amd import native
+        n, ni, cap = self.n, self.ni, self.cap
+        cols = dump_sample(n, 8 + 4 * ni + 8 * 12 + 4 * 4 + 4 * 4 + 4 + 4 * cap * 6 * 4)
+        m = cols.size
+        air = (2 * cols[:, None] + np.arange(2)).reshape(-1)     # aircraft 2e + a: rows of the joined tracks
+        lane = (4 * cols[:, None] + np.arange(4)).reshape(-1)    # track 4e + 2a + backward
+        rows = take_units(self.rows, lane, 0)
+        tracks = native.split_joined_tracks(take_units(self.traj, air, 0), rows, cap)
+        return {"unit_index": (self.ranges[-1]["first"] + cols).astype(np.float64),
+                "geom_val": np.ascontiguousarray(take_units(self.geom_val, cols, 1).T), "geo": take_units(self.geo, cols, 0).astype(np.float64),
+                "model_of": take_units(self.mof, lane, 0).reshape(m, 4).astype(np.float32), "rows": rows.reshape(m, 4).astype(np.float32),
+                "attempts": take_units(self.att, cols, 0).astype(np.float32), "tracks": tracks.reshape(m, 4, cap, 6)}
 
     def step(self, k):
         from em_model_manned_bayes_amd import sharding
@@ -725,11 +792,12 @@ class GpuTelemetry:
 
 
 # ------------------------------------------------------------------------------------------------
-def measure(w, pl, args, warmup, steps, settle_max=0):
+def measure(w, pl, args, warmup, steps, settle_max=0, dump_dir=None):
     """warmup untimed steps, then `steps` timed ones bracketed by barrier + device synchronisation on both sides; the launch
     durations come from HIP events on the stream the kernels are launched on.  Returns (elapsed_s max over ranks, [ms per step]).
     settle_max > 0 (the entries of `configs`, which start after seconds of GPU idleness): between the warm-up and the timed region, untimed
-    groups of four back-to-back steps until the last two of a group agree within 1 % (w.settle says how many it took)."""
+    groups of four back-to-back steps until the last two of a group agree within 1 % (w.settle says how many it took).
+    dump_dir: write the last timed step's outputs there (write_outputs) before anything else runs on the buffers."""
     # one untimed barrier + max-reduce first: a process group's first collectives set its communicator up (RCCL: lazily, hundreds of ms
     # with 8 ranks) -- that must never land between t0 and t1 of a 0.1 s timed region
     pl.barrier()
@@ -793,6 +861,8 @@ def measure(w, pl, args, warmup, steps, settle_max=0):
     elapsed = pl.max_over_ranks(t1 - t0)
     step_ms = [pl.elapsed_ms(a, b) for a, b in ev]
     w.check()
+    if dump_dir:
+        write_outputs(w, dump_dir)
     if tel and tel.dir and getattr(args, "telemetry_s", 0.0) > 0.0:
         # The SMU's clock / power readings are moving averages that trail the load by more than a second (tools/power_probe.sh: 2 s from
         # idle to the sustained values), the timed region lasts tens of milliseconds: what the box does under THIS step is read in an
@@ -1091,7 +1161,8 @@ def run_rank(args, rank, local_rank, world, pl=None, out=sys.stdout):
         except Exception as ex:
             hp = {"error": "%s: %s" % (type(ex).__name__, ex)}
     w = make_workload(args, pl, rank, world)
-    elapsed, step_ms = measure(w, pl, args, args.warmup, args.steps)
+    dump_dir = args.dump_outputs and (args.dump_outputs if world == 1 else os.path.join(args.dump_outputs, "rank%d" % rank))
+    elapsed, step_ms = measure(w, pl, args, args.warmup, args.steps, dump_dir=dump_dir)
     if getattr(args, "ranges_out", None) and hasattr(w, "digest") and hasattr(pl, "torch"):
         os.makedirs(args.ranges_out, exist_ok=True)
         with open(os.path.join(args.ranges_out, "rank%d.json" % rank), "w") as f:
@@ -1189,6 +1260,8 @@ def main(argv=None):
         return 0
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
+    if args.steps < 1:
+        raise SystemExit("--steps must be >= 1")
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         return launch_ranks(args, argv)
     rank = int(os.environ.get("RANK", "0"))

@@ -899,20 +899,65 @@ def test_bench_ranks_of_the_other_configs_cover_disjoint_ranges(config, n, termi
             assert got == rk["digest"], (rk["rank"], got, rk["digest"])
 
 
-def test_bench_launcher_with_eight_ranks(tmp_path):
-    """The node layout of SCALE runs, executed on hardware before a driver ever needs it: `python bench.py --gpus 8` as its own launcher --
-    eight rank processes (spawned, watched, rank 0's line relayed), here sharing the box's one GPU behind a gloo barrier (--oversubscribe,
-    a test-only flag the line reports).  Tiny n: what is tested is the launcher and the rank logic, not a rate."""
+def test_bench_launcher_with_four_ranks(tmp_path):
+    """The launcher of SCALE runs with more ranks than the two-rank tests, executed on hardware before a driver ever needs it: `python bench.py
+    --gpus 4` as its own launcher -- four rank processes (spawned, watched, rank 0's line relayed), here sharing the box's one GPU behind a gloo
+    barrier (--oversubscribe, a test-only flag the line reports).  Four, not a node's eight: with this test process they are five processes on
+    one GPU, and nothing in the launcher or the rank logic depends on the rank count (eight ranks: tests/test_multiprocess.py,
+    test_eight_rank_dry_run_covers_the_range_once).  Tiny n: what is tested is the launcher and the rank
+    logic, not a rate."""
     import json
     import subprocess
+    W = 4
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK")}
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "8", "--steps", "2", "--warmup", "1", "--n", "20000", "--no-cpu-baseline", "--oversubscribe"]
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(W), "--steps", "2", "--warmup", "1", "--n", "20000", "--no-cpu-baseline", "--oversubscribe"]
     r = subprocess.run(cmd, env=env, capture_output=True, timeout=1200)
     assert r.returncode == 0, r.stderr.decode()[-2000:]
     line = json.loads(r.stdout.decode().strip().splitlines()[-1])
-    assert line["n_gpus"] == 8 and line["oversubscribed"] is True and line["scaling"] == "weak"
-    assert line["value"] > 0 and abs(line["value"] - 8 * 20000 * 2 / (line["ms_per_step"] * 2e-3)) < 1e-6 * line["value"]   # the whole job's units / the slowest rank's time
+    assert line["n_gpus"] == W and line["oversubscribed"] is True and line["scaling"] == "weak"
+    assert line["value"] > 0 and abs(line["value"] - W * 20000 * 2 / (line["ms_per_step"] * 2e-3)) < 1e-6 * line["value"]   # the whole job's units / the slowest rank's time
     assert "configs" not in line and "cpu_baseline" not in line
+
+
+def test_bench_dump_outputs(tmp_path):
+    """`bench.py --dump-outputs DIR`: the last timed step's outputs, a fixed seeded sample of a full-size step within 64 MB, equal to the oracle
+    for the sampled trajectories (written before the telemetry run reuses the buffers); the terminal config's tracks are cut to the rows the
+    step wrote, so two runs dump the same arrays."""
+    import json
+    import subprocess
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK")}
+    n, warm, steps = 200000, 1, 2
+    d = str(tmp_path / "uncor")
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", str(steps), "--warmup", str(warm), "--n", str(n), "--no-cpu-baseline", "--dump-outputs", d]
+    r = subprocess.run(cmd, env=env, capture_output=True, timeout=900)
+    assert r.returncode == 0, r.stderr.decode()[-2000:]
+    line = json.loads(r.stdout.decode().strip().splitlines()[-1])
+    assert line["steps"] == steps and line["ms_per_step"] > 0
+    o = {f[:-4]: np.load(os.path.join(d, f)) for f in os.listdir(d)}
+    assert set(o) == {"unit_index", "init_bin", "init_val", "dyn_bin", "dyn_val"} and sum(a.nbytes for a in o.values()) <= 64_000_000
+    assert all(a.dtype in (np.float32, np.float64) for a in o.values())
+    idx = o["unit_index"].astype(np.int64)
+    m = idx.size
+    assert 1000 < m < n and np.all(np.diff(idx) > 0) and idx[0] >= (warm + steps - 1) * n and idx[-1] < (warm + steps) * n
+    assert o["dyn_bin"].shape == (m, 240, 3) and o["init_val"].shape == (m, 7)
+    from em_model_manned_bayes_amd import em_io
+    om = O.OracleModel(O.parse_model_txt(em_io.materialize_model("uncor_1200code_v2p1", str(tmp_path))))
+    for j in np.linspace(0, m - 1, 24).astype(int):
+        ref = O.uncor_sample(om, 1, 240, 0x5EED0002, first_index=int(idx[j]), want_events=False)
+        assert np.array_equal(o["init_bin"][j], ref["init_bin"][0]) and np.array_equal(o["init_val"][j], ref["init_val"][0].astype(np.float32)), j
+        assert np.array_equal(o["dyn_bin"][j], ref["dense_bin"][0]) and np.array_equal(o["dyn_val"][j], ref["dense_val"][0].astype(np.float32)), j
+    dumps = []
+    for rep in range(2):
+        d = str(tmp_path / ("terminal%d" % rep))
+        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--config", "terminal", "--steps", "1", "--warmup", "1", "--n", "20000", "--no-cpu-baseline",
+               "--telemetry-s", "0", "--dump-outputs", d]
+        r = subprocess.run(cmd, env=env, capture_output=True, timeout=900)
+        assert r.returncode == 0, r.stderr.decode()[-2000:]
+        dumps.append({f[:-4]: np.load(os.path.join(d, f)) for f in os.listdir(d)})
+    a, b = dumps
+    assert set(a) == {"unit_index", "geom_val", "geo", "model_of", "rows", "attempts", "tracks"} and sum(x.nbytes for x in a.values()) <= 64_000_000
+    assert a["tracks"].shape[1:] == (4, 123, 6) and a["rows"].max() >= 2
+    assert set(b) == set(a) and all(np.array_equal(a[k], b[k]) for k in a)
 
 
 @pytest.fixture(scope="module")

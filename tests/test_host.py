@@ -746,18 +746,15 @@ num2cell numel onCleanup parse randi readmatrix repmat rethrow rng seconds sind 
 strsplit timetable toc tic zeros inputParser struct isnumeric isfield""".split())
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/code/matlab"), reason="needs the reference mount (build container only)")
 def test_matlab_files_call_only_functions_that_exist():
     """Every name the shipped .m files call like a function is a variable of that file, one of our own functions, a function or
-    method of the reference (read from the mount), the mex gateway, or on a hand-kept list of MATLAB builtins: a misspelt helper
-    would otherwise only surface on a machine with MATLAB."""
+    method of the reference (tests/golden/reference_matlab_functions.txt, written by tests/golden/make_reference_fixtures.py), the
+    mex gateway, or on a hand-kept list of MATLAB builtins: a misspelt helper would otherwise only surface on a machine with MATLAB."""
     import glob
     files = glob.glob(os.path.join(ROOT, "em_model_manned_bayes_amd", "matlab", "**", "*.m"), recursive=True) + glob.glob(os.path.join(ROOT, "tools", "matlab", "*.m"))
     fun_re = r"function\s+(?:\[?([^=\n]*?)\]?\s*=\s*)?([A-Za-z_]\w*)\s*(?:\(([^)]*)\))?"
     known = {"emgpu_mex"} | {os.path.basename(f)[:-2] for f in files}
-    for f in glob.glob("/root/reference/code/matlab/**/*.m", recursive=True):
-        known.add(os.path.basename(f)[:-2])
-        known |= {m.group(2) for m in re.finditer(fun_re, open(f, errors="ignore").read())}
+    known |= set(open(os.path.join(ROOT, "tests", "golden", "reference_matlab_functions.txt")).read().split())
     for f in files:
         text = "\n".join(_matlab_code_lines(open(f).read()))
         names = set(re.findall(r"([A-Za-z_]\w*)\s*(?:\([^=\n]*\)|\{[^=\n]*\})?\s*=(?!=)", text))          # assigned

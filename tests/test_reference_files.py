@@ -1,9 +1,11 @@
-"""Container-only checks against the reference mount (/root/reference is absent on the GPU box: every
-test here skips there).  (1) The product's C++ loader (emgpu_model_load_txt, the em_read.m replacement)
-parses EVERY model file the reference ships, directly from where it lies, and agrees entry for entry with
-the oracle's independent parser and with the packed copy under models/.  (2) The MATLAB-readable
-goldens under tests/golden/matlab/ are what the oracle produces today."""
-import glob
+"""Checks against the files the reference ships.  (1) The product's C++ loader (emgpu_model_load_txt, the
+em_read.m replacement) parses EVERY model file the reference ships, byte for byte as shipped, and agrees
+entry for entry with the oracle's independent parser and with the packed copy under models/.  The shipped
+files are rebuilt from models/ with the few lines in which they differ (tests/golden/reference_models.json,
+written by tests/golden/make_reference_fixtures.py) and checked against their recorded SHA-256.  (2) The
+MATLAB-readable goldens under tests/golden/matlab/ are what the oracle produces today."""
+import hashlib
+import json
 import os
 
 import numpy as np
@@ -14,13 +16,33 @@ import em_model_manned_bayes_amd as E
 from em_model_manned_bayes_amd import em_io
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-REF_MODELS = "/root/reference/model"
-FILES = sorted(glob.glob(os.path.join(REF_MODELS, "**", "*.txt"), recursive=True))
+SHIPPED = json.load(open(os.path.join(ROOT, "tests", "golden", "reference_models.json")))
 
 
-@pytest.mark.skipif(not FILES, reason="the reference mount is only present in the build container")
-@pytest.mark.parametrize("path", FILES, ids=[os.path.relpath(f, REF_MODELS) for f in FILES])
-def test_native_loader_reads_the_reference_file_as_shipped(path):
+def shipped_file(entry, out_dir):
+    """The reference's model file as shipped: em_write's text of the packed copy with the recorded lines put back."""
+    lines = open(em_io.materialize_model(entry["stem"], out_dir), "rb").read().decode("ascii").split("\n")
+    for i, text in entry["lines"]:
+        lines[i] = text
+    data = "\n".join(lines).encode("ascii")
+    assert hashlib.sha256(data).hexdigest() == entry["sha256"], "%s: models/%s.npz no longer rebuilds the shipped file" % (entry["path"], entry["stem"])
+    path = os.path.join(out_dir, "shipped", entry["path"])
+    os.makedirs(os.path.dirname(path), exist_ok=True)
+    with open(path, "wb") as fh:
+        fh.write(data)
+    return path
+
+
+def test_every_shipped_model_file_is_covered():
+    """The parametrization below is never empty: one case per model file the reference ships, each with its packed copy under models/."""
+    stems = {e["stem"] for e in SHIPPED}
+    assert len(SHIPPED) == 27 and len(stems) == len(SHIPPED)
+    assert stems == {os.path.splitext(f)[0] for f in os.listdir(os.path.join(ROOT, "models")) if f.endswith(".npz")}
+
+
+@pytest.mark.parametrize("entry", SHIPPED, ids=[e["path"] for e in SHIPPED])
+def test_native_loader_reads_the_reference_file_as_shipped(entry, tmp_path):
+    path = shipped_file(entry, str(tmp_path))
     p = E.em_read(path)                  # product: C++ loader behind the em_read name
     q = O.parse_model_txt(path)          # oracle: independent numpy parser
     assert p["labels_initial"] == q["labels_initial"] and p["n_initial"] == q["n_initial"]
