@@ -542,7 +542,7 @@ static void launch_dbn(emgpu_ctx *ctx, const Uploaded &u, const EmgpuRun &A, hip
     else e = emgpu::launch_dbn_generic(u.cp.plan, A, stream, &name);
     ctx->last_kernel = name;
     ctx->last_launches++;
-    if (e != hipSuccess) throw Error(EMGPU_ERR_HIP, std::string("kernel launch: ") + hipGetErrorString(e));
+    launch_ok(e);
 }
 
 // Run fn(d) for d = 0..n-1 on one host thread per device and fold the results: the first
@@ -734,7 +734,7 @@ int emgpu_sample_dbn_blocks_device(emgpu_ctx *ctx, const emgpu_model *const *mod
         hipError_t e = emgpu::launch_uncor_fast_mixed(A, (int)G.members.size(), planf, first, nn, col, G.shape, st, &name);
         ctx->last_kernel = name;
         ctx->last_launches++;
-        if (e != hipSuccess) throw Error(EMGPU_ERR_HIP, std::string("kernel launch: ") + hipGetErrorString(e));
+        launch_ok(e);
     }
     return EMGPU_OK;
     EMGPU_CATCH
@@ -816,7 +816,7 @@ int emgpu_sample_bn_device(emgpu_ctx *ctx, const emgpu_model *h, const emgpu_bn_
     const char *name = "";
     hipError_t e = emgpu::launch_bn(u.cp.plan, A, ctx->stream, &name);
     ctx->last_kernel = name;
-    if (e != hipSuccess) return fail(EMGPU_ERR_HIP, std::string("kernel launch: ") + hipGetErrorString(e));
+    launch_ok(e);
     return EMGPU_OK;
     EMGPU_CATCH
 }
@@ -827,35 +827,26 @@ int emgpu_sample_bn_host(emgpu_ctx *ctx, const emgpu_model *h, const emgpu_bn_pa
     CTX_LOCK(ctx);
     HIP_OK(hipSetDevice(ctx->device));
     const size_t n = (size_t)(p->n > 0 ? p->n : 0), ni = h->m.n_initial;
-    uint8_t *db = nullptr; float *dv = nullptr; int32_t *da = nullptr, *ds = nullptr; double *dw = nullptr;
-    int rc;
-    try {
-        if (out_bin) HIP_OK(hipMalloc((void **)&db, ni * n + 1));
-        if (out_val) HIP_OK(hipMalloc((void **)&dv, ni * n * 4 + 4));
-        if (attempts) HIP_OK(hipMalloc((void **)&da, n * 4 + 4));
-        emgpu_bn_params pd = *p;
-        if (p->start && n) {
-            HIP_OK(hipMalloc((void **)&ds, n * ni * 4));
-            HIP_OK(hipMemcpyAsync(ds, p->start, n * ni * 4, hipMemcpyHostToDevice, ctx->stream));
-            HIP_OK(hipStreamSynchronize(ctx->stream));
-            pd.start = ds;
-        }
-        if (p->log_weight) { HIP_OK(hipMalloc((void **)&dw, n * 8 + 8)); pd.log_weight = dw; }
-        rc = emgpu_sample_bn_device(ctx, h, &pd, db, dv, da);
-        if (rc == EMGPU_OK) {
-            if (p->log_weight && n) HIP_OK(hipMemcpyAsync(p->log_weight, dw, n * 8, hipMemcpyDeviceToHost, ctx->stream));
-            if (out_bin && n) HIP_OK(hipMemcpyAsync(out_bin, db, ni * n, hipMemcpyDeviceToHost, ctx->stream));
-            if (out_val && n) HIP_OK(hipMemcpyAsync(out_val, dv, ni * n * 4, hipMemcpyDeviceToHost, ctx->stream));
-            if (attempts && n) HIP_OK(hipMemcpyAsync(attempts, da, n * 4, hipMemcpyDeviceToHost, ctx->stream));
-            rc = emgpu_ctx_sync(ctx);
-        }
-    } catch (...) {
-        (void)hipStreamSynchronize(ctx->stream);
-        (void)hipFree(db); (void)hipFree(dv); (void)hipFree(da); (void)hipFree(ds); (void)hipFree(dw);
-        throw;
+    CallBuffers b(ctx);
+    uint8_t *db = out_bin ? b.alloc<uint8_t>(ni * n + 1) : nullptr;
+    float *dv = out_val ? b.alloc<float>(ni * n * 4 + 4) : nullptr;
+    int32_t *da = attempts ? b.alloc<int32_t>(n * 4 + 4) : nullptr;
+    emgpu_bn_params pd = *p;
+    if (p->start && n) {
+        int32_t *ds = b.alloc<int32_t>(n * ni * 4);
+        b.up(ds, p->start, n * ni * 4);
+        HIP_OK(hipStreamSynchronize(ctx->stream));
+        pd.start = ds;
     }
-    (void)hipStreamSynchronize(ctx->stream);
-    (void)hipFree(db); (void)hipFree(dv); (void)hipFree(da); (void)hipFree(ds); (void)hipFree(dw);
+    if (p->log_weight) pd.log_weight = b.alloc<double>(n * 8 + 8);
+    int rc = emgpu_sample_bn_device(ctx, h, &pd, db, dv, da);
+    if (rc == EMGPU_OK) {
+        b.down(p->log_weight, pd.log_weight, n * 8);
+        b.down(out_bin, db, ni * n);
+        b.down(out_val, dv, ni * n * 4);
+        b.down(attempts, da, n * 4);
+        rc = emgpu_ctx_sync(ctx);
+    }
     return rc;
     EMGPU_CATCH
 }
@@ -887,36 +878,29 @@ int emgpu_debug_uncor_dynamics_host(emgpu_ctx *ctx, int64_t n, int32_t T, int32_
         for (int c = 0; c < T; c++)
             for (int k = 0; k < 3; k++) h_dyn[((((size_t)c / 4) * 3 + k) * n + i) * 4 + c % 4] = controls[((size_t)i * T + c) * 3 + k];   // rows: \dot h, \dot psi, \dot v
     }
-    float *d_init = nullptr, *d_dyn = nullptr; double *d_tr = nullptr, *d_lim = nullptr; uint8_t *d_acc = nullptr;
-    int rc = EMGPU_OK;
-    try {
-        HIP_OK(hipMalloc((void **)&d_init, h_init.size() * 4)); HIP_OK(hipMalloc((void **)&d_dyn, h_dyn.size() * 4));
-        HIP_OK(hipMalloc((void **)&d_tr, (size_t)n * S * 8 * 8)); HIP_OK(hipMalloc((void **)&d_lim, 3 * 8)); HIP_OK(hipMalloc((void **)&d_acc, (size_t)n));
-        const double lim[3] = {-1e300, 1e300, 1e300};
-        HIP_OK(hipMemcpyAsync(d_init, h_init.data(), h_init.size() * 4, hipMemcpyHostToDevice, ctx->stream));
-        HIP_OK(hipMemcpyAsync(d_dyn, h_dyn.data(), h_dyn.size() * 4, hipMemcpyHostToDevice, ctx->stream));
-        HIP_OK(hipMemcpyAsync(d_lim, lim, sizeof lim, hipMemcpyHostToDevice, ctx->stream));
-        EmgpuUTrackRun R;
-        memset(&R, 0, sizeof R);
-        R.n = n; R.ld = n; R.T = T; R.stride = record_stride;
-        R.iL = d_init; R.iV = d_init + n; R.iDV = d_init + 2 * n; R.iDH = d_init + 3 * n; R.iDPsi = d_init + 4 * n;
-        R.dyn_val = d_dyn; R.nd = 3; R.sDH = 0; R.sDPsi = 1; R.sDV = 2;
-        memcpy(R.dyn, dyn, sizeof R.dyn);
-        R.min_alt = -1e300; R.max_alt = 1e300; R.ordered = 0; R.lim = d_lim;
-        R.tracks = d_tr; R.S = (int64_t)S; R.accepted = d_acc;
-        const char *name = "";
-        hipError_t e = emgpu::launch_uncor_track(R, ctx->stream, &name, literal);
-        ctx->last_kernel = name;
-        if (e != hipSuccess) throw Error(EMGPU_ERR_HIP, std::string("kernel launch: ") + hipGetErrorString(e));
-        HIP_OK(hipMemcpyAsync(tracks, d_tr, (size_t)n * S * 8 * 8, hipMemcpyDeviceToHost, ctx->stream));
-        HIP_OK(hipStreamSynchronize(ctx->stream));
-    } catch (...) {
-        (void)hipStreamSynchronize(ctx->stream);
-        (void)hipFree(d_init); (void)hipFree(d_dyn); (void)hipFree(d_tr); (void)hipFree(d_lim); (void)hipFree(d_acc);
-        throw;
-    }
-    (void)hipFree(d_init); (void)hipFree(d_dyn); (void)hipFree(d_tr); (void)hipFree(d_lim); (void)hipFree(d_acc);
-    return rc;
+    CallBuffers b(ctx);
+    float *d_init = b.alloc<float>(h_init.size() * 4), *d_dyn = b.alloc<float>(h_dyn.size() * 4);
+    double *d_tr = b.alloc<double>((size_t)n * S * 8 * 8), *d_lim = b.alloc<double>(3 * 8);
+    uint8_t *d_acc = b.alloc<uint8_t>((size_t)n);
+    const double lim[3] = {-1e300, 1e300, 1e300};
+    b.up(d_init, h_init.data(), h_init.size() * 4);
+    b.up(d_dyn, h_dyn.data(), h_dyn.size() * 4);
+    b.up(d_lim, lim, sizeof lim);
+    EmgpuUTrackRun R;
+    memset(&R, 0, sizeof R);
+    R.n = n; R.ld = n; R.T = T; R.stride = record_stride;
+    R.iL = d_init; R.iV = d_init + n; R.iDV = d_init + 2 * n; R.iDH = d_init + 3 * n; R.iDPsi = d_init + 4 * n;
+    R.dyn_val = d_dyn; R.nd = 3; R.sDH = 0; R.sDPsi = 1; R.sDV = 2;
+    memcpy(R.dyn, dyn, sizeof R.dyn);
+    R.min_alt = -1e300; R.max_alt = 1e300; R.ordered = 0; R.lim = d_lim;
+    R.tracks = d_tr; R.S = (int64_t)S; R.accepted = d_acc;
+    const char *name = "";
+    hipError_t e = emgpu::launch_uncor_track(R, ctx->stream, &name, literal);
+    ctx->last_kernel = name;
+    launch_ok(e);
+    b.down(tracks, d_tr, (size_t)n * S * 8 * 8);
+    HIP_OK(hipStreamSynchronize(ctx->stream));
+    return EMGPU_OK;
     EMGPU_CATCH
 }
 
@@ -1041,6 +1025,18 @@ static const Uploaded *terminal_tables(emgpu_ctx *ctx, const emgpu_model *const 
     return first;
 }
 
+// k_terminal_propagate's run over the tables terminal_tables published in ctx->d_thr_base
+static EmgpuTermRun term_run(emgpu_ctx *ctx, uint64_t seed, uint64_t first_index, int64_t n, const double *geo, const int32_t *model_of,
+                             double tmax_s, int32_t max_resample, int32_t cap, const double (&dyn_limits)[2][5], float *traj, int32_t *rows) {
+    EmgpuTermRun A;
+    memset(&A, 0, sizeof A);
+    A.seed = seed; A.first_index = first_index; A.n = n; A.geo = geo; A.model_of = model_of; A.thr_base = ctx->d_thr_base;
+    A.tmax_s = tmax_s; A.max_resample = max_resample; A.cap = cap;
+    memcpy(A.dl, dyn_limits, sizeof A.dl);
+    A.traj = traj; A.rows = rows; A.status = ctx->d_status; A.queue = ctx->d_queue;
+    return A;
+}
+
 int emgpu_propagate_terminal_device(emgpu_ctx *ctx, const emgpu_model *const *models, int32_t n_models,
                                     const emgpu_term_params *p, const double *geo, const int32_t *model_of,
                                     float *traj, int32_t *rows) {
@@ -1051,12 +1047,7 @@ int emgpu_propagate_terminal_device(emgpu_ctx *ctx, const emgpu_model *const *mo
     CTX_LOCK(ctx);
     HIP_OK(hipSetDevice(ctx->device));
     const Uploaded *first = terminal_tables(ctx, models, n_models);
-    EmgpuTermRun A;
-    memset(&A, 0, sizeof A);
-    A.seed = p->seed; A.first_index = p->first_index; A.n = p->n; A.geo = geo; A.model_of = model_of; A.thr_base = ctx->d_thr_base;
-    A.tmax_s = p->tmax_s; A.max_resample = p->max_resample; A.cap = p->cap;
-    memcpy(A.dl, p->dyn_limits, sizeof A.dl);
-    A.traj = traj; A.rows = rows; A.status = ctx->d_status; A.queue = ctx->d_queue;
+    const EmgpuTermRun A = term_run(ctx, p->seed, p->first_index, p->n, geo, model_of, p->tmax_s, p->max_resample, p->cap, p->dyn_limits, traj, rows);
     const char *name = "";
     if ((p->flags & EMGPU_FLAG_LOCAL_SMOOTH) && EMGPU_TERMINAL_BLOCK_ROWS(p->cap) > 256) return fail(EMGPU_ERR_UNSUPPORTED, "EMGPU_FLAG_LOCAL_SMOOTH: cap above 128");
     hipError_t e = emgpu::launch_terminal_propagate(first->cp.plan, A, ctx->stream, &name);
@@ -1065,7 +1056,7 @@ int emgpu_propagate_terminal_device(emgpu_ctx *ctx, const emgpu_model *const *mo
         e = emgpu::launch_terminal_smooth(traj, rows, 2 * p->n, p->cap, ctx->stream);
         ctx->last_kernel += " + k_terminal_smooth";
     }
-    if (e != hipSuccess) return fail(EMGPU_ERR_HIP, std::string("kernel launch: ") + hipGetErrorString(e));
+    launch_ok(e);
     return EMGPU_OK;
     EMGPU_CATCH
 }
@@ -1080,31 +1071,19 @@ int emgpu_propagate_terminal_host(emgpu_ctx *ctx, const emgpu_model *const *mode
     CTX_LOCK(ctx);
     HIP_OK(hipSetDevice(ctx->device));
     const size_t n = (size_t)(p->n > 0 ? p->n : 0), nl = 4 * n;
-    double *dg = nullptr; int32_t *dm = nullptr, *dr = nullptr; float *dout = nullptr;
-    int rc;
-    try {
-        HIP_OK(hipMalloc((void **)&dg, n * 12 * sizeof(double) + 8));
-        HIP_OK(hipMalloc((void **)&dm, nl * 4 + 4));
-        HIP_OK(hipMalloc((void **)&dr, nl * 4 + 4));
-        HIP_OK(hipMalloc((void **)&dout, out_bytes + 4));
-        if (n) {
-            HIP_OK(hipMemcpyAsync(dg, geo, n * 12 * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-            HIP_OK(hipMemcpyAsync(dm, model_of, nl * 4, hipMemcpyHostToDevice, ctx->stream));
-            HIP_OK(hipMemsetAsync(dout, 0, out_bytes, ctx->stream));
-        }
-        rc = emgpu_propagate_terminal_device(ctx, models, n_models, p, dg, dm, dout, dr);
-        if (rc == EMGPU_OK && n) {
-            HIP_OK(hipMemcpyAsync(out, dout, out_bytes, hipMemcpyDeviceToHost, ctx->stream));
-            HIP_OK(hipMemcpyAsync(rows, dr, nl * 4, hipMemcpyDeviceToHost, ctx->stream));
-        }
-        if (rc == EMGPU_OK) rc = emgpu_ctx_sync(ctx);
-    } catch (...) {
-        (void)hipStreamSynchronize(ctx->stream);
-        (void)hipFree(dg); (void)hipFree(dm); (void)hipFree(dr); (void)hipFree(dout);
-        throw;
+    CallBuffers b(ctx);
+    double *dg = b.alloc<double>(n * 12 * sizeof(double) + 8);
+    int32_t *dm = b.alloc<int32_t>(nl * 4 + 4), *dr = b.alloc<int32_t>(nl * 4 + 4);
+    float *dout = b.alloc<float>(out_bytes + 4);
+    b.up(dg, geo, n * 12 * sizeof(double));
+    b.up(dm, model_of, nl * 4);
+    if (n) HIP_OK(hipMemsetAsync(dout, 0, out_bytes, ctx->stream));
+    int rc = emgpu_propagate_terminal_device(ctx, models, n_models, p, dg, dm, dout, dr);
+    if (rc == EMGPU_OK) {
+        b.down(out, dout, out_bytes);
+        b.down(rows, dr, nl * 4);
+        rc = emgpu_ctx_sync(ctx);
     }
-    (void)hipStreamSynchronize(ctx->stream);
-    (void)hipFree(dg); (void)hipFree(dm); (void)hipFree(dr); (void)hipFree(dout);
     return rc;
     EMGPU_CATCH
 }
@@ -1137,36 +1116,47 @@ int emgpu_sample_terminal_device(emgpu_ctx *ctx, const emgpu_model *gm, const em
     fill_bn(ctx, ug, g, &bp, B);
     B.out_bin = geom_bin; B.out_val = geom_val; B.attempts = attempts;
     const char *name = "";
-    hipError_t e = emgpu::launch_bn(ug.cp.plan, B, ctx->stream, &name);
-    if (e != hipSuccess) return fail(EMGPU_ERR_HIP, std::string("kernel launch: ") + hipGetErrorString(e));
+    launch_ok(emgpu::launch_bn(ug.cp.plan, B, ctx->stream, &name));
     std::string kernels = name;
     // createEncounter.m:21-49
     EmgpuTGeoRun G;
     memset(&G, 0, sizeof G);
     G.n = p->n; G.val = geom_val; G.geo = geo; G.model_of = model_of;
     for (int k = 0; k < 12; k++) G.idx[k] = p->idx[k] - 1;
-    e = emgpu::launch_terminal_geo(G, ctx->stream);
-    if (e != hipSuccess) return fail(EMGPU_ERR_HIP, std::string("kernel launch: ") + hipGetErrorString(e));
+    launch_ok(emgpu::launch_terminal_geo(G, ctx->stream));
     kernels += " + k_terminal_geo";
     // PropagateTrajectory x 4 (createEncounter.m:52-72)
-    EmgpuTermRun A;
-    memset(&A, 0, sizeof A);
-    A.seed = p->seed; A.first_index = p->first_index; A.n = p->n; A.geo = geo; A.model_of = model_of; A.thr_base = ctx->d_thr_base;
-    A.tmax_s = p->tmax_s; A.max_resample = p->max_resample; A.cap = p->cap;
-    memcpy(A.dl, p->dyn_limits, sizeof A.dl);
-    A.traj = traj; A.rows = rows; A.status = ctx->d_status; A.queue = ctx->d_queue;
-    e = emgpu::launch_terminal_propagate(first->cp.plan, A, ctx->stream, &name);
-    if (e != hipSuccess) return fail(EMGPU_ERR_HIP, std::string("kernel launch: ") + hipGetErrorString(e));
+    const EmgpuTermRun A = term_run(ctx, p->seed, p->first_index, p->n, geo, model_of, p->tmax_s, p->max_resample, p->cap, p->dyn_limits, traj, rows);
+    launch_ok(emgpu::launch_terminal_propagate(first->cp.plan, A, ctx->stream, &name));
     ctx->last_kernel = kernels + " + " + name;
     ctx->last_launches = 3;
     if (p->flags & EMGPU_FLAG_LOCAL_SMOOTH) {
-        e = emgpu::launch_terminal_smooth(traj, rows, 2 * p->n, p->cap, ctx->stream);
-        if (e != hipSuccess) return fail(EMGPU_ERR_HIP, std::string("kernel launch: ") + hipGetErrorString(e));
+        launch_ok(emgpu::launch_terminal_smooth(traj, rows, 2 * p->n, p->cap, ctx->stream));
         ctx->last_kernel = kernels + " + k_terminal_smooth + " + name;   // (the dominant kernel stays last in the list)
         ctx->last_launches = 4;
     }
     return EMGPU_OK;
     EMGPU_CATCH
+}
+
+// Synchronizes a stream when the scope ends, however it ends: the round drivers' launches read their scratch and the caller's buffers.
+struct StreamSyncOnExit {
+    hipStream_t s;
+    ~StreamSyncOnExit() { (void)hipStreamSynchronize(s); }
+};
+
+// The end of rejection round j: the lanes it rejected, in lane order, become the next round's (global index, output slot) lists
+// d_gidx / d_slot[(j & 1) ^ 1] (round j read [j & 1], round 0 none).  Returns how many.
+static size_t compact_rejected(emgpu_ctx *ctx, int j, size_t count, uint64_t first_index, const uint8_t *d_acc, uint64_t *const d_gidx[2],
+                               int64_t *const d_slot[2], uint32_t *d_count) {
+    const int cur = j & 1;
+    HIP_OK(hipMemsetAsync(d_count, 0, 4, ctx->stream));
+    launch_ok(emgpu::launch_compact_rejected((int64_t)count, first_index, d_acc, j ? d_gidx[cur] : nullptr, j ? d_slot[cur] : nullptr,
+                                             d_gidx[cur ^ 1], d_slot[cur ^ 1], d_count, ctx->stream));
+    uint32_t hc = 0;
+    HIP_OK(hipMemcpyAsync(&hc, d_count, 4, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_OK(hipStreamSynchronize(ctx->stream));
+    return hc;
 }
 
 int emgpu_track_terminal_host(emgpu_ctx *ctx, const emgpu_model *gm, const emgpu_model *const *traj_models, int32_t n_traj_models,
@@ -1188,101 +1178,80 @@ int emgpu_track_terminal_host(emgpu_ctx *ctx, const emgpu_model *gm, const emgpu
     const int cap = (int)p->tmax_s + 3;
     size_t slot = 0;
     auto dalloc = [&](size_t bytes) { return ctx_scratch(ctx, slot++, bytes ? bytes : 1); };   // kept by the ctx between calls
-    int rc = EMGPU_OK;
-    try {
-        float *d_val = (float *)dalloc(ni * n * 4);
-        double *d_geo = (double *)dalloc(n * 12 * 8);
-        int32_t *d_mo = (int32_t *)dalloc(4 * n * 4), *d_rows = (int32_t *)dalloc(4 * n * 4);
-        float *d_out = (float *)dalloc((size_t)2 * n * (size_t)EMGPU_TERMINAL_BLOCK_ROWS(cap) * 5 * 4);
-        uint8_t *d_acc = (uint8_t *)dalloc(n);
-        uint64_t *d_gidx[2] = {(uint64_t *)dalloc(n * 8), (uint64_t *)dalloc(n * 8)};
-        int64_t *d_slot[2] = {(int64_t *)dalloc(n * 8), (int64_t *)dalloc(n * 8)};
-        uint32_t *d_count = (uint32_t *)dalloc(4 * emgpu::compact_scratch_words((int64_t)n));
-        double *d_sample = sample ? (double *)dalloc(n * ni * 8) : nullptr;
-        double *d_traj = traj ? (double *)dalloc(n * 2 * (size_t)cap2 * 6 * 8) : nullptr;
-        int32_t *d_len = len ? (int32_t *)dalloc(n * 2 * 4) : nullptr;
-        double *d_meta = meta ? (double *)dalloc(n * 4 * 8) : nullptr;
-        int32_t *d_att = (int32_t *)dalloc(n * 4);
-        std::set<uint64_t> pinned{gm->m.uid};   // the trajectory tables' pointers are published before the geometry model's upload
-        for (int i = 0; i < n_traj_models; i++) if (traj_models[i]) pinned.insert(traj_models[i]->m.uid);
-        const Uploaded *first = terminal_tables(ctx, traj_models, n_traj_models, &pinned);
-        Uploaded &ug = get_uploaded(ctx, gm, &pinned);
-        emgpu_bn_params bp;
-        memset(&bp, 0, sizeof bp);
-        bp.max_attempts = p->max_attempts; bp.bounds_sample = p->bounds_sample;
-        bp.idx_own_speed = p->idx[3]; bp.idx_int_speed = p->idx[9];
-        bp.min_vel1 = p->dyn_limits[0][0]; bp.max_vel1 = p->dyn_limits[0][1]; bp.min_vel2 = p->dyn_limits[1][0]; bp.max_vel2 = p->dyn_limits[1][1];
-        size_t count = n;
-        std::string kernels;
-        for (int j = 0; j < p->max_track_attempts && count > 0; j++) {
-            const int cur = j & 1;
-            const uint64_t seed = p->seed + (uint64_t)j;
-            const uint64_t *ind = j ? d_gidx[cur] : nullptr;
-            // geometry draw (sample.m:29-77)
-            bp.seed = seed; bp.first_index = p->first_index; bp.n = (int64_t)count;
-            EmgpuBnRun B;
-            fill_bn(ctx, ug, g, &bp, B);
-            B.out_val = d_val; B.ld = (int64_t)count; B.indices = ind;
-            const char *name = "";
-            hipError_t e = emgpu::launch_bn(ug.cp.plan, B, ctx->stream, &name);
-            if (e != hipSuccess) throw Error(EMGPU_ERR_HIP, std::string("kernel launch: ") + hipGetErrorString(e));
-            kernels = name;
-            // createEncounter.m:21-49
-            EmgpuTGeoRun G;
-            memset(&G, 0, sizeof G);
-            G.n = (int64_t)count; G.val = d_val; G.geo = d_geo; G.model_of = d_mo;
-            for (int k = 0; k < 12; k++) G.idx[k] = p->idx[k] - 1;
-            e = emgpu::launch_terminal_geo(G, ctx->stream);
-            if (e != hipSuccess) throw Error(EMGPU_ERR_HIP, std::string("kernel launch: ") + hipGetErrorString(e));
-            // PropagateTrajectory x 4 (createEncounter.m:52-72)
-            EmgpuTermRun A;
-            memset(&A, 0, sizeof A);
-            A.seed = seed; A.first_index = p->first_index; A.n = (int64_t)count; A.geo = d_geo; A.model_of = d_mo; A.thr_base = ctx->d_thr_base;
-            A.tmax_s = p->tmax_s; A.max_resample = p->max_resample; A.cap = cap;
-            memcpy(A.dl, p->dyn_limits, sizeof A.dl);
-            A.traj = d_out; A.rows = d_rows; A.status = ctx->d_status; A.queue = ctx->d_queue; A.indices = ind; A.quiet = 1;
-            e = emgpu::launch_terminal_propagate(first->cp.plan, A, ctx->stream, &name);
-            if (e != hipSuccess) throw Error(EMGPU_ERR_HIP, std::string("kernel launch: ") + hipGetErrorString(e));
-            kernels += std::string(" + ") + name;
-            if (p->flags & EMGPU_FLAG_LOCAL_SMOOTH) {   // createEncounter.m:88-89 (stand-in): the filters read the smoothed speed and altitude
-                e = emgpu::launch_terminal_smooth(d_out, d_rows, 2 * (int64_t)count, cap, ctx->stream);
-                if (e != hipSuccess) throw Error(EMGPU_ERR_HIP, std::string("kernel launch: ") + hipGetErrorString(e));
-                kernels += " + k_terminal_smooth";
-            }
-            // the filters (track.m:62-145)
-            EmgpuTFilterRun F;
-            memset(&F, 0, sizeof F);
-            F.n = (int64_t)count; F.tracks = d_out; F.rows = d_rows; F.cap = cap; F.geo = d_geo; F.val = d_val; F.n_i = (int32_t)ni;
-            memcpy(F.dl, p->dyn_limits, sizeof F.dl);
-            for (int a = 0; a < 2; a++) { F.max_cum_turn[a] = p->max_cum_turn_deg[a]; F.pitch[a] = p->pitch_deg[a]; }
-            F.min_enc_time_s = p->min_enc_time_s; F.thres_dist_ft = p->thres_dist_ft; F.thres_alt_low_ft = p->thres_alt_low_ft; F.thres_vertrate_ft_s = p->thres_vertrate_ft_s;
-            F.slot = j ? d_slot[cur] : nullptr; F.accepted = d_acc;
-            F.sample = d_sample; F.traj = d_traj; F.cap2 = cap2; F.len = d_len; F.meta = d_meta; F.attempts = d_att;
-            F.attempt_no = j + 1; F.last_round = (j + 1 == p->max_track_attempts);
-            e = emgpu::launch_terminal_filter(F, ctx->stream, &name);
-            if (e != hipSuccess) throw Error(EMGPU_ERR_HIP, std::string("kernel launch: ") + hipGetErrorString(e));
-            ctx->last_kernel = kernels + " + " + name;
-            HIP_OK(hipMemsetAsync(d_count, 0, 4, ctx->stream));
-            e = emgpu::launch_compact_rejected((int64_t)count, p->first_index, d_acc, ind, j ? d_slot[cur] : nullptr, d_gidx[cur ^ 1], d_slot[cur ^ 1], d_count, ctx->stream);
-            if (e != hipSuccess) throw Error(EMGPU_ERR_HIP, std::string("kernel launch: ") + hipGetErrorString(e));
-            uint32_t hc = 0;
-            HIP_OK(hipMemcpyAsync(&hc, d_count, 4, hipMemcpyDeviceToHost, ctx->stream));
-            HIP_OK(hipStreamSynchronize(ctx->stream));
-            count = hc;
+    const StreamSyncOnExit drain{ctx->stream};
+    float *d_val = (float *)dalloc(ni * n * 4);
+    double *d_geo = (double *)dalloc(n * 12 * 8);
+    int32_t *d_mo = (int32_t *)dalloc(4 * n * 4), *d_rows = (int32_t *)dalloc(4 * n * 4);
+    float *d_out = (float *)dalloc((size_t)2 * n * (size_t)EMGPU_TERMINAL_BLOCK_ROWS(cap) * 5 * 4);
+    uint8_t *d_acc = (uint8_t *)dalloc(n);
+    uint64_t *d_gidx[2] = {(uint64_t *)dalloc(n * 8), (uint64_t *)dalloc(n * 8)};
+    int64_t *d_slot[2] = {(int64_t *)dalloc(n * 8), (int64_t *)dalloc(n * 8)};
+    uint32_t *d_count = (uint32_t *)dalloc(4 * emgpu::compact_scratch_words((int64_t)n));
+    double *d_sample = sample ? (double *)dalloc(n * ni * 8) : nullptr;
+    double *d_traj = traj ? (double *)dalloc(n * 2 * (size_t)cap2 * 6 * 8) : nullptr;
+    int32_t *d_len = len ? (int32_t *)dalloc(n * 2 * 4) : nullptr;
+    double *d_meta = meta ? (double *)dalloc(n * 4 * 8) : nullptr;
+    int32_t *d_att = (int32_t *)dalloc(n * 4);
+    std::set<uint64_t> pinned{gm->m.uid};   // the trajectory tables' pointers are published before the geometry model's upload
+    for (int i = 0; i < n_traj_models; i++) if (traj_models[i]) pinned.insert(traj_models[i]->m.uid);
+    const Uploaded *first = terminal_tables(ctx, traj_models, n_traj_models, &pinned);
+    Uploaded &ug = get_uploaded(ctx, gm, &pinned);
+    emgpu_bn_params bp;
+    memset(&bp, 0, sizeof bp);
+    bp.max_attempts = p->max_attempts; bp.bounds_sample = p->bounds_sample;
+    bp.idx_own_speed = p->idx[3]; bp.idx_int_speed = p->idx[9];
+    bp.min_vel1 = p->dyn_limits[0][0]; bp.max_vel1 = p->dyn_limits[0][1]; bp.min_vel2 = p->dyn_limits[1][0]; bp.max_vel2 = p->dyn_limits[1][1];
+    size_t count = n;
+    std::string kernels;
+    for (int j = 0; j < p->max_track_attempts && count > 0; j++) {
+        const int cur = j & 1;
+        const uint64_t seed = p->seed + (uint64_t)j;
+        const uint64_t *ind = j ? d_gidx[cur] : nullptr;
+        // geometry draw (sample.m:29-77)
+        bp.seed = seed; bp.first_index = p->first_index; bp.n = (int64_t)count;
+        EmgpuBnRun B;
+        fill_bn(ctx, ug, g, &bp, B);
+        B.out_val = d_val; B.ld = (int64_t)count; B.indices = ind;
+        const char *name = "";
+        launch_ok(emgpu::launch_bn(ug.cp.plan, B, ctx->stream, &name));
+        kernels = name;
+        // createEncounter.m:21-49
+        EmgpuTGeoRun G;
+        memset(&G, 0, sizeof G);
+        G.n = (int64_t)count; G.val = d_val; G.geo = d_geo; G.model_of = d_mo;
+        for (int k = 0; k < 12; k++) G.idx[k] = p->idx[k] - 1;
+        launch_ok(emgpu::launch_terminal_geo(G, ctx->stream));
+        // PropagateTrajectory x 4 (createEncounter.m:52-72)
+        EmgpuTermRun A = term_run(ctx, seed, p->first_index, (int64_t)count, d_geo, d_mo, p->tmax_s, p->max_resample, cap, p->dyn_limits, d_out, d_rows);
+        A.indices = ind; A.quiet = 1;
+        launch_ok(emgpu::launch_terminal_propagate(first->cp.plan, A, ctx->stream, &name));
+        kernels += std::string(" + ") + name;
+        if (p->flags & EMGPU_FLAG_LOCAL_SMOOTH) {   // createEncounter.m:88-89 (stand-in): the filters read the smoothed speed and altitude
+            launch_ok(emgpu::launch_terminal_smooth(d_out, d_rows, 2 * (int64_t)count, cap, ctx->stream));
+            kernels += " + k_terminal_smooth";
         }
-        rc = emgpu_ctx_sync(ctx);   // the geometry draw's own rejection cap
-        std::string msg = g_err;
-        auto back = [&](void *dst, const void *src, size_t bytes) { if (dst && bytes) HIP_OK(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, ctx->stream)); };
-        back(sample, d_sample, n * ni * 8); back(traj, d_traj, n * 2 * (size_t)cap2 * 6 * 8); back(len, d_len, n * 2 * 4);
-        back(meta, d_meta, n * 4 * 8); back(attempts, d_att, n * 4);
-        HIP_OK(hipStreamSynchronize(ctx->stream));
-        if (rc != EMGPU_OK) g_err = msg;
-        else if (count > 0) rc = fail(EMGPU_ERR_REJECT_CAP, "terminal track: " + std::to_string(count) + " encounters were still rejected after max_track_attempts");
-    } catch (...) {
-        (void)hipStreamSynchronize(ctx->stream);
-        throw;
+        // the filters (track.m:62-145)
+        EmgpuTFilterRun F;
+        memset(&F, 0, sizeof F);
+        F.n = (int64_t)count; F.tracks = d_out; F.rows = d_rows; F.cap = cap; F.geo = d_geo; F.val = d_val; F.n_i = (int32_t)ni;
+        memcpy(F.dl, p->dyn_limits, sizeof F.dl);
+        for (int a = 0; a < 2; a++) { F.max_cum_turn[a] = p->max_cum_turn_deg[a]; F.pitch[a] = p->pitch_deg[a]; }
+        F.min_enc_time_s = p->min_enc_time_s; F.thres_dist_ft = p->thres_dist_ft; F.thres_alt_low_ft = p->thres_alt_low_ft; F.thres_vertrate_ft_s = p->thres_vertrate_ft_s;
+        F.slot = j ? d_slot[cur] : nullptr; F.accepted = d_acc;
+        F.sample = d_sample; F.traj = d_traj; F.cap2 = cap2; F.len = d_len; F.meta = d_meta; F.attempts = d_att;
+        F.attempt_no = j + 1; F.last_round = (j + 1 == p->max_track_attempts);
+        launch_ok(emgpu::launch_terminal_filter(F, ctx->stream, &name));
+        ctx->last_kernel = kernels + " + " + name;
+        count = compact_rejected(ctx, j, count, p->first_index, d_acc, d_gidx, d_slot, d_count);
     }
-    (void)hipStreamSynchronize(ctx->stream);
+    int rc = emgpu_ctx_sync(ctx);   // the geometry draw's own rejection cap
+    std::string msg = g_err;
+    auto back = [&](void *dst, const void *src, size_t bytes) { if (dst && bytes) HIP_OK(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, ctx->stream)); };
+    back(sample, d_sample, n * ni * 8); back(traj, d_traj, n * 2 * (size_t)cap2 * 6 * 8); back(len, d_len, n * 2 * 4);
+    back(meta, d_meta, n * 4 * 8); back(attempts, d_att, n * 4);
+    HIP_OK(hipStreamSynchronize(ctx->stream));
+    if (rc != EMGPU_OK) g_err = msg;
+    else if (count > 0) rc = fail(EMGPU_ERR_REJECT_CAP, "terminal track: " + std::to_string(count) + " encounters were still rejected after max_track_attempts");
     return rc;
     EMGPU_CATCH
 }
@@ -1312,7 +1281,7 @@ int emgpu_sample2track_device(emgpu_ctx *ctx, const emgpu_track_params *p, const
     const char *name = "";
     const hipError_t e = emgpu::launch_sample2track(A, true, ctx->stream, &name);
     ctx->last_kernel = name;
-    if (e != hipSuccess) return fail(EMGPU_ERR_HIP, std::string("kernel launch: ") + hipGetErrorString(e));
+    launch_ok(e);
     return EMGPU_OK;
     EMGPU_CATCH
 }
@@ -1327,56 +1296,37 @@ int emgpu_sample2track_host(emgpu_ctx *ctx, const emgpu_track_params *p, const d
     const size_t n = (size_t)p->n, T = (size_t)p->T;
     if (n == 0) return EMGPU_OK;
     // [n][T][3] -> [T][3][n] so that a wave reads 64 consecutive doubles
-    std::vector<double> planar(T * 3 * n), hx;
+    std::vector<double> planar(T * 3 * n), hx, hv;   // (before the buffers: their copy-backs land here until the buffers' destructor syncs)
     for (size_t i = 0; i < n; i++)
         for (size_t t = 0; t < T; t++)
             for (size_t c = 0; c < 3; c++) planar[(t * 3 + c) * n + i] = updates[(i * T + t) * 3 + c];
-    double *d_in = nullptr, *d_xyz = nullptr, *d_vmm = nullptr; uint8_t *d_fl = nullptr;
-    int rc = EMGPU_OK;
-    try {
-        HIP_OK(hipMalloc((void **)&d_in, (planar.size() + 2 * n) * sizeof(double)));
-        HIP_OK(hipMalloc((void **)&d_xyz, (T + 1) * 3 * n * sizeof(double)));
-        HIP_OK(hipMalloc((void **)&d_vmm, 2 * n * sizeof(double)));
-        HIP_OK(hipMalloc((void **)&d_fl, n));
-        HIP_OK(hipMemcpyAsync(d_in, planar.data(), planar.size() * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-        HIP_OK(hipMemcpyAsync(d_in + planar.size(), alt0, n * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-        HIP_OK(hipMemcpyAsync(d_in + planar.size() + n, speed0, n * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-        EmgpuTrackRun A{};
-        A.n = p->n; A.T = p->T;
-        A.ur_speed = p->ur_speed; A.ur_vertrate = p->ur_vertrate; A.ur_heading = p->ur_heading;
-        A.min_speed = p->min_speed; A.max_speed = p->max_speed;
-        A.upd = d_in; A.alt0_d = d_in + planar.size(); A.speed0_d = d_in + planar.size() + n;
-        A.xyz = d_xyz; A.flags = d_fl; A.vmm = d_vmm;
-        const char *name = "";
-        const hipError_t e = emgpu::launch_sample2track(A, false, ctx->stream, &name);
-        ctx->last_kernel = name;
-        if (e != hipSuccess) rc = fail(EMGPU_ERR_HIP, std::string("kernel launch: ") + hipGetErrorString(e));
-        if (rc == EMGPU_OK) {
-            if (xyz) {
-                hx.resize((T + 1) * 3 * n);
-                HIP_OK(hipMemcpyAsync(hx.data(), d_xyz, hx.size() * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-            }
-            if (flags) HIP_OK(hipMemcpyAsync(flags, d_fl, n, hipMemcpyDeviceToHost, ctx->stream));
-            std::vector<double> hv;
-            if (speed_minmax) {
-                hv.resize(2 * n);
-                HIP_OK(hipMemcpyAsync(hv.data(), d_vmm, 2 * n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-            }
-            rc = emgpu_ctx_sync(ctx);
-            if (rc == EMGPU_OK && xyz)
-                for (size_t i = 0; i < n; i++)
-                    for (size_t t = 0; t <= T; t++)
-                        for (size_t c = 0; c < 3; c++) xyz[(i * (T + 1) + t) * 3 + c] = hx[(t * 3 + c) * n + i];
-            if (rc == EMGPU_OK && speed_minmax)
-                for (size_t i = 0; i < n; i++) { speed_minmax[2 * i] = hv[i]; speed_minmax[2 * i + 1] = hv[n + i]; }
-        }
-    } catch (...) {
-        (void)hipStreamSynchronize(ctx->stream);
-        (void)hipFree(d_in); (void)hipFree(d_xyz); (void)hipFree(d_vmm); (void)hipFree(d_fl);
-        throw;
-    }
-    (void)hipStreamSynchronize(ctx->stream);
-    (void)hipFree(d_in); (void)hipFree(d_xyz); (void)hipFree(d_vmm); (void)hipFree(d_fl);
+    CallBuffers b(ctx);
+    double *d_in = b.alloc<double>((planar.size() + 2 * n) * sizeof(double));
+    double *d_xyz = b.alloc<double>((T + 1) * 3 * n * sizeof(double)), *d_vmm = b.alloc<double>(2 * n * sizeof(double));
+    uint8_t *d_fl = b.alloc<uint8_t>(n);
+    b.up(d_in, planar.data(), planar.size() * sizeof(double));
+    b.up(d_in + planar.size(), alt0, n * sizeof(double));
+    b.up(d_in + planar.size() + n, speed0, n * sizeof(double));
+    EmgpuTrackRun A{};
+    A.n = p->n; A.T = p->T;
+    A.ur_speed = p->ur_speed; A.ur_vertrate = p->ur_vertrate; A.ur_heading = p->ur_heading;
+    A.min_speed = p->min_speed; A.max_speed = p->max_speed;
+    A.upd = d_in; A.alt0_d = d_in + planar.size(); A.speed0_d = d_in + planar.size() + n;
+    A.xyz = d_xyz; A.flags = d_fl; A.vmm = d_vmm;
+    const char *name = "";
+    const hipError_t e = emgpu::launch_sample2track(A, false, ctx->stream, &name);
+    ctx->last_kernel = name;
+    launch_ok(e);
+    if (xyz) { hx.resize((T + 1) * 3 * n); b.down(hx.data(), d_xyz, hx.size() * sizeof(double)); }
+    b.down(flags, d_fl, n);
+    if (speed_minmax) { hv.resize(2 * n); b.down(hv.data(), d_vmm, hv.size() * sizeof(double)); }
+    const int rc = emgpu_ctx_sync(ctx);
+    if (rc == EMGPU_OK && xyz)
+        for (size_t i = 0; i < n; i++)
+            for (size_t t = 0; t <= T; t++)
+                for (size_t c = 0; c < 3; c++) xyz[(i * (T + 1) + t) * 3 + c] = hx[(t * 3 + c) * n + i];
+    if (rc == EMGPU_OK && speed_minmax)
+        for (size_t i = 0; i < n; i++) { speed_minmax[2 * i] = hv[i]; speed_minmax[2 * i + 1] = hv[n + i]; }
     return rc;
     EMGPU_CATCH
 }
@@ -1433,73 +1383,59 @@ static int track_uncor_rounds(emgpu_ctx *ctx, const emgpu_model *h, const emgpu_
     if (n == 0) return EMGPU_OK;
     size_t slot = 0;
     auto dalloc = [&](size_t bytes) { return ctx_scratch(ctx, slot++, bytes ? bytes : 1); };   // kept by the ctx between calls
-    int rc = EMGPU_OK;
-    try {
-        float *d_iv = (float *)dalloc(ni * n * 4), *d_dv = (float *)dalloc(G4 * nd * n * 16);
-        double *d_lim = (double *)dalloc(L.table.size() * 8);
-        uint8_t *d_acc = (uint8_t *)dalloc(n);
-        uint64_t *d_gidx[2] = {(uint64_t *)dalloc(n * 8), (uint64_t *)dalloc(n * 8)};
-        int64_t *d_slot[2] = {(int64_t *)dalloc(n * 8), (int64_t *)dalloc(n * 8)};
-        uint32_t *d_count = (uint32_t *)dalloc(4 * emgpu::compact_scratch_words((int64_t)n));
-        HIP_OK(hipMemcpyAsync(d_lim, L.table.data(), L.table.size() * 8, hipMemcpyHostToDevice, ctx->stream));
-        HIP_OK(hipStreamSynchronize(ctx->stream)); // L.table is a local
-        Uploaded &u = get_uploaded(ctx, h);
-        EmgpuUTrackRun R;
-        memset(&R, 0, sizeof R);
-        R.T = (int32_t)T; R.stride = p->record_stride; R.nd = (int32_t)nd; R.sDV = sDV; R.sDH = sDH; R.sDPsi = sDPsi;
-        {   // UncorEncounterModel.m:397-414
-            const std::vector<double> &bL = m.boundaries[p->idx_L - 1], &bV = m.boundaries[p->idx_v - 1], &bDH = m.boundaries[p->idx_dh - 1];
-            R.min_alt = bL.empty() ? 0.0 : *std::min_element(bL.begin(), bL.end());
-            R.max_alt = bL.empty() ? INFINITY : *std::max_element(bL.begin(), bL.end());
-            R.dyn[0] = 1.7; R.dyn[1] = *std::max_element(bV.begin(), bV.end()) * 1.68780972222222;
-            R.dyn[2] = *std::min_element(bDH.begin(), bDH.end()) / 60.0; R.dyn[3] = *std::max_element(bDH.begin(), bDH.end()) / 60.0;
-            R.dyn[4] = 3.0 * (3.14159265358979323846 / 180.0); R.dyn[5] = 1000000.0;
-        }
-        R.ordered = L.ordered; R.rG = L.rG; R.rA = L.rA; R.rL = L.rL; R.rV = L.rV; R.ncL = L.ncL; R.ncV = L.ncV; R.discL = L.discL; R.discV = L.discV;
-        memcpy(R.cutL, L.cutL, sizeof R.cutL); memcpy(R.cutV, L.cutV, sizeof R.cutV);
-        R.lim = d_lim; R.tracks = d_tracks; R.S = (int64_t)(10 * T / (size_t)p->record_stride + 1); R.limits = d_limits;
-        R.accepted = d_acc; R.attempts = d_attempts;
-        size_t count = n;
-        for (int j = 0; j < p->max_track_attempts && count > 0; j++) {
-            const int cur = j & 1;
-            emgpu_sample_params sp;
-            memset(&sp, 0, sizeof sp);
-            sp.seed = p->seed + (uint64_t)j;                                  // :428  seed = seed + 1
-            sp.first_index = p->first_index; sp.n = (int64_t)count; sp.sample_time = p->sample_time;
-            sp.flags = p->flags & EMGPU_FLAG_QUANTIZE500; sp.max_attempts = p->max_attempts;
-            sp.idx_L = p->idx_L; sp.idx_v = p->idx_v; sp.idx_dh = p->idx_dh;
-            sp.indices = j ? d_gidx[cur] : nullptr;
-            EmgpuRun A;
-            fill_run(ctx, u, m, &sp, A);
-            A.init_val = d_iv; A.dyn_val = d_dv; A.ld = (int64_t)count;
-            launch_dbn(ctx, u, A);                                            // :424  self.sample(1, sample_time, 'seed', seed)
-            const std::string sampler = ctx->last_kernel;
-            R.n = (int64_t)count; R.ld = (int64_t)count;
-            auto row = [&](int idx) -> const float * { return idx > 0 ? d_iv + (size_t)(idx - 1) * count : nullptr; };
-            R.iG = row(p->idx_G); R.iA = row(p->idx_A); R.iL = row(p->idx_L); R.iV = row(p->idx_v);
-            R.iDV = row(p->idx_dv); R.iDH = row(p->idx_dh); R.iDPsi = row(p->idx_dpsi);
-            R.dyn_val = d_dv; R.slot = j ? d_slot[cur] : nullptr;
-            R.attempt_no = j + 1; R.last_round = (j + 1 == p->max_track_attempts);
-            const char *name = "";
-            hipError_t e = emgpu::launch_uncor_track(R, ctx->stream, &name);
-            if (e != hipSuccess) throw Error(EMGPU_ERR_HIP, std::string("kernel launch: ") + hipGetErrorString(e));
-            ctx->last_kernel = sampler + " + " + name;
-            HIP_OK(hipMemsetAsync(d_count, 0, 4, ctx->stream));
-            e = emgpu::launch_compact_rejected((int64_t)count, p->first_index, d_acc, j ? d_gidx[cur] : nullptr, j ? d_slot[cur] : nullptr,
-                                               d_gidx[cur ^ 1], d_slot[cur ^ 1], d_count, ctx->stream);
-            if (e != hipSuccess) throw Error(EMGPU_ERR_HIP, std::string("kernel launch: ") + hipGetErrorString(e));
-            uint32_t hc = 0;
-            HIP_OK(hipMemcpyAsync(&hc, d_count, 4, hipMemcpyDeviceToHost, ctx->stream));
-            HIP_OK(hipStreamSynchronize(ctx->stream));
-            count = hc;
-        }
-        rc = emgpu_ctx_sync(ctx);   // the sampler's own rejection cap
-        if (rc == EMGPU_OK && count > 0) rc = fail(EMGPU_ERR_REJECT_CAP, "track: " + std::to_string(count) + " trajectories were still rejected after max_track_attempts");
-    } catch (...) {
-        (void)hipStreamSynchronize(ctx->stream);
-        throw;
+    const StreamSyncOnExit drain{ctx->stream};
+    float *d_iv = (float *)dalloc(ni * n * 4), *d_dv = (float *)dalloc(G4 * nd * n * 16);
+    double *d_lim = (double *)dalloc(L.table.size() * 8);
+    uint8_t *d_acc = (uint8_t *)dalloc(n);
+    uint64_t *d_gidx[2] = {(uint64_t *)dalloc(n * 8), (uint64_t *)dalloc(n * 8)};
+    int64_t *d_slot[2] = {(int64_t *)dalloc(n * 8), (int64_t *)dalloc(n * 8)};
+    uint32_t *d_count = (uint32_t *)dalloc(4 * emgpu::compact_scratch_words((int64_t)n));
+    HIP_OK(hipMemcpyAsync(d_lim, L.table.data(), L.table.size() * 8, hipMemcpyHostToDevice, ctx->stream));
+    HIP_OK(hipStreamSynchronize(ctx->stream)); // L.table is a local
+    Uploaded &u = get_uploaded(ctx, h);
+    EmgpuUTrackRun R;
+    memset(&R, 0, sizeof R);
+    R.T = (int32_t)T; R.stride = p->record_stride; R.nd = (int32_t)nd; R.sDV = sDV; R.sDH = sDH; R.sDPsi = sDPsi;
+    {   // UncorEncounterModel.m:397-414
+        const std::vector<double> &bL = m.boundaries[p->idx_L - 1], &bV = m.boundaries[p->idx_v - 1], &bDH = m.boundaries[p->idx_dh - 1];
+        R.min_alt = bL.empty() ? 0.0 : *std::min_element(bL.begin(), bL.end());
+        R.max_alt = bL.empty() ? INFINITY : *std::max_element(bL.begin(), bL.end());
+        R.dyn[0] = 1.7; R.dyn[1] = *std::max_element(bV.begin(), bV.end()) * 1.68780972222222;
+        R.dyn[2] = *std::min_element(bDH.begin(), bDH.end()) / 60.0; R.dyn[3] = *std::max_element(bDH.begin(), bDH.end()) / 60.0;
+        R.dyn[4] = 3.0 * (3.14159265358979323846 / 180.0); R.dyn[5] = 1000000.0;
     }
-    (void)hipStreamSynchronize(ctx->stream);
+    R.ordered = L.ordered; R.rG = L.rG; R.rA = L.rA; R.rL = L.rL; R.rV = L.rV; R.ncL = L.ncL; R.ncV = L.ncV; R.discL = L.discL; R.discV = L.discV;
+    memcpy(R.cutL, L.cutL, sizeof R.cutL); memcpy(R.cutV, L.cutV, sizeof R.cutV);
+    R.lim = d_lim; R.tracks = d_tracks; R.S = (int64_t)(10 * T / (size_t)p->record_stride + 1); R.limits = d_limits;
+    R.accepted = d_acc; R.attempts = d_attempts;
+    size_t count = n;
+    for (int j = 0; j < p->max_track_attempts && count > 0; j++) {
+        const int cur = j & 1;
+        emgpu_sample_params sp;
+        memset(&sp, 0, sizeof sp);
+        sp.seed = p->seed + (uint64_t)j;                                  // :428  seed = seed + 1
+        sp.first_index = p->first_index; sp.n = (int64_t)count; sp.sample_time = p->sample_time;
+        sp.flags = p->flags & EMGPU_FLAG_QUANTIZE500; sp.max_attempts = p->max_attempts;
+        sp.idx_L = p->idx_L; sp.idx_v = p->idx_v; sp.idx_dh = p->idx_dh;
+        sp.indices = j ? d_gidx[cur] : nullptr;
+        EmgpuRun A;
+        fill_run(ctx, u, m, &sp, A);
+        A.init_val = d_iv; A.dyn_val = d_dv; A.ld = (int64_t)count;
+        launch_dbn(ctx, u, A);                                            // :424  self.sample(1, sample_time, 'seed', seed)
+        const std::string sampler = ctx->last_kernel;
+        R.n = (int64_t)count; R.ld = (int64_t)count;
+        auto row = [&](int idx) -> const float * { return idx > 0 ? d_iv + (size_t)(idx - 1) * count : nullptr; };
+        R.iG = row(p->idx_G); R.iA = row(p->idx_A); R.iL = row(p->idx_L); R.iV = row(p->idx_v);
+        R.iDV = row(p->idx_dv); R.iDH = row(p->idx_dh); R.iDPsi = row(p->idx_dpsi);
+        R.dyn_val = d_dv; R.slot = j ? d_slot[cur] : nullptr;
+        R.attempt_no = j + 1; R.last_round = (j + 1 == p->max_track_attempts);
+        const char *name = "";
+        launch_ok(emgpu::launch_uncor_track(R, ctx->stream, &name));
+        ctx->last_kernel = sampler + " + " + name;
+        count = compact_rejected(ctx, j, count, p->first_index, d_acc, d_gidx, d_slot, d_count);
+    }
+    int rc = emgpu_ctx_sync(ctx);   // the sampler's own rejection cap
+    if (rc == EMGPU_OK && count > 0) rc = fail(EMGPU_ERR_REJECT_CAP, "track: " + std::to_string(count) + " trajectories were still rejected after max_track_attempts");
     return rc;
 }
 
@@ -1520,27 +1456,19 @@ int emgpu_track_uncor_host(emgpu_ctx *ctx, const emgpu_model *h, const emgpu_utr
     const size_t n = (size_t)(p->n > 0 ? p->n : 0);
     if (p->record_stride < 1 || p->sample_time < 1) return fail(EMGPU_ERR_ARG, "bad record_stride / sample_time");
     const size_t S = (size_t)(10 * p->sample_time / p->record_stride + 1);
-    double *dt = nullptr, *dl = nullptr; int32_t *da = nullptr;
-    int rc;
-    try {
-        if (tracks) HIP_OK(hipMalloc((void **)&dt, n * S * 8 * sizeof(double) + 8));
-        if (limits) HIP_OK(hipMalloc((void **)&dl, n * 3 * sizeof(double) + 8));
-        HIP_OK(hipMalloc((void **)&da, n * 4 + 4));
-        rc = track_uncor_rounds(ctx, h, p, dt, dl, da);
-        if (rc == EMGPU_OK || rc == EMGPU_ERR_REJECT_CAP) {
-            const std::string msg = g_err;
-            if (tracks && n) HIP_OK(hipMemcpyAsync(tracks, dt, n * S * 8 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-            if (limits && n) HIP_OK(hipMemcpyAsync(limits, dl, n * 3 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-            if (attempts && n) HIP_OK(hipMemcpyAsync(attempts, da, n * 4, hipMemcpyDeviceToHost, ctx->stream));
-            HIP_OK(hipStreamSynchronize(ctx->stream));
-            if (rc != EMGPU_OK) g_err = msg;
-        }
-    } catch (...) {
-        (void)hipStreamSynchronize(ctx->stream);
-        (void)hipFree(dt); (void)hipFree(dl); (void)hipFree(da);
-        throw;
+    CallBuffers b(ctx);
+    double *dt = tracks ? b.alloc<double>(n * S * 8 * sizeof(double) + 8) : nullptr;
+    double *dl = limits ? b.alloc<double>(n * 3 * sizeof(double) + 8) : nullptr;
+    int32_t *da = b.alloc<int32_t>(n * 4 + 4);
+    const int rc = track_uncor_rounds(ctx, h, p, dt, dl, da);
+    if (rc == EMGPU_OK || rc == EMGPU_ERR_REJECT_CAP) {
+        const std::string msg = g_err;
+        b.down(tracks, dt, n * S * 8 * sizeof(double));
+        b.down(limits, dl, n * 3 * sizeof(double));
+        b.down(attempts, da, n * 4);
+        HIP_OK(hipStreamSynchronize(ctx->stream));
+        if (rc != EMGPU_OK) g_err = msg;
     }
-    (void)hipFree(dt); (void)hipFree(dl); (void)hipFree(da);
     return rc;
     EMGPU_CATCH
 }

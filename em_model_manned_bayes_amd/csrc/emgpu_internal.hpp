@@ -43,6 +43,11 @@ using emgpu_detail::fail;
         if (_e != hipSuccess) throw Error(EMGPU_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(_e)); \
     } while (0)
 
+// the status a launcher returned (EMGPU_CATCH turns the throw into fail(EMGPU_ERR_HIP, "kernel launch: ..."))
+inline void launch_ok(hipError_t e) {
+    if (e != hipSuccess) throw Error(EMGPU_ERR_HIP, std::string("kernel launch: ") + hipGetErrorString(e));
+}
+
 struct Uploaded {
     uint64_t version = 0;
     uint64_t last_use = 0;
@@ -112,4 +117,32 @@ void *ctx_scratch(emgpu_ctx *ctx, size_t slot, size_t bytes);   // slot-th scrat
 void ctx_release_host_side(emgpu_ctx *ctx, bool everything);    // trim (false: pools and staging) / free (true: streams and events too)
 
 #define CTX_LOCK(ctx) std::lock_guard<std::recursive_mutex> _ctx_lock((ctx)->mu)
+
+// The device buffers of one host-pointer call: fresh per call, freed when the call returns or throws, after the ctx stream has drained.
+// up / down copy on the ctx stream and do nothing for zero bytes or a null host pointer.
+class CallBuffers {
+  public:
+    explicit CallBuffers(emgpu_ctx *ctx) : ctx_(ctx) {}
+    CallBuffers(const CallBuffers &) = delete;
+    CallBuffers &operator=(const CallBuffers &) = delete;
+    ~CallBuffers() {
+        (void)hipStreamSynchronize(ctx_->stream);
+        for (void *p : ptrs_) (void)hipFree(p);
+    }
+    template <typename T> T *alloc(size_t bytes) {
+        ptrs_.push_back(nullptr);   // (the slot first: nothing can throw between the hipMalloc and the record)
+        HIP_OK(hipMalloc(&ptrs_.back(), bytes));
+        return static_cast<T *>(ptrs_.back());
+    }
+    void up(void *dst, const void *src, size_t bytes) {
+        if (bytes && src) HIP_OK(hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, ctx_->stream));
+    }
+    void down(void *dst, const void *src, size_t bytes) {
+        if (bytes && dst) HIP_OK(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, ctx_->stream));
+    }
+
+  private:
+    emgpu_ctx *ctx_;
+    std::vector<void *> ptrs_;
+};
 

@@ -1,5 +1,5 @@
 #!/bin/bash
-# tools/profile_others.sh TAG -- rocprofv3 kernel trace + stats of the non-headline workloads (one GPU), every pass bounded by `timeout`:
+# tools/profile_others.sh TAG -- rocprofv3 kernel trace + stats of the non-headline workloads (one GPU), every pass bounded by `timeout`, the first that fails ending the script:
 # the v1.2 family on k_uncor_fast<7,4,6,6>, the mixed batch in one launch, the per-timestep kernel on cor_v1 / cor_v2p1_like / glider_v1 /
 # uncor_1200code_v1 / PER_STEP / littoral_cor_v1 (frozen columns), the event-list kernels, the sample2track consumer, the
 # UncorEncounterModel.track pipeline and terminal propagation.  tools/summarize_others.py condenses the stats.
@@ -10,7 +10,8 @@ OUT=gpurun_out/others_$TAG
 rm -rf $OUT; mkdir -p $OUT
 run() { # name, program args...
   local name=$1; shift
-  timeout 240 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/$name -- python3 "$@" > $OUT/$name.log 2>&1
+  timeout 240 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/$name -- python3 "$@" > $OUT/$name.log 2>&1 ||
+    { local rc=$?; echo "profile_others.sh: $name failed with status $rc (see $OUT/$name.log)" >&2; exit $rc; }
 }
 B="--steps 5 --warmup 2 --no-cpu-baseline --no-other-configs --no-host-path"
 run v1p2 bench.py $B --model uncor_1200only_fwse_v1p2

@@ -4,6 +4,7 @@
 # (tools/profile_others.sh).  Condense with: for t in TAG TAG_per_step TAG_cor TAG_cor_v2p1_like TAG_mixed TAG_terminal; do python tools/summarize_profiles.py $t; done;
 # python tools/summarize_others.py TAG
 TAG=${1:-r04}
+set -e   # the first call that fails ends the round
 cd "$GRAFT_REPO_ROOT"
 bash tools/profile_bench.sh $TAG
 bash tools/profile_bench.sh ${TAG}_per_step --config uncor_per_step
