@@ -604,6 +604,15 @@ def track_uncor_host(ctx, model, n, sample_time, seed, want_tracks=True, **kw):
     return {"tracks": tracks, "limits": limits, "attempts": attempts, "kernel": ctx.last_kernel()}
 
 
+def track_uncor_device(ctx, model, n, sample_time, seed, tracks=0, limits=0, attempts=0, **kw):
+    """emgpu_track_uncor_device: track_uncor_host into the caller's device buffers (raw pointers, ints, 0 = skip): tracks [n, S, 8] f64,
+    limits [n, 3] f64, attempts [n] i32, in the layouts of track_uncor_host.  Returns the kernel names."""
+    p = utrack_params(model, n, sample_time, seed, **kw)
+    L.check(L.lib().emgpu_track_uncor_device(ctx._h, model._h, C.byref(p), C.c_void_p(tracks or None), C.c_void_p(limits or None),
+                                             C.c_void_p(attempts or None)))
+    return ctx.last_kernel()
+
+
 def uncor_dynamic_limits(model, initial, up_min, up_max, speed_min, speed_max, is_rotorcraft=False):
     """emgpu_uncor_dynamic_limits: getDynamicLimits.m for one trajectory (host only, no GPU needed)."""
     p = utrack_params(model, 1, 1, 0, is_rotorcraft=is_rotorcraft)
@@ -648,9 +657,11 @@ def sample_terminal_device(ctx, geom_model, traj_models, p, geom_val, geo, model
 
 def track_terminal_host(ctx, geom_model, traj_models, n, seed, dyn_limits, max_cum_turn_deg, pitch_deg, first_index=0, tmax_s=120.0,
                         min_enc_time_s=30.0, thres_dist_ft=2.5 * 6076, thres_alt_low_ft=750.0, thres_vertrate_ft_s=300.0 / 60.0,
-                        bounds_sample=None, max_track_attempts=500, max_attempts=100000, max_resample=100000, allow_cap=False, local_smooth=True):
+                        bounds_sample=None, max_track_attempts=500, max_attempts=100000, max_resample=100000, allow_cap=False, local_smooth=True,
+                        want_traj=True):
     """emgpu_track_terminal_host: CorTerminalModel.track (track.m:45-150) on the GPU.  Returns dict: sample [n, n_i], traj [n, 2, cap2, 6]
     (t_s x_nm y_nm z_ft heading_deg v_ft_s, time-ordered), len [n, 2], meta [n, 4] (tcpa_s hmd_ft vmd_ft enc_time_s), attempts [n].
+    want_traj=False: traj is None and the library gets no track buffer (it is 2 * cap2 * 48 bytes per encounter).
     local_smooth -- ONE rule for every Python layer: a function smooths by default exactly when the reference function it mirrors does.
     track.m calls createEncounter, whose lines 88-89 smooth speed and altitude, so this helper, CorTerminalModel.track and
     CorTerminalModel.createEncounter default to True; PropagateTrajectory (createEncounter.m:93-265) does not smooth, so
@@ -674,7 +685,7 @@ def track_terminal_host(ctx, geom_model, traj_models, n, seed, dyn_limits, max_c
         for k, f in enumerate(TERMINAL_GEO_FIELDS):
             p.idx[6 * a + k] = labels.index(pre + "_" + f) + 1
     ni, cap2 = geom_model.n_initial, 2 * (int(tmax_s) + 3)
-    sample = np.zeros((n, ni)); traj = np.zeros((n, 2, cap2, 6)); ln = np.zeros((n, 2), dtype=np.int32)
+    sample = np.zeros((n, ni)); traj = np.zeros((n, 2, cap2, 6)) if want_traj else None; ln = np.zeros((n, 2), dtype=np.int32)
     meta = np.zeros((n, 4)); att = np.zeros(n, dtype=np.int32)
     if len(traj_models) != 10:
         raise ValueError("traj_models: the 10 trajectory models in CorTerminalModel.m:84-100 order")
