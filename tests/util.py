@@ -169,3 +169,132 @@ def assert_f32_of_f64(got, ref, what="", abs_floor=1e-9):
         raise AssertionError("%s: %d of %d values more than one f32 step from the oracle, first at %s: %r vs %r"
                              % (what, int(bad.sum()), bad.size, tuple(k), got[tuple(k)], ref[tuple(k)]))
     return int(d.max()) if d.size else 0
+
+
+def shaped_model(rs, ni, meff=(2, 2, 2), dependent=False, parents=None, rates=None, r=None):
+    """A model in the em_read dict layout whose compiled plan is prescribed (the dispatch tests reach each kernel instance with one).
+    meff: distinct real thresholds of every transition column of each dynamic variable (its length is the number of dynamic
+    variables, initial variables 0 .. nd - 1): every column has exactly meff[k] + 1 nonzero bins, so EmgpuPlan::d_meff[k] = meff[k]
+    and d_pw[k] = 4 (meff <= 3), 8 (<= 6) or 0 (7).
+    parents: (cur, new) parent masks as emgpu_debug_parent_masks reports them, bit 4 k + q = dynamic variable k has the current
+    (cur) / new (new) value of dynamic variable q as a transition parent (new parents must come earlier: q < k).  Default: each
+    variable its own current value, plus the chain k <- k - 1 of new values when dependent.
+    rates: resample rate per initial variable (default: 0.02 - 0.15 on the dynamic variables, 0 elsewhere).
+    r: bins per initial variable (default: meff[k] + 1 .. meff[k] + 3 for the dynamic ones, at most 9; 2 .. 5 for the others).
+    Dynamic variables are continuous (boundaries r + 1); the transition table of dynamic variable k also has static variable
+    nd + k mod min(ni - nd, 4) as a parent.
+    Every table, boundary set and default draws from a stream of its own (one seed taken from rs, then the part and the variable):
+    two calls that differ in one argument differ only in what that argument reaches -- one more variable, one variable's bins or
+    meff, the rates -- which is what an eligibility-edge pair needs."""
+    meff = tuple(int(m) for m in meff)
+    nd = len(meff)
+    assert 1 <= nd <= 4 and nd <= ni
+    base = int(rs.randint(2**31))
+
+    def stream(part, v):
+        return np.random.RandomState([base, part, v])
+
+    if parents is None:
+        cur = sum(1 << (5 * k) for k in range(nd))
+        new = sum(1 << (4 * k + k - 1) for k in range(1, nd)) if dependent else 0
+    else:
+        cur, new = parents
+    if r is None:
+        r = [min(meff[v] + 1 + stream(1, v).randint(0, 3), 9) if v < nd else stream(1, v).randint(2, 6) for v in range(ni)]
+    r = np.array(r, dtype=np.int64)
+    for k in range(nd):
+        assert meff[k] + 1 <= r[k]
+    nt = ni + nd
+    rt = np.concatenate([r, r[:nd]])
+    Gi = np.zeros((ni, ni), dtype=np.uint8)
+    for v in range(1, ni):
+        p = stream(2, v).randint(v)
+        if r[p] * r[v] <= 200:
+            Gi[p, v] = 1
+    Gt = np.zeros((nt, nt), dtype=np.uint8)
+    for k in range(nd):
+        for q in range(nd):
+            if cur >> (4 * k + q) & 1:
+                Gt[q, ni + k] = 1
+            if new >> (4 * k + q) & 1:
+                assert q < k, "a new-value parent must be an earlier dynamic variable"
+                Gt[ni + q, ni + k] = 1
+        if ni > nd:
+            Gt[nd + k % min(ni - nd, 4), ni + k] = 1
+
+    def counts(s, rv, q, m=None):
+        N = s.randint(1, 2000, (rv, q)).astype(np.float64)
+        if m is None:
+            N *= s.rand(rv, q) < 0.7
+            return N
+        for j in range(q):             # exactly m + 1 nonzero bins: m distinct thresholds strictly between "always" and "never"
+            keep = np.zeros(rv, dtype=bool)
+            keep[s.choice(rv, m + 1, replace=False)] = True
+            N[~keep, j] = 0
+        return N
+
+    N_initial = [counts(stream(3, v), r[v], int(np.prod(r[Gi[:, v] > 0]))) for v in range(ni)]
+    N_transition = [np.zeros((0, 0))] * ni + [counts(stream(4, k), rt[ni + k], int(np.prod(rt[Gt[:, ni + k] > 0])), meff[k]) for k in range(nd)]
+    boundaries = []
+    for v in range(ni):
+        s = stream(5, v)
+        if v >= nd and s.rand() < 0.4:
+            boundaries.append(np.zeros(0))
+            continue
+        lo = -s.uniform(1, 50) if s.rand() < 0.5 else s.uniform(0, 100)
+        boundaries.append(np.round(np.linspace(lo, lo + s.uniform(5, 400), r[v] + 1), 3))
+    if rates is None:
+        rates = [np.round(stream(6, v).uniform(0.02, 0.15), 6) if v < nd else 0.0 for v in range(ni)]
+    rates = np.asarray(rates, dtype=np.float64)
+    assert rates.shape == (ni,)
+    return {"n_initial": ni, "n_transition": nt, "labels_initial": ['"v%d"' % (v + 1) for v in range(ni)],
+            "labels_transition": ['"v%d(t)"' % (v + 1) if v < nd else '"v%d"' % (v + 1) for v in range(ni)] + ['"v%d(t+1)"' % (k + 1) for k in range(nd)],
+            "G_initial": Gi, "G_transition": Gt, "r_initial": r, "r_transition": rt, "N_initial": N_initial,
+            "N_transition": N_transition, "boundaries": boundaries, "resample_rates": rates}
+
+
+def plan_facts(nm):
+    """What the plan compiler made of a native model, over EVERY transition column (the host-only debug hooks): per dynamic variable
+    the distinct real thresholds of each column (min and max over the columns), d_meff, the padded width; the parent masks."""
+    import ctypes as C
+    lib = L.lib()
+    cm, nw = C.c_uint32(), C.c_uint32()
+    L.check(lib.emgpu_debug_parent_masks(nm._h, C.byref(cm), C.byref(nw)))
+    out = {"cur": cm.value, "new": nw.value, "meff": [], "col_meff": [], "width": [], "r": []}
+    for k in range(nm.n_dyn):
+        tvar, r, q, meff, mp = C.c_int32(), C.c_int32(), C.c_int64(), C.c_int32(), C.c_uint32()
+        thr = np.zeros(15, dtype=np.uint32)
+        cthr = np.zeros(7, dtype=np.uint32)
+        width, pw = C.c_int32(), np.zeros(8, dtype=np.uint32)
+        lo, hi = 99, -1
+        col, ncol = 0, 1
+        while col < ncol:
+            L.check(lib.emgpu_debug_dynamic_column(nm._h, k, col, C.byref(tvar), C.byref(r), C.byref(q), thr.ctypes.data, C.byref(meff),
+                                                   cthr.ctypes.data, C.byref(mp)))
+            L.check(lib.emgpu_debug_padded_column(nm._h, k, col, C.byref(width), pw.ctypes.data))
+            d = len(set(int(x) for x in thr[: r.value - 1] if 0 < x < 0xFFFFFFFF))
+            lo, hi = min(lo, d), max(hi, d)
+            ncol = q.value
+            col += 1
+        out["meff"].append(meff.value)
+        out["col_meff"].append((lo, hi))
+        out["width"].append(width.value)
+        out["r"].append(r.value)
+    return out
+
+
+def load_row_model(spec, model_dir):
+    """(native model, oracle parms dict, path) of an instances.py model: a shipped model's name, or util.shaped_model arguments
+    (+ "seed"), written once per session under model_dir."""
+    if isinstance(spec, str):
+        return load_pair(spec, model_dir)
+    key = ("shaped",) + tuple(sorted((k, repr(v)) for k, v in spec.items()))
+    if key not in _cache:
+        import hashlib
+        import os
+        kw = dict(spec)
+        rs = np.random.RandomState(kw.pop("seed"))
+        path = os.path.join(model_dir, "shaped_%s.txt" % hashlib.sha1(repr(key).encode()).hexdigest()[:16])
+        em_io.em_write(shaped_model(rs, **kw), path)
+        _cache[key] = (native.NativeModel.load_txt(path), O.parse_model_txt(path), path)
+    return _cache[key]
