@@ -122,6 +122,12 @@ class HostStats(C.Structure):     # emgpu_host_stats_t
 TRACE_INIT, TRACE_DENSE, TRACE_EVENTS, TRACE_ATTEMPTS = 1, 2, 4, 8
 
 
+class UncorOut(C.Structure):      # emgpu_uncor_out
+    _fields_ = [("inits", C.c_void_p), ("ev_count", C.c_void_p), ("events", C.c_void_p), ("events_cap", C.c_int64),
+                ("ctrl_count", C.c_void_p), ("controls", C.c_void_p), ("controls_cap", C.c_int64), ("samples", C.c_void_p),
+                ("attempts", C.c_void_p), ("totals", C.c_void_p), ("ctrl_var", C.c_int32 * 3), ("_pad", C.c_int32)]
+
+
 class BnParams(C.Structure):
     _fields_ = [("seed", C.c_uint64), ("first_index", C.c_uint64), ("n", C.c_int64), ("flags", C.c_uint32),
                 ("max_attempts", C.c_int32), ("bounds_sample", C.c_void_p),
@@ -146,7 +152,7 @@ SYMBOLS = [
     "emgpu_track_uncor_host", "emgpu_track_uncor_device", "emgpu_uncor_dynamic_limits", "emgpu_model_start_log_weight",
     "emgpu_track_terminal_host", "emgpu_debug_parent_masks", "emgpu_last_launch_count", "emgpu_debug_pk_column", "emgpu_debug_terminal_counters", "emgpu_debug_uncor_dynamics_host", "emgpu_model_save_bin", "emgpu_model_load_bin", "emgpu_philox_rounds", "emgpu_ctx_trim",
     "emgpu_slot_map_revision", "emgpu_trace_alloc", "emgpu_trace_out", "emgpu_trace_report", "emgpu_trace_free", "emgpu_host_alloc", "emgpu_host_free", "emgpu_host_stats",
-    "emgpu_device_alloc", "emgpu_device_free",
+    "emgpu_device_alloc", "emgpu_device_free", "emgpu_sample_uncor_host",
 ]
 
 _lib = None
@@ -275,6 +281,7 @@ def lib():
     L.emgpu_ctx_free.restype = None
     L.emgpu_sample_dbn_device.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(SampleParams), C.POINTER(SampleOut)]
     L.emgpu_sample_dbn_host.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(SampleParams), C.POINTER(SampleOut)]
+    L.emgpu_sample_uncor_host.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(SampleParams), C.POINTER(UncorOut)]
     L.emgpu_sample_bn_device.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(BnParams), C.c_void_p, C.c_void_p, C.c_void_p]
     L.emgpu_sample_bn_host.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(BnParams), C.c_void_p, C.c_void_p, C.c_void_p]
     L.emgpu_discretize_bayes.argtypes = [C.c_double, C.c_void_p, C.c_int32]

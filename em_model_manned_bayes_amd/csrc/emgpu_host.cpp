@@ -4,6 +4,7 @@
 //     and another in 7.1 ms);
 //   * the pinned pool: emgpu_host_alloc / _free;
 //   * emgpu_sample_dbn_host as a pipeline: chunk k's kernel | chunk k-1's copy over PCIe | chunk k-2's copy into the caller's arrays.
+//   * emgpu_sample_uncor_host: the same pipeline, with UncorEncounterModel.sample's samples and controls built on the device.
 // Reference semantics: the loop over samples of UncorEncounterModel.m:244-300 and the host arrays it returns (:283-300).
 #include <algorithm>
 #include <chrono>
@@ -549,7 +550,7 @@ int emgpu_sample_dbn_host(emgpu_ctx *ctx, const emgpu_model *h, const emgpu_samp
     }
     if (nchunks > 1 && !ctx->h_stage[1]) HIP_OK(hipHostMalloc(&ctx->h_stage[1], ctx->h_stage_cap, hipHostMallocDefault));
     if (!ctx->copy_stream) HIP_OK(hipStreamCreateWithFlags(&ctx->copy_stream, hipStreamNonBlocking));
-    if (!ctx->h_total) HIP_OK(hipHostMalloc((void **)&ctx->h_total, 2 * sizeof(uint64_t), hipHostMallocDefault));
+    if (!ctx->h_total) HIP_OK(hipHostMalloc((void **)&ctx->h_total, 4 * sizeof(uint64_t), hipHostMallocDefault));
 
     emgpu_sample_params pd = *p;
     if (p->start) {     // the start grid and the index list are caller (host) memory here: uploaded once, every chunk reads its rows
@@ -684,6 +685,203 @@ int emgpu_sample_dbn_host(emgpu_ctx *ctx, const emgpu_model *h, const emgpu_samp
     }
     st.total_ms = ms_since(t_call);
     ctx->host_stats = st;
+    return rc;
+    EMGPU_CATCH
+}
+
+// ================================================================================================ UncorEncounterModel.sample's outputs
+int emgpu_sample_uncor_host(emgpu_ctx *ctx, const emgpu_model *h, const emgpu_sample_params *p, const emgpu_uncor_out *out) {
+    EMGPU_TRY
+    if (!ctx || !h || !p || !out) return fail(EMGPU_ERR_ARG, "null argument");
+    if (!out->inits || !out->ev_count || !out->events || !out->ctrl_count || !out->controls || !out->totals)
+        return fail(EMGPU_ERR_ARG, "inits, ev_count, events, ctrl_count, controls and totals are required");
+    if (p->event_cap < 1) return fail(EMGPU_ERR_ARG, "event_cap must be >= 1");
+    if (out->events_cap < 0 || out->controls_cap < 0) return fail(EMGPU_ERR_ARG, "events_cap and controls_cap must be >= 0");
+    if (p->start || p->indices) return fail(EMGPU_ERR_ARG, "emgpu_sample_uncor_host: start grids and index lists are not supported");
+    if (p->n < 0 || p->sample_time < 1 || p->sample_time > 65535) return fail(EMGPU_ERR_ARG, "n < 0 or sample_time outside 1..65535");
+    const Model &m = h->m;
+    for (int k = 0; k < 3; k++)
+        if (out->ctrl_var[k] < 1 || out->ctrl_var[k] > m.n_initial) return fail(EMGPU_ERR_ARG, "ctrl_var: a variable id outside 1..n_initial");
+    CTX_LOCK(ctx);
+    HIP_OK(hipSetDevice(ctx->device));
+    const auto t_call = Clock::now();
+    const size_t n = (size_t)p->n, ni = (size_t)m.n_initial, T = (size_t)p->sample_time, cap = (size_t)p->event_cap;
+    out->totals[0] = out->totals[1] = 0;
+    emgpu_host_stats_t st{};
+    if (n == 0) {   // nothing to draw: the arguments are still checked like any call's
+        emgpu_sample_out d{};
+        const int rc0 = emgpu_sample_dbn_device(ctx, h, p, &d);
+        ctx->host_stats = st;
+        return rc0 == EMGPU_OK ? emgpu_ctx_sync(ctx) : rc0;
+    }
+
+    // ---- the caller's arrays: per trajectory (a chunk is one contiguous piece of each) and packed rows; each is written by the copy engine when
+    // it is pinned, else through the staging buffer and the host threads
+    struct Arr { char *dst; size_t elem; size_t dev_off = 0, stg_off = 0; bool staged = false; };
+    Arr a_cnt{(char *)out->ev_count, 4}, a_att{(char *)out->attempts, 4}, a_ccnt{(char *)out->ctrl_count, 4}, a_init{(char *)out->inits, 8 * ni},
+        a_smp{(char *)out->samples, 8 * ni * T}, a_ev{(char *)out->events, 8}, a_ctl{(char *)out->controls, 32};
+    std::vector<Arr *> per_traj = {&a_cnt, &a_ccnt, &a_init};
+    if (out->attempts) per_traj.push_back(&a_att);
+    if (out->samples) per_traj.push_back(&a_smp);
+    bool direct = true;
+    for (Arr *a : per_traj) { a->staged = !is_pinned(a->dst); direct = direct && !a->staged; }
+    for (Arr *a : {&a_ev, &a_ctl}) { a->staged = !is_pinned(a->dst); direct = direct && !a->staged; }
+
+    size_t bpt = 16 + 4 * ni + 8 * ni + (out->samples ? 8 * ni * T : 0) + 16 * cap + 32 * cap;   // device bytes per trajectory
+    size_t target = (size_t)(direct ? 1024 : 256) << 20;
+    if (const char *e = getenv("EMGPU_HOST_CHUNK_MB")) { const long v = atol(e); if (v > 0) target = (size_t)v << 20; }
+    size_t C = std::max<size_t>(1024, target / bpt / 1024 * 1024);
+    C = std::min(C, std::max<size_t>(1024, ((size_t)0xFFFF0000u / cap) / 1024 * 1024));   // a chunk's packed rows are counted in 32 bits
+    if (C >= n) C = n;
+    else {
+        const size_t k = (n + C - 1) / C;
+        C = std::min(C, round_up((n + k - 1) / k, 1024));
+    }
+    const size_t Cp = round_up(C, 256), nchunks = (n + C - 1) / C;
+    size_t o = 0;
+    auto put = [&](size_t bytes) { const size_t at = o; o = round_up(o + bytes, 256); return at; };
+    a_cnt.dev_off = put(Cp * 4); a_att.dev_off = put(Cp * 4); a_ccnt.dev_off = put(Cp * 4);
+    const size_t o_coff = put(Cp * 4), o_iv = put(ni * Cp * 4);
+    a_init.dev_off = put(Cp * a_init.elem);
+    if (out->samples) a_smp.dev_off = put(Cp * a_smp.elem);
+    const size_t o_ev = put(Cp * cap * 8);
+    a_ev.dev_off = put(Cp * cap * 8);
+    a_ctl.dev_off = put(Cp * cap * 32);
+    const size_t o_scr = put(emgpu::pack_scratch_words((int64_t)Cp) * 4), o_fscr = put(emgpu::pack_scratch_words((int64_t)Cp) * 4);
+    const size_t dev_bytes = std::max<size_t>(o, 256);
+    size_t so = 0;
+    for (Arr *a : per_traj) if (a->staged) { a->stg_off = so; so = round_up(so + C * a->elem, 256); }
+    for (Arr *a : {&a_ev, &a_ctl}) if (a->staged) { a->stg_off = so; so = round_up(so + C * cap * a->elem, 256); }
+    const size_t stage_bytes = std::max<size_t>(so, 256);
+
+    for (size_t q = 0; q < (nchunks == 1 ? 1u : 2u); q++) {   // the chunk buffers and staging of emgpu_sample_dbn_host
+        emgpu_ctx::TraceBlock &b = ctx->chunk_buf[q];
+        if (b.bytes >= dev_bytes) continue;
+        HIP_OK(hipStreamSynchronize(ctx->stream));
+        if (b.p) { device_release(b.p); b = emgpu_ctx::TraceBlock(); }
+        b = pool_take(ctx, dev_bytes + dev_bytes / 8, nullptr, /*plain=*/true);
+        if (!b.p) return fail(EMGPU_ERR_HIP, "emgpu_sample_uncor_host: out of device memory");
+    }
+    if (ctx->h_stage_cap < stage_bytes) {
+        const size_t want_cap = stage_bytes + stage_bytes / 8;
+        for (auto &s : ctx->h_stage) { if (s) HIP_OK(hipHostFree(s)); s = nullptr; }
+        ctx->h_stage_cap = 0;
+        for (size_t b = 0; b < (nchunks == 1 ? 1u : 2u); b++) HIP_OK(hipHostMalloc(&ctx->h_stage[b], want_cap, hipHostMallocDefault));
+        ctx->h_stage_cap = want_cap;
+    }
+    if (nchunks > 1 && !ctx->h_stage[1]) HIP_OK(hipHostMalloc(&ctx->h_stage[1], ctx->h_stage_cap, hipHostMallocDefault));
+    if (!ctx->copy_stream) HIP_OK(hipStreamCreateWithFlags(&ctx->copy_stream, hipStreamNonBlocking));
+    if (!ctx->h_total) HIP_OK(hipHostMalloc((void **)&ctx->h_total, 4 * sizeof(uint64_t), hipHostMallocDefault));
+
+    Events ev(8);   // per buffer b: 4b + {kernel start, kernel end, copy start, copy end}
+    const int TH = host_threads();
+    size_t rows[2][2] = {{0, 0}, {0, 0}}, base[2][2] = {{0, 0}, {0, 0}};   // per buffer: event / control rows of its chunk and their first row in the call
+    bool fits[2][2] = {{false, false}, {false, false}};
+    size_t total_ev = 0, total_ctl = 0;
+    st.chunks = (int32_t)nchunks; st.chunk_n = (int32_t)C; st.threads = TH; st.direct = direct ? 1 : 0;
+
+    auto launch_chunk = [&](size_t k) {
+        const int b = (int)(k & 1);
+        const size_t k0 = k * C, c = std::min(C, n - k0);
+        char *dev = (char *)ctx->chunk_buf[b].p;
+        emgpu_sample_params q = *p;
+        q.n = (int64_t)c;
+        q.first_index = p->first_index + (uint64_t)k0;
+        emgpu_sample_out d{};
+        d.ld = (int64_t)Cp;
+        d.init_val = (float *)(dev + o_iv);
+        d.ev_count = (uint32_t *)(dev + a_cnt.dev_off);
+        d.events = (emgpu_event *)(dev + o_ev);
+        if (out->attempts) d.attempts = (int32_t *)(dev + a_att.dev_off);
+        HIP_OK(hipEventRecord(ev[4 * b], ctx->stream));
+        const int r = emgpu_sample_dbn_device(ctx, h, &q, &d);
+        if (r != EMGPU_OK) throw Error(r, g_err);
+        launch_ok(emgpu::launch_pack_events((int64_t)c, (uint32_t)cap, d.ev_count, (const uint64_t *)(dev + o_ev), (uint32_t *)(dev + o_scr),
+                                            (uint64_t *)(dev + a_ev.dev_off), ctx->stream));
+        emgpu::EmgpuFormatRun F{};
+        F.n = (int64_t)c; F.cap = (uint32_t)cap; F.T = (int32_t)T; F.ni = (int32_t)ni; F.ld = (int64_t)Cp;
+        F.ev_count = d.ev_count; F.ev = (const uint64_t *)(dev + o_ev); F.init_val = d.init_val;
+        F.id_dh = out->ctrl_var[0]; F.id_dpsi = out->ctrl_var[1]; F.id_dv = out->ctrl_var[2];
+        F.ctrl_count = (uint32_t *)(dev + a_ccnt.dev_off); F.ctrl_off = (uint32_t *)(dev + o_coff); F.scratch = (uint32_t *)(dev + o_fscr);
+        F.inits = (double *)(dev + a_init.dev_off); F.samples = out->samples ? (double *)(dev + a_smp.dev_off) : nullptr;
+        F.controls = (double *)(dev + a_ctl.dev_off);
+        launch_ok(emgpu::launch_format_uncor(F, ctx->stream));
+        HIP_OK(hipMemcpyAsync(&ctx->h_total[2 * b], dev + o_scr, sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
+        HIP_OK(hipMemcpyAsync(&ctx->h_total[2 * b + 1], dev + o_fscr, sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
+        HIP_OK(hipEventRecord(ev[4 * b + 1], ctx->stream));
+        HIP_OK(hipEventSynchronize(ev[4 * b + 1]));   // how many rows cross PCIe is known only now
+        rows[b][0] = (size_t)ctx->h_total[2 * b]; rows[b][1] = (size_t)ctx->h_total[2 * b + 1];
+        base[b][0] = total_ev; base[b][1] = total_ctl;
+        total_ev += rows[b][0]; total_ctl += rows[b][1];
+        fits[b][0] = total_ev <= (size_t)out->events_cap; fits[b][1] = total_ctl <= (size_t)out->controls_cap;
+        // ---- the copy: behind the kernel, on the copy stream
+        HIP_OK(hipStreamWaitEvent(ctx->copy_stream, ev[4 * b + 1], 0));
+        HIP_OK(hipEventRecord(ev[4 * b + 2], ctx->copy_stream));
+        char *stg = (char *)ctx->h_stage[b];
+        auto down = [&](const Arr &a, size_t first, size_t count) {
+            if (!count) return;
+            char *dst = a.staged ? stg + a.stg_off : a.dst + first * a.elem;
+            HIP_OK(hipMemcpyAsync(dst, dev + a.dev_off, count * a.elem, hipMemcpyDeviceToHost, ctx->copy_stream));
+            st.bytes_d2h += (int64_t)(count * a.elem);
+        };
+        for (const Arr *a : per_traj) down(*a, k0, c);
+        if (fits[b][0]) down(a_ev, base[b][0], rows[b][0]);   // (a call whose rows outgrow the caller's arrays still counts them: the totals)
+        if (fits[b][1]) down(a_ctl, base[b][1], rows[b][1]);
+        st.event_rows += (int64_t)rows[b][0];
+        HIP_OK(hipEventRecord(ev[4 * b + 3], ctx->copy_stream));
+    };
+
+    auto drain_chunk = [&](size_t k) {
+        const int b = (int)(k & 1);
+        const size_t k0 = k * C, c = std::min(C, n - k0);
+        HIP_OK(hipEventSynchronize(ev[4 * b + 3]));
+        float ms = 0.f;
+        HIP_OK(hipEventElapsedTime(&ms, ev[4 * b], ev[4 * b + 1])); st.kernel_ms += ms;
+        HIP_OK(hipEventElapsedTime(&ms, ev[4 * b + 2], ev[4 * b + 3])); st.d2h_ms += ms;
+        const auto t0 = Clock::now();
+        const char *stg = (const char *)ctx->h_stage[b];
+        struct Job { char *dst; const char *src; size_t bytes; };
+        std::vector<Job> jobs;
+        auto add = [&](const Arr &a, size_t first, size_t count) {   // in pieces of about 1 MiB, so that the threads share a large array
+            if (!a.staged || !count) return;
+            const size_t bytes = count * a.elem, piece = (size_t)1 << 20;
+            for (size_t q = 0; q < bytes; q += piece) jobs.push_back({a.dst + first * a.elem + q, stg + a.stg_off + q, std::min(piece, bytes - q)});
+        };
+        for (const Arr *a : per_traj) add(*a, k0, c);
+        if (fits[b][0]) add(a_ev, base[b][0], rows[b][0]);
+        if (fits[b][1]) add(a_ctl, base[b][1], rows[b][1]);
+        const int TT = (int)std::min<size_t>((size_t)TH, std::max<size_t>(1, jobs.size()));
+        run_parallel(TT, [&](int t) {
+            for (size_t j = (size_t)t; j < jobs.size(); j += (size_t)TT) memcpy(jobs[j].dst, jobs[j].src, jobs[j].bytes);
+        });
+        st.scatter_ms += ms_since(t0);
+    };
+
+    int rc = EMGPU_OK;
+    try {
+        for (size_t k = 0; k <= nchunks; k++) {
+            if (k < nchunks) launch_chunk(k);
+            if (k > 0) drain_chunk(k - 1);
+        }
+        rc = emgpu_ctx_sync(ctx);   // deferred per-trajectory errors of every chunk (rejection cap, event cap)
+    } catch (...) {
+        (void)hipStreamSynchronize(ctx->stream);
+        if (ctx->copy_stream) (void)hipStreamSynchronize(ctx->copy_stream);
+        throw;
+    }
+    st.total_ms = ms_since(t_call);
+    ctx->host_stats = st;
+    if (rc == EMGPU_ERR_EVENT_CAP) {   // a list outgrew event_cap: what the lists need in full; their control rows are at most as many
+        uint64_t need = 0;
+        for (size_t i = 0; i < n; i++) need += out->ev_count[i];
+        out->totals[0] = out->totals[1] = (int64_t)need;
+        return rc;
+    }
+    out->totals[0] = (int64_t)total_ev;
+    out->totals[1] = (int64_t)total_ctl;
+    if (rc == EMGPU_OK && (total_ev > (size_t)out->events_cap || total_ctl > (size_t)out->controls_cap))
+        return fail(EMGPU_ERR_EVENT_CAP, "emgpu_sample_uncor_host: the call has " + std::to_string(total_ev) + " event rows and " + std::to_string(total_ctl) +
+                                             " control rows, events_cap / controls_cap are " + std::to_string(out->events_cap) + " / " + std::to_string(out->controls_cap));
     return rc;
     EMGPU_CATCH
 }

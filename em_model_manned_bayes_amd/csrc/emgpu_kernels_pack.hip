@@ -60,12 +60,18 @@ __global__ void __launch_bounds__(256) k_pack_rows(int64_t n, uint32_t cap, cons
 
 size_t pack_scratch_words(int64_t n) { return 4 + (size_t)((n + 255) / 256); }
 
-hipError_t launch_pack_events(int64_t n, uint32_t cap, const uint32_t *cnt, const uint64_t *ev, uint32_t *scratch, uint64_t *packed, hipStream_t s) {
+hipError_t launch_scan_counts(int64_t n, uint32_t cap, const uint32_t *cnt, uint32_t *scratch, hipStream_t s) {
     if (n <= 0) return hipMemsetAsync(scratch, 0, 2 * sizeof(uint32_t), s);
     const unsigned nb = (unsigned)((n + 255) / 256);
     hipLaunchKernelGGL(k_pack_count, dim3(nb), dim3(256), 0, s, n, cap, cnt, scratch);
     hipLaunchKernelGGL(k_pack_scan, dim3(1), dim3(1024), 0, s, (uint32_t)nb, scratch);
-    hipLaunchKernelGGL(k_pack_rows, dim3(nb), dim3(256), 0, s, n, cap, cnt, ev, scratch, packed);
+    return hipGetLastError();
+}
+
+hipError_t launch_pack_events(int64_t n, uint32_t cap, const uint32_t *cnt, const uint64_t *ev, uint32_t *scratch, uint64_t *packed, hipStream_t s) {
+    const hipError_t e = launch_scan_counts(n, cap, cnt, scratch, s);
+    if (n <= 0 || e != hipSuccess) return e;
+    hipLaunchKernelGGL(k_pack_rows, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, n, cap, cnt, ev, scratch, packed);
     return hipGetLastError();
 }
 

@@ -41,5 +41,26 @@ hipError_t launch_compact_rejected(int64_t n, uint64_t first_index, const uint8_
 // receive the total row count (u64) and word 2 + b the first packed row of workgroup b's 256 lists; packed: room for n x cap rows
 size_t pack_scratch_words(int64_t n);
 hipError_t launch_pack_events(int64_t n, uint32_t cap, const uint32_t *cnt, const uint64_t *ev, uint32_t *scratch, uint64_t *packed, hipStream_t s);
+// the first two steps of launch_pack_events alone: scratch receives the total of min(cnt[i], cap) (u64 in words 0-1) and, in word 2 + b, the
+// exclusive prefix of workgroup b's 256 counts
+hipError_t launch_scan_counts(int64_t n, uint32_t cap, const uint32_t *cnt, uint32_t *scratch, hipStream_t s);
+// UncorEncounterModel.sample's outputs from a chunk's event lists [n][cap] (emgpu_kernels_format.hip), for emgpu_sample_uncor_host
+struct EmgpuFormatRun {
+    int64_t n;               // lists of the chunk
+    uint32_t cap;            // rows per list in `ev`
+    int32_t T, ni;           // sample_time, n_initial
+    int64_t ld;              // trajectory dimension of init_val ([ni][ld])
+    const uint32_t *ev_count;
+    const uint64_t *ev;      // emgpu_event rows, list i at ev + i * cap
+    const float *init_val;
+    int32_t id_dh, id_dpsi, id_dv;   // 1-based variable ids of the control columns (UncorEncounterModel.m:291)
+    uint32_t *ctrl_count;    // [n] out: rows with dt > 0
+    uint32_t *ctrl_off;      // [n] out: first control row of list i within the chunk
+    uint32_t *scratch;       // pack_scratch_words(n) words: words 0-1 receive the chunk's total control rows (u64)
+    double *inits;           // [n][ni] out
+    double *samples;         // [n][ni][T] out, or null
+    double *controls;        // [rows][4] out, room for sum(min(ev_count, cap)) rows
+};
+hipError_t launch_format_uncor(const EmgpuFormatRun &F, hipStream_t s);
 hipError_t launch_sample2track(const EmgpuTrackRun &A, bool dense, hipStream_t s, const char **name);
 } // namespace emgpu

@@ -11,7 +11,9 @@ model in place of the un-vendored em-core dynamics ("dynamics unpinned"); its 'g
 and raises NotImplementedError.  CorTerminalModel.track (geometry draw -> createEncounter -> the filters of track.m) runs on
 the GPU as well, given the trajectory-model files.
 """
+import operator
 import os
+from collections.abc import Sequence
 
 import numpy as np
 
@@ -52,6 +54,78 @@ class EncounterModelEvents:
     def event(self, m):
         m = np.asarray(m, dtype=np.float64).reshape(-1, 4)
         self.time_s, self.verticalRate_fps, self.turnRate_radps, self.longitudeAccel_ftpss = m[:, 0], m[:, 1], m[:, 2], m[:, 3]
+
+
+class _LazyPerSample(Sequence):
+    """A read-only sequence of n per-sample objects that are built from flat arrays when they are accessed, not before: what
+    UncorEncounterModel.sample(..., lazy=True) returns in place of a list.  [i] (negative i included) builds item i; a slice builds a list;
+    iteration builds one item at a time."""
+    __slots__ = ("_n",)
+
+    def __init__(self, n):
+        self._n = int(n)
+
+    def __len__(self):
+        return self._n
+
+    def __getitem__(self, i):
+        if isinstance(i, slice):
+            return [self._item(j) for j in range(*i.indices(self._n))]
+        i = operator.index(i)
+        if i < 0:
+            i += self._n
+        if not 0 <= i < self._n:
+            raise IndexError("sample index out of range")
+        return self._item(i)
+
+    def __iter__(self):
+        for i in range(self._n):
+            yield self._item(i)
+
+    def __repr__(self):
+        return "<%s of %d samples>" % (type(self).__name__, self._n)
+
+
+class LazyEvents(_LazyPerSample):
+    """out_events: item i is list i as the [k, 3] float64 matrix [dt, var, value] the eager call holds.  `flat` (native.EVENT_DTYPE rows,
+    list after list), `counts` and `offsets` (n + 1 row offsets) serve vectorised consumers."""
+    __slots__ = ("flat", "counts", "offsets")
+
+    def __init__(self, flat, counts):
+        super().__init__(len(counts))
+        self.flat, self.counts = flat, counts
+        self.offsets = np.concatenate(([0], np.cumsum(counts, dtype=np.int64)))
+
+    def _item(self, i):
+        r = self.flat[self.offsets[i]: self.offsets[i + 1]]
+        m = np.empty((r.shape[0], 3))
+        m[:, 0], m[:, 1], m[:, 2] = r["dt"], r["var"], r["value"]
+        return m
+
+
+class LazySamples(_LazyPerSample):
+    """out_samples: item i is the [n_initial, T] float64 view flat[i] of the [n, n_initial, T] block `flat`."""
+    __slots__ = ("flat",)
+
+    def __init__(self, flat):
+        super().__init__(flat.shape[0])
+        self.flat = flat
+
+    def _item(self, i):
+        return self.flat[i]
+
+
+class LazyControls(_LazyPerSample):
+    """out_EME: item i is an EncounterModelEvents over rows offsets[i]:offsets[i + 1] of the [rows, 4] float64 control matrix `flat`."""
+    __slots__ = ("flat", "counts", "offsets")
+
+    def __init__(self, flat, counts):
+        super().__init__(len(counts))
+        self.flat, self.counts = flat, counts
+        self.offsets = np.concatenate(([0], np.cumsum(counts, dtype=np.int64)))
+
+    def _item(self, i):
+        return EncounterModelEvents._of_rows(self.flat[self.offsets[i]: self.offsets[i + 1]])
 
 
 class EncounterModel:
@@ -307,9 +381,13 @@ class UncorEncounterModel(EncounterModel):
         self.isRotorcraft = "rotorcraft" in os.path.basename(str(parameters_filename))  # :181-185
 
     def sample(self, n_samples, sample_time, seed=None, isQuantize500=False, layers=None,
-               transition_mode=L.TRANSITION_REFERENCE_AUTO, max_attempts=1000, first_index=None, ctx=None):
+               transition_mode=L.TRANSITION_REFERENCE_AUTO, max_attempts=1000, first_index=None, ctx=None, lazy=False):
         """[out_inits, out_events, out_samples, out_EME] = sample(self, n_samples, sample_time, 'seed', s,
-        'isQuantize500', b, 'layers', L)   (UncorEncounterModel.m:192-313)."""
+        'isQuantize500', b, 'layers', L)   (UncorEncounterModel.m:192-313).
+
+        lazy=True: the same four outputs, bit for bit, with out_samples and the controls built on the GPU (emgpu_sample_uncor_host) and
+        out_events / out_samples / out_EME handed out as LazyEvents / LazySamples / LazyControls: sequences that build sample i's object when
+        it is accessed."""
         labs = self.labels_initial
 
         def find(name):
@@ -330,6 +408,8 @@ class UncorEncounterModel(EncounterModel):
         ni, T = self.n_initial, int(sample_time)
         out_inits = np.zeros((n_samples, ni))
         out_events, out_samples, out_EME = [None] * n_samples, [None] * n_samples, [None] * n_samples
+        if lazy:
+            return self._sample_lazy(ctx, n_samples, T, s, first, flags, layers, transition_mode, max_attempts, idxL, idxV, idxDH, idxDPsi, idxDV)
         tm = self.temporal_map
         idxEME = [int(np.nonzero(tm[:, 0] == v)[0][0]) + 1 for v in (idxDH, idxDPsi, idxDV)]  # :291
         vars_dyn = tm[:, 0].astype(np.int64) - 1
@@ -399,6 +479,38 @@ class UncorEncounterModel(EncounterModel):
         tm["format_s"] = tm["total_s"] - tm["native_s"]
         self.last_sample_timing = tm
         return out_inits, out_events, out_samples, out_EME
+
+    def _sample_lazy(self, ctx, n, T, s, first, flags, layers, transition_mode, max_attempts, idxL, idxV, idxDH, idxDPsi, idxDV):
+        """sample(..., lazy=True): one library call builds the four outputs on the device; out_EME's columns are the variables of idxEME
+        (:291) in that order, dh, dpsi, dv."""
+        import time as _time
+        t_call, tm = _time.perf_counter(), {"native_s": 0.0, "kernel_ms": 0.0, "d2h_ms": 0.0, "bytes_d2h": 0, "calls": 0}
+        cap, retries = 256, 0
+        while True:
+            t_nat = _time.perf_counter()
+            try:
+                res = native.sample_uncor_host(ctx, self.native, n, T, s, (idxDH, idxDPsi, idxDV), event_cap=cap, first_index=first,
+                                               flags=flags, layers=layers, transition_mode=transition_mode, max_attempts=max_attempts,
+                                               idx_L=idxL, idx_v=idxV, idx_dh=idxDH)
+            except L.EmgpuError as e:
+                tm["native_s"] += _time.perf_counter() - t_nat
+                if e.code != L.ERR_EVENT_CAP or e.ev_count.max(initial=0) <= cap:
+                    raise
+                while cap < e.ev_count.max():   # the longest list did not fit: the room the eager path's doublings end at
+                    cap *= 2
+                retries += 1
+                continue
+            break
+        tm["native_s"] += _time.perf_counter() - t_nat
+        st = res["host_stats"]
+        tm["kernel_ms"], tm["d2h_ms"], tm["bytes_d2h"], tm["calls"] = st["kernel_ms"], st["d2h_ms"], st["bytes_d2h"], 1
+        tm["event_cap"], tm["retries"] = cap, retries
+        out = (res["inits"], LazyEvents(res["events"], res["ev_count"]), LazySamples(res["samples"]),
+               LazyControls(res["controls"], res["ctrl_count"]))
+        tm["total_s"] = _time.perf_counter() - t_call
+        tm["format_s"] = tm["total_s"] - tm["native_s"]
+        self.last_sample_timing = tm
+        return out
 
     TRACK_FIELDS = ("time_s", "north_ft", "east_ft", "up_ft", "speed_ft_s", "phi_rad", "theta_rad", "psi_rad")
 

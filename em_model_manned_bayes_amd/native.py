@@ -467,6 +467,42 @@ def sample_dbn_host(ctx, model, n, sample_time, seed, want_dense=True, want_even
     return out
 
 
+def sample_uncor_host(ctx, model, n, sample_time, seed, ctrl_var, event_cap=256, events_cap=None, controls_cap=None, want_samples=True,
+                      pinned=True, **kw):
+    """emgpu_sample_uncor_host: UncorEncounterModel.sample's arrays built on the device.  Returns a dict:
+    inits [n, n_i] f64, ev_count [n] u32, events [rows] EVENT_DTYPE (list after list), ctrl_count [n] u32, controls [rows, 4] f64
+    (trajectory after trajectory), samples [n, n_i, T] f64 (None unless want_samples), attempts [n] i32, kernel, host_stats.
+    ctrl_var: the 1-based ids of "\\dot h", "\\dot \\psi", "\\dot v".
+    pinned: the per-trajectory arrays come from the context's pinned pool (the copy engine writes straight into them); False: pageable
+    numpy arrays, filled through the library's staging buffers.  The packed rows go into arrays of events_cap / controls_cap rows (default
+    n * event_cap: pinned when `pinned` and a capacity is given, else pageable, whose untouched pages cost nothing) and are returned trimmed.
+    A list longer than event_cap, or rows beyond a capacity, raise EmgpuError(ERR_EVENT_CAP) with `.totals` (the rows needed, see emgpu.h)
+    and `.ev_count` set: a retry with that much room gives the same draws."""
+    ni, T, n = model.n_initial, int(sample_time), int(n)
+    p, keep = make_params(n, T, seed, event_cap=int(event_cap), **kw)
+    empty = ctx.pinned_empty if pinned else (lambda shape, dt: np.empty(shape, dtype=dt))
+    rows_empty = lambda cap_, shape, dt: (empty if cap_ is not None else (lambda sh, d: np.empty(sh, dtype=d)))(shape, dt)
+    ev_cap = int(events_cap) if events_cap is not None else n * int(event_cap)
+    ct_cap = int(controls_cap) if controls_cap is not None else n * int(event_cap)
+    o = L.UncorOut()
+    inits, ec, cc, att = empty((n, ni), np.float64), empty((n,), np.uint32), empty((n,), np.uint32), empty((n,), np.int32)
+    ev = rows_empty(events_cap, (max(ev_cap, 1),), EVENT_DTYPE)
+    ctl = rows_empty(controls_cap, (max(ct_cap, 1), 4), np.float64)
+    smp = empty((n, ni, T), np.float64) if want_samples else None
+    totals = np.zeros(2, dtype=np.int64)
+    o.inits, o.ev_count, o.ctrl_count, o.attempts, o.events, o.controls = _p(inits), _p(ec), _p(cc), _p(att), _p(ev), _p(ctl)
+    o.events_cap, o.controls_cap, o.samples, o.totals = ev_cap, ct_cap, _p(smp), _p(totals)
+    o.ctrl_var[:] = [int(v) for v in ctrl_var]
+    rc = L.lib().emgpu_sample_uncor_host(ctx._h, model._h, C.byref(p), C.byref(o))
+    if rc == L.ERR_EVENT_CAP:
+        e = L.EmgpuError(rc, L.lib().emgpu_last_error().decode("utf-8", "replace"))
+        e.totals, e.ev_count = (int(totals[0]), int(totals[1])), np.array(ec)
+        raise e
+    L.check(rc)
+    return {"inits": inits, "ev_count": ec, "events": ev[: int(totals[0])], "ctrl_count": cc, "controls": ctl[: int(totals[1])],
+            "samples": smp, "attempts": att, "kernel": ctx.last_kernel(), "host_stats": ctx.host_stats()}
+
+
 def split_rows(a, ends):
     """[a[0:ends[0]], a[ends[0]:ends[1]], ...] as views -- what np.split(a, ends[:-1]) returns, without its per-piece swapaxes round trip
     (a million pieces: 1 us each instead of 3)."""

@@ -248,6 +248,34 @@ int emgpu_sample_dbn_device(emgpu_ctx *ctx, const emgpu_model *m, const emgpu_sa
 int emgpu_sample_dbn_host(emgpu_ctx *ctx, const emgpu_model *m, const emgpu_sample_params *p,
                           const emgpu_sample_out *out);
 
+/* UncorEncounterModel.sample's four outputs (UncorEncounterModel.m:283-300), built on the device: HOST pointers, synchronous.  The pipeline of
+ * emgpu_sample_dbn_host, with three steps more on the launch stream after a chunk's event lists are packed -- events2samples.m:9-26 (samples),
+ * events2controls.m:11-31 with the unit conversions of :291-297 (controls) and the inits as f64 -- so that what crosses PCIe is the caller's
+ * arrays themselves.  Each array is written by the copy engine when it is pinned, else through the library's staging buffers.
+ *   samples[i][v][t]  the value of the latest row of list i that names variable v and ends at at <= t with at < T (at = the sum of dt over the
+ *                     list up to and including the row), else init_val of v -- column t of out_samples{i}
+ *   controls          one row per event row with dt > 0: [t0, x_dh / 60, x_dpsi * (pi / 180), x_dv * 1.68780972222222], t0 the list time
+ *                     before the row, x_* the samples of ctrl_var[0..2] at column t0 -- out_EME{i}.event
+ * Both lists are packed over the call: list i's rows start at the sum of the counts before it.  The draws are those of emgpu_sample_dbn_host
+ * with the same params (counter-based: chunking and capacities do not change them), and ctx's last kernel is the sampler's.
+ * EMGPU_ERR_EVENT_CAP when a list outgrows event_cap (totals: the rows the lists need in full, for both totals) or the rows outgrow events_cap /
+ * controls_cap (totals: exact); a retry with that room gives the same draws.  params.start and params.indices are not supported. */
+typedef struct {
+    double *inits;          /* [n][n_initial] row-major: out_inits                                                               */
+    uint32_t *ev_count;     /* [n] rows of list i (> event_cap => EMGPU_ERR_EVENT_CAP)                                          */
+    emgpu_event *events;    /* [events_cap] rows, list after list                                                                */
+    int64_t events_cap;
+    uint32_t *ctrl_count;   /* [n] control rows of trajectory i (its event rows with dt > 0)                                     */
+    double *controls;       /* [controls_cap][4] rows [t, dh ft/s, dpsi rad/s, dv ft/s^2], trajectory after trajectory          */
+    int64_t controls_cap;
+    double *samples;        /* [n][n_initial][sample_time], or NULL: not wanted                                                  */
+    int32_t *attempts;      /* [n], or NULL                                                                                      */
+    int64_t *totals;        /* [2] out: event rows, control rows of the call                                                     */
+    int32_t ctrl_var[3];    /* 1-based ids of "\dot h", "\dot \psi", "\dot v": the control columns in idxEME order (:291)         */
+    int32_t _pad;
+} emgpu_uncor_out;
+int emgpu_sample_uncor_host(emgpu_ctx *ctx, const emgpu_model *m, const emgpu_sample_params *p, const emgpu_uncor_out *out);
+
 /* ------------------------------------------------------------------------------------------------
  * Trace placement (round 6).  WHERE a 36 GB trace lies in device memory decides how fast the sampler writes it: the same launch takes
  * 5.9, 6.6 or 7.0 ms depending on the allocation, launch after launch (profiles/r05_placement_probe.txt, profiles/r06_placement_probe.txt).
