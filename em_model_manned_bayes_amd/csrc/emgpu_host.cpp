@@ -3,14 +3,13 @@
 //     measured with the caller's own launch (profiles/r05_placement_probe.txt: the same launch writes one 36 GB allocation in 6.0 ms
 //     and another in 7.1 ms);
 //   * the pinned pool: emgpu_host_alloc / _free;
-//   * emgpu_sample_dbn_host as a pipeline: chunk k's kernel | chunk k-1's copy over PCIe | chunk k-2's copy into the caller's arrays.
-//   * emgpu_sample_uncor_host: the same pipeline, with UncorEncounterModel.sample's samples and controls built on the device.
+//   * emgpu_sample_dbn_host and emgpu_sample_uncor_host (UncorEncounterModel.sample's samples and controls built on the device): one driver,
+//     run_chunks, pipelines both -- chunk k's launches | chunk k-1's copy over PCIe | chunk k-2's copy into the caller's arrays.
 // Reference semantics: the loop over samples of UncorEncounterModel.m:244-300 and the host arrays it returns (:283-300).
 #include <algorithm>
 #include <chrono>
 #include <cstdlib>
 #include <cstring>
-#include <functional>
 #include <map>
 #include <mutex>
 #include <system_error>
@@ -245,6 +244,111 @@ void run_parallel(int T, F fn) {   // fn(t) for t = 0..T-1, fn(0) on the calling
     fn(0);
     for (int t = started; t < T; t++) fn(t);
     for (auto &x : th) x.join();
+}
+
+// ------------------------------------------------------------------------------------------------ the host path's chunked pipeline
+struct ChunkPlan { size_t n, C, Cp, nchunks; };   // n trajectories in chunks of C (the last one may be short), C padded to Cp on the device
+// `bpt` device bytes per trajectory; chunks of equal size, and with event lists (event_cap > 0) a chunk's packed rows counted in 32 bits
+ChunkPlan chunk_plan(size_t n, size_t bpt, bool direct, size_t event_cap) {
+    size_t target = (size_t)(direct ? 1024 : 256) << 20;   // pinned outputs: larger pieces (the copy engine writes row by row into the caller's pitch)
+    if (const char *e = getenv("EMGPU_HOST_CHUNK_MB")) { const long v = atol(e); if (v > 0) target = (size_t)v << 20; }
+    size_t C = std::max<size_t>(1024, target / std::max<size_t>(bpt, 1) / 1024 * 1024);
+    if (event_cap) C = std::min(C, std::max<size_t>(1024, ((size_t)0xFFFF0000u / event_cap) / 1024 * 1024));
+    if (C >= n) C = n;
+    else {   // chunks of equal size: the last one is not a sliver (and a staged copy moves whole chunk buffers)
+        const size_t k = (n + C - 1) / C;
+        C = std::min(C, round_up((n + k - 1) / k, 1024));
+    }
+    return {n, C, round_up(C, 256), (n + C - 1) / C};
+}
+
+// chunk buffers (blocks of the trace pool's allocator, unprobed) and pinned staging buffers of these sizes, one of each for a single chunk, two
+// otherwise; the copy stream and h_total.  false: out of device memory
+bool provision(emgpu_ctx *ctx, size_t nchunks, size_t dev_bytes, size_t stage_bytes) {
+    const size_t nbuf = nchunks == 1 ? 1 : 2;
+    for (size_t q = 0; q < nbuf; q++) {
+        emgpu_ctx::TraceBlock &b = ctx->chunk_buf[q];
+        if (b.bytes >= dev_bytes) continue;
+        HIP_OK(hipStreamSynchronize(ctx->stream));
+        if (b.p) { device_release(b.p); b = emgpu_ctx::TraceBlock(); }
+        // (plain hipMalloc blocks: these buffers are the SOURCE of copies, which is all their placement could matter for -- measured: it does not)
+        b = pool_take(ctx, dev_bytes + dev_bytes / 8, nullptr, /*plain=*/true);   // (some headroom: batch sizes that wobble do not reallocate)
+        if (!b.p) return false;
+    }
+    if (ctx->h_stage_cap < stage_bytes) {
+        const size_t want_cap = stage_bytes + stage_bytes / 8;
+        for (auto &s : ctx->h_stage) { if (s) HIP_OK(hipHostFree(s)); s = nullptr; }
+        ctx->h_stage_cap = 0;
+        for (size_t b = 0; b < nbuf; b++) HIP_OK(hipHostMalloc(&ctx->h_stage[b], want_cap, hipHostMallocDefault));
+        ctx->h_stage_cap = want_cap;
+    }
+    if (nbuf == 2 && !ctx->h_stage[1]) HIP_OK(hipHostMalloc(&ctx->h_stage[1], ctx->h_stage_cap, hipHostMallocDefault));
+    if (!ctx->copy_stream) HIP_OK(hipStreamCreateWithFlags(&ctx->copy_stream, hipStreamNonBlocking));
+    if (!ctx->h_total) HIP_OK(hipHostMalloc((void **)&ctx->h_total, 4 * sizeof(uint64_t), hipHostMallocDefault));
+    return true;
+}
+
+// Launch k / drain k-1 over the chunks: launch(k0, c, b) on the ctx stream and copy(k0, c, b) on the copy stream behind it for trajectories
+// [k0, k0 + c) in chunk buffer b, then scatter(...) of the chunk before it on the host.  wait_rows: the host waits for the launches before
+// copy() (which reads the row counts they left in h_total[2b], h_total[2b + 1]).  Stores the call's host_stats; emgpu_ctx_sync's status.
+template <typename Launch, typename Copy, typename Scatter>
+int run_chunks(emgpu_ctx *ctx, const ChunkPlan &P, bool direct, bool wait_rows, Clock::time_point t_call, emgpu_host_stats_t &st, Launch launch,
+               Copy copy, Scatter scatter) {
+    st.chunks = (int32_t)P.nchunks; st.chunk_n = (int32_t)P.C; st.threads = host_threads(); st.direct = direct ? 1 : 0;
+    Events ev(8);   // per buffer b: 4b + {kernel start, kernel end, copy start, copy end}
+    int rc = EMGPU_OK;
+    try {
+        for (size_t k = 0; k <= P.nchunks; k++) {
+            if (k < P.nchunks) {
+                const int b = (int)(k & 1);
+                const size_t k0 = k * P.C, c = std::min(P.C, P.n - k0);
+                HIP_OK(hipEventRecord(ev[4 * b], ctx->stream));
+                launch(k0, c, b);
+                HIP_OK(hipEventRecord(ev[4 * b + 1], ctx->stream));
+                if (wait_rows) HIP_OK(hipEventSynchronize(ev[4 * b + 1]));   // (the launch stream holds nothing but this chunk)
+                HIP_OK(hipStreamWaitEvent(ctx->copy_stream, ev[4 * b + 1], 0));
+                HIP_OK(hipEventRecord(ev[4 * b + 2], ctx->copy_stream));
+                copy(k0, c, b);
+                HIP_OK(hipEventRecord(ev[4 * b + 3], ctx->copy_stream));
+            }
+            if (k > 0) {
+                const int b = (int)((k - 1) & 1);
+                const size_t k0 = (k - 1) * P.C, c = std::min(P.C, P.n - k0);
+                HIP_OK(hipEventSynchronize(ev[4 * b + 3]));
+                float ms = 0.f;
+                HIP_OK(hipEventElapsedTime(&ms, ev[4 * b], ev[4 * b + 1])); st.kernel_ms += ms;
+                HIP_OK(hipEventElapsedTime(&ms, ev[4 * b + 2], ev[4 * b + 3])); st.d2h_ms += ms;
+                const auto t0 = Clock::now();
+                scatter(k0, c, b);
+                st.scatter_ms += ms_since(t0);
+            }
+        }
+        rc = emgpu_ctx_sync(ctx);   // deferred per-trajectory errors of every chunk (rejection cap, event cap, presets)
+    } catch (...) {
+        (void)hipStreamSynchronize(ctx->stream);
+        if (ctx->copy_stream) (void)hipStreamSynchronize(ctx->copy_stream);
+        throw;
+    }
+    st.total_ms = ms_since(t_call);
+    ctx->host_stats = st;
+    return rc;
+}
+
+struct Job { char *dst; const char *src; size_t bytes; };
+// the jobs on TT threads (job j on thread j % TT), then more(t) on each thread t
+template <typename More>
+void run_jobs(const std::vector<Job> &jobs, int TT, More more) {
+    run_parallel(TT, [&](int t) {
+        for (size_t j = (size_t)t; j < jobs.size(); j += (size_t)TT) memcpy(jobs[j].dst, jobs[j].src, jobs[j].bytes);
+        more(t);
+    });
+}
+
+int sample_nothing(emgpu_ctx *ctx, const emgpu_model *h, const emgpu_sample_params *p) {   // n == 0: the arguments are still checked like any call's
+    emgpu_sample_out d{};
+    const int rc = emgpu_sample_dbn_device(ctx, h, p, &d);
+    ctx->host_stats = emgpu_host_stats_t{};
+    return rc == EMGPU_OK ? emgpu_ctx_sync(ctx) : rc;
 }
 } // namespace
 
@@ -484,13 +588,7 @@ int emgpu_sample_dbn_host(emgpu_ctx *ctx, const emgpu_model *h, const emgpu_samp
     if ((out->ev_count != nullptr) != (out->events != nullptr)) return fail(EMGPU_ERR_ARG, "ev_count and events go together");
     if (out->events && p->event_cap < 1) return fail(EMGPU_ERR_ARG, "event_cap must be >= 1");
     const size_t cap = out->events ? (size_t)p->event_cap : 0;
-    emgpu_host_stats_t st{};
-    if (n == 0) {   // nothing to draw: the arguments are still checked like any call's
-        emgpu_sample_out d{};
-        const int rc0 = emgpu_sample_dbn_device(ctx, h, p, &d);
-        ctx->host_stats = st;
-        return rc0 == EMGPU_OK ? emgpu_ctx_sync(ctx) : rc0;
-    }
+    if (n == 0) return sample_nothing(ctx, h, p);
 
     // ---- one chunk on the device: [small arrays | large arrays | event lists | packed rows | pack scratch]; what is staged is a prefix
     struct Arr { void *dst; size_t rows, elem, dev_off; bool offset_by_col; };
@@ -503,18 +601,8 @@ int emgpu_sample_dbn_host(emgpu_ctx *ctx, const emgpu_model *h, const emgpu_samp
     bpt += (out->init_bin ? ni : 0) + (out->init_val ? 4 * ni : 0);
     bpt += (out->dyn_bin ? 4 * G4 * nd : 0) + (out->dyn_val ? 16 * G4 * nd : 0);
     bpt += 16 * cap;   // the lists and their packed copy
-    // pinned outputs: one pitched copy per array (56.5 GB/s of the 57 GB/s a plain pinned copy reaches; row-by-row linear copies: 46 -- tools/host_path_probe.py)
-    static const bool direct_rows = [] { const char *e = getenv("EMGPU_HOST_DIRECT"); return e && !strcmp(e, "rows"); }();
-    size_t target = (size_t)(direct ? 1024 : 256) << 20;   // pinned outputs: larger pieces (the copy engine writes row by row into the caller's pitch)
-    if (const char *e = getenv("EMGPU_HOST_CHUNK_MB")) { const long v = atol(e); if (v > 0) target = (size_t)v << 20; }
-    size_t C = std::max<size_t>(1024, target / std::max<size_t>(bpt, 1) / 1024 * 1024);
-    if (cap) C = std::min(C, std::max<size_t>(1024, ((size_t)0xFFFF0000u / cap) / 1024 * 1024));   // a chunk's packed rows are counted in 32 bits
-    if (C >= n) C = n;
-    else {   // chunks of equal size: the last one is not a sliver (and a staged copy moves whole chunk buffers)
-        const size_t k = (n + C - 1) / C;
-        C = std::min(C, round_up((n + k - 1) / k, 1024));
-    }
-    const size_t Cp = round_up(C, 256), nchunks = (n + C - 1) / C;
+    const ChunkPlan P = chunk_plan(n, bpt, direct, cap);
+    const size_t C = P.C, Cp = P.Cp;
     size_t o = 0;
     auto put = [&](size_t bytes) { const size_t at = o; o = round_up(o + bytes, 256); return at; };
     if (out->ev_count) small.push_back({out->ev_count, 1, 4, put(Cp * 4), true});
@@ -530,27 +618,7 @@ int emgpu_sample_dbn_host(emgpu_ctx *ctx, const emgpu_model *h, const emgpu_samp
     const size_t o_scratch = cap ? put(emgpu::pack_scratch_words((int64_t)Cp) * 4) : 0;
     const size_t dev_bytes = std::max<size_t>(o, 256);
     const size_t stage_bytes = std::max<size_t>(stage_prefix + (cap ? C * cap * 8 : 0), 256);
-
-    // the chunk buffers are blocks of the trace pool's allocator (nothing is probed: these launches are microseconds beside their copies)
-    for (size_t q = 0; q < (nchunks == 1 ? 1u : 2u); q++) {
-        emgpu_ctx::TraceBlock &b = ctx->chunk_buf[q];
-        if (b.bytes >= dev_bytes) continue;
-        HIP_OK(hipStreamSynchronize(ctx->stream));
-        if (b.p) { device_release(b.p); b = emgpu_ctx::TraceBlock(); }
-        // (plain hipMalloc blocks: these buffers are the SOURCE of copies, which is all their placement could matter for -- measured: it does not)
-        b = pool_take(ctx, dev_bytes + dev_bytes / 8, nullptr, /*plain=*/true);   // (some headroom: batch sizes that wobble do not reallocate)
-        if (!b.p) return fail(EMGPU_ERR_HIP, "emgpu_sample_dbn_host: out of device memory");
-    }
-    if (ctx->h_stage_cap < stage_bytes) {
-        const size_t want_cap = stage_bytes + stage_bytes / 8;
-        for (auto &s : ctx->h_stage) { if (s) HIP_OK(hipHostFree(s)); s = nullptr; }
-        ctx->h_stage_cap = 0;
-        for (size_t b = 0; b < (nchunks == 1 ? 1u : 2u); b++) HIP_OK(hipHostMalloc(&ctx->h_stage[b], want_cap, hipHostMallocDefault));
-        ctx->h_stage_cap = want_cap;
-    }
-    if (nchunks > 1 && !ctx->h_stage[1]) HIP_OK(hipHostMalloc(&ctx->h_stage[1], ctx->h_stage_cap, hipHostMallocDefault));
-    if (!ctx->copy_stream) HIP_OK(hipStreamCreateWithFlags(&ctx->copy_stream, hipStreamNonBlocking));
-    if (!ctx->h_total) HIP_OK(hipHostMalloc((void **)&ctx->h_total, 4 * sizeof(uint64_t), hipHostMallocDefault));
+    if (!provision(ctx, P.nchunks, dev_bytes, stage_bytes)) return fail(EMGPU_ERR_HIP, "emgpu_sample_dbn_host: out of device memory");
 
     emgpu_sample_params pd = *p;
     if (p->start) {     // the start grid and the index list are caller (host) memory here: uploaded once, every chunk reads its rows
@@ -565,15 +633,9 @@ int emgpu_sample_dbn_host(emgpu_ctx *ctx, const emgpu_model *h, const emgpu_samp
     }
     if (p->start || p->indices) HIP_OK(hipStreamSynchronize(ctx->stream));
 
-    Events ev(8);   // per buffer b: 4b + {kernel start, kernel end, copy start, copy end}
-    const int T = host_threads();
-    int rc = EMGPU_OK;
+    emgpu_host_stats_t st{};
     size_t packed_rows[2] = {0, 0};
-    st.chunks = (int32_t)nchunks; st.chunk_n = (int32_t)C; st.threads = T; st.direct = direct ? 1 : 0;
-
-    auto launch_chunk = [&](size_t k) {
-        const int b = (int)(k & 1);
-        const size_t k0 = k * C, c = std::min(C, n - k0);
+    auto launch = [&](size_t k0, size_t c, int b) {
         char *dev = (char *)ctx->chunk_buf[b].p;
         emgpu_sample_params q = pd;
         q.n = (int64_t)c;
@@ -594,63 +656,44 @@ int emgpu_sample_dbn_host(emgpu_ctx *ctx, const emgpu_model *h, const emgpu_samp
             else d.dyn_val = (float *)(dev + a.dev_off);
         }
         if (cap) d.events = (emgpu_event *)(dev + o_ev);
-        HIP_OK(hipEventRecord(ev[4 * b], ctx->stream));
         const int r = emgpu_sample_dbn_device(ctx, h, &q, &d);
         if (r != EMGPU_OK) throw Error(r, g_err);
         if (cap) {
             hipError_t e = emgpu::launch_pack_events((int64_t)c, (uint32_t)cap, d.ev_count, (const uint64_t *)(dev + o_ev), (uint32_t *)(dev + o_scratch),
                                                      (uint64_t *)(dev + o_packed), ctx->stream);
             if (e != hipSuccess) throw Error(EMGPU_ERR_HIP, std::string("pack launch: ") + hipGetErrorString(e));
-            HIP_OK(hipMemcpyAsync(&ctx->h_total[b], dev + o_scratch, sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
+            HIP_OK(hipMemcpyAsync(&ctx->h_total[2 * b], dev + o_scratch, sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
         }
-        HIP_OK(hipEventRecord(ev[4 * b + 1], ctx->stream));
-        if (cap) {   // how many rows cross PCIe is known only now (the launch stream holds nothing but this chunk)
-            HIP_OK(hipEventSynchronize(ev[4 * b + 1]));
-            packed_rows[b] = (size_t)ctx->h_total[b];
-        }
-        // ---- the copy: behind the kernel, on the copy stream
-        HIP_OK(hipStreamWaitEvent(ctx->copy_stream, ev[4 * b + 1], 0));
-        HIP_OK(hipEventRecord(ev[4 * b + 2], ctx->copy_stream));
+    };
+    auto copy = [&](size_t k0, size_t c, int b) {
+        const char *dev = (const char *)ctx->chunk_buf[b].p;
         char *stg = (char *)ctx->h_stage[b];
         if (stage_prefix) HIP_OK(hipMemcpyAsync(stg, dev, stage_prefix, hipMemcpyDeviceToHost, ctx->copy_stream));
         st.bytes_d2h += (int64_t)stage_prefix;
+        if (cap) packed_rows[b] = (size_t)ctx->h_total[2 * b];   // how many rows cross PCIe is known only now
         if (cap && packed_rows[b]) {
             HIP_OK(hipMemcpyAsync(stg + stage_prefix, dev + o_packed, packed_rows[b] * 8, hipMemcpyDeviceToHost, ctx->copy_stream));
             st.bytes_d2h += (int64_t)packed_rows[b] * 8;
             st.event_rows += (int64_t)packed_rows[b];
         }
-        if (direct)
+        if (direct)   // pinned outputs: one pitched copy per array (56.5 GB/s of the 57 GB/s a plain pinned copy reaches -- tools/host_path_probe.py)
             for (const Arr &a : large) {
                 char *dst = (char *)a.dst + (off + k0) * a.elem;
                 if (ld == c && Cp == c) HIP_OK(hipMemcpyAsync(dst, dev + a.dev_off, a.rows * c * a.elem, hipMemcpyDeviceToHost, ctx->copy_stream));
-                else if (direct_rows)   // row by row: linear copies (the copy engine's fastest form), 1-16 MB each
-                    for (size_t r = 0; r < a.rows; r++)
-                        HIP_OK(hipMemcpyAsync(dst + r * ld * a.elem, dev + a.dev_off + r * Cp * a.elem, c * a.elem, hipMemcpyDeviceToHost, ctx->copy_stream));
                 else HIP_OK(hipMemcpy2DAsync(dst, ld * a.elem, dev + a.dev_off, Cp * a.elem, c * a.elem, a.rows, hipMemcpyDeviceToHost, ctx->copy_stream));
                 st.bytes_d2h += (int64_t)(a.rows * c * a.elem);
             }
-        HIP_OK(hipEventRecord(ev[4 * b + 3], ctx->copy_stream));
     };
-
-    auto drain_chunk = [&](size_t k) {
-        const int b = (int)(k & 1);
-        const size_t k0 = k * C, c = std::min(C, n - k0);
-        HIP_OK(hipEventSynchronize(ev[4 * b + 3]));
-        float ms = 0.f;
-        HIP_OK(hipEventElapsedTime(&ms, ev[4 * b], ev[4 * b + 1])); st.kernel_ms += ms;
-        HIP_OK(hipEventElapsedTime(&ms, ev[4 * b + 2], ev[4 * b + 3])); st.d2h_ms += ms;
-        const auto t0 = Clock::now();
+    auto scatter = [&](size_t k0, size_t c, int b) {
         const char *stg = (const char *)ctx->h_stage[b];
-        struct Job { char *dst; const char *src; size_t bytes; };
         std::vector<Job> jobs;
         for (const Arr &a : small) jobs.push_back({(char *)a.dst + ((a.offset_by_col ? off : 0) + k0) * a.elem, stg + a.dev_off, c * a.elem});
         if (!direct)
             for (const Arr &a : large)
                 for (size_t r = 0; r < a.rows; r++) jobs.push_back({(char *)a.dst + (r * ld + off + k0) * a.elem, stg + a.dev_off + r * Cp * a.elem, c * a.elem});
         std::vector<uint32_t> offs;
-        const uint32_t *cnt = nullptr;
         if (cap) {   // the lists' first packed rows: a prefix sum over the chunk's counts (what the device did, redone on 4 c bytes)
-            cnt = (const uint32_t *)(stg + small[0].dev_off);
+            const uint32_t *cnt = (const uint32_t *)(stg + small[0].dev_off);
             offs.resize(c + 1);
             uint32_t run = 0;
             for (size_t i = 0; i < c; i++) { offs[i] = run; run += std::min<uint32_t>(cnt[i], (uint32_t)cap); }
@@ -659,33 +702,17 @@ int emgpu_sample_dbn_host(emgpu_ctx *ctx, const emgpu_model *h, const emgpu_samp
         }
         size_t moved = cap ? packed_rows[b] * 8 : 0;
         for (const Job &j : jobs) moved += j.bytes;
-        const int TT = (int)std::min<size_t>((size_t)T, std::max<size_t>(1, moved >> 20));   // a thread per MiB, at most T
-        run_parallel(TT, [&](int t) {
-            for (size_t j = (size_t)t; j < jobs.size(); j += (size_t)TT) memcpy(jobs[j].dst, jobs[j].src, jobs[j].bytes);
-            if (cap) {
-                const uint64_t *packed = (const uint64_t *)(stg + stage_prefix);
-                emgpu_event *hev = out->events + (off + k0) * cap;
-                const size_t i0 = c * (size_t)t / (size_t)TT, i1 = c * ((size_t)t + 1) / (size_t)TT;
-                for (size_t i = i0; i < i1; i++) memcpy(hev + i * cap, packed + offs[i], (size_t)(offs[i + 1] - offs[i]) * 8);
-            }
+        const int TT = (int)std::min<size_t>((size_t)host_threads(), std::max<size_t>(1, moved >> 20));   // a thread per MiB, at most host_threads()
+        run_jobs(jobs, TT, [&](int t) {
+            if (!cap) return;
+            const uint64_t *packed = (const uint64_t *)(stg + stage_prefix);
+            emgpu_event *hev = out->events + (off + k0) * cap;
+            const size_t i0 = c * (size_t)t / (size_t)TT, i1 = c * ((size_t)t + 1) / (size_t)TT;
+            for (size_t i = i0; i < i1; i++) memcpy(hev + i * cap, packed + offs[i], (size_t)(offs[i + 1] - offs[i]) * 8);
         });
-        st.scatter_ms += ms_since(t0);
     };
-
-    try {
-        for (size_t k = 0; k <= nchunks; k++) {
-            if (k < nchunks) launch_chunk(k);
-            if (k > 0) drain_chunk(k - 1);
-        }
-        rc = emgpu_ctx_sync(ctx);   // deferred per-trajectory errors of every chunk (rejection cap, event cap, presets)
-    } catch (...) {
-        (void)hipStreamSynchronize(ctx->stream);
-        if (ctx->copy_stream) (void)hipStreamSynchronize(ctx->copy_stream);
-        throw;
-    }
-    st.total_ms = ms_since(t_call);
-    ctx->host_stats = st;
-    return rc;
+    // the row count is waited for only when there are lists: a dense-only chunk's copies queue behind its launches without the host
+    return run_chunks(ctx, P, direct, /*wait_rows=*/cap > 0, t_call, st, launch, copy, scatter);
     EMGPU_CATCH
 }
 
@@ -707,13 +734,7 @@ int emgpu_sample_uncor_host(emgpu_ctx *ctx, const emgpu_model *h, const emgpu_sa
     const auto t_call = Clock::now();
     const size_t n = (size_t)p->n, ni = (size_t)m.n_initial, T = (size_t)p->sample_time, cap = (size_t)p->event_cap;
     out->totals[0] = out->totals[1] = 0;
-    emgpu_host_stats_t st{};
-    if (n == 0) {   // nothing to draw: the arguments are still checked like any call's
-        emgpu_sample_out d{};
-        const int rc0 = emgpu_sample_dbn_device(ctx, h, p, &d);
-        ctx->host_stats = st;
-        return rc0 == EMGPU_OK ? emgpu_ctx_sync(ctx) : rc0;
-    }
+    if (n == 0) return sample_nothing(ctx, h, p);
 
     // ---- the caller's arrays: per trajectory (a chunk is one contiguous piece of each) and packed rows; each is written by the copy engine when
     // it is pinned, else through the staging buffer and the host threads
@@ -727,17 +748,9 @@ int emgpu_sample_uncor_host(emgpu_ctx *ctx, const emgpu_model *h, const emgpu_sa
     for (Arr *a : per_traj) { a->staged = !is_pinned(a->dst); direct = direct && !a->staged; }
     for (Arr *a : {&a_ev, &a_ctl}) { a->staged = !is_pinned(a->dst); direct = direct && !a->staged; }
 
-    size_t bpt = 16 + 4 * ni + 8 * ni + (out->samples ? 8 * ni * T : 0) + 16 * cap + 32 * cap;   // device bytes per trajectory
-    size_t target = (size_t)(direct ? 1024 : 256) << 20;
-    if (const char *e = getenv("EMGPU_HOST_CHUNK_MB")) { const long v = atol(e); if (v > 0) target = (size_t)v << 20; }
-    size_t C = std::max<size_t>(1024, target / bpt / 1024 * 1024);
-    C = std::min(C, std::max<size_t>(1024, ((size_t)0xFFFF0000u / cap) / 1024 * 1024));   // a chunk's packed rows are counted in 32 bits
-    if (C >= n) C = n;
-    else {
-        const size_t k = (n + C - 1) / C;
-        C = std::min(C, round_up((n + k - 1) / k, 1024));
-    }
-    const size_t Cp = round_up(C, 256), nchunks = (n + C - 1) / C;
+    const size_t bpt = 16 + 4 * ni + 8 * ni + (out->samples ? 8 * ni * T : 0) + 16 * cap + 32 * cap;   // device bytes per trajectory
+    const ChunkPlan P = chunk_plan(n, bpt, direct, cap);
+    const size_t C = P.C, Cp = P.Cp;
     size_t o = 0;
     auto put = [&](size_t bytes) { const size_t at = o; o = round_up(o + bytes, 256); return at; };
     a_cnt.dev_off = put(Cp * 4); a_att.dev_off = put(Cp * 4); a_ccnt.dev_off = put(Cp * 4);
@@ -753,36 +766,13 @@ int emgpu_sample_uncor_host(emgpu_ctx *ctx, const emgpu_model *h, const emgpu_sa
     for (Arr *a : per_traj) if (a->staged) { a->stg_off = so; so = round_up(so + C * a->elem, 256); }
     for (Arr *a : {&a_ev, &a_ctl}) if (a->staged) { a->stg_off = so; so = round_up(so + C * cap * a->elem, 256); }
     const size_t stage_bytes = std::max<size_t>(so, 256);
+    if (!provision(ctx, P.nchunks, dev_bytes, stage_bytes)) return fail(EMGPU_ERR_HIP, "emgpu_sample_uncor_host: out of device memory");
 
-    for (size_t q = 0; q < (nchunks == 1 ? 1u : 2u); q++) {   // the chunk buffers and staging of emgpu_sample_dbn_host
-        emgpu_ctx::TraceBlock &b = ctx->chunk_buf[q];
-        if (b.bytes >= dev_bytes) continue;
-        HIP_OK(hipStreamSynchronize(ctx->stream));
-        if (b.p) { device_release(b.p); b = emgpu_ctx::TraceBlock(); }
-        b = pool_take(ctx, dev_bytes + dev_bytes / 8, nullptr, /*plain=*/true);
-        if (!b.p) return fail(EMGPU_ERR_HIP, "emgpu_sample_uncor_host: out of device memory");
-    }
-    if (ctx->h_stage_cap < stage_bytes) {
-        const size_t want_cap = stage_bytes + stage_bytes / 8;
-        for (auto &s : ctx->h_stage) { if (s) HIP_OK(hipHostFree(s)); s = nullptr; }
-        ctx->h_stage_cap = 0;
-        for (size_t b = 0; b < (nchunks == 1 ? 1u : 2u); b++) HIP_OK(hipHostMalloc(&ctx->h_stage[b], want_cap, hipHostMallocDefault));
-        ctx->h_stage_cap = want_cap;
-    }
-    if (nchunks > 1 && !ctx->h_stage[1]) HIP_OK(hipHostMalloc(&ctx->h_stage[1], ctx->h_stage_cap, hipHostMallocDefault));
-    if (!ctx->copy_stream) HIP_OK(hipStreamCreateWithFlags(&ctx->copy_stream, hipStreamNonBlocking));
-    if (!ctx->h_total) HIP_OK(hipHostMalloc((void **)&ctx->h_total, 4 * sizeof(uint64_t), hipHostMallocDefault));
-
-    Events ev(8);   // per buffer b: 4b + {kernel start, kernel end, copy start, copy end}
-    const int TH = host_threads();
+    emgpu_host_stats_t st{};
     size_t rows[2][2] = {{0, 0}, {0, 0}}, base[2][2] = {{0, 0}, {0, 0}};   // per buffer: event / control rows of its chunk and their first row in the call
     bool fits[2][2] = {{false, false}, {false, false}};
     size_t total_ev = 0, total_ctl = 0;
-    st.chunks = (int32_t)nchunks; st.chunk_n = (int32_t)C; st.threads = TH; st.direct = direct ? 1 : 0;
-
-    auto launch_chunk = [&](size_t k) {
-        const int b = (int)(k & 1);
-        const size_t k0 = k * C, c = std::min(C, n - k0);
+    auto launch = [&](size_t k0, size_t c, int b) {
         char *dev = (char *)ctx->chunk_buf[b].p;
         emgpu_sample_params q = *p;
         q.n = (int64_t)c;
@@ -793,7 +783,6 @@ int emgpu_sample_uncor_host(emgpu_ctx *ctx, const emgpu_model *h, const emgpu_sa
         d.ev_count = (uint32_t *)(dev + a_cnt.dev_off);
         d.events = (emgpu_event *)(dev + o_ev);
         if (out->attempts) d.attempts = (int32_t *)(dev + a_att.dev_off);
-        HIP_OK(hipEventRecord(ev[4 * b], ctx->stream));
         const int r = emgpu_sample_dbn_device(ctx, h, &q, &d);
         if (r != EMGPU_OK) throw Error(r, g_err);
         launch_ok(emgpu::launch_pack_events((int64_t)c, (uint32_t)cap, d.ev_count, (const uint64_t *)(dev + o_ev), (uint32_t *)(dev + o_scr),
@@ -808,15 +797,13 @@ int emgpu_sample_uncor_host(emgpu_ctx *ctx, const emgpu_model *h, const emgpu_sa
         launch_ok(emgpu::launch_format_uncor(F, ctx->stream));
         HIP_OK(hipMemcpyAsync(&ctx->h_total[2 * b], dev + o_scr, sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
         HIP_OK(hipMemcpyAsync(&ctx->h_total[2 * b + 1], dev + o_fscr, sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
-        HIP_OK(hipEventRecord(ev[4 * b + 1], ctx->stream));
-        HIP_OK(hipEventSynchronize(ev[4 * b + 1]));   // how many rows cross PCIe is known only now
+    };
+    auto copy = [&](size_t k0, size_t c, int b) {
         rows[b][0] = (size_t)ctx->h_total[2 * b]; rows[b][1] = (size_t)ctx->h_total[2 * b + 1];
         base[b][0] = total_ev; base[b][1] = total_ctl;
         total_ev += rows[b][0]; total_ctl += rows[b][1];
         fits[b][0] = total_ev <= (size_t)out->events_cap; fits[b][1] = total_ctl <= (size_t)out->controls_cap;
-        // ---- the copy: behind the kernel, on the copy stream
-        HIP_OK(hipStreamWaitEvent(ctx->copy_stream, ev[4 * b + 1], 0));
-        HIP_OK(hipEventRecord(ev[4 * b + 2], ctx->copy_stream));
+        const char *dev = (const char *)ctx->chunk_buf[b].p;
         char *stg = (char *)ctx->h_stage[b];
         auto down = [&](const Arr &a, size_t first, size_t count) {
             if (!count) return;
@@ -828,19 +815,9 @@ int emgpu_sample_uncor_host(emgpu_ctx *ctx, const emgpu_model *h, const emgpu_sa
         if (fits[b][0]) down(a_ev, base[b][0], rows[b][0]);   // (a call whose rows outgrow the caller's arrays still counts them: the totals)
         if (fits[b][1]) down(a_ctl, base[b][1], rows[b][1]);
         st.event_rows += (int64_t)rows[b][0];
-        HIP_OK(hipEventRecord(ev[4 * b + 3], ctx->copy_stream));
     };
-
-    auto drain_chunk = [&](size_t k) {
-        const int b = (int)(k & 1);
-        const size_t k0 = k * C, c = std::min(C, n - k0);
-        HIP_OK(hipEventSynchronize(ev[4 * b + 3]));
-        float ms = 0.f;
-        HIP_OK(hipEventElapsedTime(&ms, ev[4 * b], ev[4 * b + 1])); st.kernel_ms += ms;
-        HIP_OK(hipEventElapsedTime(&ms, ev[4 * b + 2], ev[4 * b + 3])); st.d2h_ms += ms;
-        const auto t0 = Clock::now();
+    auto scatter = [&](size_t k0, size_t c, int b) {
         const char *stg = (const char *)ctx->h_stage[b];
-        struct Job { char *dst; const char *src; size_t bytes; };
         std::vector<Job> jobs;
         auto add = [&](const Arr &a, size_t first, size_t count) {   // in pieces of about 1 MiB, so that the threads share a large array
             if (!a.staged || !count) return;
@@ -850,27 +827,9 @@ int emgpu_sample_uncor_host(emgpu_ctx *ctx, const emgpu_model *h, const emgpu_sa
         for (const Arr *a : per_traj) add(*a, k0, c);
         if (fits[b][0]) add(a_ev, base[b][0], rows[b][0]);
         if (fits[b][1]) add(a_ctl, base[b][1], rows[b][1]);
-        const int TT = (int)std::min<size_t>((size_t)TH, std::max<size_t>(1, jobs.size()));
-        run_parallel(TT, [&](int t) {
-            for (size_t j = (size_t)t; j < jobs.size(); j += (size_t)TT) memcpy(jobs[j].dst, jobs[j].src, jobs[j].bytes);
-        });
-        st.scatter_ms += ms_since(t0);
+        run_jobs(jobs, (int)std::min<size_t>((size_t)host_threads(), std::max<size_t>(1, jobs.size())), [](int) {});   // a thread per job, at most host_threads()
     };
-
-    int rc = EMGPU_OK;
-    try {
-        for (size_t k = 0; k <= nchunks; k++) {
-            if (k < nchunks) launch_chunk(k);
-            if (k > 0) drain_chunk(k - 1);
-        }
-        rc = emgpu_ctx_sync(ctx);   // deferred per-trajectory errors of every chunk (rejection cap, event cap)
-    } catch (...) {
-        (void)hipStreamSynchronize(ctx->stream);
-        if (ctx->copy_stream) (void)hipStreamSynchronize(ctx->copy_stream);
-        throw;
-    }
-    st.total_ms = ms_since(t_call);
-    ctx->host_stats = st;
+    const int rc = run_chunks(ctx, P, direct, /*wait_rows=*/true, t_call, st, launch, copy, scatter);
     if (rc == EMGPU_ERR_EVENT_CAP) {   // a list outgrew event_cap: what the lists need in full; their control rows are at most as many
         uint64_t need = 0;
         for (size_t i = 0; i < n; i++) need += out->ev_count[i];

@@ -105,10 +105,10 @@ struct emgpu_ctx {
     TraceBlock chunk_buf[2];
     void *h_stage[2] = {nullptr, nullptr};
     size_t h_stage_cap = 0;
-    uint64_t *h_total = nullptr;   // pinned, 4 words: per chunk buffer, rows of its packed event lists (and of its control rows)
+    uint64_t *h_total = nullptr;   // pinned, 2 words per chunk buffer: rows of its packed event lists, rows of its control rows
     struct HostBlock { void *p = nullptr; size_t bytes = 0; bool in_use = false; };
     std::vector<HostBlock> host_pool;
-    emgpu_host_stats_t host_stats{};   // phases of the last emgpu_sample_dbn_host call
+    emgpu_host_stats_t host_stats{};   // phases of the last emgpu_sample_dbn_host / emgpu_sample_uncor_host call
 };
 
 // emgpu_capi.cpp

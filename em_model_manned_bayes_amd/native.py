@@ -211,7 +211,7 @@ class Context:
         return L.lib().emgpu_last_kernel_name(self._h).decode()
 
     def host_stats(self):
-        """emgpu_host_stats: the phases of the last sample_dbn_host call on this context, as a dict."""
+        """emgpu_host_stats: the phases of the last sample_dbn_host or sample_uncor_host call on this context, as a dict."""
         st = L.HostStats()
         L.check(L.lib().emgpu_host_stats(self._h, C.byref(st)))
         return {f: getattr(st, f) for f, _ in L.HostStats._fields_}

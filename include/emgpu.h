@@ -330,8 +330,9 @@ int emgpu_device_free(emgpu_ctx *ctx, void *p);
 int emgpu_host_alloc(emgpu_ctx *ctx, uint64_t bytes, void **out);
 int emgpu_host_free(emgpu_ctx *ctx, void *p);   /* back to the pool; emgpu_ctx_trim releases the pool's free blocks */
 
-/* Phases of the last emgpu_sample_dbn_host call on this ctx (the call is a pipeline: chunk k's kernel runs while chunk k-1 crosses PCIe
- * and chunk k-2 is copied from staging into the caller's arrays, so the phases overlap and do not add up to total_ms). */
+/* Phases of the last emgpu_sample_dbn_host or emgpu_sample_uncor_host call on this ctx (either call is a pipeline: chunk k's kernel runs
+ * while chunk k-1 crosses PCIe and chunk k-2 is copied from staging into the caller's arrays, so the phases overlap and do not add up to
+ * total_ms). */
 typedef struct {
     double total_ms;        /* wall time of the call                                                                    */
     double kernel_ms;       /* sum of the chunks' launch durations (HIP events on the launch stream)                    */

@@ -45,6 +45,31 @@ def test_host_pipeline_of_several_chunks_matches_oracle(name, pinned, gpu_ctx, m
     assert de["host_stats"]["bytes_d2h"] >= n * (5 * nm.n_initial + 4 + 20 * ((T + 3) // 4) * nm.n_dyn)
 
 
+@pytest.mark.parametrize("pinned_large", [("dyn_val",), ("init_bin", "init_val", "dyn_bin")])
+def test_host_pipeline_with_pinned_and_pageable_large_outputs_matches_oracle(pinned_large, gpu_ctx, model_dir, small_chunks):
+    """Some large outputs pinned, the others pageable: every large output goes through staging (direct == 0), in six chunks, and the
+    trace equals the oracle's."""
+    nm, pp, _ = load_pair("uncor_1200code_v2p1", model_dir)
+    n, T, seed, first, cap = 5300, 240, 0x5EED0003, 2**34 + 9, 512
+    idx = uncor_indices(pp)
+    ref = O.uncor_sample(O.OracleModel(pp), n, T, seed, mode=O.RNG_PHILOX, first_index=first)
+    ni, nd, G4 = nm.n_initial, nm.n_dyn, (T + 3) // 4
+    shapes = dict(init_bin=((ni, n), np.uint8), init_val=((ni, n), np.float32), dyn_bin=((G4, nd, n), np.uint32), dyn_val=((G4, nd, n, 4), np.float32))
+    a = {k: gpu_ctx.pinned_empty(*s) if k in pinned_large else np.zeros(*s) for k, s in shapes.items()}
+    ec, ev, att = np.zeros(n, np.uint32), np.zeros((n, cap), native.EVENT_DTYPE), np.zeros(n, np.int32)
+    p, keep = native.make_params(n, T, seed, first_index=first, event_cap=cap, **idx)
+    o = L.SampleOut()
+    for k, v in a.items():
+        setattr(o, k, v.ctypes.data)
+    o.ev_count, o.events, o.attempts = ec.ctypes.data, ev.ctypes.data, att.ctypes.data
+    L.check(L.lib().emgpu_sample_dbn_host(gpu_ctx._h, nm._h, C.byref(p), C.byref(o)))
+    st = gpu_ctx.host_stats()
+    assert st["chunks"] == 6 and st["chunk_n"] == 1024 and st["direct"] == 0, st
+    got = dict(init_bin=a["init_bin"].T.copy(), init_val=a["init_val"].T.copy(), dyn_bin=native.unpack_dyn_bin(a["dyn_bin"], T),
+               dyn_val=native.unpack_dyn_val(a["dyn_val"], T), attempts=att, events=[ev[i, : ec[i]] for i in range(n)])
+    assert_uncor_parity(got, ref, T)
+
+
 def test_host_pipeline_fills_columns_of_a_larger_pageable_array(gpu_ctx, model_dir, small_chunks):
     """ld / col_offset through the chunked path: three calls fill one caller-owned trace (pageable numpy arrays, as a C or MATLAB host has
     them), columns outside the calls untouched; equal to one call for the whole range."""

@@ -1,5 +1,7 @@
 """UncorEncounterModel.sample(..., lazy=True) on the GPU: the four outputs against the eager call bit for bit (dtype, shape and every element),
 and against the oracle's events2samples / events2controls."""
+import ctypes as C
+
 import numpy as np
 import pytest
 
@@ -142,3 +144,62 @@ def test_lazy_sample_matches_reference_outputs(gpu_ctx, model_dir):
             ctl[:, 1] /= 60.0; ctl[:, 2] = np.deg2rad(ctl[:, 2]); ctl[:, 3] *= 1.68780972222222
             np.testing.assert_allclose(out_EME[i].event, ctl, rtol=1.2e-7, atol=0)
             assert out_EME[i].event[0, 0] == 0
+
+
+def _uncor_host_call(ctx, nm, n, T, seed, ctrl, ids, traj_pinned, rows_pinned, events_cap, controls_cap):
+    """emgpu_sample_uncor_host through ctypes, the per-trajectory arrays and the row arrays each pinned (the context's pool) or pageable.
+    Returns (rc, totals, arrays trimmed to the totals, host_stats)."""
+    ni = nm.n_initial
+    tr = ctx.pinned_empty if traj_pinned else (lambda shape, dt: np.full(shape, 0xAB, dtype=dt) if np.dtype(dt).kind in "ui" else np.full(shape, np.nan, dt))
+    ro = ctx.pinned_empty if rows_pinned else (lambda shape, dt: np.zeros(shape, dtype=dt))
+    p, keep = native.make_params(n, T, seed, event_cap=256, first_index=77, **ids)
+    a = dict(inits=tr((n, ni), np.float64), ev_count=tr((n,), np.uint32), ctrl_count=tr((n,), np.uint32), attempts=tr((n,), np.int32),
+             samples=tr((n, ni, T), np.float64), events=ro((max(events_cap, 1),), native.EVENT_DTYPE), controls=ro((max(controls_cap, 1), 4), np.float64))
+    totals = np.zeros(2, dtype=np.int64)
+    o = L.UncorOut()
+    for k, v in a.items():
+        setattr(o, k, v.ctypes.data)
+    o.events_cap, o.controls_cap, o.totals = events_cap, controls_cap, totals.ctypes.data
+    o.ctrl_var[:] = list(ctrl)
+    rc = L.lib().emgpu_sample_uncor_host(ctx._h, nm._h, C.byref(p), C.byref(o))
+    a["events"], a["controls"] = a["events"][: int(totals[0])], a["controls"][: int(totals[1])]
+    return rc, (int(totals[0]), int(totals[1])), {k: np.array(v) for k, v in a.items()}, ctx.host_stats()
+
+
+@pytest.mark.parametrize("traj_pinned,rows_pinned", [(True, True), (False, False), (True, False), (False, True)])
+def test_uncor_host_across_several_chunks_equals_one_chunk(traj_pinned, rows_pinned, gpu_ctx, model_dir, monkeypatch):
+    """emgpu_sample_uncor_host in chunks of 1 024 trajectories (five chunks) against one chunk, bit for bit, with the per-trajectory arrays
+    and the row arrays pinned or pageable in every combination; then capacities that run out in a later chunk (events in the second,
+    controls in the third): ERR_EVENT_CAP with the one-chunk call's totals."""
+    mdl = E.UncorEncounterModel(parameters_filename=em_io.materialize_model("uncor_1200code_v2p1", model_dir))
+    nm, labs = mdl.native, mdl.labels_initial
+    var = lambda s: labs.index('"%s"' % s) + 1
+    ids = dict(idx_L=var("L"), idx_v=var("v"), idx_dh=var("\\dot h"))
+    ctrl = (var("\\dot h"), var("\\dot \\psi"), var("\\dot v"))
+    n, T, seed = 5000, 240, 31
+    call = lambda ev_cap, ct_cap: _uncor_host_call(gpu_ctx, nm, n, T, seed, ctrl, ids, traj_pinned, rows_pinned, ev_cap, ct_cap)
+    monkeypatch.setenv("EMGPU_HOST_CHUNK_MB", "8192")
+    rc, totals, one, st = call(n * 256, n * 256)
+    assert rc == L.OK and st["chunks"] == 1 and totals == (len(one["events"]), len(one["controls"]))
+    assert one["attempts"].min() >= 1 and totals[0] > 0 and totals[1] > 0
+    rc, t_exact, one_exact, _ = call(*totals)
+    assert rc == L.OK and t_exact == totals
+    monkeypatch.setenv("EMGPU_HOST_CHUNK_MB", "1")
+    rc, t_many, many, st = call(*totals)
+    assert rc == L.OK and t_many == totals
+    assert st["chunks"] == 5 and st["chunk_n"] == 1024 and st["direct"] == int(traj_pinned and rows_pinned), st
+    assert st["event_rows"] == totals[0]
+    for k in one:
+        assert _same(many[k], one[k]), k
+        assert _same(one_exact[k], one[k]), k
+    # capacities that run out after the first chunk: the rows the call needs, as from one chunk
+    ev_cap = int(one["ev_count"][:2048].sum()) - 1
+    ct_cap = int(one["ctrl_count"][:3072].sum()) - 1
+    assert ev_cap >= int(one["ev_count"][:1024].sum()) and ct_cap >= int(one["ctrl_count"][:2048].sum())
+    for caps in ((ev_cap, totals[1]), (totals[0], ct_cap), (ev_cap, ct_cap)):
+        rc, t_short, _, st = call(*caps)
+        assert rc == L.ERR_EVENT_CAP and t_short == totals and st["chunks"] == 5, (caps, t_short)
+        monkeypatch.setenv("EMGPU_HOST_CHUNK_MB", "8192")
+        rc, t_short1, _, st = call(*caps)
+        assert rc == L.ERR_EVENT_CAP and t_short1 == totals and st["chunks"] == 1, (caps, t_short1)
+        monkeypatch.setenv("EMGPU_HOST_CHUNK_MB", "1")

@@ -1,5 +1,5 @@
 """tools/host_path_probe.py [n] -- emgpu_sample_dbn_host at n x 240 s of uncor_1200code_v2p1 under the pipeline's knobs (one child process per
-setting: the knobs are read once): EMGPU_HOST_DIRECT (pinned outputs: rows | 2d), EMGPU_HOST_CHUNK_MB, EMGPU_HOST_THREADS."""
+setting: the knobs are read once): EMGPU_HOST_CHUNK_MB, EMGPU_HOST_THREADS."""
 import json, os, subprocess, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CHILD = r"""
@@ -27,7 +27,7 @@ res["pageable"] = ctx.host_stats()
 print("RESULT " + json.dumps(res))
 """
 n = int(sys.argv[1]) if len(sys.argv) > 1 else 1_000_000
-settings = [{}, {"EMGPU_HOST_DIRECT": "2d"}, {"EMGPU_HOST_CHUNK_MB": "4096"}, {"EMGPU_HOST_CHUNK_MB": "512"}, {"EMGPU_HOST_CHUNK_MB": "128"},
+settings = [{}, {"EMGPU_HOST_CHUNK_MB": "4096"}, {"EMGPU_HOST_CHUNK_MB": "512"}, {"EMGPU_HOST_CHUNK_MB": "128"},
             {"EMGPU_HOST_CHUNK_MB": "64"}, {"EMGPU_HOST_THREADS": "4"}, {"EMGPU_HOST_THREADS": "16"}, {"EMGPU_HOST_THREADS": "16", "EMGPU_HOST_CHUNK_MB": "128"},
             {"EMGPU_HOST_THREADS": "2"}]
 for sset in settings:
