@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- throughput of the MI355X-native encounter sampler on N GPUs of one node.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config uncor|cor|mixed|terminal]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config uncor|cor|mixed|terminal] [--full]
 
 --config uncor (default; BASELINE.json configs[1], the configuration the headline metric is quoted
 on): uncor_1200code_v2p1 initial + transition DBN, 10 M trajectories x 240 s per GPU,
@@ -18,10 +18,14 @@ index range with no collective (torch.distributed is only the barrier and the ma
 
 Prints ONE JSON line on rank 0 (contract in the task statement), including
   roofline     -- algorithmic bytes / average step duration on the launch stream (HIP events)
-                  against the 8 TB/s HBM3E peak,
+                  against the 8 TB/s HBM3E peak.
+A plain run does only what that line's headline needs: it sets up (trace placement included), pre-warms, warms up, times the
+K steps, writes --dump-outputs and prints the line.  Everything else it can measure takes runs of its own and comes with --full:
   cpu_baseline -- the CPU oracle (oracle/em_oracle.c, "port") timed on this host, rank 0, N=1 only,
-  configs      -- BASELINE.json configs[2..4] + config 2 under PER_STEP, one short entry each,
-  host_path    -- emgpu_sample_dbn_host end to end (PCIe-inclusive; never the headline).
+  configs      -- BASELINE.json configs[2..4] + config 2 under PER_STEP, one short entry each (default config only),
+  host_path    -- emgpu_sample_dbn_host end to end (PCIe-inclusive; never the headline; default config only),
+  roofline.streaming_write / sclk_mhz / socket_power_w, config.box_state -- the write ceiling of the step's own buffers and the
+                  GPU's telemetry, each measured after the timed region.
 The line holds NUMBERS ONLY (it must fit the few KB of tail its reader keeps): what every field means and how it is measured is
 NOTES below = profiles/r06_bench_notes.json (`--write-notes`); the verbose record of a run (settle groups, telemetry, pre-warm) goes to
 stderr as one `DETAIL {...}` line and to `--detail-out FILE`.
@@ -114,10 +118,15 @@ def parse_args(argv=None):
     ap.add_argument("--model", default=None, help="uncor / cor: another packed model (or a reference-format .txt path)")
     ap.add_argument("--seconds", type=int, default=DEFAULT_T, help="trajectory length (the headline metric is quoted at 240)")
     ap.add_argument("--per-step", action="store_true", help="PER_STEP transition semantics instead of REFERENCE_AUTO")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need, in runs of their own after (host path: before) the timed region: the CPU "
+                         "baseline, the GPU telemetry (--telemetry-s) and the write ceiling (roofline.streaming_write) of the measured config, and on "
+                         "the default config the other configs and the host path.  Off: the run sets up, warms up, times the steps, writes "
+                         "--dump-outputs and prints the line")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the `cpu_baseline` object")
     ap.add_argument("--ld-pad", type=int, default=1024, help="pad the trace's leading dimension to a multiple of this many columns")
     ap.add_argument("--no-other-configs", action="store_true",
-                    help="skip the `configs` object (BASELINE.json configs[2..4] measured in the same process after the headline)")
+                    help="--full: skip the `configs` object (BASELINE.json configs[2..4] measured in the same process after the headline)")
     ap.add_argument("--step-gap-ms", type=float, default=0.0,
                     help="DIAGNOSTIC (tools/power_probe.sh): idle this long after every launch; the line then says so and is no benchmark line")
     ap.add_argument("--other-steps", type=int, default=10, help="timed steps of each entry of `configs` (after --other-warmup untimed steps and the settle phase)")
@@ -139,7 +148,7 @@ def parse_args(argv=None):
                          "trace lies in memory decides how fast it is written (profiles/r05_placement_probe.txt).  0 (default): the library's own "
                          "policy (3, more while the two fastest disagree by over 1 %%); 1: the first allocation as it comes.  The line reports the "
                          "candidates' times (roofline.placement) and the first one's as roofline.first_allocation_ms")
-    ap.add_argument("--no-host-path", action="store_true", help="skip the `host_path` object (emgpu_sample_dbn_host end to end at 1 M trajectories)")
+    ap.add_argument("--no-host-path", action="store_true", help="--full: skip the `host_path` object (emgpu_sample_dbn_host end to end at 1 M trajectories)")
     ap.add_argument("--host-n", type=int, default=1_000_000, help="trajectories of the `host_path` measurements")
     ap.add_argument("--detail-out", default=None, help="write the verbose record of the run (what the line leaves out: settle groups, pre-warm, telemetry, samples) to this file")
     ap.add_argument("--verbose-line", action="store_true",
@@ -147,7 +156,7 @@ def parse_args(argv=None):
                          "roofline.gpu_telemetry, roofline.avg_step_ms ... pass this); the default line holds numbers only")
     ap.add_argument("--write-notes", default=None, help="write NOTES (what every field of the line means and how it is measured) to this file and exit")
     ap.add_argument("--telemetry-s", type=float, default=2.5,
-                    help="seconds of untimed back-to-back steps AFTER the timed region during which the shader clock and socket power are read (0: skip); "
+                    help="--full: seconds of untimed back-to-back steps AFTER the timed region during which the shader clock and socket power are read (0: skip); "
                          "nothing is sampled inside the timed region")
     ap.add_argument("--ranges-out", default=None,
                     help="TEST HOOK: a directory into which every rank writes rank<r>.json = the global index range (and model blocks) of every step it "
@@ -797,7 +806,8 @@ def measure(w, pl, args, warmup, steps, settle_max=0, dump_dir=None):
     durations come from HIP events on the stream the kernels are launched on.  Returns (elapsed_s max over ranks, [ms per step]).
     settle_max > 0 (the entries of `configs`, which start after seconds of GPU idleness): between the warm-up and the timed region, untimed
     groups of four back-to-back steps until the last two of a group agree within 1 % (w.settle says how many it took).
-    dump_dir: write the last timed step's outputs there (write_outputs) before anything else runs on the buffers."""
+    dump_dir: write the last timed step's outputs there (write_outputs) before anything else runs on the buffers.
+    --full: then --telemetry-s of untimed steps while the GPU's clock and power are read (w.telemetry)."""
     # one untimed barrier + max-reduce first: a process group's first collectives set its communicator up (RCCL: lazily, hundreds of ms
     # with 8 ranks) -- that must never land between t0 and t1 of a 0.1 s timed region
     pl.barrier()
@@ -806,7 +816,7 @@ def measure(w, pl, args, warmup, steps, settle_max=0, dump_dir=None):
     # milliseconds of GPU idleness, and the governor drops the clock within 3 ms: the first timed steps then read 5-10 % long)
     ev = [(pl.event(), pl.event()) for _ in range(steps)]
     tel = None
-    if hasattr(pl, "torch") and getattr(args, "telemetry_s", 0.0) > 0.0:
+    if getattr(args, "full", False) and hasattr(pl, "torch") and getattr(args, "telemetry_s", 0.0) > 0.0:
         idx = getattr(getattr(pl, "dev", None), "index", 0) or 0
         try:
             pr = pl.torch.cuda.get_device_properties(idx)
@@ -863,7 +873,7 @@ def measure(w, pl, args, warmup, steps, settle_max=0, dump_dir=None):
     w.check()
     if dump_dir:
         write_outputs(w, dump_dir)
-    if tel and tel.dir and getattr(args, "telemetry_s", 0.0) > 0.0:
+    if tel and tel.dir:
         # The SMU's clock / power readings are moving averages that trail the load by more than a second (tools/power_probe.sh: 2 s from
         # idle to the sustained values), the timed region lasts tens of milliseconds: what the box does under THIS step is read in an
         # untimed run of the same back-to-back launches, from its last 40 %.
@@ -902,7 +912,8 @@ def box_state(tel, w=None):
     return "below-the-power-limit"   # (e.g. 1 27x W at the full 2 39x MHz: a kernel that never reaches the limit)
 
 
-def roofline_of(w, step_ms, lib_version):
+def roofline_of(w, step_ms, lib_version, write_ceiling=True):
+    """The roofline figures of the timed steps; write_ceiling: also time the write ceiling on the step's buffers (runs of its own, --full)."""
     avg_step_s = (sum(step_ms) / len(step_ms)) * 1e-3
     alg = w.bytes_per_unit * w.n
     achieved = alg / avg_step_s / 1e9
@@ -939,7 +950,7 @@ def roofline_of(w, step_ms, lib_version):
         r["bound"] = "valu-issue"
         if insts and r.get("sclk_mhz"):
             r["issue_frac"] = insts * 4.0 / (1024.0 * (r["avg_launch_ms"] * 1e-3) * (r["sclk_mhz"] * 1e6))
-    sw = w.streaming_write() if hasattr(w, "streaming_write") else None
+    sw = w.streaming_write() if write_ceiling and hasattr(w, "streaming_write") else None
     if sw:   # measured AFTER the timed region (the buffers' contents were checked by then)
         r["streaming_write"] = sw
         r["frac_of_streaming_write"] = achieved / sw["GB/s"]
@@ -957,11 +968,12 @@ NOTES = {
               "values are f32 at the boundary (f64 arithmetic inside, rounded on store), uniforms 32-bit",
     "roofline": "achieved = algorithmic bytes (SURVEY.md 8d) / average launch duration from HIP events on the launch stream; peak = 8 TB/s; traffic = "
                 "WRITE_SIZE + 2 x FETCH_SIZE of a committed PMC pass of the same kernel, launch size and source hash (profiles/*_summary.json), else null; "
-                "frac_of_streaming_write = achieved / what torch's fill kernel reaches on the same buffers on this box",
+                "frac_of_streaming_write = achieved / what torch's fill kernel reaches on the same buffers on this box (--full); sclk_mhz, socket_power_w = "
+                "the GPU's telemetry under the same step after the timed region (--full)",
     "placement": "the trace comes from emgpu_trace_alloc (include/emgpu.h): the library allocates `candidates` traces, loads the device for 0.5 s, times "
                  "2 untimed + 5 timed launches of this workload's own call on each, twice, keeps the fastest and frees the others; ms = per candidate in "
                  "allocation order; first_allocation_ms = ms[0] = what a caller who keeps its first allocation gets on this box (profiles/r05_placement_probe.txt)",
-    "configs": "BASELINE.json configs[2..4] at their single-GPU sizes + config 2 under PER_STEP, measured in this process after the headline: 5 warm-up steps, "
+    "configs": "--full, default config: BASELINE.json configs[2..4] at their single-GPU sizes + config 2 under PER_STEP, measured in this process after the headline: 5 warm-up steps, "
                "settle (groups of 4 untimed steps until the last two agree within 1 % and two groups' means within 0.5 %, at most 48), 10 timed steps; "
                "cpu = the oracle on all allowed cores, about 3 s per leg",
     "uncor_per_step": "config 2 under EMGPU_TRANSITION_PER_STEP: the true per-timestep DBN of dbn_sample.m:65-93 instead of the frozen-parent branch "
@@ -973,9 +985,9 @@ NOTES = {
                 "draw with rejection) + k_terminal_geo + k_terminal_propagate; frac follows SURVEY.md 8(d): 75 B + 15 B per track-second; "
                 "frac_of_output_bytes charges what is stored: 75 B + 20 B per row written; bound valu-issue: issue_frac = SQ_INSTS_VALU x 4 cycles / "
                 "(1 024 SIMDs x kernel time x sclk) from the committed PMC pass",
-    "cpu_baseline": "oracle/em_oracle.c (scalar port of the reference algorithm), Philox mode, thread-private dense outputs, on `cores` threads = the cgroup's "
+    "cpu_baseline": "--full, one GPU: oracle/em_oracle.c (scalar port of the reference algorithm), Philox mode, thread-private dense outputs, on `cores` threads = the cgroup's "
                     "CPU quota; single_thread_value beside it; MATLAB itself is not installed and cannot be timed",
-    "host_path": "emgpu_sample_dbn_host end to end at --host-n trajectories x 240 s of uncor_1200code_v2p1, third call of each kind (the first pins memory), "
+    "host_path": "--full, default config: emgpu_sample_dbn_host end to end at --host-n trajectories x 240 s of uncor_1200code_v2p1, third call of each kind (the first pins memory), "
                  "measured BEFORE the headline (a process that has laid a torch tensor over a 36 GB trace -- this script's own plumbing -- and freed the trace copies at "
                  "47 GB/s afterwards: tools/host_path_bisect.sh): "
                  "dense_pinned = outputs in emgpu_host_alloc memory (the copy engine writes into the caller's arrays); dense_pageable = the caller's own "
@@ -984,7 +996,7 @@ NOTES = {
                  "pinned_d2h_GBps = one 1 GiB hipMemcpy device -> pinned on this box; class_sample = UncorEncounterModel.sample(n, 240) (class level, "
                  "event lists + numpy reconstruction of out_samples / EncounterModelEvents): native_s = the library calls, format_s = the numpy / Python part",
     "box_state": "fast / slow / below-the-power-limit by socket power and shader clock under the step (HISTORY.md section 7); since round 5 known to follow "
-                 "the trace's placement, which the library now picks",
+                 "the trace's placement, which the library now picks; read from the telemetry of --full (a plain run says unknown)",
 }
 
 
@@ -1152,7 +1164,7 @@ def run_rank(args, rank, local_rank, world, pl=None, out=sys.stdout):
     pl = pl or TorchRocm(rank, local_rank, world, args.oversubscribe)
     default_run = world == 1 and args.config == "uncor" and not args.model and not args.n and hasattr(pl, "release")
     hp, hp_detail = None, {"host_path": {}}
-    if rank == 0 and default_run and not args.no_host_path:
+    if rank == 0 and args.full and default_run and not args.no_host_path:
         # FIRST, in the state a consumer's process is in: once this process has laid a torch tensor over a 36 GB trace (the plumbing of the checks
         # below) and then FREED that trace, the host path's copies run at 47 instead of 56.5 GB/s (40 instead of 55 through the staging buffers) --
         # tools/host_path_bisect.sh; a trace that is only touched through the C ABI, or that stays alive, does not have that effect
@@ -1175,7 +1187,7 @@ def run_rank(args, rank, local_rank, world, pl=None, out=sys.stdout):
         total = w.n * world * args.steps
         lib_version = L.lib().emgpu_version().decode()
         kernel = w.kernel_name()
-        roof = roofline_of(w, step_ms, lib_version)
+        roof = roofline_of(w, step_ms, lib_version, write_ceiling=args.full)
         wc = w.config()
         detail = {"config": wc, "roofline": roof, "configs": {}, "host_path": hp_detail["host_path"], "notes": NOTES}
         line = {
@@ -1196,11 +1208,11 @@ def run_rank(args, rank, local_rank, world, pl=None, out=sys.stdout):
             line["oversubscribed"] = True
         if args.step_gap_ms > 0.0:
             line["diagnostic"] = "idle gaps of %g ms between the launches (--step-gap-ms): value and ms_per_step include them" % args.step_gap_ms
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             c = w.cpu_baseline(args.cpu_sample)
             detail["cpu_baseline"] = c
             line["cpu_baseline"] = compact_cpu(c)
-        if default_run and not args.no_other_configs:
+        if args.full and default_run and not args.no_other_configs:
             if hasattr(w, "close"):
                 w.close()
             w = None

@@ -820,7 +820,9 @@ def test_bench_launches_its_own_ranks(tmp_path):
     if torch.cuda.device_count() < 2:
         r = subprocess.run(cmd, env=env, capture_output=True, timeout=900)
         assert r.returncode == 3 and r.stdout.decode().strip() == ""
-    r = subprocess.run(cmd[:2] + ["--config", "mixed", "--steps", "2", "--warmup", "1", "--n", "300000", "--no-cpu-baseline"], env=env, capture_output=True, timeout=900)
+    # --full: the write ceiling and the telemetry asserted below are measured in runs of their own, which a plain run leaves out
+    r = subprocess.run(cmd[:2] + ["--config", "mixed", "--steps", "2", "--warmup", "1", "--n", "300000", "--no-cpu-baseline", "--full"], env=env,
+                       capture_output=True, timeout=900)
     assert r.returncode == 0, r.stderr.decode()[-2000:]
     line = json.loads(r.stdout.decode().strip().splitlines()[-1])
     assert line["n_gpus"] == 1 and line["config"]["kernel"] == "k_uncor_fast_mixed<7,4,6,6>" and len(line["config"]["models"]) == 6
@@ -917,6 +919,28 @@ def test_bench_launcher_with_four_ranks(tmp_path):
     assert line["n_gpus"] == W and line["oversubscribed"] is True and line["scaling"] == "weak"
     assert line["value"] > 0 and abs(line["value"] - W * 20000 * 2 / (line["ms_per_step"] * 2e-3)) < 1e-6 * line["value"]   # the whole job's units / the slowest rank's time
     assert "configs" not in line and "cpu_baseline" not in line
+
+
+def test_a_plain_bench_run_is_lean():
+    """`bench.py --steps K --warmup W` on the default config (the headline's full 10 M x 240 s step): the line's headline and nothing that
+    takes runs of its own (CPU baseline, other configs, host path, write ceiling, telemetry: --full), and at most 30 s of the whole process
+    outside its K + W steps."""
+    import json
+    import subprocess
+    import time
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK")}
+    steps, warm = 10, 5
+    t0 = time.perf_counter()
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", str(steps), "--warmup", str(warm)], env=env,
+                       capture_output=True, timeout=600)
+    wall = time.perf_counter() - t0
+    assert r.returncode == 0, r.stderr.decode()[-2000:]
+    line = json.loads(r.stdout.decode().strip().splitlines()[-1])
+    assert line["n_gpus"] == 1 and line["steps"] == steps and line["warmup"] == warm and line["value"] > 0 and line["higher_is_better"] is True
+    assert abs(line["value"] - 10_000_000 * steps / (line["ms_per_step"] * steps * 1e-3)) < 1e-6 * line["value"]
+    assert not {"cpu_baseline", "configs", "host_path"} & set(line), sorted(line)
+    assert "streaming_write_GBps" not in line["roofline"] and "sclk_mhz" not in line["roofline"] and len(line["roofline"]["step_ms"]) == steps
+    assert wall - (steps + warm) * line["ms_per_step"] * 1e-3 < 30.0, wall
 
 
 def test_bench_dump_outputs(tmp_path):

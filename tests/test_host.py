@@ -959,3 +959,112 @@ def test_bench_box_state_rule():
     assert bench.box_state(tel(1287.0, 2392.0)).startswith("below-the-power-limit")        # full clock: the kernel never reaches the limit
     assert bench.box_state(tel(1293.0, 2273.0)).startswith("below-the-power-limit")        # (between the two: 6.56 ms in profiles/r05_placement_probe.txt)
     assert bench.box_state(None).startswith("unknown") and bench.box_state({}).startswith("unknown")
+
+
+def test_a_plain_bench_run_measures_only_its_headline(monkeypatch):
+    """bench.run_rank without --full: set up, warm up, the timed steps and the line -- no host path, CPU baseline, other configs, telemetry
+    or write ceiling, each of which takes runs of its own; with --full every one of them runs and is in the line, and the --no-* options
+    still narrow it.  A workload and plumbing that count what runs stand in for the GPU."""
+    import io
+    import json
+    import time
+    import types
+    sys.path.insert(0, ROOT)
+    import bench
+    ran = []
+
+    def no_device(idx):
+        raise RuntimeError("no device here")
+
+    class Pl:
+        torch = types.SimpleNamespace(cuda=types.SimpleNamespace(get_device_properties=no_device))
+
+        def barrier(self):
+            pass
+
+        def max_over_ranks(self, x):
+            return x
+
+        def event(self):
+            return [0.0]
+
+        def record(self, ev):
+            ev[0] = time.perf_counter()
+
+        def elapsed_ms(self, a, b):
+            return (b[0] - a[0]) * 1e3
+
+        def release(self):
+            pass
+
+        def finish(self):
+            pass
+
+    class W:
+        n, bytes_per_unit, launches_per_step, ranges = 1000, 3635, 1, []
+
+        def step(self, k):
+            ran.append("step")
+
+        def sync(self):
+            pass
+
+        def check(self):
+            pass
+
+        def close(self):
+            pass
+
+        def kernel_name(self):
+            return "k_fake"
+
+        def config(self):
+            return {"workload": "fake"}
+
+        def streaming_write(self):
+            ran.append("streaming_write")
+            return {"GB/s": 5000.0}
+
+        def cpu_baseline(self, n, seconds=10.0):
+            ran.append("cpu_baseline")
+            return {"value": 1.0, "unit": "u", "cores": 1, "kind": "port", "single_thread_value": 1.0, "sample": "s"}
+
+    class Tel:
+        def __init__(self, *a):
+            self.dir = self.card = "fake"
+
+        def start(self):
+            ran.append("telemetry")
+
+        def stop(self):
+            pass
+
+        def summary(self, tail=1.0):
+            return {"sclk_mhz": {"median": 2000.0}, "socket_power_w": {"median": 1300.0}}
+
+    monkeypatch.setattr(bench, "make_workload", lambda args, pl, rank, world: W())
+    monkeypatch.setattr(bench, "host_path", lambda args, pl, detail: ran.append("host_path") or {"n": 1})
+    monkeypatch.setattr(bench, "other_configs", lambda args, pl, lib_version, detail: ran.append("other_configs") or {})
+    monkeypatch.setattr(bench, "GpuTelemetry", Tel)
+
+    def run(*extra):
+        del ran[:]
+        out = io.StringIO()
+        args = bench.parse_args(["--steps", "3", "--warmup", "2", "--prewarm-s", "0", "--telemetry-s", "0.01"] + list(extra))
+        line = bench.run_rank(args, 0, 0, 1, pl=Pl(), out=out)
+        assert json.loads(out.getvalue()) == line
+        assert line["metric"] == bench.CONFIGS["uncor"]["metric"] and line["unit"] == "trajectories/s" and line["higher_is_better"] is True
+        assert line["steps"] == 3 and abs(line["value"] * line["ms_per_step"] * 1e-3 - 1000) < 1e-6 * 1000 and line["dtype"]
+        return line, [x for x in ran if x != "step"]
+
+    line, extra = run()
+    assert extra == [] and ran == ["step"] * 5                      # the warm-up and the timed steps, nothing else
+    assert not {"cpu_baseline", "configs", "host_path"} & set(line) and line["config"]["box_state"].startswith("unknown")
+    assert "streaming_write_GBps" not in line["roofline"] and "sclk_mhz" not in line["roofline"] and line["roofline"]["step_ms"]
+    line, extra = run("--full")
+    assert extra == ["host_path", "telemetry", "streaming_write", "cpu_baseline", "other_configs"], extra
+    assert line["host_path"] == {"n": 1} and line["configs"] == {} and line["cpu_baseline"]["value"] == 1.0
+    assert line["roofline"]["streaming_write_GBps"] == 5000.0 and line["roofline"]["sclk_mhz"] == 2000.0
+    assert line["config"]["box_state"] == "below-the-power-limit"
+    _, extra = run("--full", "--no-cpu-baseline", "--no-other-configs", "--no-host-path")
+    assert extra == ["telemetry", "streaming_write"], extra

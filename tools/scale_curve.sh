@@ -21,10 +21,10 @@ for N in ${GPUS:-1 2 4 8}; do
   if [ "$N" -gt "$have" ]; then echo "n=$N: skipped (only $have GPU(s) visible)"; continue; fi
   rm -rf $OUT/ranges_n$N
   if [ "$N" -eq 1 ]; then
-    python bench.py --gpus 1 --steps ${STEPS:-20} --warmup ${WARMUP:-5} --no-other-configs --no-host-path --ranges-out $OUT/ranges_n$N --detail-out $OUT/n$N.detail.json "$@" > $OUT/n$N.json 2> $OUT/n$N.err
+    python bench.py --full --gpus 1 --steps ${STEPS:-20} --warmup ${WARMUP:-5} --no-other-configs --no-host-path --ranges-out $OUT/ranges_n$N --detail-out $OUT/n$N.detail.json "$@" > $OUT/n$N.json 2> $OUT/n$N.err
   else
     HSA_ENABLE_IPC_MODE_LEGACY=0 python -m torch.distributed.run --nnodes=1 --nproc-per-node $N --master-addr 127.0.0.1 --master-port ${PORT:-29511} \
-      bench.py --gpus $N --steps ${STEPS:-20} --warmup ${WARMUP:-5} --ranges-out $OUT/ranges_n$N --detail-out $OUT/n$N.detail.json "$@" > $OUT/n$N.json 2> $OUT/n$N.err
+      bench.py --full --gpus $N --steps ${STEPS:-20} --warmup ${WARMUP:-5} --ranges-out $OUT/ranges_n$N --detail-out $OUT/n$N.detail.json "$@" > $OUT/n$N.json 2> $OUT/n$N.err
   fi
   echo "n=$N rc=$? $(tail -1 $OUT/n$N.json | cut -c1-240)"
 done
