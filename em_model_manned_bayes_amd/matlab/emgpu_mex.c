@@ -1,12 +1,15 @@
 /*
  * emgpu_mex.c -- MATLAB gateway to libemgpu.so (include/emgpu.h).
  *
- * NOT RUN: neither MATLAB nor mex.h exists in the build image (tests only type-check this file against a
- * declaration-only stand-in, tests/stubs/mex.h); this is the binding a maintainer compiles on a machine
- * that has both:
+ * A maintainer compiles it on a machine that has MATLAB:
  *     mex -R2018a emgpu_mex.c -I<repo>/include -L<repo>/em_model_manned_bayes_amd -lemgpu
+ * RUN WITHOUT MATLAB: neither MATLAB nor its mex.h exists in the build image, so the tests compile this file against a small
+ * working implementation of the mex API (tests/stubs/mex.h + mex_runtime.c) and execute every command below through it:
+ * tests/test_mex_gateway.py (model commands, usage and error table) and tests/test_gpu_mex_gateway.py (every sampling command
+ * against native.py and the CPU oracle).  NOT RUN: the .m classes and shadows that call this file; they need MATLAB.
  *
  * One entry point, dispatched on a command string (MATLAB calls are single threaded).  Handles are uint64 scalars.
+ * Seeds, first indices and counts arrive as MATLAB doubles: they are exact up to 2^53 - 1 and no further.
  *
  *   model
  *     h = emgpu_mex('load_txt', filename, idxZeroBoundaries, isOverwriteZeroBoundaries)            em_read.m:1,41-42
@@ -19,6 +22,7 @@
  *         emgpu_mex('free', h)
  *   devices
  *     n = emgpu_mex('device_count');   emgpu_mex('use_devices', [0 1 ...])   later sample_uncor calls are split over them
+ *         emgpu_mex('shutdown')            frees the gateway's device contexts (also done when the mex file is cleared); the next call makes new ones
  *   sampling
  *     S = emgpu_mex('bn_sample', h, num_samples, seed, first_index)                                bn_sample.m:1 (bins)
  *     [initial, ev_count, events] = emgpu_mex('sample_uncor', h, n, T, seed, first_index, flags, idxL, idxV, idxDH, layers, event_cap)
@@ -36,6 +40,7 @@
  *         CorTerminalModel.track (track.m:45-150) in device rounds: dyn_limits 5 x 2, cumturn_pitch = [maxCumTurn1 maxCumTurn2 pitch1 pitch2],
  *         thresholds = [minEncTime_s thresDist_ft thresAltLow_ft thresVertRate_ft_s], idx12 = variable ids of own / int {distance bearing alt
  *         speed heading intent}; sample n_i x n, traj 6 x cap2 x 2 x n, len 2 x n, meta 4 x n [tcpa_s hmd_ft vmd_ft enc_time_s]
+ *         at max_track_attempts the call RETURNS (no error): attempts = -1 and all-zero sample / traj / len / meta mark the encounters still rejected
  *     [xyz, flags, vminmax] = emgpu_mex('sample2track', alt0, speed0, updates, ur, min_speed, max_speed)   sample2track.m:182-243
  *
  * Errors keep the reference's identifiers where it has them: prior:notdbe / prior:unknown (bn_dirichlet_prior.m:28,37);
@@ -59,10 +64,15 @@ static void shutdown_all(void) {
     g_nctx = 0;
 }
 
+static emgpu_model *g_pending = NULL; /* a model this call created and has not handed out yet: freed when the call ends in an error */
+
 static void check(int rc) {
     if (rc >= 0) return;
     const char *id = "emgpu:error";
-    const char *msg = emgpu_last_error();
+    char msg[1024];
+    strncpy(msg, emgpu_last_error(), sizeof msg - 1);
+    msg[sizeof msg - 1] = 0;
+    if (g_pending) { emgpu_model_free(g_pending); g_pending = NULL; }
     switch (rc) {
     case EMGPU_ERR_PRIOR: id = strstr(msg, "Second argument") ? "prior:unknown" : "prior:notdbe"; break;
     case EMGPU_ERR_PRESET: id = "emgpu:preset"; break;      /* 'Attempt to preset a dependent variable' */
@@ -83,8 +93,11 @@ static void need(int nrhs, int n, const char *usage) {
     if (nrhs < n) mexErrMsgIdAndTxt("emgpu:usage", "%s", usage);
 }
 
+/* handles are uint64: what MATLAB makes of a mistyped one (a double, a logical, text, a cell, a struct) is refused before it is read as one */
+static int is_handles(const mxArray *a) { return !mxIsDouble(a) && !mxIsLogical(a) && !mxIsChar(a) && !mxIsCell(a) && !mxIsStruct(a); }
+
 static emgpu_model *handle_of(const mxArray *a) {
-    if (mxGetNumberOfElements(a) < 1) mexErrMsgIdAndTxt("emgpu:usage", "empty model handle");
+    if (!is_handles(a) || mxGetNumberOfElements(a) < 1) mexErrMsgIdAndTxt("emgpu:usage", "a model handle is the uint64 that load_txt / from_struct / load_bin returned");
     return (emgpu_model *)(uintptr_t)(*(uint64_t *)mxGetData(a));
 }
 
@@ -156,6 +169,28 @@ static mxArray *labels_cell(emgpu_model *m, int field) {
     return cell;
 }
 
+/* cell of character vectors -> one '\n'-separated string (emgpu_model_desc.labels_*); NULL when the struct has no such cell */
+static char *labels_joined(const mxArray *cell) {
+    if (!cell || !mxIsCell(cell) || mxIsEmpty(cell)) return NULL;
+    const size_t n = mxGetNumberOfElements(cell);
+    size_t len = 0;
+    for (size_t i = 0; i < n; i++) {
+        const mxArray *c = mxGetCell(cell, i);
+        if (!c || !mxIsChar(c)) mexErrMsgIdAndTxt("emgpu:usage", "labels must be cells of character vectors");
+        len += mxGetNumberOfElements(c) + 1;
+    }
+    char *out = (char *)mxMalloc(len + 1);
+    size_t o = 0;
+    for (size_t i = 0; i < n; i++) {
+        const mxArray *c = mxGetCell(cell, i);
+        const size_t k = mxGetNumberOfElements(c);
+        if (mxGetString(c, out + o, k + 1)) mexErrMsgIdAndTxt("emgpu:usage", "labels must be cells of character vectors");
+        o += k;
+        out[o++] = i + 1 < n ? '\n' : 0;
+    }
+    return out;
+}
+
 static void events_out(mxArray *plhs[], int nlhs, size_t n, size_t ni, size_t cap, const float *iv, const uint32_t *ec, const emgpu_event *ev) {
     plhs[0] = mxCreateDoubleMatrix((mwSize)n, (mwSize)ni, mxREAL);
     for (size_t v = 0; v < ni; v++) for (size_t i = 0; i < n; i++) mxGetPr(plhs[0])[v * n + i] = iv[v * n + i];
@@ -176,11 +211,13 @@ static void events_out(mxArray *plhs[], int nlhs, size_t n, size_t ni, size_t ca
 
 void mexFunction(int nlhs, mxArray *plhs[], int nrhs, const mxArray *prhs[]) {
     char cmd[64];
+    g_pending = NULL;
     if (nrhs < 1) mexErrMsgIdAndTxt("emgpu:usage", "first argument must be a command string");
     get_string(prhs[0], cmd, sizeof cmd);
 
     if (!strcmp(cmd, "load_txt") || !strcmp(cmd, "em_read")) {
-        need(nrhs, 2, "emgpu_mex('load_txt' | 'em_read', filename, idxZeroBoundaries, isOverwriteZeroBoundaries)");
+        need(nrhs, 2, strcmp(cmd, "em_read") ? "h = emgpu_mex('load_txt', filename, idxZeroBoundaries, isOverwriteZeroBoundaries)"
+                                             : "s = emgpu_mex('em_read', filename, idxZeroBoundaries, isOverwriteZeroBoundaries)");
         char path[4096];
         get_string(prhs[1], path, sizeof path);
         int32_t idx[EMGPU_MEX_MAX_VARS];
@@ -198,9 +235,15 @@ void mexFunction(int nlhs, mxArray *plhs[], int nrhs, const mxArray *prhs[]) {
             return;
         }
         /* the struct of em_read.m:47-141 */
+        g_pending = m;
         emgpu_model_info_t info;
         check(emgpu_model_info(m, &info));
         const int ni = info.n_initial, nt = info.n_transition;
+        if (ni > EMGPU_MEX_MAX_VARS || nt > 2 * EMGPU_MEX_MAX_VARS) {
+            g_pending = NULL;
+            emgpu_model_free(m);
+            mexErrMsgIdAndTxt("emgpu:usage", "model size outside 1..%d initial variables", EMGPU_MEX_MAX_VARS);
+        }
         static const char *fields[] = {"labels_initial", "n_initial", "G_initial", "order_initial", "r_initial", "N_initial", "labels_transition",
                                        "n_transition", "G_transition", "order_transition", "r_transition", "N_transition", "boundaries",
                                        "resample_rates", "temporal_map", "zero_bins", "bounds_initial", "cutpoints_initial"};
@@ -240,14 +283,14 @@ void mexFunction(int nlhs, mxArray *plhs[], int nrhs, const mxArray *prhs[]) {
         mxArray *bounds = mxCreateDoubleMatrix((mwSize)ni, 2, mxREAL);
         for (int v = 0; v < ni; v++) {
             const int64_t nb = emgpu_model_get_f64(m, EMGPU_F_BOUNDARIES, v + 1, NULL, 0);
-            mxArray *b = mxCreateDoubleMatrix((mwSize)(nb > 0 ? nb : 0), nb > 0 ? 1 : 0, mxREAL);      /* '*' -> empty (em_read.m:97-99) */
+            mxArray *b = mxCreateDoubleMatrix((mwSize)(nb > 0 ? nb : 0), 1, mxREAL);      /* a column; '*' or overwritten -> 0 x 1 (em_read.m:97-99, 120) */
             mxArray *c;
             if (nb > 0) {
                 check((int)emgpu_model_get_f64(m, EMGPU_F_BOUNDARIES, v + 1, mxGetPr(b), nb));
                 double lo = mxGetPr(b)[0], hi = mxGetPr(b)[0];
                 for (int64_t i = 1; i < nb; i++) { lo = fmin(lo, mxGetPr(b)[i]); hi = fmax(hi, mxGetPr(b)[i]); }
                 mxGetPr(bounds)[v] = lo; mxGetPr(bounds)[ni + v] = hi;                                 /* em_read.m:133-134 */
-                c = mxCreateDoubleMatrix(1, (mwSize)(nb - 2), mxREAL);
+                c = mxCreateDoubleMatrix(1, (mwSize)(nb > 2 ? nb - 2 : 0), mxREAL);                   /* (2:end-1)' */
                 for (int64_t i = 1; i + 1 < nb; i++) mxGetPr(c)[i - 1] = mxGetPr(b)[i];
             } else {
                 c = mxCreateDoubleMatrix(1, (mwSize)(r[v] - 1), mxREAL);                              /* 2:n, em_read.m:130-131 */
@@ -264,13 +307,14 @@ void mexFunction(int nlhs, mxArray *plhs[], int nrhs, const mxArray *prhs[]) {
         mxArray *rates = mxCreateDoubleMatrix((mwSize)ni, 1, mxREAL);
         check((int)emgpu_model_get_f64(m, EMGPU_F_RESAMPLE_RATES, 0, mxGetPr(rates), ni));
         mxSetField(s, 0, "resample_rates", rates);
+        g_pending = NULL;
         emgpu_model_free(m);
         plhs[0] = s;
     } else if (!strcmp(cmd, "save_bin")) {
         need(nrhs, 3, "emgpu_mex('save_bin', h, filename)");
         char path[4096];
         get_string(prhs[2], path, sizeof path);
-        check(emgpu_model_save_bin((const emgpu_model *)(uintptr_t)(*(uint64_t *)mxGetData(prhs[1])), path));
+        check(emgpu_model_save_bin(handle_of(prhs[1]), path));
     } else if (!strcmp(cmd, "load_bin")) {
         need(nrhs, 2, "h = emgpu_mex('load_bin', filename)");
         char path[4096];
@@ -291,6 +335,8 @@ void mexFunction(int nlhs, mxArray *plhs[], int nrhs, const mxArray *prhs[]) {
         const mxArray *zb = mxGetField(P, 0, "zero_bins");
         const int nt = (Gt && !mxIsEmpty(Gt)) ? (int)mxGetM(Gt) : 0;
         if (ni < 1 || ni > EMGPU_MEX_MAX_VARS || nt > 2 * EMGPU_MEX_MAX_VARS) mexErrMsgIdAndTxt("emgpu:usage", "model size outside 1..%d initial variables", EMGPU_MEX_MAX_VARS);
+        if ((int)mxGetN(Gi) != ni || (int)mxGetNumberOfElements(Ni) < ni || (!mxIsLogical(Gi) && !mxIsDouble(Gi)))
+            mexErrMsgIdAndTxt("emgpu:usage", "G_initial must be n x n logical or double and N_initial hold n cells");
         emgpu_model_desc d;
         memset(&d, 0, sizeof d);
         int32_t r_i[EMGPU_MEX_MAX_VARS], r_t[2 * EMGPU_MEX_MAX_VARS], tmap[2 * EMGPU_MEX_MAX_VARS], blen[EMGPU_MEX_MAX_VARS], zbin[EMGPU_MEX_MAX_VARS];
@@ -299,34 +345,41 @@ void mexFunction(int nlhs, mxArray *plhs[], int nrhs, const mxArray *prhs[]) {
         d.N_initial = concat_cells(Ni, 0, ni, &d.n_N_initial);
         if (nt) {
             if (!Nt || !mxIsCell(Nt) || !rt) mexErrMsgIdAndTxt("emgpu:usage", "parms needs N_transition and r_transition (dbn_sample.m:25-33)");
+            if ((int)mxGetN(Gt) != nt || (int)mxGetNumberOfElements(Nt) < nt || (int)mxGetNumberOfElements(rt) < nt || nt < ni || (!mxIsLogical(Gt) && !mxIsDouble(Gt)))
+                mexErrMsgIdAndTxt("emgpu:usage", "G_transition must be n_t x n_t logical or double, N_transition and r_transition hold n_t entries");
             for (int i = 0; i < nt; i++) r_t[i] = (int32_t)mxGetPr(rt)[i];
             d.n_transition = nt; d.G_transition = graph_rows(Gt, nt); d.r_transition = r_t;
             d.N_transition = concat_cells(Nt, ni, nt, &d.n_N_transition);                              /* em_read.m:92 */
             if (tm && !mxIsEmpty(tm)) {
                 d.n_dyn = (int32_t)mxGetM(tm);
-                if (d.n_dyn > EMGPU_MEX_MAX_VARS) mexErrMsgIdAndTxt("emgpu:usage", "temporal_map has too many rows");
+                if (d.n_dyn > EMGPU_MEX_MAX_VARS || mxGetN(tm) != 2) mexErrMsgIdAndTxt("emgpu:usage", "temporal_map must be n_dyn x 2 with at most %d rows", EMGPU_MEX_MAX_VARS);
                 for (int k = 0; k < d.n_dyn; k++) { tmap[2 * k] = (int32_t)mxGetPr(tm)[k]; tmap[2 * k + 1] = (int32_t)mxGetPr(tm)[d.n_dyn + k]; }
                 d.temporal_map = tmap;
             }
         }
         double *bflat = NULL;
-        if (bnd && mxIsCell(bnd)) {
+        if (bnd && mxIsCell(bnd) && (int)mxGetNumberOfElements(bnd) >= ni) {
             int64_t tot = 0;
             bflat = concat_cells(bnd, 0, ni, &tot);
             for (int i = 0; i < ni; i++) { const mxArray *c = mxGetCell(bnd, i); blen[i] = c ? (int32_t)mxGetNumberOfElements(c) : 0; }
             d.boundaries = bflat; d.bnd_len = blen;
         }
-        if (zb && mxIsCell(zb)) {
+        if (zb && mxIsCell(zb) && (int)mxGetNumberOfElements(zb) >= ni) {
             for (int i = 0; i < ni; i++) { const mxArray *c = mxGetCell(zb, i); zbin[i] = (c && !mxIsEmpty(c)) ? (int32_t)mxGetPr(c)[0] : 0; }
             d.zero_bins = zbin;
         }
         if (rates && (int)mxGetNumberOfElements(rates) == ni) d.resample_rates = mxGetPr(rates);
+        char *lab_i = labels_joined(mxGetField(P, 0, "labels_initial")), *lab_t = nt ? labels_joined(mxGetField(P, 0, "labels_transition")) : NULL;
+        d.labels_initial = lab_i; d.labels_transition = lab_t;
         emgpu_model *m = NULL;
         const int rc = emgpu_model_from_arrays(&d, &m);
+        if (lab_i) mxFree(lab_i);
+        if (lab_t) mxFree(lab_t);
         mxFree((void *)d.G_initial); mxFree((void *)d.N_initial);
         if (nt) { mxFree((void *)d.G_transition); mxFree((void *)d.N_transition); }
         if (bflat) mxFree(bflat);
         check(rc);
+        g_pending = m;
         const mxArray *st = mxGetField(P, 0, "start");
         if (st && mxIsCell(st) && (int)mxGetNumberOfElements(st) == ni) {
             int32_t s32[EMGPU_MEX_MAX_VARS];
@@ -337,6 +390,7 @@ void mexFunction(int nlhs, mxArray *plhs[], int nrhs, const mxArray *prhs[]) {
             }
             check(emgpu_model_set_start(m, s32, ni));
         }
+        g_pending = NULL;
         plhs[0] = mxCreateNumericMatrix(1, 1, mxUINT64_CLASS, mxREAL);
         *(uint64_t *)mxGetData(plhs[0]) = (uint64_t)(uintptr_t)m;
     } else if (!strcmp(cmd, "set_prior")) {
@@ -355,9 +409,10 @@ void mexFunction(int nlhs, mxArray *plhs[], int nrhs, const mxArray *prhs[]) {
     } else if (!strcmp(cmd, "set_alpha")) {
         need(nrhs, 3, "emgpu_mex('set_alpha', h, dirichlet_initial, dirichlet_transition)");
         emgpu_model *m = handle_of(prhs[1]);
-        for (int pass = 0; pass < 2 && 2 + pass < nrhs; pass++) {
-            const mxArray *cell = prhs[2 + pass];
-            if (!mxIsCell(cell)) continue;
+        const mxArray *alpha[2] = {prhs[2], nrhs > 3 ? prhs[3] : NULL};
+        for (int pass = 0; pass < 2; pass++) {
+            const mxArray *cell = alpha[pass];
+            if (!cell || !mxIsCell(cell)) continue;
             const int n = (int)mxGetNumberOfElements(cell);
             for (int i = 0; i < n; i++) {
                 const mxArray *c = mxGetCell(cell, i);
@@ -428,7 +483,7 @@ void mexFunction(int nlhs, mxArray *plhs[], int nrhs, const mxArray *prhs[]) {
         mxFree(iv); mxFree(ec); mxFree(ev);
         if (layers_rm) mxFree(layers_rm);
     } else if (!strcmp(cmd, "geom_sample")) {
-        need(nrhs, 5, "[outInits, attempts] = emgpu_mex('geom_sample', h, n, seed, first_index, bounds_sample, idxOwn, idxInt, lim1, lim2)");
+        need(nrhs, 5, "[outInits, attempts, logWeight] = emgpu_mex('geom_sample', h, n, seed, first_index, bounds_sample, idxOwnSpeed, idxIntSpeed, lim1, lim2, startGrid)");
         emgpu_model *m = handle_of(prhs[1]);
         const size_t ni = (size_t)n_initial_of(m);
         emgpu_bn_params p;
@@ -444,6 +499,7 @@ void mexFunction(int nlhs, mxArray *plhs[], int nrhs, const mxArray *prhs[]) {
         }
         p.min_vel1 = p.min_vel2 = 0; p.max_vel1 = p.max_vel2 = INFINITY;
         if (nrhs > 9) {
+            if (mxGetNumberOfElements(prhs[8]) != 2 || mxGetNumberOfElements(prhs[9]) != 2) mexErrMsgIdAndTxt("emgpu:usage", "lim1 and lim2 are [min max] speeds");
             p.idx_own_speed = (int32_t)mxGetScalar(prhs[6]); p.idx_int_speed = (int32_t)mxGetScalar(prhs[7]);
             p.min_vel1 = mxGetPr(prhs[8])[0]; p.max_vel1 = mxGetPr(prhs[8])[1]; p.min_vel2 = mxGetPr(prhs[9])[0]; p.max_vel2 = mxGetPr(prhs[9])[1];
         }
@@ -471,7 +527,7 @@ void mexFunction(int nlhs, mxArray *plhs[], int nrhs, const mxArray *prhs[]) {
     } else if (!strcmp(cmd, "propagate_terminal")) {
         need(nrhs, 8, "[out, rows] = emgpu_mex('propagate_terminal', handles, geo, model_of, seed, first_index, tmax_s, dyn_limits)");
         const int nm = (int)mxGetNumberOfElements(prhs[1]);
-        if (nm < 1 || nm > 64) mexErrMsgIdAndTxt("emgpu:usage", "1..64 trajectory models");
+        if (nm < 1 || nm > 64 || !is_handles(prhs[1])) mexErrMsgIdAndTxt("emgpu:usage", "1..64 trajectory models");
         const emgpu_model *models[64];
         for (int i = 0; i < nm; i++) models[i] = (const emgpu_model *)(uintptr_t)((uint64_t *)mxGetData(prhs[1]))[i];
         emgpu_term_params p;
@@ -531,7 +587,7 @@ void mexFunction(int nlhs, mxArray *plhs[], int nrhs, const mxArray *prhs[]) {
     } else if (!strcmp(cmd, "track_terminal")) {
         need(nrhs, 10, "[sample, traj, len, meta, attempts] = emgpu_mex('track_terminal', hGeom, handles, n, seed, first_index, dyn_limits, cumturn_pitch, thresholds, idx12, bounds_sample, max_track_attempts)");
         emgpu_model *gm = handle_of(prhs[1]);
-        if (mxGetNumberOfElements(prhs[2]) != 10) mexErrMsgIdAndTxt("emgpu:usage", "handles: the 10 trajectory models in CorTerminalModel.m:84-100 order");
+        if (mxGetNumberOfElements(prhs[2]) != 10 || !is_handles(prhs[2])) mexErrMsgIdAndTxt("emgpu:usage", "handles: the 10 trajectory models in CorTerminalModel.m:84-100 order");
         const emgpu_model *models[10];
         for (int i = 0; i < 10; i++) models[i] = (const emgpu_model *)(uintptr_t)((uint64_t *)mxGetData(prhs[2]))[i];
         emgpu_ttrack_params p;
@@ -562,17 +618,28 @@ void mexFunction(int nlhs, mxArray *plhs[], int nrhs, const mxArray *prhs[]) {
         const int rc = emgpu_track_terminal_host(ctx0(), gm, models, 10, &p, mxGetPr(plhs[0]), mxGetPr(tr), cap2, ln, mxGetPr(mt), att);
         if (bs) mxFree(bs);
         if (rc != EMGPU_ERR_REJECT_CAP) check(rc);           /* at the cap the accepted encounters are still returned: attempts = -1 marks the rest */
+        if (rc == EMGPU_ERR_REJECT_CAP)                      /* the library copies the rows of a rejected encounter back as its device buffers held them */
+            for (size_t i = 0; i < n; i++) {                 /* (whatever an earlier call left there): MATLAB gets zeros instead                         */
+                if (att[i] >= 0) continue;
+                memset(mxGetPr(plhs[0]) + i * ni, 0, sizeof(double) * ni);
+                memset(mxGetPr(tr) + i * 2 * (size_t)cap2 * 6, 0, sizeof(double) * 2 * (size_t)cap2 * 6);
+                memset(mxGetPr(mt) + 4 * i, 0, sizeof(double) * 4);
+                ln[2 * i] = ln[2 * i + 1] = 0;
+            }
         if (nlhs > 1) plhs[1] = tr;
         if (nlhs > 2) { plhs[2] = mxCreateDoubleMatrix(2, (mwSize)n, mxREAL); for (size_t i = 0; i < 2 * n; i++) mxGetPr(plhs[2])[i] = ln[i]; }
         if (nlhs > 3) plhs[3] = mt;
         if (nlhs > 4) { plhs[4] = mxCreateDoubleMatrix((mwSize)n, 1, mxREAL); for (size_t i = 0; i < n; i++) mxGetPr(plhs[4])[i] = att[i]; }
         mxFree(ln); mxFree(att);
     } else if (!strcmp(cmd, "sample2track")) {
-        need(nrhs, 7, "sample2track needs alt0, speed0, updates, ur, min_speed, max_speed");
+        need(nrhs, 7, "[xyz, flags, vminmax] = emgpu_mex('sample2track', alt0, speed0, updates, ur, min_speed, max_speed)");
         emgpu_track_params tp;
         memset(&tp, 0, sizeof tp);
         tp.n = (int64_t)mxGetNumberOfElements(prhs[1]);
         tp.T = tp.n ? (int32_t)(mxGetNumberOfElements(prhs[3]) / (3 * (size_t)tp.n)) : 1;
+        if (mxGetNumberOfElements(prhs[2]) != (size_t)tp.n || mxGetNumberOfElements(prhs[4]) != 3 || tp.T < 1 ||
+            (tp.n && mxGetNumberOfElements(prhs[3]) != 3 * (size_t)tp.T * (size_t)tp.n))
+            mexErrMsgIdAndTxt("emgpu:usage", "alt0 and speed0 hold n values, updates is 3 x T x n, ur = [speed vertrate heading]");
         tp.ur_speed = mxGetPr(prhs[4])[0]; tp.ur_vertrate = mxGetPr(prhs[4])[1]; tp.ur_heading = mxGetPr(prhs[4])[2];
         tp.min_speed = mxGetScalar(prhs[5]); tp.max_speed = mxGetScalar(prhs[6]);
         /* column-major 3 x T x n == row-major [n][T][3], 3 x (T+1) x n == [n][T+1][3], 2 x n == [n][2]: no transposes */

@@ -1,7 +1,7 @@
-/* tests/stubs/mex.h -- declaration-only stand-in for MATLAB's mex.h, used ONLY by
- * tests/test_host.py::test_mex_gateway_compiles to syntax- and type-check
- * em_model_manned_bayes_amd/matlab/emgpu_mex.c with gcc -fsyntax-only.  Nothing here is ever linked or run;
- * a real build uses MATLAB's own header. */
+/* tests/stubs/mex.h -- stand-in for MATLAB's mex.h: the declarations em_model_manned_bayes_amd/matlab/emgpu_mex.c needs.
+ * Two builds include it: tests/test_host.py::test_mex_gateway_compiles type-checks the gateway against it (gcc -fsyntax-only),
+ * and tests/mexrt.py compiles the gateway together with tests/stubs/mex_runtime.c, which implements every function declared
+ * here, into a shared object that the gateway tests run.  A real build uses MATLAB's own header. */
 #ifndef EMGPU_TEST_MEX_STUB_H
 #define EMGPU_TEST_MEX_STUB_H
 #include <stddef.h>

@@ -651,8 +651,9 @@ def test_random_models_parse_identically(tmp_path):
 
 
 def test_mex_gateway_compiles():
-    """The MATLAB gateway cannot be run here (no MATLAB); it is at least type-checked against the C ABI header with a
-    declaration-only stand-in for mex.h (tests/stubs/mex.h)."""
+    """The MATLAB gateway type-checks against the C ABI header and the stand-in for mex.h (tests/stubs/mex.h) on its own, and holds
+    every command the .m files send.  (It is RUN, against tests/stubs/mex_runtime.c, by tests/test_mex_gateway.py and
+    tests/test_gpu_mex_gateway.py.)"""
     import subprocess
     r = subprocess.run(["gcc", "-fsyntax-only", "-std=c99", "-Wall", "-Werror", "-I" + os.path.join(ROOT, "tests", "stubs"),
                         "-I" + os.path.join(ROOT, "include"), os.path.join(ROOT, "em_model_manned_bayes_amd", "matlab", "emgpu_mex.c")],
@@ -662,7 +663,8 @@ def test_mex_gateway_compiles():
     src = open(os.path.join(ROOT, "em_model_manned_bayes_amd", "matlab", "emgpu_mex.c")).read()
     have = set(re.findall(r'!strcmp\(cmd, "([a-z_0-9]+)"\)', src))
     assert {"load_txt", "em_read", "from_struct", "set_prior", "set_alpha", "set_start", "bn_sample", "sample_uncor", "geom_sample",
-            "propagate_terminal", "track_uncor", "sample2track", "device_count", "use_devices", "free", "save_bin", "load_bin"} <= have
+            "propagate_terminal", "track_uncor", "track_terminal", "sample2track", "device_count", "use_devices", "free", "save_bin", "load_bin",
+            "shutdown"} <= have
     used = set()
     mdir = os.path.join(ROOT, "em_model_manned_bayes_amd", "matlab")
     for base, _, files in os.walk(mdir):
