@@ -128,6 +128,11 @@ class UncorOut(C.Structure):      # emgpu_uncor_out
                 ("attempts", C.c_void_p), ("totals", C.c_void_p), ("ctrl_var", C.c_int32 * 3), ("_pad", C.c_int32)]
 
 
+class TextOut(C.Structure):       # emgpu_text_out
+    _fields_ = [("initial", C.c_void_p), ("initial_cap", C.c_int64), ("transition", C.c_void_p), ("transition_cap", C.c_int64),
+                ("totals", C.c_void_p), ("id_first", C.c_int64), ("init_val", C.c_void_p), ("dyn_val", C.c_void_p)]
+
+
 class BnParams(C.Structure):
     _fields_ = [("seed", C.c_uint64), ("first_index", C.c_uint64), ("n", C.c_int64), ("flags", C.c_uint32),
                 ("max_attempts", C.c_int32), ("bounds_sample", C.c_void_p),
@@ -153,6 +158,7 @@ SYMBOLS = [
     "emgpu_track_terminal_host", "emgpu_debug_parent_masks", "emgpu_last_launch_count", "emgpu_debug_pk_column", "emgpu_debug_terminal_counters", "emgpu_debug_uncor_dynamics_host", "emgpu_model_save_bin", "emgpu_model_load_bin", "emgpu_philox_rounds", "emgpu_ctx_trim",
     "emgpu_slot_map_revision", "emgpu_trace_alloc", "emgpu_trace_out", "emgpu_trace_report", "emgpu_trace_free", "emgpu_host_alloc", "emgpu_host_free", "emgpu_host_stats",
     "emgpu_device_alloc", "emgpu_device_free", "emgpu_sample_uncor_host",
+    "emgpu_sample_text_host", "emgpu_text_bound", "emgpu_format_g_host", "emgpu_debug_format_paths",
 ]
 
 _lib = None
@@ -316,6 +322,10 @@ def lib():
     L.emgpu_host_stats.argtypes = [C.c_void_p, C.POINTER(HostStats)]
     L.emgpu_device_alloc.argtypes = [C.c_void_p, C.c_uint64, C.POINTER(C.c_void_p)]
     L.emgpu_device_free.argtypes = [C.c_void_p, C.c_void_p]
+    L.emgpu_sample_text_host.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(SampleParams), C.POINTER(TextOut)]
+    L.emgpu_text_bound.argtypes = [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p]
+    L.emgpu_format_g_host.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p]
+    L.emgpu_debug_format_paths.argtypes = [C.c_void_p, C.c_void_p]
     _lib = L
     return L
 

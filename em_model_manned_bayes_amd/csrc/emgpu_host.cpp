@@ -3,8 +3,8 @@
 //     measured with the caller's own launch (profiles/r05_placement_probe.txt: the same launch writes one 36 GB allocation in 6.0 ms
 //     and another in 7.1 ms);
 //   * the pinned pool: emgpu_host_alloc / _free;
-//   * emgpu_sample_dbn_host and emgpu_sample_uncor_host (UncorEncounterModel.sample's samples and controls built on the device): one driver,
-//     run_chunks, pipelines both -- chunk k's launches | chunk k-1's copy over PCIe | chunk k-2's copy into the caller's arrays.
+//   * emgpu_sample_dbn_host, emgpu_sample_uncor_host (UncorEncounterModel.sample's samples and controls built on the device) and
+//     emgpu_sample_text_host (em_sample's two text files formatted on the device, em_sample.m:85-99): one driver, run_chunks, pipelines all three -- chunk k's launches | chunk k-1's copy over PCIe | chunk k-2's copy into the caller's arrays.
 // Reference semantics: the loop over samples of UncorEncounterModel.m:244-300 and the host arrays it returns (:283-300).
 #include <algorithm>
 #include <chrono>
@@ -248,7 +248,8 @@ void run_parallel(int T, F fn) {   // fn(t) for t = 0..T-1, fn(0) on the calling
 
 // ------------------------------------------------------------------------------------------------ the host path's chunked pipeline
 struct ChunkPlan { size_t n, C, Cp, nchunks; };   // n trajectories in chunks of C (the last one may be short), C padded to Cp on the device
-// `bpt` device bytes per trajectory; chunks of equal size, and with event lists (event_cap > 0) a chunk's packed rows counted in 32 bits
+// `bpt` device bytes per trajectory; chunks of equal size, and with event lists (event_cap > 0: rows per list) or text rows (bytes per
+// trajectory at most) a chunk's packed rows / bytes counted in 32 bits
 ChunkPlan chunk_plan(size_t n, size_t bpt, bool direct, size_t event_cap) {
     size_t target = (size_t)(direct ? 1024 : 256) << 20;   // pinned outputs: larger pieces (the copy engine writes row by row into the caller's pitch)
     if (const char *e = getenv("EMGPU_HOST_CHUNK_MB")) { const long v = atol(e); if (v > 0) target = (size_t)v << 20; }
@@ -843,6 +844,182 @@ int emgpu_sample_uncor_host(emgpu_ctx *ctx, const emgpu_model *h, const emgpu_sa
                                              " control rows, events_cap / controls_cap are " + std::to_string(out->events_cap) + " / " + std::to_string(out->controls_cap));
     return rc;
     EMGPU_CATCH
+}
+
+// ================================================================================================ em_sample's text files
+int emgpu_text_bound(const emgpu_model *h, int64_t n, int32_t sample_time, int64_t bytes[2]) {
+    if (!h || !bytes) return fail(EMGPU_ERR_ARG, "null argument");
+    if (n < 0 || sample_time < 1) return fail(EMGPU_ERR_ARG, "n < 0 or sample_time < 1");
+    bytes[0] = n * (int64_t)emgpu::text_row_bound_initial(h->m.n_initial);
+    bytes[1] = n * (int64_t)sample_time * (int64_t)emgpu::text_row_bound_transition(h->m.n_dyn());
+    return EMGPU_OK;
+}
+
+int emgpu_sample_text_host(emgpu_ctx *ctx, const emgpu_model *h, const emgpu_sample_params *p, const emgpu_text_out *out) {
+    EMGPU_TRY
+    if (!ctx || !h || !p || !out) return fail(EMGPU_ERR_ARG, "null argument");
+    if (!out->initial || !out->transition || !out->totals) return fail(EMGPU_ERR_ARG, "initial, transition and totals are required");
+    if (out->initial_cap < 0 || out->transition_cap < 0) return fail(EMGPU_ERR_ARG, "initial_cap and transition_cap must be >= 0");
+    if (p->start || p->indices) return fail(EMGPU_ERR_ARG, "emgpu_sample_text_host: start grids and index lists are not supported");
+    if (p->n < 0 || p->sample_time < 1) return fail(EMGPU_ERR_ARG, "n < 0 or sample_time < 1");
+    if (out->id_first < 0 || out->id_first > ((int64_t)1 << 53) - p->n) return fail(EMGPU_ERR_ARG, "id_first < 0 or id_first + n > 2^53");
+    CTX_LOCK(ctx);
+    HIP_OK(hipSetDevice(ctx->device));
+    const auto t_call = Clock::now();
+    const Model &m = h->m;
+    const size_t n = (size_t)p->n, ni = (size_t)m.n_initial, nd = (size_t)m.n_dyn(), T = (size_t)p->sample_time, G4 = (T + 3) / 4;
+    const size_t rb_i = emgpu::text_row_bound_initial((int)ni), wt = T * emgpu::text_row_bound_transition((int)nd);   // worst case per trajectory
+    out->totals[0] = out->totals[1] = 0;
+    if (n == 0) return sample_nothing(ctx, h, p);
+
+    // ---- the caller's buffers: the two texts (a chunk's bytes go behind the chunks' before it) and, when wanted, the dense arrays; each is
+    // written by the copy engine when it is pinned, else through the staging buffer and the host threads
+    struct Arr { char *dst; size_t rows, elem; size_t dev_off = 0, stg_off = 0; bool staged = false; };
+    Arr a_iv{(char *)out->init_val, ni, 4}, a_dv{(char *)out->dyn_val, G4 * nd, 16};
+    struct Txt { char *dst; size_t cap, per; size_t dev_off = 0, stg_off = 0; bool staged = false; };
+    Txt tx[2] = {{out->initial, (size_t)out->initial_cap, rb_i}, {out->transition, (size_t)out->transition_cap, wt}};
+    std::vector<Arr *> arrs;
+    if (out->init_val && ni) arrs.push_back(&a_iv);
+    if (out->dyn_val && nd) arrs.push_back(&a_dv);
+    bool direct = true;
+    for (Arr *a : arrs) { a->staged = !is_pinned(a->dst); direct = direct && !a->staged; }
+    for (Txt &t : tx) { t.staged = !is_pinned(t.dst); direct = direct && !t.staged; }
+
+    const size_t bpt = 5 * ni + 20 * G4 * nd + 12 + rb_i + wt;   // device bytes per trajectory
+    // the scans count a chunk's bytes in 32 bits: the chunk is sized by a trajectory's worst case
+    const ChunkPlan P = chunk_plan(n, bpt, direct, std::max(rb_i, wt));
+    const size_t C = P.C, Cp = P.Cp;
+    if (C * std::max(rb_i, wt) > (size_t)0xFFFFFFFFu) return fail(EMGPU_ERR_ARG, "emgpu_sample_text_host: sample_time too large: a chunk's text would not fit 32 bits");
+    size_t o = 0;
+    auto put = [&](size_t bytes) { const size_t at = o; o = round_up(o + std::max<size_t>(bytes, 1), 256); return at; };
+    a_iv.dev_off = put(ni * Cp * 4);
+    a_dv.dev_off = put(G4 * nd * Cp * 16);
+    // (the sampler is asked for what emgpu_sample_dbn_host's callers ask it for, bins and attempts too: the same kernel instance serves both)
+    const size_t o_ib = put(ni * Cp), o_db = put(G4 * nd * Cp * 4), o_at = put(Cp * 4);
+    const size_t o_ci = put(Cp * 4), o_ct = put(Cp * 4);
+    const size_t o_si = put(emgpu::pack_scratch_words((int64_t)Cp) * 4), o_st = put(emgpu::pack_scratch_words((int64_t)Cp) * 4);
+    for (Txt &t : tx) t.dev_off = put(C * t.per);
+    const size_t dev_bytes = std::max<size_t>(o, 256);
+    size_t so = 0;
+    for (Arr *a : arrs) if (a->staged) { a->stg_off = so; so = round_up(so + a->rows * Cp * a->elem, 256); }
+    for (Txt &t : tx) if (t.staged) { t.stg_off = so; so = round_up(so + C * t.per, 256); }
+    const size_t stage_bytes = std::max<size_t>(so, 256);
+    if (!provision(ctx, P.nchunks, dev_bytes, stage_bytes)) return fail(EMGPU_ERR_HIP, "emgpu_sample_text_host: out of device memory");
+
+    emgpu_host_stats_t st{};
+    size_t bytes[2][2] = {{0, 0}, {0, 0}}, base[2][2] = {{0, 0}, {0, 0}}, total[2] = {0, 0};   // per buffer: the chunk's bytes and their place in the call's
+    bool fits[2][2] = {{false, false}, {false, false}};
+    auto launch = [&](size_t k0, size_t c, int b) {
+        char *dev = (char *)ctx->chunk_buf[b].p;
+        emgpu_sample_params q = *p;
+        q.n = (int64_t)c;
+        q.first_index = p->first_index + (uint64_t)k0;
+        emgpu_sample_out d{};
+        d.ld = (int64_t)Cp;
+        d.init_val = (float *)(dev + a_iv.dev_off);
+        d.init_bin = (uint8_t *)(dev + o_ib);
+        d.attempts = (int32_t *)(dev + o_at);
+        if (nd) { d.dyn_val = (float *)(dev + a_dv.dev_off); d.dyn_bin = (uint32_t *)(dev + o_db); }
+        const int r = emgpu_sample_dbn_device(ctx, h, &q, &d);
+        if (r != EMGPU_OK) throw Error(r, g_err);
+        emgpu::EmgpuTextRun R{};
+        R.n = (int64_t)c; R.T = (int32_t)T; R.ni = (int32_t)ni; R.nd = (int32_t)nd; R.ld = (int64_t)Cp;
+        R.init_val = d.init_val; R.dyn_val = (const float *)(dev + a_dv.dev_off); R.id_first = out->id_first + (int64_t)k0;
+        R.cnt_i = (uint32_t *)(dev + o_ci); R.cnt_t = (uint32_t *)(dev + o_ct); R.scr_i = (uint32_t *)(dev + o_si); R.scr_t = (uint32_t *)(dev + o_st);
+        R.text_i = dev + tx[0].dev_off; R.text_t = dev + tx[1].dev_off;
+        launch_ok(emgpu::launch_text_rows(R, ctx->stream));
+        HIP_OK(hipMemcpyAsync(&ctx->h_total[2 * b], dev + o_si, sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
+        HIP_OK(hipMemcpyAsync(&ctx->h_total[2 * b + 1], dev + o_st, sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
+    };
+    auto copy = [&](size_t k0, size_t c, int b) {
+        const char *dev = (const char *)ctx->chunk_buf[b].p;
+        char *stg = (char *)ctx->h_stage[b];
+        for (int x = 0; x < 2; x++) {   // how many bytes cross PCIe is known only now
+            bytes[b][x] = (size_t)ctx->h_total[2 * b + x];
+            if (bytes[b][x] > c * tx[x].per) throw Error(EMGPU_ERR_HIP, "emgpu_sample_text_host: a chunk's text outgrew its bound");
+            base[b][x] = total[x];
+            total[x] += bytes[b][x];
+            fits[b][x] = total[x] <= tx[x].cap;
+            if (!fits[b][x] || !bytes[b][x]) continue;   // (a call whose text outgrows the caller's buffer still counts it: the totals)
+            HIP_OK(hipMemcpyAsync(tx[x].staged ? stg + tx[x].stg_off : tx[x].dst + base[b][x], dev + tx[x].dev_off, bytes[b][x], hipMemcpyDeviceToHost, ctx->copy_stream));
+            st.bytes_d2h += (int64_t)bytes[b][x];
+        }
+        for (const Arr *a : arrs) {
+            if (a->staged) HIP_OK(hipMemcpyAsync(stg + a->stg_off, dev + a->dev_off, a->rows * Cp * a->elem, hipMemcpyDeviceToHost, ctx->copy_stream));
+            else HIP_OK(hipMemcpy2DAsync(a->dst + k0 * a->elem, n * a->elem, dev + a->dev_off, Cp * a->elem, c * a->elem, a->rows, hipMemcpyDeviceToHost, ctx->copy_stream));
+            st.bytes_d2h += (int64_t)(a->rows * (a->staged ? Cp : c) * a->elem);
+        }
+    };
+    auto scatter = [&](size_t k0, size_t c, int b) {
+        const char *stg = (const char *)ctx->h_stage[b];
+        std::vector<Job> jobs;
+        for (int x = 0; x < 2; x++) {
+            if (!tx[x].staged || !fits[b][x]) continue;
+            const size_t piece = (size_t)1 << 20;   // in pieces of about 1 MiB, so that the threads share a large text
+            for (size_t q = 0; q < bytes[b][x]; q += piece) jobs.push_back({tx[x].dst + base[b][x] + q, stg + tx[x].stg_off + q, std::min(piece, bytes[b][x] - q)});
+        }
+        for (const Arr *a : arrs)
+            if (a->staged)
+                for (size_t r = 0; r < a->rows; r++) jobs.push_back({a->dst + (r * n + k0) * a->elem, stg + a->stg_off + r * Cp * a->elem, c * a->elem});
+        run_jobs(jobs, (int)std::min<size_t>((size_t)host_threads(), std::max<size_t>(1, jobs.size())), [](int) {});
+    };
+    const int rc = run_chunks(ctx, P, direct, /*wait_rows=*/true, t_call, st, launch, copy, scatter);
+    out->totals[0] = (int64_t)total[0];
+    out->totals[1] = (int64_t)total[1];
+    if (rc == EMGPU_OK && (total[0] > tx[0].cap || total[1] > tx[1].cap))
+        return fail(EMGPU_ERR_EVENT_CAP, "emgpu_sample_text_host: the texts have " + std::to_string(total[0]) + " and " + std::to_string(total[1]) +
+                                             " bytes, initial_cap / transition_cap are " + std::to_string(out->initial_cap) + " / " + std::to_string(out->transition_cap));
+    return rc;
+    EMGPU_CATCH
+}
+
+int emgpu_format_g_host(emgpu_ctx *ctx, const float *x, int64_t n, char *out, int64_t cap, uint64_t *offsets) {
+    EMGPU_TRY
+    if (!ctx || !offsets || (n > 0 && !x) || (cap > 0 && !out)) return fail(EMGPU_ERR_ARG, "null argument");
+    if (n < 0 || cap < 0) return fail(EMGPU_ERR_ARG, "n < 0 or cap < 0");
+    CTX_LOCK(ctx);
+    HIP_OK(hipSetDevice(ctx->device));
+    offsets[0] = 0;
+    if (n == 0) return EMGPU_OK;
+    const size_t C = (size_t)std::min<int64_t>(n, (int64_t)1 << 22);   // values per pass: their text is counted in 32 bits (12 C bytes)
+    uint64_t total = 0, paths[2] = {0, 0};
+    {
+        CallBuffers B(ctx);
+        float *d_x = B.alloc<float>(C * 4);
+        uint32_t *d_cnt = B.alloc<uint32_t>(C * 4), *d_scr = B.alloc<uint32_t>(emgpu::pack_scratch_words((int64_t)C) * 4);
+        char *d_text = B.alloc<char>(C * 12);
+        uint64_t *d_off = B.alloc<uint64_t>(C * 8);
+        unsigned long long *d_paths = B.alloc<unsigned long long>(16);
+        HIP_OK(hipMemsetAsync(d_paths, 0, 16, ctx->stream));
+        for (size_t k0 = 0; k0 < (size_t)n; k0 += C) {
+            const size_t c = std::min(C, (size_t)n - k0);
+            B.up(d_x, x + k0, c * 4);
+            launch_ok(emgpu::launch_format_g(d_x, (int64_t)c, d_cnt, d_scr, d_text, total, d_off, d_paths, ctx->stream));
+            uint64_t bytes = 0;
+            B.down(&bytes, d_scr, sizeof bytes);
+            B.down(offsets + k0, d_off, c * 8);
+            HIP_OK(hipStreamSynchronize(ctx->stream));
+            if (bytes > c * 12) throw Error(EMGPU_ERR_HIP, "emgpu_format_g_host: a pass's text outgrew its bound");
+            if (total + bytes <= (uint64_t)cap) { B.down(out + total, d_text, (size_t)bytes); HIP_OK(hipStreamSynchronize(ctx->stream)); }
+            total += bytes;
+        }
+        B.down(paths, d_paths, sizeof paths);
+        HIP_OK(hipStreamSynchronize(ctx->stream));
+    }
+    ctx->format_paths[0] += paths[0];
+    ctx->format_paths[1] += paths[1];
+    offsets[n] = total;
+    if (total > (uint64_t)cap) return fail(EMGPU_ERR_EVENT_CAP, "emgpu_format_g_host: the text has " + std::to_string(total) + " bytes, cap is " + std::to_string(cap));
+    return EMGPU_OK;
+    EMGPU_CATCH
+}
+
+int emgpu_debug_format_paths(emgpu_ctx *ctx, uint64_t out[2]) {
+    if (!ctx || !out) return fail(EMGPU_ERR_ARG, "null argument");
+    CTX_LOCK(ctx);
+    out[0] = ctx->format_paths[0]; out[1] = ctx->format_paths[1];
+    ctx->format_paths[0] = ctx->format_paths[1] = 0;
+    return EMGPU_OK;
 }
 
 } // extern "C"

@@ -108,7 +108,8 @@ struct emgpu_ctx {
     uint64_t *h_total = nullptr;   // pinned, 2 words per chunk buffer: rows of its packed event lists, rows of its control rows
     struct HostBlock { void *p = nullptr; size_t bytes = 0; bool in_use = false; };
     std::vector<HostBlock> host_pool;
-    emgpu_host_stats_t host_stats{};   // phases of the last emgpu_sample_dbn_host / emgpu_sample_uncor_host call
+    emgpu_host_stats_t host_stats{};   // phases of the last emgpu_sample_dbn_host / emgpu_sample_uncor_host / emgpu_sample_text_host call
+    uint64_t format_paths[2] = {0, 0}; // emgpu_format_g_host: values formatted on the 64-bit / the multiword path (emgpu_debug_format_paths)
 };
 
 // emgpu_capi.cpp

@@ -62,5 +62,23 @@ struct EmgpuFormatRun {
     double *controls;        // [rows][4] out, room for sum(min(ev_count, cap)) rows
 };
 hipError_t launch_format_uncor(const EmgpuFormatRun &F, hipStream_t s);
+// em_sample's text rows from a chunk's dense trace (emgpu_kernels_text.hip), for emgpu_sample_text_host: em_sample.m:85-99
+struct EmgpuTextRun {
+    int64_t n;               // trajectories of the chunk
+    int32_t T, ni, nd;       // sample_time, n_initial, n_dyn
+    int64_t ld;              // trajectory dimension of init_val ([ni][ld]) and dyn_val ([G4][nd][ld][4])
+    const float *init_val, *dyn_val;
+    int64_t id_first;        // the id printed for trajectory 0 of the chunk (>= 0)
+    uint32_t *cnt_i, *cnt_t; // [n] out: bytes of trajectory i's initial row / of its T transition rows
+    uint32_t *scr_i, *scr_t; // pack_scratch_words(n) words each: words 0-1 receive the chunk's bytes (u64)
+    char *text_i, *text_t;   // out: the rows, trajectory after trajectory; room for n * text_row_bound_initial(ni) / n * T * text_row_bound_transition(nd)
+};
+uint32_t text_row_bound_initial(int ni);      // 21 + 13 ni: "%d " of an id below 2^63, then ni values of at most 12 characters and what follows each
+uint32_t text_row_bound_transition(int nd);   // 13 (2 + nd): id, second and nd values, each "%g" at most 12 characters, and what follows each
+hipError_t launch_text_rows(const EmgpuTextRun &R, hipStream_t s);
+// "%g" of n f32 values, one after the other: cnt [n], scratch pack_scratch_words(n) words (words 0-1: the bytes, u64), text: room for 12 n bytes,
+// offsets [n]: base + the first byte of value i; paths[0] / paths[1] += the finite non-zero values formatted on the 64-bit / the multiword path
+hipError_t launch_format_g(const float *x, int64_t n, uint32_t *cnt, uint32_t *scratch, char *text, uint64_t base, uint64_t *offsets,
+                           unsigned long long *paths, hipStream_t s);
 hipError_t launch_sample2track(const EmgpuTrackRun &A, bool dense, hipStream_t s, const char **name);
 } // namespace emgpu

@@ -4,11 +4,13 @@
 Same names, arguments and file formats as code/matlab/em_sample.m and code/matlab/sample2track.m.
 Sampling and the track integration run on the GPU (libemgpu: emgpu_sample_dbn_host,
 emgpu_sample2track_host); parsing and formatting are host-side Python, as they are host-side MATLAB
-in the reference.  A device-resident consumer that skips the text files exists as
+in the reference -- em_sample(text="device") formats its rows on the GPU too (emgpu_sample_text_host) and
+writes the same bytes.  A device-resident consumer that skips the text files exists as
 native.sample2track_device (it reads the sampler's dense trace in place).
 """
 import os
 import re
+import time
 
 import numpy as np
 
@@ -17,6 +19,10 @@ from .em_io import em_read
 from .functions import _model_of, _take, bn_dirichlet_prior
 
 FT_PER_NM = 1852.0 / 0.3048          # unitsratio('ft', 'nm')
+
+
+# what the last em_sample(text="device") spent where: library calls, their phases (emgpu_host_stats, summed over the calls), file writes
+last_text_stats = {}
 
 
 def _g(x):
@@ -31,7 +37,7 @@ def _g(x):
 
 def em_sample(parameters_filename, initial_output_filename=None, transition_output_filename=None, num_initial_samples=100,
               num_transition_samples=60, start=None, isOverwriteZeroBoundaries=False, idxZeroBoundaries=(1, 2, 3),
-              rng_seed=42, prior=0, ctx=None):
+              rng_seed=42, prior=0, ctx=None, text="host", return_arrays=True, id_first=1, text_batch=None):
     """em_sample(parameters_filename, 'initial_output_filename', ..., 'num_initial_samples', 100,
     'num_transition_samples', 60, 'start', {}, 'rng_seed', 42)  (em_sample.m:1-104).
 
@@ -39,7 +45,16 @@ def em_sample(parameters_filename, initial_output_filename=None, transition_outp
     rows (the dense trace of the dynamic variables at t = 0 .. num_transition_samples-1).
     `prior`: em_sample.m:52 assigns the string 'constant', which bn_dirichlet_prior.m:28 rejects
     (prior:notdbe), so the reference as shipped stops there; the constant prior 0 is what its
-    documentation describes and is the default here.  Returns (initial [n, n_initial], trace [n, T, n_dyn])."""
+    documentation describes and is the default here.  Returns (initial [n, n_initial], trace [n, T, n_dyn]).
+
+    text: "host" formats every row in Python ("%g" per value); "device" writes the same two files from rows formatted on the GPU
+    (native.sample_text_host), in batches of text_batch trajectories (default: as many as keep the pinned text buffers near 256 MiB, by
+    native.text_bound), so host memory stays bounded whatever num_initial_samples is.  Device writer only: return_arrays=False returns
+    (None, None) and keeps no array of the run; id_first is the id of the first trajectory (a run continued from an earlier file)."""
+    if text not in ("host", "device"):
+        raise ValueError("em_sample: text must be 'host' or 'device', not %r" % (text,))
+    if text == "host" and (not return_arrays or int(id_first) != 1 or text_batch is not None):
+        raise ValueError("em_sample: return_arrays=False, id_first and text_batch belong to text='device'")
     out_dir = os.path.join(os.environ.get("AEM_DIR_BAYES", "."), "output")
     initial_output_filename = initial_output_filename or os.path.join(out_dir, "initial.txt")
     transition_output_filename = transition_output_filename or os.path.join(out_dir, "transition.txt")
@@ -49,26 +64,68 @@ def em_sample(parameters_filename, initial_output_filename=None, transition_outp
     m = _model_of(parms, di, dt, start)
     n, T = int(num_initial_samples), int(num_transition_samples)
     seed, first = _take(rng_seed, n)
+    tm = np.asarray(parms["temporal_map"]).reshape(-1, 2)
+    header_initial = "id " + "".join("%s " % s for s in parms["labels_initial"]) + "\n"                                         # :64-68
+    header_transition = "initial_id t " + "".join("%s " % parms["labels_transition"][int(r[1]) - 1] for r in tm) + "\n"       # :71-75
+    for f in (initial_output_filename, transition_output_filename):
+        if os.path.dirname(f):
+            os.makedirs(os.path.dirname(f), exist_ok=True)
+    if text == "device":
+        return _em_sample_device_text(ctx or native.default_context(), m, n, T, seed, first, initial_output_filename, transition_output_filename,
+                                      header_initial, header_transition, return_arrays, int(id_first), text_batch)
     # dbn_hierarchical_sample + events2samples (em_sample.m:78-82): no rejection test, dense trace
     res = native.sample_dbn_host(ctx or native.default_context(), m, n, T, seed, first_index=first, want_dense=True,
                                  max_attempts=1)
     initial = res["init_val"].astype(np.float64)
     trace = res["dyn_val"].astype(np.float64)
-    tm = np.asarray(parms["temporal_map"]).reshape(-1, 2)
-    for f in (initial_output_filename, transition_output_filename):
-        if os.path.dirname(f):
-            os.makedirs(os.path.dirname(f), exist_ok=True)
     with open(initial_output_filename, "w", encoding="utf-8", newline="\n") as f:
-        f.write("id " + "".join("%s " % s for s in parms["labels_initial"]) + "\n")             # :64-68
+        f.write(header_initial)
         for i in range(n):
             f.write("%d " % (i + 1) + " ".join(_g(v) for v in initial[i]) + "\n")                # :85-88
     with open(transition_output_filename, "w", encoding="utf-8", newline="\n") as f:
-        f.write("initial_id t " + "".join("%s " % parms["labels_transition"][int(r[1]) - 1] for r in tm) + "\n")   # :71-75
+        f.write(header_transition)
         rows = []
         for i in range(n):
             for j in range(T):
                 rows.append("%s %s " % (_g(i + 1), _g(j)) + " ".join(_g(v) for v in trace[i, j]) + "\n")        # :91-96
         f.write("".join(rows))
+    return initial, trace
+
+
+def _em_sample_device_text(ctx, m, n, T, seed, first, initial_filename, transition_filename, header_initial, header_transition, return_arrays,
+                           id_first, text_batch):
+    """em_sample's files from rows formatted on the device: batch after batch of trajectories through native.sample_text_host into one pair of
+    pinned buffers, each batch's bytes appended to the files.  last_text_stats says where the time went."""
+    st = {"calls": 0, "batch": 0, "library_ms": 0.0, "kernel_ms": 0.0, "d2h_ms": 0.0, "scatter_ms": 0.0, "write_ms": 0.0, "bytes": 0}
+    per_i, per_t = native.text_bound(m, 1, T)
+    batch = int(text_batch) if text_batch is not None else max(1024, (256 << 20) // max(per_t, per_i))
+    batch = max(1, min(batch, max(n, 1)))
+    buffers = (ctx.pinned_empty((batch * per_i,), np.uint8), ctx.pinned_empty((batch * per_t,), np.uint8))
+    initial = np.empty((n, m.n_initial), dtype=np.float64) if return_arrays else None
+    trace = np.empty((n, T, m.n_dyn), dtype=np.float64) if return_arrays else None
+    with open(initial_filename, "wb") as fi, open(transition_filename, "wb") as ft:
+        fi.write(header_initial.encode("utf-8"))
+        ft.write(header_transition.encode("utf-8"))
+        for b0 in range(0, n, batch):
+            c = min(batch, n - b0)
+            res = native.sample_text_host(ctx, m, c, T, seed, id_first=id_first + b0, want_arrays=return_arrays, buffers=buffers,
+                                          first_index=first + b0, max_attempts=1)
+            t0 = time.perf_counter()
+            fi.write(res["initial"].data)
+            ft.write(res["transition"].data)
+            st["write_ms"] += (time.perf_counter() - t0) * 1e3
+            st["calls"] += 1
+            st["library_ms"] += res["host_stats"]["total_ms"]
+            for k in ("kernel_ms", "d2h_ms", "scatter_ms"):
+                st[k] += res["host_stats"][k]
+            st["bytes"] += sum(res["totals"])
+            if return_arrays:
+                initial[b0:b0 + c] = res["init_val"]
+                if m.n_dyn:
+                    trace[b0:b0 + c] = res["dyn_val"]
+    st["batch"] = batch
+    last_text_stats.clear()
+    last_text_stats.update(st)
     return initial, trace
 
 

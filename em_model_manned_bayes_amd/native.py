@@ -503,6 +503,80 @@ def sample_uncor_host(ctx, model, n, sample_time, seed, ctrl_var, event_cap=256,
             "samples": smp, "attempts": att, "kernel": ctx.last_kernel(), "host_stats": ctx.host_stats()}
 
 
+def text_bound(model, n, sample_time):
+    """emgpu_text_bound: (bytes of the initial text, bytes of the transition text) that always hold sample_text_host's rows:
+    n (21 + 13 n_initial) and n sample_time 13 (2 + n_dyn)."""
+    b = np.zeros(2, dtype=np.int64)
+    L.check(L.lib().emgpu_text_bound(model._h, int(n), int(sample_time), _p(b)))
+    return int(b[0]), int(b[1])
+
+
+def sample_text_host(ctx, model, n, sample_time, seed, id_first=1, want_arrays=True, pinned=True, initial_cap=None, transition_cap=None,
+                     buffers=None, raw=False, **kw):
+    """emgpu_sample_text_host: the rows of em_sample's initial and transition files (without their header lines), formatted on the device.
+    Returns a dict: initial, transition (uint8 arrays: the bytes, views of the call's buffers), totals, init_val [n, n_i] f32 and
+    dyn_val [n, T, n_d] f32 (the values the rows print; None unless want_arrays; raw: in the library's layout, as sample_dbn_host returns
+    them), kernel, host_stats.  id_first: the id of trajectory 0.  pinned: the buffers come from the context's pinned pool, else pageable numpy
+    arrays.  initial_cap / transition_cap: bytes of the buffers (default: text_bound); buffers: (initial, transition) uint8 arrays of a caller
+    who makes several calls.  Text that outgrows a buffer raises EmgpuError(ERR_EVENT_CAP) with `.totals` (the bytes needed): a retry with
+    that room gives the same bytes."""
+    ni, nd, T, n = model.n_initial, model.n_dyn, int(sample_time), int(n)
+    p, keep = make_params(n, T, seed, **kw)
+    empty = ctx.pinned_empty if pinned else (lambda shape, dt: np.empty(shape, dtype=dt))
+    if buffers is not None:
+        bi, bt = buffers
+    else:
+        b0, b1 = text_bound(model, n, T)
+        bi = empty((max(int(b0 if initial_cap is None else initial_cap), 1),), np.uint8)
+        bt = empty((max(int(b1 if transition_cap is None else transition_cap), 1),), np.uint8)
+    o = L.TextOut()
+    totals = np.zeros(2, dtype=np.int64)
+    o.initial, o.transition, o.totals, o.id_first = _p(bi), _p(bt), _p(totals), int(id_first)
+    o.initial_cap = bi.size if initial_cap is None else int(initial_cap)
+    o.transition_cap = bt.size if transition_cap is None else int(transition_cap)
+    iv = dv = None
+    if want_arrays:
+        iv = empty((ni, n), np.float32)
+        o.init_val = _p(iv)
+        if nd > 0:
+            dv = empty(((T + 3) // 4, nd, n, 4), np.float32)
+            o.dyn_val = _p(dv)
+    rc = L.lib().emgpu_sample_text_host(ctx._h, model._h, C.byref(p), C.byref(o))
+    if rc == L.ERR_EVENT_CAP:
+        e = L.EmgpuError(rc, L.lib().emgpu_last_error().decode("utf-8", "replace"))
+        e.totals = (int(totals[0]), int(totals[1]))
+        raise e
+    L.check(rc)
+    out = {"initial": bi[: int(totals[0])], "transition": bt[: int(totals[1])], "totals": (int(totals[0]), int(totals[1])),
+           "init_val": None, "dyn_val": None, "kernel": ctx.last_kernel(), "host_stats": ctx.host_stats()}
+    if want_arrays:
+        out["init_val"] = iv if raw else iv.T.copy()
+        if dv is not None:
+            out["dyn_val"] = dv if raw else unpack_dyn_val(dv, T)
+    return out
+
+
+def format_g(ctx, x, cap=None, return_paths=False):
+    """emgpu_format_g_host: "%g" of every f32 value of x by the device formatter of sample_text_host, non-finite values spelled NaN / Inf / -Inf.
+    Returns the list of strings; return_paths: also (values formatted on the 64-bit path, on the multiword path) -- emgpu_debug_format_paths."""
+    x = np.ascontiguousarray(x, dtype=np.float32).reshape(-1)
+    n = x.size
+    cap = 12 * n if cap is None else int(cap)
+    buf = np.empty(max(cap, 1), dtype=np.uint8)
+    offs = np.zeros(n + 1, dtype=np.uint64)
+    paths = np.zeros(2, dtype=np.uint64)
+    if return_paths:
+        L.check(L.lib().emgpu_debug_format_paths(ctx._h, _p(paths)))   # (reading clears)
+    L.check(L.lib().emgpu_format_g_host(ctx._h, _p(x), n, _p(buf), cap, _p(offs)))
+    text = buf[: int(offs[n])].tobytes().decode("ascii")
+    o = offs.astype(np.int64).tolist()
+    strings = [text[a:b] for a, b in zip(o[:-1], o[1:])]
+    if return_paths:
+        L.check(L.lib().emgpu_debug_format_paths(ctx._h, _p(paths)))
+        return strings, (int(paths[0]), int(paths[1]))
+    return strings
+
+
 def split_rows(a, ends):
     """[a[0:ends[0]], a[ends[0]:ends[1]], ...] as views -- what np.split(a, ends[:-1]) returns, without its per-piece swapaxes round trip
     (a million pieces: 1 us each instead of 3)."""

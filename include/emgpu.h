@@ -276,6 +276,40 @@ typedef struct {
 } emgpu_uncor_out;
 int emgpu_sample_uncor_host(emgpu_ctx *ctx, const emgpu_model *m, const emgpu_sample_params *p, const emgpu_uncor_out *out);
 
+/* em_sample's two text files (em_sample.m:57-104; RUN_1_emsample.m), formatted on the device: HOST pointers, synchronous.  The pipeline of
+ * emgpu_sample_dbn_host with the dense trace as its device-side product; behind a chunk's sampler launch its rows are formatted (an exact C "%g":
+ * six significant digits rounded half to even on the binary value of the f32 widened to double, NaN / Inf / -Inf spelled so) and packed, and
+ * what crosses PCIe is the bytes of the files, without their header lines:
+ *   initial     one row per trajectory i: "%d " of id_first + i, the n_initial values as "%g" joined by one space, "\n"     (em_sample.m:85-88)
+ *   transition  one row per (i, t), t = 0 .. sample_time-1, trajectory after trajectory: "%g %g " of id_first + i and t, the n_dyn values of second t
+ *               in temporal-map order as "%g" joined by one space, "\n" (:91-96; the id goes through "%g" here: 1000000 prints as 1e+06)
+ * The draws are those of emgpu_sample_dbn_host with the same params (counter-based: chunking and capacities do not change them), the model's own
+ * `start` applies, and ctx's last kernel is the sampler's.  totals[0], totals[1]: the bytes of the two texts.  EMGPU_ERR_EVENT_CAP when a text
+ * outgrows its capacity (totals: exact, the buffer's content undefined); a retry with that room gives the same bytes.  Pinned buffers
+ * (emgpu_host_alloc) are written by the copy engine, pageable ones through the library's staging buffers.  emgpu_text_bound gives capacities
+ * that always suffice: bytes[0] = n (21 + 13 n_initial), bytes[1] = n sample_time 13 (2 + n_dyn) -- a "%g" is at most 12 characters, an id
+ * through "%d" at most 20, and one character follows each.  params.start and params.indices are not supported; id_first >= 0 and
+ * id_first + n <= 2^53 (beyond, an id is no longer a double).  emgpu_host_stats describes the call. */
+typedef struct {
+    char *initial;          /* [initial_cap] bytes                                                                               */
+    int64_t initial_cap;
+    char *transition;       /* [transition_cap] bytes                                                                            */
+    int64_t transition_cap;
+    int64_t *totals;        /* [2] out: bytes of the initial / the transition text                                               */
+    int64_t id_first;       /* the id of trajectory 0 (em_sample.m:85 counts from 1)                                             */
+    float *init_val;        /* [n_initial][n], or NULL: the values the rows print, as emgpu_sample_out lays them out              */
+    float *dyn_val;         /* [G4][n_dyn][n][4], or NULL                                                                        */
+} emgpu_text_out;
+int emgpu_sample_text_host(emgpu_ctx *ctx, const emgpu_model *m, const emgpu_sample_params *p, const emgpu_text_out *out);
+int emgpu_text_bound(const emgpu_model *m, int64_t n, int32_t sample_time, int64_t bytes[2]);
+/* "%g" of n f32 values by the same device function, one after the other without separators: value i is out[offsets[i] .. offsets[i + 1])
+ * (offsets: n + 1 entries).  EMGPU_ERR_EVENT_CAP when cap bytes do not hold them (offsets[n]: the bytes needed).  For tests of the formatter
+ * on chosen values, and for callers that write text of their own. */
+int emgpu_format_g_host(emgpu_ctx *ctx, const float *x, int64_t n, char *out, int64_t cap, uint64_t *offsets);
+/* Test hook: how many finite non-zero values the emgpu_format_g_host calls on this ctx have formatted on the 64-bit path (out[0]) and on the
+ * multiword path (out[1]: f32 values of 2^64 and more, and below 10^-6) since the counters were last read; reading clears them. */
+int emgpu_debug_format_paths(emgpu_ctx *ctx, uint64_t out[2]);
+
 /* ------------------------------------------------------------------------------------------------
  * Trace placement (round 6).  WHERE a 36 GB trace lies in device memory decides how fast the sampler writes it: the same launch takes
  * 5.9, 6.6 or 7.0 ms depending on the allocation, launch after launch (profiles/r05_placement_probe.txt, profiles/r06_placement_probe.txt).
@@ -330,7 +364,7 @@ int emgpu_device_free(emgpu_ctx *ctx, void *p);
 int emgpu_host_alloc(emgpu_ctx *ctx, uint64_t bytes, void **out);
 int emgpu_host_free(emgpu_ctx *ctx, void *p);   /* back to the pool; emgpu_ctx_trim releases the pool's free blocks */
 
-/* Phases of the last emgpu_sample_dbn_host or emgpu_sample_uncor_host call on this ctx (either call is a pipeline: chunk k's kernel runs
+/* Phases of the last emgpu_sample_dbn_host, emgpu_sample_uncor_host or emgpu_sample_text_host call on this ctx (each call is a pipeline: chunk k's kernel runs
  * while chunk k-1 crosses PCIe and chunk k-2 is copied from staging into the caller's arrays, so the phases overlap and do not add up to
  * total_ms). */
 typedef struct {
