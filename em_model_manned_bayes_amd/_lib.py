@@ -133,6 +133,16 @@ class TextOut(C.Structure):       # emgpu_text_out
                 ("totals", C.c_void_p), ("id_first", C.c_int64), ("init_val", C.c_void_p), ("dyn_val", C.c_void_p)]
 
 
+class TracksTextIn(C.Structure):    # emgpu_tracks_text_in
+    _fields_ = [("text", C.c_void_p), ("nbytes", C.c_int64), ("ncol", C.c_int32), ("col_vertrate", C.c_int32), ("col_acc", C.c_int32),
+                ("col_turnrate", C.c_int32), ("id", C.c_void_p), ("alt0", C.c_void_p), ("speed0", C.c_void_p)]
+
+
+class TracksTextOut(C.Structure):   # emgpu_tracks_text_out
+    _fields_ = [("flags", C.c_void_p), ("speed_minmax", C.c_void_p), ("lengths", C.c_void_p), ("csv", C.c_void_p), ("csv_cap", C.c_int64),
+                ("offsets", C.c_void_p), ("totals", C.c_void_p), ("xyz", C.c_void_p), ("xyz_cap", C.c_int64), ("phase_ms", C.c_void_p)]
+
+
 class BnParams(C.Structure):
     _fields_ = [("seed", C.c_uint64), ("first_index", C.c_uint64), ("n", C.c_int64), ("flags", C.c_uint32),
                 ("max_attempts", C.c_int32), ("bounds_sample", C.c_void_p),
@@ -159,6 +169,7 @@ SYMBOLS = [
     "emgpu_slot_map_revision", "emgpu_trace_alloc", "emgpu_trace_out", "emgpu_trace_report", "emgpu_trace_free", "emgpu_host_alloc", "emgpu_host_free", "emgpu_host_stats",
     "emgpu_device_alloc", "emgpu_device_free", "emgpu_sample_uncor_host",
     "emgpu_sample_text_host", "emgpu_text_bound", "emgpu_format_g_host", "emgpu_debug_format_paths",
+    "emgpu_parse_table_host", "emgpu_format_f0_host", "emgpu_csv_bound", "emgpu_tracks_text_host",
 ]
 
 _lib = None
@@ -326,6 +337,11 @@ def lib():
     L.emgpu_text_bound.argtypes = [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p]
     L.emgpu_format_g_host.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p]
     L.emgpu_debug_format_paths.argtypes = [C.c_void_p, C.c_void_p]
+    L.emgpu_parse_table_host.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
+    L.emgpu_format_f0_host.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p]
+    L.emgpu_csv_bound.argtypes = [C.c_int64, C.c_int64]
+    L.emgpu_csv_bound.restype = C.c_int64
+    L.emgpu_tracks_text_host.argtypes = [C.c_void_p, C.POINTER(TrackParams), C.POINTER(TracksTextIn), C.POINTER(TracksTextOut)]
     _lib = L
     return L
 

@@ -1,9 +1,11 @@
 // emgpu_kernels_track.hip -- sample2track.m:183-237: the 1 Hz dead-reckoning track that the
 // reference builds from the files em_sample wrote, and its rejection tests, for n trajectories.
-// One lane = one trajectory.  Two input forms:
+// One lane = one trajectory.  Three input forms:
 //   DENSE  -- the sampler's device output as it lies in HBM (init_val rows + the time-blocked
 //             dyn_val float4 blocks): the device consumer of the hot path;
-//   PLANAR -- f64 columns parsed from initial.txt / transition.txt, laid out [T][3][n].
+//   PLANAR -- f64 columns parsed from initial.txt / transition.txt, laid out [T][3][n];
+//   TABLE  -- the transition table as the device parser left it ([rows][ncol] row-major): lane i reads its own len[i] rows, so tracks of
+//             different lengths run in one launch; positions go out track after track, [second][3] (k_sample2track_table).
 // Per trajectory and second: one f64 sin/cos pair (quadrant-exact like cosd/sind, Horner sums), 5 adds, 5 multiplies;
 // reads 12 B (DENSE) and writes 24 B of f64 track.  Bound: HBM.
 #include <hip/hip_runtime.h>
@@ -73,6 +75,47 @@ __global__ void __launch_bounds__(256) k_sample2track(const EmgpuTrackRun A) {
     }
     if (A.flags) A.flags[i] = (uint8_t)fl;
     if (A.vmm) { A.vmm[i] = lo; A.vmm[n + i] = hi; }
+}
+
+// The TABLE form: the same operations in the same order as above (positions, flags and speed range are bit-equal on the same values).
+__global__ void __launch_bounds__(256) k_sample2track_table(const EmgpuTrackTableRun A) {
+#pragma clang fp contract(off)
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= A.n) return;
+    double z = A.alt0[i];
+    double sp = A.speed0[i] * A.ur_speed;
+    double x = 0.0, y = 0.0, hd = 0.0;
+    const double vmin = A.min_speed * A.ur_speed, vmax = A.max_speed * A.ur_speed;
+    double lo = sp, hi = sp;
+    uint32_t fl = 0u;
+    if (z < 0.0) fl |= 1u;
+    if (sp <= vmin || sp >= vmax) fl |= 2u;
+    double *out = A.xyz ? A.xyz + 3 * A.xoff[i] : nullptr;
+    if (out) { out[0] = x; out[1] = y; out[2] = z; }
+    const int64_t f = A.first[i];
+    const int T = A.len[i];
+    for (int t = 0; t < T; t++) {
+        const double *row = A.table + (size_t)(A.rowidx ? A.rowidx[f + t] : f + t) * (size_t)A.ncol;
+        const double dz = row[A.c_vr] * A.ur_vertrate, dsp = row[A.c_acc] * A.ur_speed, dhd = row[A.c_tr] * A.ur_heading;
+        double sh, ch;
+        k_sincosd(hd, sh, ch);
+        const double xn = x + sp * ch, yn = y + sp * sh;
+        z = z + dz; sp = sp + dsp; hd = hd + dhd;
+        x = xn; y = yn;
+        if (z < 0.0) fl |= 1u;
+        if (sp <= vmin || sp >= vmax) fl |= 2u;
+        lo = sp < lo ? sp : lo; hi = sp > hi ? sp : hi;
+        if (out) { out[3 * (t + 1)] = x; out[3 * (t + 1) + 1] = y; out[3 * (t + 1) + 2] = z; }
+    }
+    if (A.flags) A.flags[i] = (uint8_t)fl;
+    if (A.vmm) { A.vmm[2 * i] = lo; A.vmm[2 * i + 1] = hi; }
+}
+
+hipError_t launch_sample2track_table(const EmgpuTrackTableRun &A, hipStream_t s, const char **name) {
+    *name = "k_sample2track_table";
+    if (A.n <= 0) return hipSuccess;
+    hipLaunchKernelGGL(k_sample2track_table, dim3((unsigned)((A.n + 255) / 256)), dim3(256), 0, s, A);
+    return hipGetLastError();
 }
 
 hipError_t launch_sample2track(const EmgpuTrackRun &A, bool dense, hipStream_t s, const char **name) {

@@ -81,4 +81,64 @@ hipError_t launch_text_rows(const EmgpuTextRun &R, hipStream_t s);
 hipError_t launch_format_g(const float *x, int64_t n, uint32_t *cnt, uint32_t *scratch, char *text, uint64_t base, uint64_t *offsets,
                            unsigned long long *paths, hipStream_t s);
 hipError_t launch_sample2track(const EmgpuTrackRun &A, bool dense, hipStream_t s, const char **name);
+
+// ---- sample2track's files on the device (emgpu_tracks_text_host, emgpu_parse_table_host)
+// One chunk of a numeric text table (emgpu_kernels_parse.hip): bytes [0, nbytes) begin at a line start and end behind a newline or at the end of
+// the file.  `text` is 4-byte aligned and readable up to nbytes rounded up to a multiple of 4.
+struct EmgpuHardToken { uint64_t pos; uint32_t off, _pad; };   // table element (row * ncol + column) and the token's first byte within the chunk
+constexpr uint32_t kParseTile = 64;                            // bytes of text per lane of the counting passes
+struct EmgpuParseRun {
+    const uint8_t *text;
+    uint32_t nbytes;
+    int32_t ncol;
+    uint32_t *cnt;             // [tiles] out: rows (lines holding more than separators) that begin in each tile of kParseTile bytes
+    uint32_t *scratch;         // pack_scratch_words(tiles) words: words 0-1 receive the chunk's rows (u64)
+    uint32_t rows;             // (launch_parse_rows) the chunk's rows
+    double *table;             // [..][ncol] row-major; the chunk's first row is row_base
+    int64_t row_base, table_rows;   // rows the table has room for: rows beyond are checked, not stored
+    EmgpuHardToken *hard;      // [hard_cap] out: tokens outside the exact fast path, for the host's strtod
+    uint32_t hard_cap;
+    uint32_t *hard_count;      // out (+=): hard tokens met, also those the list had no room for
+    unsigned long long *err;   // out (min=): the first byte of the first malformed row (chunk offset); ~0 before
+};
+hipError_t launch_parse_count(const EmgpuParseRun &P, hipStream_t s);   // cnt, scratch
+hipError_t launch_parse_rows(const EmgpuParseRun &P, hipStream_t s);    // table, hard, err
+hipError_t launch_parse_patch(double *table, const EmgpuHardToken *hard, const double *val, uint32_t n, hipStream_t s);   // table[hard[i].pos] = val[i]
+// Runs of equal ids in column 0 of table [R][ncol] (sample2track.m:192-193 without a sort): mark + scan + fill give run_id / run_first
+// (scratch words 0-1: the number of runs); the runs go into an open-addressing table (keys: 2^k entries preset to ~0, *dup = 1 when an id owns
+// two runs); each of n wanted ids is matched to its run (first row and length; length 0 when there is none).
+struct EmgpuRunTable {
+    const double *table; int32_t ncol; int64_t R;
+    uint32_t *cnt, *scratch;                 // [R], pack_scratch_words(R)
+    double *run_id; int64_t *run_first;      // [runs]
+    unsigned long long *keys; uint32_t *vals; uint32_t mask; uint32_t *dup;
+};
+hipError_t launch_run_mark(const EmgpuRunTable &G, hipStream_t s);
+hipError_t launch_run_fill(const EmgpuRunTable &G, hipStream_t s);
+hipError_t launch_run_match(const EmgpuRunTable &G, uint32_t runs, int64_t n, const double *ids, int64_t *first, int32_t *len, hipStream_t s);
+// k_sample2track_table: lane i integrates len[i] rows of the parsed table, rows first[i] .. (or rowidx[first[i] ..] when ids are interleaved)
+struct EmgpuTrackTableRun {
+    int64_t n;
+    double ur_speed, ur_vertrate, ur_heading, min_speed, max_speed;
+    const double *alt0, *speed0;            // [n]
+    const double *table; int32_t ncol, c_vr, c_acc, c_tr;
+    const int64_t *first; const int32_t *len; const int64_t *rowidx;
+    const uint64_t *xoff;                   // [n + 1]: first position row of track i (len[i] + 1 rows each)
+    double *xyz;                            // [xoff[n]][3] out
+    uint8_t *flags; double *vmm;            // [n], [n][2] out
+};
+hipError_t launch_sample2track_table(const EmgpuTrackTableRun &A, hipStream_t s, const char **name);
+// sample2track.m:277-278 (emgpu_kernels_csv.hip): "time_s,x_ft,y_ft,z_ft\n" and "%i,%0.0f,%0.0f,%0.0f\n" per second for every track with flags 0
+struct EmgpuCsvRun {
+    int64_t n;
+    const uint8_t *flags; const int32_t *len; const uint64_t *xoff; const double *xyz;
+    uint32_t *cnt;               // [n] out (launch_csv_len): bytes of track i's file; 0: rejected, or left to the host formatter
+    uint8_t *hostfmt;            // [n] out: 1 = accepted, but a coordinate is not finite or 2^63 and more in magnitude
+    const uint64_t *off;         // [n] (launch_csv_emit): first byte of track i's file in csv
+    char *csv;
+};
+hipError_t launch_csv_len(const EmgpuCsvRun &C, hipStream_t s);
+hipError_t launch_csv_emit(const EmgpuCsvRun &C, hipStream_t s);
+// "%0.0f" of n doubles, one after the other (emgpu_format_f0_host): as launch_format_g; a value the device does not format has length 0
+hipError_t launch_format_f0(const double *x, int64_t n, uint32_t *cnt, uint32_t *scratch, char *text, uint64_t base, uint64_t *offsets, hipStream_t s);
 } // namespace emgpu

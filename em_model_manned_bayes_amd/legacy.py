@@ -5,7 +5,8 @@ Same names, arguments and file formats as code/matlab/em_sample.m and code/matla
 Sampling and the track integration run on the GPU (libemgpu: emgpu_sample_dbn_host,
 emgpu_sample2track_host); parsing and formatting are host-side Python, as they are host-side MATLAB
 in the reference -- em_sample(text="device") formats its rows on the GPU too (emgpu_sample_text_host) and
-writes the same bytes.  A device-resident consumer that skips the text files exists as
+writes the same bytes, and sample2track(text="device") parses both files, integrates the tracks and formats the CSV rows on the GPU
+(emgpu_parse_table_host, emgpu_tracks_text_host) and writes the same files.  A device-resident consumer that skips the text files exists as
 native.sample2track_device (it reads the sampler's dense trace in place).
 """
 import os
@@ -23,6 +24,9 @@ FT_PER_NM = 1852.0 / 0.3048          # unitsratio('ft', 'nm')
 
 # what the last em_sample(text="device") spent where: library calls, their phases (emgpu_host_stats, summed over the calls), file writes
 last_text_stats = {}
+# what the last sample2track(text="device") spent where: file reads, the library call and its phases (upload, the three kernel groups, download,
+# host work), file writes; bytes, rows, hard tokens, host-formatted tracks
+last_track_stats = {}
 
 
 def _g(x):
@@ -168,13 +172,21 @@ def sample2track(parameters_filename, initial_filename, transition_filename, num
                  label_initial_acceleration="dotV", label_initial_vertrate="dotH", label_initial_turnrate="dotPsi",
                  label_transition_speed="dotV_t_1_", label_transition_altitude="dotH_t_1_", label_transition_heading="dotPsi_t_1_",
                  isOverwriteZeroBoundaries=False, idxZeroBoundaries=(1, 2, 3), min_altitude_ft=0, rng_seed=42, isPlot=False,
-                 write_files=True, verbose=True, ctx=None):
+                 write_files=True, verbose=True, ctx=None, text="host"):
     """[is_good, T_initial] = sample2track(parameters_filename, initial_filename, transition_filename, ...)
     (sample2track.m:1-287): 1 Hz dead reckoning of every sampled trajectory (on the GPU), CFIT and speed
     rejection, one `BAYES_t<T>_id<i>_alt<z0>_speed<v0>.csv` per accepted track under
     out_dir_parent/[G<g>/A<a>/]<alt>ft/.  T_initial is returned as a dict of columns (units converted like
     sample2track.m:126-128).  When the initial file holds more than num_max_tracks rows the reference keeps
-    randperm(rows, num_max_tracks) of MATLAB's stream; here numpy's RandomState(rng_seed) chooses them."""
+    randperm(rows, num_max_tracks) of MATLAB's stream; here numpy's RandomState(rng_seed) chooses them.
+
+    text: "host" reads both files with numpy.loadtxt, groups the transition rows on the host and formats every CSV row in Python;
+    "device" parses both files on the GPU (native.parse_table, native.tracks_text_host), integrates the tracks from the parsed table where
+    it lies and formats the CSV rows there: the same return values, directories, file names and file bytes.  The device reader's grammar is
+    narrower than loadtxt's: plain decimal numbers, nan and inf, separated by spaces or tabs; no '#' comments.  Host memory is about the
+    transition file plus the CSV text; files larger than memory are out of scope.  last_track_stats says where the time went."""
+    if text not in ("host", "device"):
+        raise ValueError("sample2track: text must be 'host' or 'device', not %r" % (text,))
     out_dir_parent = out_dir_parent or os.path.join(os.environ.get("AEM_DIR_BAYES", "."), "output", "tracks")
     parameters = em_read(parameters_filename, isOverwriteZeroBoundaries=isOverwriteZeroBoundaries, idxZeroBoundaries=list(idxZeroBoundaries))
     tm = np.asarray(parameters["temporal_map"]).reshape(-1, 2)
@@ -182,6 +194,13 @@ def sample2track(parameters_filename, initial_filename, transition_filename, num
     labels_trans = [make_valid_name(_erase(parameters["labels_transition"][int(r[1]) - 1])) for r in tm]  # :64
     names_i = ["id"] + labels_init
     names_t = ["id", "t"] + labels_trans
+    if text == "device":
+        return _sample2track_device_text(ctx or native.default_context(), parameters, parameters_filename, initial_filename, transition_filename,
+                                         names_i, names_t, labels_init, int(num_max_tracks), out_dir_parent,
+                                         (label_initial_geographic, label_initial_airspace, label_initial_altitude, label_initial_speed,
+                                          label_initial_acceleration, label_initial_vertrate),
+                                         (label_transition_speed, label_transition_altitude, label_transition_heading),
+                                         int(rng_seed), write_files, verbose)
     Ti = _read_table(initial_filename, len(names_i))
     Tt = _read_table(transition_filename, len(names_t))
     if Ti.shape[0] > num_max_tracks:                                                                       # :75-77
@@ -284,6 +303,146 @@ def sample2track(parameters_filename, initial_filename, transition_filename, num
         with open(os.path.join(out_dir, out_name), "w", encoding="utf-8", newline="\n") as f:              # :274-279
             f.write("time_s,x_ft,y_ft,z_ft\n")
             f.write("".join("%i,%0.0f,%0.0f,%0.0f\n" % (t, xyz[t, 0], xyz[t, 1], xyz[t, 2]) for t in range(xyz.shape[0])))
+
+    T_initial = {name: Ti[:, c].copy() for c, name in enumerate(names_i)}
+    T_initial[names_i[ci_spd]] *= ur_speed                                                                 # :126-128
+    if ci_acc is not None:
+        T_initial[names_i[ci_acc]] *= ur_speed
+    if ci_vr is not None:
+        T_initial[names_i[ci_vr]] *= ur_vertrate
+    return is_good, T_initial
+
+
+def _read_rows(filename, ctx=None):
+    """The bytes of a table file behind its header line: (uint8 array, bytes of the header line).  ctx: into pinned memory of its pool."""
+    size = os.path.getsize(filename)
+    buf = ctx.pinned_empty((max(size, 1),), np.uint8) if ctx is not None else np.empty(max(size, 1), dtype=np.uint8)
+    with open(filename, "rb") as f:
+        got = f.readinto(memoryview(buf)[:size]) if size else 0
+    data = buf[:got]
+    nl = np.flatnonzero(data[: 1 << 16] == 10)
+    if nl.size == 0:
+        nl = np.flatnonzero(data == 10)
+    head = int(nl[0]) + 1 if nl.size else got
+    return data[head:], head
+
+
+def _sample2track_device_text(ctx, parameters, parameters_filename, initial_filename, transition_filename, names_i, names_t, labels_init,
+                              num_max_tracks, out_dir_parent, labels_i, labels_t, rng_seed, write_files, verbose):
+    """sample2track(text="device"): the steps of sample2track above with both tables parsed, the tracks integrated and the CSV rows formatted
+    on the device; selection, directories and file names are computed here from the initial table, as there."""
+    st = {}
+    t0 = time.perf_counter()
+    rows_i, _ = _read_rows(initial_filename)
+    Ti = native.parse_table(ctx, rows_i, len(names_i), header_lines=1)
+    rows_t, _ = _read_rows(transition_filename, ctx)
+    st["read_ms"] = (time.perf_counter() - t0) * 1e3
+    n_initial_rows = Ti.shape[0]
+    if Ti.shape[0] > num_max_tracks:                                                                       # :75-77
+        keep = np.random.RandomState(rng_seed).permutation(Ti.shape[0])[:num_max_tracks]
+        Ti = Ti[keep]
+    num_tracks = Ti.shape[0]
+
+    def col(names, label):
+        return names.index(label) if label in names else None
+
+    ci_geo, ci_air, ci_alt, ci_spd, ci_acc, ci_vr = (col(names_i, l) for l in labels_i)
+    cu_acc, cu_vr, cu_tr = (col(names_t, l) for l in labels_t)
+    for what, c in (("altitude", ci_alt), ("speed", ci_spd), ("transition speed", cu_acc), ("transition altitude", cu_vr),
+                    ("transition heading", cu_tr)):
+        if c is None:
+            raise ValueError("sample2track: no %s column with the given label" % what)
+    b_alt = np.asarray(parameters["boundaries"][labels_init.index(labels_i[2])], dtype=np.float64)
+    b_spd = np.asarray(parameters["boundaries"][labels_init.index(labels_i[3])], dtype=np.float64)
+    min_alt, max_alt = float(b_alt[0]), float(b_alt[-1])                                                   # :100-101
+    min_speed, max_speed = float(b_spd[0]), float(b_spd[-1])                                               # :104-105
+    ur_speed, ur_vertrate, ur_heading = FT_PER_NM / 3600.0, 1.0 / 60.0, 1.0                                # :113-123
+    is_uncor = "uncor_" in os.path.basename(parameters_filename)
+
+    # the CSV buffer: sized from the look of the file's first rows, and from the library's exact total when that was too little
+    csv_cap = None
+    if write_files:
+        head = rows_t[: 1 << 20]
+        per_line = head.size / max(int(np.count_nonzero(head == 10)), 1)
+        share = num_tracks / max(n_initial_rows, 1)
+        csv_cap = int(num_tracks * 64 + rows_t.size / max(per_line, 1.0) * share * 30) + (1 << 16)
+    args = (ctx, rows_t, len(names_t), (cu_vr, cu_acc, cu_tr), Ti[:, 0], Ti[:, ci_alt], Ti[:, ci_spd], ur_speed, ur_vertrate, ur_heading,
+            min_speed, max_speed)
+    t0 = time.perf_counter()
+    try:
+        res = native.tracks_text_host(*args, want_csv=write_files, csv_cap=csv_cap)
+    except native.L.EmgpuError as e:
+        if e.code != native.L.ERR_EVENT_CAP:
+            raise
+        res = native.tracks_text_host(*args, want_csv=write_files, csv_cap=int(e.totals[0]))
+    host_xyz = None
+    if write_files and res["totals"]["host_formatted"]:     # coordinates the device does not format: those files are written as the host path writes them
+        host_xyz = native.tracks_text_host(*args, want_csv=False, want_xyz=True)["xyz"]
+    st["library_ms"] = (time.perf_counter() - t0) * 1e3
+    flags, vmm, lengths = res["flags"], res["speed_minmax"], res["lengths"]
+    is_good = flags == 0                                                                                   # :243
+
+    # altitude directories, step 100 ft (:150-158)
+    if min_alt % 100.0 != 0:
+        Lgrid = np.arange(np.floor(min_alt - 50.0), max_alt + 200.0 + 1e-9, 100.0)
+    else:
+        Lgrid = np.arange(min_alt, max_alt + 200.0 + 1e-9, 100.0)
+    if Lgrid[0] < 0:
+        Lgrid[0] = 0.0
+    is_geo, is_air = ci_geo is not None, ci_air is not None
+    t0 = time.perf_counter()
+    if write_files:
+        os.makedirs(out_dir_parent, exist_ok=True)
+        if is_uncor and is_geo and is_air:                                                                # :161-173
+            for g in np.unique(Ti[:, ci_geo]):
+                for a in np.unique(Ti[:, ci_air]):
+                    for l in Lgrid:
+                        os.makedirs(os.path.join(out_dir_parent, "G%i" % g, "A%i" % a, "%ift" % l), exist_ok=True)
+        else:                                                                                              # :175-178
+            for l in Lgrid:
+                os.makedirs(os.path.join(out_dir_parent, "%ift" % l), exist_ok=True)
+    csv = res["csv"]
+    offs = res["offsets"].astype(np.int64).tolist() if write_files else None
+    made = set()
+    for i in range(num_tracks):
+        if not is_good[i]:
+            if verbose:
+                print("Reject i=%i, CFIT = %i, v = [%0.3f, %0.3f]" % (i + 1, int(flags[i] & 1), vmm[i, 0], vmm[i, 1]))   # :284
+            continue
+        if not write_files:
+            continue
+        z0, v0 = Ti[i, ci_alt], Ti[i, ci_spd] * ur_speed
+        out_name = "BAYES_t%i_id%i_alt%i_speed%i.csv" % (lengths[i], i + 1, _matlab_round(z0), _matlab_round(v0))               # :249
+        k = int(np.searchsorted(Lgrid, z0, side="right")) - 1                                              # discretize(z0, L), :263
+        if z0 == Lgrid[-1]:
+            k = len(Lgrid) - 2
+        if k < 0 or k >= len(Lgrid) - 1:
+            raise ValueError("sample2track: initial altitude %g ft is outside the altitude directories" % z0)
+        parts = []
+        if is_geo:
+            parts.append("G%i" % Ti[i, ci_geo])                                                            # :253-255
+        if is_air:
+            parts.append("A%i" % Ti[i, ci_air])                                                            # :258-260
+        parts.append("%ift" % Lgrid[k])
+        out_dir = os.path.join(out_dir_parent, *parts)
+        if out_dir not in made:
+            os.makedirs(out_dir, exist_ok=True)
+            made.add(out_dir)
+        if offs[i + 1] > offs[i]:
+            with open(os.path.join(out_dir, out_name), "wb") as f:                                         # :274-279
+                f.write(csv[offs[i]:offs[i + 1]].data)
+        else:
+            xyz = host_xyz[i]
+            with open(os.path.join(out_dir, out_name), "w", encoding="utf-8", newline="\n") as f:
+                f.write("time_s,x_ft,y_ft,z_ft\n")
+                f.write("".join("%i,%0.0f,%0.0f,%0.0f\n" % (t, xyz[t, 0], xyz[t, 1], xyz[t, 2]) for t in range(xyz.shape[0])))
+    st["write_ms"] = (time.perf_counter() - t0) * 1e3
+    st.update({"library_call_ms": res["host_stats"]["total_ms"], "bytes_transition": int(rows_t.size), "tracks": int(num_tracks),
+               "accepted": int(is_good.sum())})
+    st.update({k + "_ms": v for k, v in res["phase_ms"].items()})
+    st.update(res["totals"])
+    last_track_stats.clear()
+    last_track_stats.update(st)
 
     T_initial = {name: Ti[:, c].copy() for c, name in enumerate(names_i)}
     T_initial[names_i[ci_spd]] *= ur_speed                                                                 # :126-128

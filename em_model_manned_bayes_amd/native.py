@@ -2,6 +2,7 @@
 sampling calls with numpy (host) or raw device pointers (torch tensors' data_ptr()).
 """
 import ctypes as C
+import re
 
 import numpy as np
 
@@ -830,6 +831,141 @@ def sample2track_host(ctx, alt0, speed0, updates, ur_speed, ur_vertrate, ur_head
     vmm = np.zeros((n, 2))
     L.check(L.lib().emgpu_sample2track_host(ctx._h, C.byref(p), _p(alt0), _p(speed0), _p(updates), _p(xyz), _p(flags), _p(vmm)))
     return xyz, flags, vmm
+
+
+def _buffer_address(data):
+    """(address, bytes, keep-alive) of a bytes-like object or a uint8 array, without a copy."""
+    if isinstance(data, np.ndarray):
+        a = np.ascontiguousarray(data).view(np.uint8).reshape(-1)
+        return a.ctypes.data, a.size, a
+    if isinstance(data, (bytes, bytearray, memoryview)):
+        a = np.frombuffer(data, dtype=np.uint8)
+        return (a.ctypes.data if a.size else 0), a.size, a
+    raise TypeError("text: bytes, bytearray, memoryview or a uint8 array")
+
+
+_LINE = re.compile(r"line (\d+)")
+
+
+def _parse_error(rc, header_lines, what):
+    """EMGPU_ERR_PARSE as the ValueError the host reader raises; the line is counted from the top of the file."""
+    msg = L.lib().emgpu_last_error().decode("utf-8", "replace")
+    m = _LINE.search(msg)
+    if m:
+        msg = "%s: line %d is not a row of numbers with the expected columns (%s)" % (what, int(m.group(1)) + header_lines, msg)
+    e = ValueError(msg)
+    e.line = int(m.group(1)) + header_lines if m else None
+    return e
+
+
+def parse_table(ctx, data, ncol, return_stats=False, header_lines=0, rows_cap=None):
+    """emgpu_parse_table_host: the numeric text table `data` (bytes-like, or a uint8 array -- a pinned one is read by the copy engine in
+    place) parsed on the device -> f64 [rows, ncol], every value bit-equal to float(token).  Grammar: include/emgpu.h (narrower than
+    numpy.loadtxt: no '#' comments).  A malformed line raises ValueError with `.line` (1-based, plus header_lines: the lines the caller cut off
+    in front).  return_stats: also {"rows", "hard_tokens"} (hard tokens: those the device hands to the host's strtod).  rows_cap: rows of the
+    output array (default: what the bytes can hold at most); too few raise EmgpuError(ERR_EVENT_CAP) with `.rows`."""
+    addr, nbytes, keep = _buffer_address(data)
+    ncol = int(ncol)
+    cap = nbytes // (2 * ncol) + 1 if rows_cap is None else int(rows_cap)
+    out = np.empty((max(cap, 1), ncol), dtype=np.float64)
+    rows, hard = C.c_int64(0), C.c_uint64(0)
+    rc = L.lib().emgpu_parse_table_host(ctx._h, C.c_void_p(addr), nbytes, ncol, _p(out), cap, C.byref(rows), C.byref(hard))
+    del keep
+    if rc == L.ERR_PARSE:
+        raise _parse_error(rc, int(header_lines), "parse_table")
+    if rc == L.ERR_EVENT_CAP:
+        e = L.EmgpuError(rc, L.lib().emgpu_last_error().decode("utf-8", "replace"))
+        e.rows = int(rows.value)
+        raise e
+    L.check(rc)
+    table = out[: int(rows.value)]
+    if rows_cap is None and table.shape[0] < out.shape[0] // 2:
+        table = table.copy()
+    return (table, {"rows": int(rows.value), "hard_tokens": int(hard.value)}) if return_stats else table
+
+
+def format_f0(ctx, x, cap=None):
+    """emgpu_format_f0_host: "%0.0f" of every double of x by the device function the CSV rows use.  Returns the list of strings; a value the
+    device does not format (not finite, or 2^63 and more in magnitude) gives None."""
+    x = np.ascontiguousarray(x, dtype=np.float64).reshape(-1)
+    n = x.size
+    cap = 20 * n if cap is None else int(cap)
+    buf = np.empty(max(cap, 1), dtype=np.uint8)
+    offs = np.zeros(n + 1, dtype=np.uint64)
+    L.check(L.lib().emgpu_format_f0_host(ctx._h, _p(x), n, _p(buf), cap, _p(offs)))
+    text = buf[: int(offs[n])].tobytes().decode("ascii")
+    o = offs.astype(np.int64).tolist()
+    return [text[a:b] if b > a else None for a, b in zip(o[:-1], o[1:])]
+
+
+def csv_bound(n, rows):
+    """emgpu_csv_bound: bytes that always hold the CSV text of n tracks with `rows` position rows in all: 22 n + 74 rows."""
+    return int(L.lib().emgpu_csv_bound(int(n), int(rows)))
+
+
+def tracks_text_host(ctx, text, ncol, cols, ids, alt0, speed0, ur_speed, ur_vertrate, ur_heading, min_speed, max_speed, want_csv=True,
+                     csv=None, csv_cap=None, want_xyz=False, header_lines=1):
+    """emgpu_tracks_text_host: the transition table `text` (bytes-like or uint8 array; pinned: no staging) parsed on the device, the tracks of
+    the wanted ids integrated from it and their CSV files formatted there.  cols: the 0-based columns of vertical rate, acceleration, turn rate.
+    Returns a dict: flags [n] u8, speed_minmax [n, 2], lengths [n] i32, offsets [n + 1] u64 and csv (uint8: file i is csv[offsets[i]:
+    offsets[i + 1]]; None unless want_csv), totals {"csv_bytes", "rows", "hard_tokens", "host_formatted", "noncontiguous"}, xyz (list of
+    [lengths[i] + 1, 3] views, when want_xyz), phase_ms, kernel, host_stats.  csv: a uint8 buffer of the caller's (default: a pinned one of
+    csv_cap bytes, or measured by a first call that writes nothing).  A buffer that is too small raises EmgpuError(ERR_EVENT_CAP) with
+    `.totals`.  A malformed line raises ValueError (its line counted with header_lines in front)."""
+    addr, nbytes, keep = _buffer_address(text)
+    ids = np.ascontiguousarray(ids, dtype=np.float64).reshape(-1)
+    alt0 = np.ascontiguousarray(alt0, dtype=np.float64).reshape(-1)
+    speed0 = np.ascontiguousarray(speed0, dtype=np.float64).reshape(-1)
+    n = ids.size
+    assert alt0.size == n and speed0.size == n
+    p = track_params(n, 1, ur_speed, ur_vertrate, ur_heading, min_speed, max_speed)
+    i = L.TracksTextIn()
+    i.text, i.nbytes, i.ncol = addr, nbytes, int(ncol)
+    i.col_vertrate, i.col_acc, i.col_turnrate = (int(c) for c in cols)
+    i.id, i.alt0, i.speed0 = _p(ids), _p(alt0), _p(speed0)
+    flags, vmm, lengths = np.zeros(n, dtype=np.uint8), np.zeros((n, 2)), np.zeros(n, dtype=np.int32)
+    offsets, totals, phase = np.zeros(n + 1, dtype=np.uint64), np.zeros(5, dtype=np.int64), np.zeros(6)
+
+    def call(csv_buf, cap, xyz_buf=None):
+        o = L.TracksTextOut()
+        o.flags, o.speed_minmax, o.lengths, o.totals, o.phase_ms = _p(flags), _p(vmm), _p(lengths), _p(totals), _p(phase)
+        if want_csv:
+            o.offsets = _p(offsets)
+            if csv_buf is not None:
+                o.csv, o.csv_cap = _p(csv_buf), int(cap)
+        if xyz_buf is not None:
+            o.xyz, o.xyz_cap = _p(xyz_buf), xyz_buf.shape[0]
+        rc = L.lib().emgpu_tracks_text_host(ctx._h, C.byref(p), C.byref(i), C.byref(o))
+        if rc == L.ERR_PARSE:
+            raise _parse_error(rc, int(header_lines), "tracks_text_host")
+        if rc == L.ERR_EVENT_CAP:
+            e = L.EmgpuError(rc, L.lib().emgpu_last_error().decode("utf-8", "replace"))
+            e.totals = totals.copy()
+            raise e
+        L.check(rc)
+
+    xyz_buf = None
+    if want_csv and csv is None and csv_cap is None:
+        call(None, 0)                                      # measured first: the buffer is sized from the totals
+        csv_cap = int(totals[0])
+    if want_csv and csv is None:
+        csv = ctx.pinned_empty((max(int(csv_cap), 1),), np.uint8)
+    if want_csv:
+        csv_cap = csv.size if csv_cap is None else int(csv_cap)
+    call(csv, csv_cap)
+    if want_xyz:
+        xyz_buf = np.empty((int(lengths.astype(np.int64).sum()) + n, 3))
+        call(csv, csv_cap, xyz_buf)
+    del keep
+    out = {"flags": flags, "speed_minmax": vmm, "lengths": lengths, "offsets": offsets if want_csv else None,
+           "csv": csv[: int(totals[0])] if want_csv else None,
+           "totals": dict(zip(("csv_bytes", "rows", "hard_tokens", "host_formatted", "noncontiguous"), (int(v) for v in totals))),
+           "phase_ms": dict(zip(("h2d", "parse", "track", "csv", "d2h", "host"), (float(v) for v in phase))),
+           "kernel": ctx.last_kernel(), "host_stats": ctx.host_stats(), "xyz": None}
+    if want_xyz:
+        ends = np.cumsum(lengths.astype(np.int64) + 1)
+        out["xyz"] = split_rows(xyz_buf, ends)
+    return out
 
 
 def sample2track_device(ctx, params, alt0, speed0, dyn_val, xyz=0, flags=0, speed_minmax=0):

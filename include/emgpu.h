@@ -364,7 +364,7 @@ int emgpu_device_free(emgpu_ctx *ctx, void *p);
 int emgpu_host_alloc(emgpu_ctx *ctx, uint64_t bytes, void **out);
 int emgpu_host_free(emgpu_ctx *ctx, void *p);   /* back to the pool; emgpu_ctx_trim releases the pool's free blocks */
 
-/* Phases of the last emgpu_sample_dbn_host, emgpu_sample_uncor_host or emgpu_sample_text_host call on this ctx (each call is a pipeline: chunk k's kernel runs
+/* Phases of the last emgpu_sample_dbn_host, emgpu_sample_uncor_host, emgpu_sample_text_host or emgpu_tracks_text_host call on this ctx (each call is a pipeline: chunk k's kernel runs
  * while chunk k-1 crosses PCIe and chunk k-2 is copied from staging into the caller's arrays, so the phases overlap and do not add up to
  * total_ms). */
 typedef struct {
@@ -530,6 +530,71 @@ int emgpu_sample2track_device(emgpu_ctx *ctx, const emgpu_track_params *p, const
                               const float *dyn_val, double *xyz, uint8_t *flags, double *speed_minmax);
 int emgpu_sample2track_host(emgpu_ctx *ctx, const emgpu_track_params *p, const double *alt0, const double *speed0,
                             const double *updates, double *xyz, uint8_t *flags, double *speed_minmax);
+
+/* ------------------------------------------------------------------------------------------------
+ * sample2track's files read and written on the device (sample2track.m:69-72 readtable, :192-193 the rows of an id, :183-243 the track,
+ * :274-279 the CSV file): what legacy.sample2track(text="device") is made of.
+ *
+ * emgpu_parse_table_host -- a numeric text table (the bytes of initial.txt / transition.txt behind their header line) -> out [rows][ncol] f64,
+ * row-major, rows in file order (:69-72).  Lines end in "\n" (a "\r" in front of it is dropped; the last line may lack it); lines that hold
+ * only spaces and tabs are skipped; numbers are separated by runs of spaces or tabs, and separators may trail.  A number is
+ *     [+-]? (digits [. digits?] | . digits) ([eE] [+-]? digits)?     or     [+-]? (nan | inf | infinity), in any letter case.
+ * Narrower than numpy.loadtxt on purpose: no '#' comments, no hex, no '_'.  Anything else, or a line that does not hold ncol numbers, is
+ * EMGPU_ERR_PARSE, and emgpu_last_error names the 1-based line (of `text`) of the first such line.  EXACT: every value is the correctly rounded
+ * double of its decimal text (strtod), the sign of -0 included.  On the device: with w the mantissa's digits as an integer and d the decimal
+ * exponent (the exponent field minus the digits behind the point), w < 2^53 and |d| <= 22 give w * 10^d or w / 10^-d in one IEEE operation;
+ * every other number is a HARD token, finished by the host with strtod (*hard_tokens: how many; none in a file em_sample wrote from the shipped
+ * models: "%g" prints six digits, and their values lie between 10^-4 and 10^6).  The text goes up in chunks cut at a newline
+ * (EMGPU_HOST_CHUNK_MB), one chunk's copy behind the parse of the one before; pinned text (emgpu_host_alloc) without staging.
+ * EMGPU_ERR_EVENT_CAP when rows_cap rows do not hold the table (*rows: exact).
+ *
+ * emgpu_format_f0_host -- "%0.0f" of n doubles by the device function the CSV rows use, one after the other: value i is
+ * out[offsets[i] .. offsets[i + 1]) (offsets: n + 1 entries; capacity protocol of emgpu_format_g_host).  For |v| < 2^63: the digits of v rounded
+ * to the nearest integer, ties to even, behind a '-' when v's sign bit is set ("-0" for -0.3).  Other values have length 0: the device does
+ * not format them.
+ *
+ * emgpu_tracks_text_host -- the transition text is parsed as above and stays on the device; runs of equal ids in its column 0 are found
+ * without a sort and each of the p->n wanted ids is matched to its run (an id without rows: a track of length 0; the same id twice: the same
+ * rows twice; ids are compared as doubles); k_sample2track_table integrates every track from its rows where they lie (same operations as
+ * emgpu_sample2track_host: bit-equal results), and for every track with flags 0 the bytes of its file are formatted on the device:
+ * "time_s,x_ft,y_ft,z_ft\n", then "%i,%0.0f,%0.0f,%0.0f\n" for t = 0 .. lengths[i] (:277-278).  When an id owns more than one run (interleaved
+ * rows) the rows of an id are selected on the host by a stable sort of the id column, as the reference's logical index does, and
+ * totals[4] = 1; the results are the same.  p: the unit ratios and the speed limits (p->T is not used: every track has its own length).
+ *   totals[0] bytes of the CSV text   [1] rows of the transition table   [2] hard tokens   [3] accepted tracks left to the caller's formatter
+ *   (a coordinate that is not finite, or 2^63 and more in magnitude: offsets[i + 1] == offsets[i] although flags[i] == 0; ask for xyz)
+ *   [4] 1: the ids were not contiguous
+ * csv == NULL with offsets: the files are measured, not written; offsets == NULL: no CSV work at all.  EMGPU_ERR_EVENT_CAP when csv_cap bytes
+ * do not hold the text, or xyz_cap rows the positions (every other output is complete, totals exact; a retry with that room gives the same
+ * bytes).  emgpu_csv_bound(n, rows) = 22 n + 74 rows always suffices for n files with `rows` position rows in all (a line: 10 characters of
+ * "%i", three times a sign and 19 digits, three commas, the newline); real files are near 20 bytes per row.  Host memory: the transition text
+ * and the CSV text; files larger than memory are out of scope.  emgpu_host_stats describes the call.
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct {
+    const char *text;          /* the transition table's rows (behind the header line)                                              */
+    int64_t nbytes;
+    int32_t ncol;              /* numbers per row; column 0 is the id                                                               */
+    int32_t col_vertrate, col_acc, col_turnrate;   /* 0-based columns of the three updates (:131-133)                              */
+    const double *id;          /* [n] per wanted track: its id, initial altitude (ft) and speed (model units), from the initial table */
+    const double *alt0;
+    const double *speed0;
+} emgpu_tracks_text_in;
+typedef struct {
+    uint8_t *flags;            /* [n] bit 0 CFIT, bit 1 speed (as emgpu_sample2track_host)                                         */
+    double *speed_minmax;      /* [n][2], or NULL                                                                                   */
+    int32_t *lengths;          /* [n] transition rows of track i, or NULL                                                           */
+    char *csv;                 /* [csv_cap] the files' bytes, track after track, or NULL                                            */
+    int64_t csv_cap;
+    uint64_t *offsets;         /* [n + 1] file i is csv[offsets[i] .. offsets[i + 1]); NULL: no CSV work                            */
+    int64_t *totals;           /* [5] see above                                                                                     */
+    double *xyz;               /* [xyz_cap][3] positions, track after track, lengths[i] + 1 rows each, or NULL                       */
+    int64_t xyz_cap;
+    double *phase_ms;          /* [6] upload, parse kernels, grouping + track kernels, CSV kernels, download, host work; or NULL    */
+} emgpu_tracks_text_out;
+int emgpu_parse_table_host(emgpu_ctx *ctx, const char *text, int64_t nbytes, int32_t ncol, double *out, int64_t rows_cap, int64_t *rows,
+                           uint64_t *hard_tokens);
+int emgpu_format_f0_host(emgpu_ctx *ctx, const double *x, int64_t n, char *out, int64_t cap, uint64_t *offsets);
+int64_t emgpu_csv_bound(int64_t n, int64_t rows);
+int emgpu_tracks_text_host(emgpu_ctx *ctx, const emgpu_track_params *p, const emgpu_tracks_text_in *in, const emgpu_tracks_text_out *out);
 
 /* ------------------------------------------------------------------------------------------------
  * UncorEncounterModel.track (@UncorEncounterModel/UncorEncounterModel.m:318-471) with coordSys 'NEU': per trajectory
