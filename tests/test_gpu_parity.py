@@ -1126,9 +1126,10 @@ class _FusedTerminal:
     """One emgpu_sample_terminal_device call (the entry point bench.py --config terminal times: k_bn -> k_terminal_geo -> k_terminal_propagate,
     @CorTerminalModel/sample.m:29-77 -> createEncounter.m:13-72) into torch buffers on cuda:0."""
 
-    def __init__(self, t, n, cap=123):
+    def __init__(self, t, n, cap=123, propagate_kernel="k_terminal_propagate<35,6,4>"):
         import torch
         self.torch, self.t, self.n, self.cap = torch, t, n, cap
+        self.propagate_kernel = propagate_kernel          # the instance the trajectory models' shape must be given
         self.dev = torch.device("cuda", 0)
         self.ctx = native.Context(0, stream=torch.cuda.current_stream(self.dev).cuda_stream)
         ni = t.native.n_initial
@@ -1152,7 +1153,7 @@ class _FusedTerminal:
                                       attempts=self.att.data_ptr())
         self.ctx.sync()
         k = self.ctx.last_kernel()
-        assert k.startswith("k_bn<16>") and " + k_terminal_geo + k_terminal_propagate<35,6,4>" in k, k
+        assert k.startswith("k_bn<16>") and " + k_terminal_geo + " + self.propagate_kernel in k and k.endswith(self.propagate_kernel), k
         assert self.ctx.last_launches() == 3
 
     def check_slice_against_oracle(self, oms, om_geom, seed, first_index, lo, m, stride=1):
