@@ -57,7 +57,7 @@ __device__ __forceinline__ void load_cthr_full(uint32_t (&th)[M], const uint32_t
 }
 // The hot loop compares high halfwords only, so the registers hold two threshold halves each
 // (threshold 2q in the low word, 2q+1 in the high word: SDWA selects the word); the rare exact pass
-// reloads the full column from the table.
+// reloads the full column from the table, or rebuilds it from on-chip state (eight_seconds_exact_chip).
 // Entries of the byte table carry bit 7 when the bin is the variable's zero bin: the "zero bin" flag of a second
 // is then bit 7 of its packed byte, and the whole 8-bit stream is gathered from the two packed words with one
 // multiply each (zero_stream below) instead of one compare + carry per second.
@@ -93,25 +93,42 @@ __device__ __forceinline__ uint32_t zero_stream(uint32_t a, uint32_t b) { return
 //     at an x_h where its predecessor in the chain reports a tie, so the block is redone exactly anyway;
 //   * H_t = 0 has no T' (it would be -1): it gets T' = 0 and x_h = 0 is treated as a tie by a separate test of the
 //     draws themselves (p = 2^-16 per draw, like any other tie).
-// Thresholds beyond meff (the instance is built for M >= meff) get T' = 0xFFFF: never fired, never a tie.
+// Thresholds beyond meff (the instance is built for M >= meff) get T' = 0xFFFF: never fired, never a tie.  So do the copies of the last
+// real threshold that pad a column of fewer than meff distinct ones (p[t] == p[t-1]; pushed through the +1 of the first refinement every
+// copy became a tie value of its own, H+1, H+2, ...) and a column's "never" (0xFFFFFFFF: the draws are clamped below it): the count
+// then stops at the number d of real thresholds, and nibble d of the map holds the column's last bin like every nibble after it.
+// zc: 1 in both halfwords when the column has a real threshold with H_t = 0, else 0 -- only such a lane has to treat x_h = 0 as a tie.
+// lw, dl: what the exact pass needs beside the T' to put the full thresholds together again without a load from the table (kept in the
+// lane's LDS row by the instances that have the words, ChipCol below): the thresholds' low halves, two per word like the T', and three
+// bits per slot, T'_t + 1 - H_t (0 for an ordinary threshold, 1 for H_t = 0, the shift of a shifted one: at most t + 1) or 7 = "never".
 // The byte table is indexed by the number of FIRED thresholds n (entries 0-3 in bnl, 4-7 in bnh; for M <= 3 by 2n, the sum of
 // the min(d, 2) itself) and carries the zero-bin flag in bit 7 like the by-borrows table of the exact pass.
 template <int M>
-__device__ __forceinline__ void load_cthr_pk(uint32_t (&tp)[(M + 1) / 2], uint32_t &bnl, uint32_t &bnh, const uint32_t *__restrict__ p, int meff, uint32_t zbin1) {
+__device__ __forceinline__ void load_cthr_pk(uint32_t (&tp)[(M + 1) / 2], uint32_t &bnl, uint32_t &bnh, uint32_t &zc, uint32_t (&lw)[(M + 1) / 2], uint32_t &dl,
+                                             const uint32_t *__restrict__ p, int meff, uint32_t zbin1) {
     static_assert(M >= 1 && M <= 7, "the byte table has 8 entries");
-    uint32_t tq[M];
-    uint32_t prev = 0u;
+    uint32_t tq[M], lq[M];
+    uint32_t prev = 0u, xprev = 0u, z = 0u, codes = 0u;
 #pragma unroll
     for (int t = 0; t < M; t++) {
-        uint32_t v = 0xFFFFu;
+        uint32_t v = 0xFFFFu, code = 7u, low = 0xFFFFu;
         if (t < meff) {
-            const uint32_t h = p[t] >> 16;
-            v = h ? h - 1u : 0u;
-            if (t > 0 && v <= prev) v = prev + 1u;
-            v = v > 0xFFFFu ? 0xFFFFu : v;
+            const uint32_t x = p[t];
+            if (x != 0xFFFFFFFFu && !(t > 0 && x == xprev)) {   // a real threshold: neither "never" nor a padding copy
+                const uint32_t h = x >> 16;
+                v = h ? h - 1u : 0u;
+                z |= h ? 0u : 0x00010001u;
+                if (t > 0 && v <= prev) v = prev + 1u;
+                v = v > 0xFFFFu ? 0xFFFFu : v;
+                code = v + 1u - h; low = x & 0xFFFFu;
+            }
+            xprev = x;
         }
-        tq[t] = v; prev = v;
+        tq[t] = v; prev = v; lq[t] = low; codes |= code << (3 * t);
     }
+    zc = z; dl = codes;
+#pragma unroll
+    for (int q = 0; q < (M + 1) / 2; q++) lw[q] = lq[2 * q] | ((2 * q + 1 < M ? lq[2 * q + 1] : 0xFFFFu) << 16);
 #pragma unroll
     for (int q = 0; q < (M + 1) / 2; q++) tp[q] = tq[2 * q] | ((2 * q + 1 < M ? tq[2 * q + 1] : 0xFFFFu) << 16);
     const uint32_t map = p[meff];
@@ -129,8 +146,8 @@ __device__ __forceinline__ void load_cthr_pk(uint32_t (&tp)[(M + 1) / 2], uint32
 // Eight seconds of one dynamic variable, interior block (every second is a draw), decided from the high halfwords:
 // same outputs as eight_seconds_pass<M, false, false>.  Returns bit 0 when a transition compare of this lane needs the low
 // halfword, bit 1 when a resample compare does (the caller then redoes the block exactly).  No carries, no VCC: nothing here needs wait states.
-template <int M>
-__device__ __forceinline__ uint32_t eight_seconds_pk(const uint4 &th, const uint4 &rh, const uint32_t (&tp)[(M + 1) / 2], uint32_t bnl, uint32_t bnh,
+template <int M, bool ZL = true>
+__device__ __forceinline__ uint32_t eight_seconds_pk(const uint4 &th, const uint4 &rh, const uint32_t (&tp)[(M + 1) / 2], uint32_t bnl, uint32_t bnh, uint32_t zc,
                                                  uint32_t RR1, uint32_t cur_in, uint32_t &cur_out, uint32_t &pbA, uint32_t &pbB, uint32_t &hit8, uint32_t &chg8) {
     uint32_t nb2[4], par = 0u, hitA = 0u;
 #pragma unroll
@@ -154,12 +171,15 @@ __device__ __forceinline__ uint32_t eight_seconds_pk(const uint4 &th, const uint
         asm("v_pk_min_u16 %0, %0, 2 op_sel_hi:[1,0]" : "+v"(u));
         hitA = p ? ((hitA << 2) | u) : u;
     }
-    // x_h = 0 ties with a threshold whose high half is 0 (it has no T'): treat every such draw as a tie
+    // x_h = 0 ties with a threshold whose high half is 0 (it has no T'): a lane whose column has one (zc = 1 | 1 << 16) treats every
+    // such draw as a tie; on the others (zc = 0) x_h = 0 fires nothing and the difference below saturates to 0.  ZL = false: every lane
+    // does (the event-list forms: three more registers would cost k_uncor_fast_ev<7,6,6,6> its fourth wave)
     uint32_t mz, zt;
     asm("v_pk_min_u16 %0, %1, %2" : "=v"(mz) : "v"(th.x), "v"(th.y));
     asm("v_pk_min_u16 %0, %0, %1" : "+v"(mz) : "v"(th.z));
     asm("v_pk_min_u16 %0, %0, %1" : "+v"(mz) : "v"(th.w));
-    asm("v_pk_sub_u16 %0, 1, %1 op_sel_hi:[0,1] clamp" : "=v"(zt) : "v"(mz));              // 1 in a half <=> that half of mz is 0
+    if constexpr (ZL) asm("v_pk_sub_u16 %0, %1, %2 clamp" : "=v"(zt) : "v"(zc), "v"(mz));  // 1 in a half <=> zc and that half of mz is 0
+    else asm("v_pk_sub_u16 %0, 1, %1 op_sel_hi:[0,1] clamp" : "=v"(zt) : "v"(mz));          // 1 in a half <=> that half of mz is 0
     pbA = __builtin_amdgcn_perm(nb2[1], nb2[0], 0x06040200u);
     pbB = __builtin_amdgcn_perm(nb2[3], nb2[2], 0x06040200u);
     hit8 = (hitA & 0xAAu) | ((hitA >> 17) & 0x55u);                                          // bit 1 of every 2-bit field, MSB-first
@@ -251,7 +271,7 @@ __device__ __forceinline__ bool eight_seconds_pass(const uint4 &th, const uint4 
     return !EXACT && dmin == 0u;
 }
 
-// rare path, kept out of line so that the hot loop stays small in the instruction cache
+// rare path, kept out of line so that the hot loop stays small in the instruction cache (the instances without room for ChipCol)
 template <int M>
 __device__ __attribute__((noinline)) void eight_seconds_exact(uint32_t c0, uint32_t c1r, uint32_t attempt, uint32_t k0, uint32_t k1,
                                                               uint4 th, uint4 rh, uint32_t tvar, uint32_t ivar, int g8, int T,
@@ -275,10 +295,64 @@ __device__ __attribute__((noinline)) void eight_seconds_exact(uint32_t c0, uint3
     out[0] = cur; out[1] = a; out[2] = b; out[3] = h; out[4] = c;
 }
 
+// Where an instance keeps (lw, dl) of its three columns: the lane's three spare words of its LDS row and the two words of the
+// worker's global index, free where no index list can be in use.  Instances with more than four words of low halves, and the index-list
+// and event-list forms, keep the reload from the table (the lane's column number in the spare words).
+template <int M0, int M1, int M2>
+struct ChipCol {
+    static constexpr int kW1 = (M0 + 1) / 2, kW2 = kW1 + (M1 + 1) / 2, kWD = kW2 + (M2 + 1) / 2;   // word number of variable 1's, variable 2's low halves, of the codes
+    static constexpr bool kFits = kWD + 1 <= 5 && 3 * (M0 + M1 + M2) <= 32;
+    static constexpr int kS1 = 3 * M0, kS2 = 3 * (M0 + M1);                                        // bit number of a variable's codes
+    static constexpr int word(int w) { return CoopLds<3, true>::kSpare + (w < 3 ? w : w + 1); }    // (the word between is the kind mask)
+    static_assert(!kFits || word(4) < CoopLds<3, true>::kStride, "lane row");
+};
+
+struct ExactOut { uint32_t cur, pbA, pbB, hit8, chg8; };
+
+// selector of the v_perm_b32 that turns the by-fired-count byte table (bnh:bnl) into the by-borrows one: entry b <- entry of M - b fired
 template <int M>
+constexpr uint32_t borrows_selector(int first) {
+    uint32_t sel = 0u;
+    for (int q = 0; q < 4; q++) {
+        const int n = M - (first + q);
+        sel |= (n >= 0 ? (uint32_t)(M <= 3 ? 2 * n : n) : 0x0cu) << (8 * q);
+    }
+    return sel;
+}
+
+// The exact pass of an instance that holds its columns on chip: no vector memory operation (a load here would wait for the wave's
+// outstanding trace stores: one counter serves both), the five result words come back in registers.  The thresholds are rebuilt from
+// the T', the low halves and the codes; a padding copy is "never" here too, so the count stops at the real thresholds like in the
+// packed pass and the by-borrows table is that pass's table read backwards.  Inlined as a cold block: a callable function begins by
+// waiting for every outstanding memory operation of the wave, the trace stores among them, which is what this pass is there to avoid.
+template <int M>
+__device__ __forceinline__ ExactOut eight_seconds_exact_chip(uint32_t c0, uint32_t c1r, uint32_t attempt, uint32_t k0, uint32_t k1,
+                                                                       uint4 th, uint4 rh, uint32_t tvar, uint32_t ivar, int g8, int T,
+                                                                       uint32_t tp0, uint32_t tp1, uint32_t lw0, uint32_t lw1, uint32_t codes, uint32_t bnl, uint32_t bnh,
+                                                                       uint32_t Rres, uint32_t cur_in, uint32_t which /* wave-uniform: 1 transition, 2 resample low halfwords needed */) {
+    static_assert(M <= 4, "two words of T' and of low halves");
+    const Rng rng{c0, c1r, attempt, k0, k1};
+    uint4 tl = make_uint4(0u, 0u, 0u, 0u), rl = make_uint4(0u, 0u, 0u, 0u);   // (a block that no lane needs is not generated: eight_seconds_exact)
+    if (which & 1u) tl = rng.block(EMGPU_SEC_TRANS_LO, tvar, (uint32_t)g8);
+    if (which & 2u) rl = rng.block(EMGPU_SEC_RES_LO, ivar, (uint32_t)g8);
+    uint32_t thr[M];
+#pragma unroll
+    for (int t = 0; t < M; t++) {
+        const uint32_t tq = ((t < 2 ? tp0 : tp1) >> (16 * (t & 1))) & 0xFFFFu, low = ((t < 2 ? lw0 : lw1) >> (16 * (t & 1))) & 0xFFFFu;
+        const uint32_t code = (codes >> (3 * t)) & 7u;
+        thr[t] = code == 7u ? 0xFFFFFFFFu : (((tq + 1u - code) << 16) | low);
+    }
+    const uint32_t bml = __builtin_amdgcn_perm(bnh, bnl, borrows_selector<M>(0)), bmh = __builtin_amdgcn_perm(bnh, bnl, borrows_selector<M>(4));
+    ExactOut o;
+    eight_seconds_pass<M, true, true>(th, rh, tl, rl, g8, T, thr, bml, bmh, kSelBase, Rres, cur_in, o.cur, o.pbA, o.pbB, o.hit8, o.chg8);
+    return o;
+}
+
+// CHIP: col_slot is the lane's LDS row, (lw, dl) at its words LW0, LW1 and DW, the codes from bit DS (ChipCol); else *col_slot is the lane's column number
+template <int M, bool ZL = true, bool CHIP = false, int LW0 = 0, int LW1 = 0, int DW = 0, int DS = 0>
 __device__ __forceinline__ void eight_seconds(const Rng &rng, uint32_t tvar, uint32_t ivar, int g8, int T,
                                               const uint32_t *ctab /* the variable's compacted table */, int meff, const uint32_t *col_slot /* LDS: this lane's column */,
-                                              const uint32_t (&thr)[(M + 1) / 2], uint32_t bnl, uint32_t bnh, uint32_t zbin1, uint32_t Rres, uint32_t RR1, uint32_t &cur1,
+                                              const uint32_t (&thr)[(M + 1) / 2], uint32_t bnl, uint32_t bnh, uint32_t zc, uint32_t zbin1, uint32_t Rres, uint32_t RR1, uint32_t &cur1,
                                               uint32_t &pbA, uint32_t &pbB, uint32_t &hit8, uint32_t &chg8, uint32_t &zer8) {
     const uint4 th = rng.block(EMGPU_SEC_TRANS, tvar, (uint32_t)g8);
     const uint4 rh = rng.block(EMGPU_SEC_RES, ivar, (uint32_t)g8);
@@ -290,7 +364,7 @@ __device__ __forceinline__ void eight_seconds(const Rng &rng, uint32_t tvar, uin
     const bool edge = 8 * g8 + 7 >= T; // the block runs past the end of the trajectory
     uint32_t redo = edge ? 3u : 0u;
     if (!edge) {
-        const uint32_t amb = eight_seconds_pk<M>(th, rh, thr, bnl, bnh, RR1, cur1, cur_out, pbA, pbB, hit8, chg8);
+        const uint32_t amb = eight_seconds_pk<M, ZL>(th, rh, thr, bnl, bnh, zc, RR1, cur1, cur_out, pbA, pbB, hit8, chg8);
         redo = (__ballot(amb & 1u) != 0ull ? 1u : 0u) | (__ballot(amb & 2u) != 0ull ? 2u : 0u);
         if (g8 == 0) {
             // Second 0 of a trajectory is the initial state, not a draw (slot 0 is never used,
@@ -302,12 +376,19 @@ __device__ __forceinline__ void eight_seconds(const Rng &rng, uint32_t tvar, uin
             chg8 = (chg8 & 0x3Fu) | ((nb_1 != cur1) ? 0x40u : 0u);
         }
     }
-    if (redo) {
+    if (__builtin_expect(redo != 0u, 0)) {
         EMGPU_COUNT(0, (int)(threadIdx.x & 63), 1);
+        if constexpr (CHIP) {
+            const uint32_t lw0 = col_slot[LW0], lw1 = M > 2 ? col_slot[LW1] : 0u, codes = col_slot[DW] >> DS;   // (LDS reads)
+            const ExactOut o = eight_seconds_exact_chip<M>(rng.c0, rng.c1, rng.attempt, rng.k0, rng.k1, th, rh, tvar, ivar, g8, T, thr[0], thr[M > 2 ? 1 : 0], lw0, lw1, codes,
+                                                           bnl, bnh, Rres, cur1, redo);
+            cur_out = o.cur; pbA = o.pbA; pbB = o.pbB; hit8 = o.hit8; chg8 = o.chg8;
+        } else {
         uint32_t out[5];
         const uint32_t *thr_col = ctab + (size_t)(*col_slot) * (uint32_t)(meff + 1);
         eight_seconds_exact<M>(rng.c0, rng.c1, rng.attempt, rng.k0, rng.k1, th, rh, tvar, ivar, g8, T, thr_col, meff, zbin1, Rres, cur1, redo, out);
         cur_out = out[0]; pbA = out[1]; pbB = out[2]; hit8 = out[3]; chg8 = out[4];
+        }
     }
     cur1 = cur_out;                      // still carries the zero-bin flag
     zer8 = zero_stream(pbA, pbB);        // dediscretize.m:24-25 (the bit of second 0 of a trajectory is never consumed)
@@ -395,7 +476,10 @@ __device__ __forceinline__ void uncor_fast_body(const EmgpuPlan &P, const EmgpuR
         cur1[k] = (uint32_t)pick<NI>(bin, P.d_ipos[k]) + 1u;
         cval[k] = (float)pick<NI>(val, P.d_ipos[k]);
     }
-    uint32_t th0[(M0 + 1) / 2], th1[(M1 + 1) / 2], th2[(M2 + 1) / 2], bl0, bl1, bl2, bh0, bh1, bh2;
+    uint32_t th0[(M0 + 1) / 2], th1[(M1 + 1) / 2], th2[(M2 + 1) / 2], bl0, bl1, bl2, bh0, bh1, bh2, zc0, zc1, zc2;
+    using CC = ChipCol<M0, M1, M2>;
+    constexpr bool CHIP = CC::kFits && !IDX && !EV;
+    uint32_t *const row = reinterpret_cast<uint32_t *>(&W.res[lane * CoopLds<3, LB>::kStride]);
     {
         uint32_t col[3];
 #pragma unroll
@@ -407,12 +491,22 @@ __device__ __forceinline__ void uncor_fast_body(const EmgpuPlan &P, const EmgpuR
             for (int q = 0; q < 3; q++) c += P.d_stride_cur[k][q] * (uint32_t)(cur1[q] - 1);
             col[k] = c;
         }
-        load_cthr_pk<M0>(th0, bl0, bh0, P.cthr + P.d_coff[0] + (size_t)col[0] * (uint32_t)(P.d_meff[0] + 1), P.d_meff[0], (uint32_t)P.d_zero[0]);
-        load_cthr_pk<M1>(th1, bl1, bh1, P.cthr + P.d_coff[1] + (size_t)col[1] * (uint32_t)(P.d_meff[1] + 1), P.d_meff[1], (uint32_t)P.d_zero[1]);
-        load_cthr_pk<M2>(th2, bl2, bh2, P.cthr + P.d_coff[2] + (size_t)col[2] * (uint32_t)(P.d_meff[2] + 1), P.d_meff[2], (uint32_t)P.d_zero[2]);
-        // the exact pass finds its column again through the lane's spare LDS words
+        uint32_t lw0[(M0 + 1) / 2], lw1[(M1 + 1) / 2], lw2[(M2 + 1) / 2], dl0, dl1, dl2;
+        load_cthr_pk<M0>(th0, bl0, bh0, zc0, lw0, dl0, P.cthr + P.d_coff[0] + (size_t)col[0] * (uint32_t)(P.d_meff[0] + 1), P.d_meff[0], (uint32_t)P.d_zero[0]);
+        load_cthr_pk<M1>(th1, bl1, bh1, zc1, lw1, dl1, P.cthr + P.d_coff[1] + (size_t)col[1] * (uint32_t)(P.d_meff[1] + 1), P.d_meff[1], (uint32_t)P.d_zero[1]);
+        load_cthr_pk<M2>(th2, bl2, bh2, zc2, lw2, dl2, P.cthr + P.d_coff[2] + (size_t)col[2] * (uint32_t)(P.d_meff[2] + 1), P.d_meff[2], (uint32_t)P.d_zero[2]);
+        if constexpr (CHIP) {   // the exact pass rebuilds its thresholds from the registers and these words
 #pragma unroll
-        for (int k = 0; k < 3; k++) reinterpret_cast<uint32_t *>(&W.res[lane * CoopLds<3, LB>::kStride + CoopLds<3, LB>::kSpare])[k] = col[k];
+            for (int q = 0; q < (M0 + 1) / 2; q++) row[CC::word(q)] = lw0[q];
+#pragma unroll
+            for (int q = 0; q < (M1 + 1) / 2; q++) row[CC::word(CC::kW1 + q)] = lw1[q];
+#pragma unroll
+            for (int q = 0; q < (M2 + 1) / 2; q++) row[CC::word(CC::kW2 + q)] = lw2[q];
+            row[CC::word(CC::kWD)] = dl0 | (dl1 << CC::kS1) | (dl2 << CC::kS2);
+        } else {                // the exact pass finds its column again through the lane's spare LDS words
+#pragma unroll
+            for (int k = 0; k < 3; k++) row[CoopLds<3, LB>::kSpare + k] = col[k];
+        }
     }
     // from here on the current bin carries the zero-bin flag like the entries of the byte tables
 #pragma unroll
@@ -429,7 +523,7 @@ __device__ __forceinline__ void uncor_fast_body(const EmgpuPlan &P, const EmgpuR
         const uint64_t a = (uint64_t)(P.cthr + P.d_coff[k]);
         h_ctab[k] = reinterpret_cast<const uint32_t *>(((uint64_t)U((uint32_t)(a >> 32)) << 32) | U((uint32_t)a));
     }
-    const uint32_t *col_slot = reinterpret_cast<const uint32_t *>(&W.res[lane * CoopLds<3, LB>::kStride + CoopLds<3, LB>::kSpare]);
+    const uint32_t *col_slot = CHIP ? row : row + CoopLds<3, LB>::kSpare;
     EvPlan E{};
     EvState S{};
     EvStateW SW{};
@@ -453,9 +547,9 @@ __device__ __forceinline__ void uncor_fast_body(const EmgpuPlan &P, const EmgpuR
         if constexpr (EV) prevw = (cur1[0] & 0x7Fu) | ((cur1[1] & 0x7Fu) << 8) | ((cur1[2] & 0x7Fu) << 16);
         {
             uint32_t hit8[3], chg8[3], zer8[3];
-            eight_seconds<M0>(rng, h_tvar[0], iv0, g8, T, h_ctab[0], (int)h_meff[0], col_slot + 0, th0, bl0, bh0, h_zero[0], h_Rk[0], h_RR1[0], cur1[0], pbA[0], pbB[0], hit8[0], chg8[0], zer8[0]);
-            eight_seconds<M1>(rng, h_tvar[1], iv1, g8, T, h_ctab[1], (int)h_meff[1], col_slot + 1, th1, bl1, bh1, h_zero[1], h_Rk[1], h_RR1[1], cur1[1], pbA[1], pbB[1], hit8[1], chg8[1], zer8[1]);
-            eight_seconds<M2>(rng, h_tvar[2], iv2, g8, T, h_ctab[2], (int)h_meff[2], col_slot + 2, th2, bl2, bh2, h_zero[2], h_Rk[2], h_RR1[2], cur1[2], pbA[2], pbB[2], hit8[2], chg8[2], zer8[2]);
+            eight_seconds<M0, !EV, CHIP, CC::word(0), CC::word(1), CC::word(CC::kWD), 0>(rng, h_tvar[0], iv0, g8, T, h_ctab[0], (int)h_meff[0], col_slot, th0, bl0, bh0, zc0, h_zero[0], h_Rk[0], h_RR1[0], cur1[0], pbA[0], pbB[0], hit8[0], chg8[0], zer8[0]);
+            eight_seconds<M1, !EV, CHIP, CC::word(CC::kW1), CC::word(CC::kW1 + 1), CC::word(CC::kWD), CC::kS1>(rng, h_tvar[1], iv1, g8, T, h_ctab[1], (int)h_meff[1], col_slot + (CHIP ? 0 : 1), th1, bl1, bh1, zc1, h_zero[1], h_Rk[1], h_RR1[1], cur1[1], pbA[1], pbB[1], hit8[1], chg8[1], zer8[1]);
+            eight_seconds<M2, !EV, CHIP, CC::word(CC::kW2), CC::word(CC::kW2 + 1), CC::word(CC::kWD), CC::kS2>(rng, h_tvar[2], iv2, g8, T, h_ctab[2], (int)h_meff[2], col_slot + (CHIP ? 0 : 2), th2, bl2, bh2, zc2, h_zero[2], h_Rk[2], h_RR1[2], cur1[2], pbA[2], pbB[2], hit8[2], chg8[2], zer8[2]);
 #pragma unroll
             for (int k = 0; k < 3; k++) {      // the streams stay MSB-first: bit (7-j) <-> second j
                 need8[k] = (hit8[k] | chg8[k]) & ~zer8[k];   // a dediscretize draw is due (dediscretize.m:24-39)
