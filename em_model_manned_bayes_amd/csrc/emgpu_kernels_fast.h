@@ -143,12 +143,28 @@ __device__ __forceinline__ void load_cthr_pk(uint32_t (&tp)[(M + 1) / 2], uint32
     bnl = lo; bnh = hi;
 }
 
+// The bins of the four packed words (seconds 2p in byte 0, 2p+1 in byte 2 of nb2[p]) -> pbA, pbB, the "changed" stream and the bin the
+// block ends on: shared by the high-halfword pass and the exact recount.
+__device__ __forceinline__ void pack_bins_pk(const uint32_t (&nb2)[4], uint32_t cur_in, uint32_t &cur_out, uint32_t &pbA, uint32_t &pbB, uint32_t &chg8) {
+    pbA = __builtin_amdgcn_perm(nb2[1], nb2[0], 0x06040200u);
+    pbB = __builtin_amdgcn_perm(nb2[3], nb2[2], 0x06040200u);
+    // changed <=> the bin differs from the second before (dbn_sample.m:151-161); the low nibble alone tells
+    const uint32_t prevA = (pbA << 8) | cur_in, prevB = __builtin_amdgcn_alignbit(pbB, pbA, 24);
+    // bins are < 16 and only bit 7 (the zero flag) may be set above them: bit 4 of byte + 0x0F is the carry out of the low nibble
+    const uint32_t yA = (pbA ^ prevA) + 0x0F0F0F0Fu, yB = (pbB ^ prevB) + 0x0F0F0F0Fu;
+    chg8 = byte_bit_stream<4>(yA, yB);
+    cur_out = pbB >> 24;
+}
+
 // Eight seconds of one dynamic variable, interior block (every second is a draw), decided from the high halfwords:
-// same outputs as eight_seconds_pass<M, false, false>.  Returns bit 0 when a transition compare of this lane needs the low
-// halfword, bit 1 when a resample compare does (the caller then redoes the block exactly).  No carries, no VCC: nothing here needs wait states.
+// same outputs as eight_seconds_pass<M, false, false>.  Returns a word that is non-zero when some compare of this lane needs the low
+// halfword (the caller then redoes the block exactly): tie_t | tie_r, the transition compares' and the resample compares' share of it,
+// which only the redo looks at apart.  No carries, no VCC: nothing here needs wait states.
+// zwave (ZL only, wave-uniform): some lane of the wave has a column with a real threshold below 2^16; the x_h = 0 test is for those waves.
 template <int M, bool ZL = true>
-__device__ __forceinline__ uint32_t eight_seconds_pk(const uint4 &th, const uint4 &rh, const uint32_t (&tp)[(M + 1) / 2], uint32_t bnl, uint32_t bnh, uint32_t zc,
-                                                 uint32_t RR1, uint32_t cur_in, uint32_t &cur_out, uint32_t &pbA, uint32_t &pbB, uint32_t &hit8, uint32_t &chg8) {
+__device__ __forceinline__ uint32_t eight_seconds_pk(const uint4 &th, const uint4 &rh, const uint32_t (&tp)[(M + 1) / 2], uint32_t bnl, uint32_t bnh, uint32_t zc, bool zwave,
+                                                 uint32_t RR1, uint32_t cur_in, uint32_t &cur_out, uint32_t &pbA, uint32_t &pbB, uint32_t &hit8, uint32_t &chg8,
+                                                 uint32_t &tie_t, uint32_t &tie_r) {
     uint32_t nb2[4], par = 0u, hitA = 0u;
 #pragma unroll
     for (int p = 0; p < 4; p++) {
@@ -174,22 +190,19 @@ __device__ __forceinline__ uint32_t eight_seconds_pk(const uint4 &th, const uint
     // x_h = 0 ties with a threshold whose high half is 0 (it has no T'): a lane whose column has one (zc = 1 | 1 << 16) treats every
     // such draw as a tie; on the others (zc = 0) x_h = 0 fires nothing and the difference below saturates to 0.  ZL = false: every lane
     // does (the event-list forms: three more registers would cost k_uncor_fast_ev<7,6,6,6> its fourth wave)
-    uint32_t mz, zt;
-    asm("v_pk_min_u16 %0, %1, %2" : "=v"(mz) : "v"(th.x), "v"(th.y));
-    asm("v_pk_min_u16 %0, %0, %1" : "+v"(mz) : "v"(th.z));
-    asm("v_pk_min_u16 %0, %0, %1" : "+v"(mz) : "v"(th.w));
-    if constexpr (ZL) asm("v_pk_sub_u16 %0, %1, %2 clamp" : "=v"(zt) : "v"(zc), "v"(mz));  // 1 in a half <=> zc and that half of mz is 0
-    else asm("v_pk_sub_u16 %0, 1, %1 op_sel_hi:[0,1] clamp" : "=v"(zt) : "v"(mz));          // 1 in a half <=> that half of mz is 0
-    pbA = __builtin_amdgcn_perm(nb2[1], nb2[0], 0x06040200u);
-    pbB = __builtin_amdgcn_perm(nb2[3], nb2[2], 0x06040200u);
+    uint32_t mz, zt = 0u;
+    if (!ZL || zwave) {   // (wave-uniform)
+        asm("v_pk_min_u16 %0, %1, %2" : "=v"(mz) : "v"(th.x), "v"(th.y));
+        asm("v_pk_min_u16 %0, %0, %1" : "+v"(mz) : "v"(th.z));
+        asm("v_pk_min_u16 %0, %0, %1" : "+v"(mz) : "v"(th.w));
+        if constexpr (ZL) asm("v_pk_sub_u16 %0, %1, %2 clamp" : "=v"(zt) : "v"(zc), "v"(mz));  // 1 in a half <=> zc and that half of mz is 0
+        else asm("v_pk_sub_u16 %0, 1, %1 op_sel_hi:[0,1] clamp" : "=v"(zt) : "v"(mz));          // 1 in a half <=> that half of mz is 0
+    }
     hit8 = (hitA & 0xAAu) | ((hitA >> 17) & 0x55u);                                          // bit 1 of every 2-bit field, MSB-first
-    // changed <=> the bin differs from the second before (dbn_sample.m:151-161); the low nibble alone tells
-    const uint32_t prevA = (pbA << 8) | cur_in, prevB = __builtin_amdgcn_alignbit(pbB, pbA, 24);
-    // bins are < 16 and only bit 7 (the zero flag) may be set above them: bit 4 of byte + 0x0F is the carry out of the low nibble
-    const uint32_t yA = (pbA ^ prevA) + 0x0F0F0F0Fu, yB = (pbB ^ prevB) + 0x0F0F0F0Fu;
-    chg8 = byte_bit_stream<4>(yA, yB);
-    cur_out = pbB >> 24;
-    return ((((par & 0x00010001u) | zt) != 0u) ? 1u : 0u) | (((hitA & 0x00550055u) != 0u) ? 2u : 0u);
+    pack_bins_pk(nb2, cur_in, cur_out, pbA, pbB, chg8);
+    tie_t = (par & 0x00010001u) | zt;
+    tie_r = hitA & 0x00550055u;
+    return tie_t | tie_r;
 }
 
 // Eight seconds of one dynamic variable.  Outputs: bins packed 1-based 4 per word (pbA: seconds
@@ -348,48 +361,144 @@ __device__ __forceinline__ ExactOut eight_seconds_exact_chip(uint32_t c0, uint32
     return o;
 }
 
+// (A_h, A_l) > (x_h, x_l) for the seconds 2p and 2p+1 of a word pair at once: 1 in a half where it holds, else 0.  A is one 32-bit value in
+// two 16-bit pieces -- half SEL of ah / al (0: low, 1: high), the same for both seconds -- x_h and x_l come two seconds per word.
+//   g = sat(x_h - A_h) > 0 <=> x_h > A_h;   b = sat(A_h - x_h) > 0 <=> x_h < A_h;   c = sat(A_l - x_l) > 0 <=> x_l < A_l
+//   A > x  <=>  b > 0  or  (g == 0 and c > 0)  <=>  sat(min(b | c | always, 1) - g) == 1      (b > 0 makes g = 0)
+// `always` (1 in both halves or 0) makes it hold wherever x_h <= A_h: with A_h = 0xFFFF, everywhere.  Saturating 16-bit arithmetic only:
+// no carry, no VCC, no wait state, and nothing that ties one second to its own basic block.
+template <int SEL>
+__device__ __forceinline__ uint32_t pk_gt32(uint32_t ah, uint32_t al, uint32_t xh, uint32_t xl, uint32_t always) {
+    uint32_t g, b, c, k, r;
+    if (SEL) {
+        asm("v_pk_sub_u16 %0, %1, %2 op_sel:[0,1] op_sel_hi:[1,1] clamp" : "=v"(g) : "v"(xh), "v"(ah));
+        asm("v_pk_sub_u16 %0, %1, %2 op_sel:[1,0] op_sel_hi:[1,1] clamp" : "=v"(b) : "v"(ah), "v"(xh));
+        asm("v_pk_sub_u16 %0, %1, %2 op_sel:[1,0] op_sel_hi:[1,1] clamp" : "=v"(c) : "v"(al), "v"(xl));
+    } else {
+        asm("v_pk_sub_u16 %0, %1, %2 op_sel:[0,0] op_sel_hi:[1,0] clamp" : "=v"(g) : "v"(xh), "v"(ah));
+        asm("v_pk_sub_u16 %0, %1, %2 op_sel:[0,0] op_sel_hi:[0,1] clamp" : "=v"(b) : "v"(ah), "v"(xh));
+        asm("v_pk_sub_u16 %0, %1, %2 op_sel:[0,0] op_sel_hi:[0,1] clamp" : "=v"(c) : "v"(al), "v"(xl));
+    }
+    const uint32_t e = b | c | always;
+    asm("v_pk_min_u16 %0, %1, 1 op_sel_hi:[1,0]" : "=v"(k) : "v"(e));
+    asm("v_pk_sub_u16 %0, %1, %2 clamp" : "=v"(r) : "v"(k), "v"(g));
+    return r;
+}
+
+// The exact recount of an interior block (every second is a draw) of an instance that holds its columns on chip: what
+// eight_seconds_exact_chip computes there, two seconds per instruction and in a straight line.  Per threshold t of the lane's column:
+//   code_t = 7 ("never", a padding copy): it fires for no draw -- the draws are clamped below 0xFFFFFFFF -- and is counted as not fired;
+//   else H_t = T'_t + 1 - code_t, L_t = the stored low half, and it has NOT fired <=> (H_t, L_t) > (x_h, x_l).  A real threshold is at most
+//   0xFFFFFFFE, so the clamp of the draw (0xFFFFFFFF -> 0xFFFFFFFE) changes none of these compares: the draw is used as it is.
+// n = M - #{not fired} indexes the high-halfword pass's own byte table (by 2n for M <= 3).  A resample hit <=> (R_h, R_l) > (r_h, r_l).
+// which (wave-uniform): bit 0 -- some lane has a transition tie: the low halfwords tl are drawn and bins, "changed" and the last bin are
+// recounted; bit 1 -- the same for the resample compares, rl and hit8.  The other outputs stay as the high-halfword pass left them: no lane
+// had a tie there, so it decided every one of those compares, and decided them like this count would.
+template <int M>
+__device__ __forceinline__ void eight_seconds_recount_pk(const Rng &rng, uint32_t tvar, uint32_t ivar, int g8, uint32_t which, const uint4 &th, const uint4 &rh,
+                                                         const uint32_t (&tp)[(M + 1) / 2], const uint32_t (&lw)[(M + 1) / 2], uint32_t codes, uint32_t bnl, uint32_t bnh,
+                                                         uint32_t RR1, uint32_t Rres, uint32_t cur_in,
+                                                         uint32_t &cur_out, uint32_t &pbA, uint32_t &pbB, uint32_t &hit8, uint32_t &chg8) {
+    if (which & 1u) {
+        const uint4 tl = rng.block(EMGPU_SEC_TRANS_LO, tvar, (uint32_t)g8);
+        uint32_t hp[(M + 1) / 2], nv[M];
+#pragma unroll
+        for (int q = 0; q < (M + 1) / 2; q++) {
+            const uint32_t c0 = (codes >> (6 * q)) & 7u, c1 = 2 * q + 1 < M ? (codes >> (6 * q + 3)) & 7u : 7u;
+            const uint32_t n0 = (c0 + 1u) >> 3, n1 = (c1 + 1u) >> 3;                      // 1 <=> "never"
+            nv[2 * q] = n0 * 0x00010001u;
+            if (2 * q + 1 < M) nv[2 * q + 1] = n1 * 0x00010001u;
+            // T' + 1 - code stays within its halfword (a real threshold: it is H_t; "never": 0xFFFF + 1 - 7); "never" gets H = 0xFFFF
+            hp[q] = (tp[q] + 0x00010001u - (c0 | (c1 << 16))) | (n0 * 0xFFFFu) | (n1 * 0xFFFF0000u);
+        }
+        uint32_t nb2[4];
+#pragma unroll
+        for (int p = 0; p < 4; p++) {
+            const uint32_t w = word_of(th, p), wl = word_of(tl, p);
+            uint32_t acc = 0u;
+#pragma unroll
+            for (int t = 0; t < M; t++) {                                                    // select_random.m:19-20 for seconds 2p, 2p+1
+                const uint32_t nf = (t & 1) ? pk_gt32<1>(hp[t >> 1], lw[t >> 1], w, wl, nv[t]) : pk_gt32<0>(hp[t >> 1], lw[t >> 1], w, wl, nv[t]);
+                if (t == 0) asm("v_pk_sub_u16 %0, %2, %1 op_sel_hi:[0,1]" : "=v"(acc) : "v"(nf), "n"(M));
+                else asm("v_pk_sub_u16 %0, %0, %1" : "+v"(acc) : "v"(nf));
+            }
+            uint32_t cnt = acc;
+            if (M <= 3) asm("v_pk_lshlrev_b16 %0, 1, %1 op_sel_hi:[0,1]" : "=v"(cnt) : "v"(acc));
+            nb2[p] = __builtin_amdgcn_perm(bnh, bnl, cnt);                                   // dbn_sample.m:144
+        }
+        pack_bins_pk(nb2, cur_in, cur_out, pbA, pbB, chg8);
+    }
+    if (which & 2u) {
+        const uint4 rl = rng.block(EMGPU_SEC_RES_LO, ivar, (uint32_t)g8);
+        // (the empty asm keeps the two words from being computed ahead of the loop, where each would hold a scalar register for its whole length)
+        asm volatile("" : "+s"(RR1), "+s"(Rres));
+        const uint32_t Rh = RR1 - 0x00010001u, Rl = (Rres & 0xFFFFu) * 0x00010001u;
+        uint32_t hitA = 0u;
+#pragma unroll
+        for (int p = 0; p < 4; p++) {                                                        // resample_events.m:24
+            const uint32_t u = pk_gt32<0>(Rh, Rl, word_of(rh, p), word_of(rl, p), 0u);
+            hitA = p ? ((hitA << 2) | u) : u;
+        }
+        hit8 = ((hitA << 1) & 0xAAu) | ((hitA >> 16) & 0x55u);                               // bit 0 of every 2-bit field, MSB-first
+    }
+}
+
 // CHIP: col_slot is the lane's LDS row, (lw, dl) at its words LW0, LW1 and DW, the codes from bit DS (ChipCol); else *col_slot is the lane's column number
 template <int M, bool ZL = true, bool CHIP = false, int LW0 = 0, int LW1 = 0, int DW = 0, int DS = 0>
 __device__ __forceinline__ void eight_seconds(const Rng &rng, uint32_t tvar, uint32_t ivar, int g8, int T,
                                               const uint32_t *ctab /* the variable's compacted table */, int meff, const uint32_t *col_slot /* LDS: this lane's column */,
-                                              const uint32_t (&thr)[(M + 1) / 2], uint32_t bnl, uint32_t bnh, uint32_t zc, uint32_t zbin1, uint32_t Rres, uint32_t RR1, uint32_t &cur1,
+                                              const uint32_t (&thr)[(M + 1) / 2], uint32_t bnl, uint32_t bnh, uint32_t zc, bool zwave, uint32_t zbin1, uint32_t Rres, uint32_t RR1, uint32_t &cur1,
                                               uint32_t &pbA, uint32_t &pbB, uint32_t &hit8, uint32_t &chg8, uint32_t &zer8) {
     const uint4 th = rng.block(EMGPU_SEC_TRANS, tvar, (uint32_t)g8);
     const uint4 rh = rng.block(EMGPU_SEC_RES, ivar, (uint32_t)g8);
     uint32_t cur_out = cur1;
     // Interior blocks (every second 1 <= c < T) run the unguarded high-halfword pass inline.  The
     // last (partial) block of a trajectory, and any block in which SOME lane of the wave met a tie,
-    // take the out-of-line exact pass (full 32-bit draws, guarded): lanes without a tie get the
+    // are done again exactly (full 32-bit draws): lanes without a tie get the
     // same answers again, so control flow stays wave-uniform.
     const bool edge = 8 * g8 + 7 >= T; // the block runs past the end of the trajectory
-    uint32_t redo = edge ? 3u : 0u;
+    bool redo = edge;
+    uint32_t tie_t = 0u, tie_r = 0u;
+    // Second 0 of a trajectory is the initial state, not a draw (slot 0 is never used,
+    // dbn_sample.m:133,138).  The unguarded passes treat it as one: put the initial bin back,
+    // clear its flags (streams are MSB-first: second j is bit 7-j) and re-derive "changed" of second 1.
+    auto second0 = [&]() {
+        const uint32_t nb_1 = (pbA >> 8) & 0xFFu;
+        pbA = (pbA & 0xFFFFFF00u) | cur1;
+        hit8 &= 0x7Fu;
+        chg8 = (chg8 & 0x3Fu) | ((nb_1 != cur1) ? 0x40u : 0u);
+    };
     if (!edge) {
-        const uint32_t amb = eight_seconds_pk<M, ZL>(th, rh, thr, bnl, bnh, zc, RR1, cur1, cur_out, pbA, pbB, hit8, chg8);
-        redo = (__ballot(amb & 1u) != 0ull ? 1u : 0u) | (__ballot(amb & 2u) != 0ull ? 2u : 0u);
-        if (g8 == 0) {
-            // Second 0 of a trajectory is the initial state, not a draw (slot 0 is never used,
-            // dbn_sample.m:133,138).  The unguarded pass treated it as one: put the initial bin back,
-            // clear its flags (streams are MSB-first: second j is bit 7-j) and re-derive "changed" of second 1.
-            const uint32_t nb_1 = (pbA >> 8) & 0xFFu;
-            pbA = (pbA & 0xFFFFFF00u) | cur1;
-            hit8 &= 0x7Fu;
-            chg8 = (chg8 & 0x3Fu) | ((nb_1 != cur1) ? 0x40u : 0u);
-        }
+        const uint32_t amb = eight_seconds_pk<M, ZL>(th, rh, thr, bnl, bnh, zc, zwave, RR1, cur1, cur_out, pbA, pbB, hit8, chg8, tie_t, tie_r);
+        redo = __ballot(amb != 0u) != 0ull;   // one ballot on the hot path; which halfword block is missing matters to the redo alone
+        if constexpr (!CHIP) { if (g8 == 0) second0(); }   // (the guarded exact pass leaves second 0 alone by itself)
     }
-    if (__builtin_expect(redo != 0u, 0)) {
+    if (__builtin_expect(redo, 0)) {
         EMGPU_COUNT(0, (int)(threadIdx.x & 63), 1);
+        // wave-uniform: 1 transition, 2 resample low halfwords needed.  (The empty asm pins the two compares to this block: derived from
+        // the pass's words alone they were hoisted into the hot path, beside the one ballot they are there to replace.)
+        asm volatile("" : "+v"(tie_t), "+v"(tie_r));
+        const uint32_t which = edge ? 3u : ((__ballot(tie_t != 0u) != 0ull ? 1u : 0u) | (__ballot(tie_r != 0u) != 0ull ? 2u : 0u));
         if constexpr (CHIP) {
             const uint32_t lw0 = col_slot[LW0], lw1 = M > 2 ? col_slot[LW1] : 0u, codes = col_slot[DW] >> DS;   // (LDS reads)
-            const ExactOut o = eight_seconds_exact_chip<M>(rng.c0, rng.c1, rng.attempt, rng.k0, rng.k1, th, rh, tvar, ivar, g8, T, thr[0], thr[M > 2 ? 1 : 0], lw0, lw1, codes,
-                                                           bnl, bnh, Rres, cur1, redo);
-            cur_out = o.cur; pbA = o.pbA; pbB = o.pbB; hit8 = o.hit8; chg8 = o.chg8;
+            if (!edge) {
+                uint32_t lw[(M + 1) / 2];
+                lw[0] = lw0;
+                if constexpr (M > 2) lw[1] = lw1;
+                eight_seconds_recount_pk<M>(rng, tvar, ivar, g8, which, th, rh, thr, lw, codes, bnl, bnh, RR1, Rres, cur1, cur_out, pbA, pbB, hit8, chg8);
+            } else {   // once per trajectory: the guarded pass
+                const ExactOut o = eight_seconds_exact_chip<M>(rng.c0, rng.c1, rng.attempt, rng.k0, rng.k1, th, rh, tvar, ivar, g8, T, thr[0], thr[M > 2 ? 1 : 0], lw0, lw1, codes,
+                                                               bnl, bnh, Rres, cur1, which);
+                cur_out = o.cur; pbA = o.pbA; pbB = o.pbB; hit8 = o.hit8; chg8 = o.chg8;
+            }
         } else {
         uint32_t out[5];
         const uint32_t *thr_col = ctab + (size_t)(*col_slot) * (uint32_t)(meff + 1);
-        eight_seconds_exact<M>(rng.c0, rng.c1, rng.attempt, rng.k0, rng.k1, th, rh, tvar, ivar, g8, T, thr_col, meff, zbin1, Rres, cur1, redo, out);
+        eight_seconds_exact<M>(rng.c0, rng.c1, rng.attempt, rng.k0, rng.k1, th, rh, tvar, ivar, g8, T, thr_col, meff, zbin1, Rres, cur1, which, out);
         cur_out = out[0]; pbA = out[1]; pbB = out[2]; hit8 = out[3]; chg8 = out[4];
         }
     }
+    if constexpr (CHIP) { if (!edge && g8 == 0) second0(); }   // after the recount, which treats second 0 as a draw like the pass it corrects
     cur1 = cur_out;                      // still carries the zero-bin flag
     zer8 = zero_stream(pbA, pbB);        // dediscretize.m:24-25 (the bit of second 0 of a trajectory is never consumed)
     pbA &= 0x7F7F7F7Fu; pbB &= 0x7F7F7F7Fu;
@@ -508,6 +617,8 @@ __device__ __forceinline__ void uncor_fast_body(const EmgpuPlan &P, const EmgpuR
             for (int k = 0; k < 3; k++) row[CoopLds<3, LB>::kSpare + k] = col[k];
         }
     }
+    // the x_h = 0 test of the 8-second loop is for waves in which some lane's column has a real threshold below 2^16
+    const bool zw0 = __ballot(zc0 != 0u) != 0ull, zw1 = __ballot(zc1 != 0u) != 0ull, zw2 = __ballot(zc2 != 0u) != 0ull;
     // from here on the current bin carries the zero-bin flag like the entries of the byte tables
 #pragma unroll
     for (int k = 0; k < 3; k++) cur1[k] |= (cur1[k] == (uint32_t)P.d_zero[k]) ? kZeroFlag : 0u;
@@ -520,6 +631,9 @@ __device__ __forceinline__ void uncor_fast_body(const EmgpuPlan &P, const EmgpuR
     for (int k = 0; k < 3; k++) {
         h_tvar[k] = U(P.d_tvar[k]); h_meff[k] = U(P.d_meff[k]); h_zero[k] = U(P.d_zero[k]);
         h_Rk[k] = U(F.Rk[k]); h_RR1[k] = U(F.RR1[k]); h_slot[k] = U(F.slot[k]);
+        // each word in a scalar register of its own: as parts of the argument load's eight-register tuple they are spilled and reloaded together,
+        // the hot words (RR1, slot) with the cold one (Rk), as soon as the loop runs short of scalar registers
+        asm("" : "+s"(h_Rk[k]), "+s"(h_RR1[k]), "+s"(h_slot[k]));
         const uint64_t a = (uint64_t)(P.cthr + P.d_coff[k]);
         h_ctab[k] = reinterpret_cast<const uint32_t *>(((uint64_t)U((uint32_t)(a >> 32)) << 32) | U((uint32_t)a));
     }
@@ -547,9 +661,9 @@ __device__ __forceinline__ void uncor_fast_body(const EmgpuPlan &P, const EmgpuR
         if constexpr (EV) prevw = (cur1[0] & 0x7Fu) | ((cur1[1] & 0x7Fu) << 8) | ((cur1[2] & 0x7Fu) << 16);
         {
             uint32_t hit8[3], chg8[3], zer8[3];
-            eight_seconds<M0, !EV, CHIP, CC::word(0), CC::word(1), CC::word(CC::kWD), 0>(rng, h_tvar[0], iv0, g8, T, h_ctab[0], (int)h_meff[0], col_slot, th0, bl0, bh0, zc0, h_zero[0], h_Rk[0], h_RR1[0], cur1[0], pbA[0], pbB[0], hit8[0], chg8[0], zer8[0]);
-            eight_seconds<M1, !EV, CHIP, CC::word(CC::kW1), CC::word(CC::kW1 + 1), CC::word(CC::kWD), CC::kS1>(rng, h_tvar[1], iv1, g8, T, h_ctab[1], (int)h_meff[1], col_slot + (CHIP ? 0 : 1), th1, bl1, bh1, zc1, h_zero[1], h_Rk[1], h_RR1[1], cur1[1], pbA[1], pbB[1], hit8[1], chg8[1], zer8[1]);
-            eight_seconds<M2, !EV, CHIP, CC::word(CC::kW2), CC::word(CC::kW2 + 1), CC::word(CC::kWD), CC::kS2>(rng, h_tvar[2], iv2, g8, T, h_ctab[2], (int)h_meff[2], col_slot + (CHIP ? 0 : 2), th2, bl2, bh2, zc2, h_zero[2], h_Rk[2], h_RR1[2], cur1[2], pbA[2], pbB[2], hit8[2], chg8[2], zer8[2]);
+            eight_seconds<M0, !EV, CHIP, CC::word(0), CC::word(1), CC::word(CC::kWD), 0>(rng, h_tvar[0], iv0, g8, T, h_ctab[0], (int)h_meff[0], col_slot, th0, bl0, bh0, zc0, zw0, h_zero[0], h_Rk[0], h_RR1[0], cur1[0], pbA[0], pbB[0], hit8[0], chg8[0], zer8[0]);
+            eight_seconds<M1, !EV, CHIP, CC::word(CC::kW1), CC::word(CC::kW1 + 1), CC::word(CC::kWD), CC::kS1>(rng, h_tvar[1], iv1, g8, T, h_ctab[1], (int)h_meff[1], col_slot + (CHIP ? 0 : 1), th1, bl1, bh1, zc1, zw1, h_zero[1], h_Rk[1], h_RR1[1], cur1[1], pbA[1], pbB[1], hit8[1], chg8[1], zer8[1]);
+            eight_seconds<M2, !EV, CHIP, CC::word(CC::kW2), CC::word(CC::kW2 + 1), CC::word(CC::kWD), CC::kS2>(rng, h_tvar[2], iv2, g8, T, h_ctab[2], (int)h_meff[2], col_slot + (CHIP ? 0 : 2), th2, bl2, bh2, zc2, zw2, h_zero[2], h_Rk[2], h_RR1[2], cur1[2], pbA[2], pbB[2], hit8[2], chg8[2], zer8[2]);
 #pragma unroll
             for (int k = 0; k < 3; k++) {      // the streams stay MSB-first: bit (7-j) <-> second j
                 need8[k] = (hit8[k] | chg8[k]) & ~zer8[k];   // a dediscretize draw is due (dediscretize.m:24-39)
