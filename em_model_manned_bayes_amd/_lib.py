@@ -170,6 +170,7 @@ SYMBOLS = [
     "emgpu_device_alloc", "emgpu_device_free", "emgpu_sample_uncor_host",
     "emgpu_sample_text_host", "emgpu_text_bound", "emgpu_format_g_host", "emgpu_debug_format_paths",
     "emgpu_parse_table_host", "emgpu_format_f0_host", "emgpu_csv_bound", "emgpu_tracks_text_host",
+    "emgpu_start_grid_log_weight", "emgpu_track_uncor_grid_host", "emgpu_track_uncor_grid_device",
 ]
 
 _lib = None
@@ -288,6 +289,9 @@ def lib():
     L.emgpu_sample_dbn_multi_device.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.POINTER(SampleParams), C.POINTER(SampleOut)]
     for f in (L.emgpu_track_uncor_host, L.emgpu_track_uncor_device):
         f.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(UTrackParams), C.c_void_p, C.c_void_p, C.c_void_p]
+    for f in (L.emgpu_track_uncor_grid_host, L.emgpu_track_uncor_grid_device):
+        f.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(UTrackParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.emgpu_start_grid_log_weight.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
     L.emgpu_track_terminal_host.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(TTrackParams), C.c_void_p, C.c_void_p, C.c_int32,
                                             C.c_void_p, C.c_void_p, C.c_void_p]
     L.emgpu_uncor_dynamic_limits.argtypes = [C.c_void_p, C.POINTER(UTrackParams), C.c_void_p] + [C.c_double] * 4 + [C.c_void_p]

@@ -307,6 +307,14 @@ int emgpu_model_start_log_weight(const emgpu_model *h, double *out) {
     EMGPU_CATCH
 }
 
+int emgpu_start_grid_log_weight(const emgpu_model *h, const int32_t *start, int64_t n, double *out) {
+    EMGPU_TRY
+    if (!h || n < 0 || (n > 0 && (!start || !out))) return fail(EMGPU_ERR_ARG, "null argument or n < 0");
+    emgpu::start_grid_log_weight(h->m, start, n, out);
+    return EMGPU_OK;
+    EMGPU_CATCH
+}
+
 int emgpu_model_set_zero_bins(emgpu_model *h, const int32_t *zero_bins, int32_t n) {
     if (!h || !zero_bins || n != h->m.n_initial) return fail(EMGPU_ERR_ARG, "zero_bins needs n_initial entries");
     for (int i = 0; i < n; i++)
@@ -531,16 +539,37 @@ static void bind_outputs(EmgpuRun &A, const Model &m, const emgpu_sample_params 
     (void)m;
 }
 
+// The block of device memory a launch reads its start grid / log-weight pointers through (one per ctx, rewritten per launch).
+static const EmgpuPresets *upload_presets(emgpu_ctx *ctx, Uploaded &u, const Model &m, const int32_t *start, double *log_weight, const int64_t *row) {
+    EmgpuPresets Q;
+    memset(&Q, 0, sizeof Q);
+    Q.start = start; Q.log_weight = log_weight; Q.row = row;
+    if (Q.log_weight) { ensure_logp(ctx, u, m); Q.logp = u.d_logp; memcpy(Q.lp_off, u.lp_off, sizeof Q.lp_off); }
+    if (!ctx->d_presets) HIP_OK(hipMalloc((void **)&ctx->d_presets, sizeof(EmgpuPresets)));
+    HIP_OK(hipStreamSynchronize(ctx->stream));   // (an earlier launch may still read the block)
+    HIP_OK(hipMemcpyAsync(ctx->d_presets, &Q, sizeof Q, hipMemcpyHostToDevice, ctx->stream));
+    HIP_OK(hipStreamSynchronize(ctx->stream));   // Q is a local
+    return ctx->d_presets;
+}
+
 static void launch_dbn(emgpu_ctx *ctx, const Uploaded &u, const EmgpuRun &A, hipStream_t stream = nullptr, const EmgpuPresets *presets = nullptr) {
     const char *name = "";
     hipError_t e;
     if (!stream) stream = ctx->stream;
-    if (presets) e = emgpu::launch_dbn_generic(u.cp.plan, A, stream, &name, presets);   // a start grid / per-sample log-weights: the general kernel
+    char ps_name[64];
+    std::string suffix;
+    // a start grid / per-sample log-weights: the +start instances of the fast kernel serve the dense outputs alone and the list alone of a
+    // fast-branch model; the list and the dense trace together, and every other model, run on the general kernel
+    if (presets && emgpu::fast_uncor_eligible(u.cp.plan, A) && emgpu::uncor_fast_start_form(u.cp.plan, A) != 0) {
+        e = emgpu::launch_uncor_fast_start(u.cp.plan, A, presets, stream, ps_name);
+        name = ps_name; suffix = "+start";
+    }
+    else if (presets) e = emgpu::launch_dbn_generic(u.cp.plan, A, stream, &name, presets);
     else if (emgpu::fast_uncor_eligible(u.cp.plan, A)) e = emgpu::launch_uncor_fast(u.cp.plan, A, stream, &name);
     else if (emgpu::step2_eligible(u.cp.plan, A)) e = emgpu::launch_dbn_step2(u.cp.plan, A, stream, &name);
     else if (emgpu::step_eligible(u.cp.plan, A)) e = emgpu::launch_dbn_step(u.cp.plan, A, stream, &name);
     else e = emgpu::launch_dbn_generic(u.cp.plan, A, stream, &name);
-    ctx->last_kernel = name;
+    ctx->last_kernel = name + suffix;   // (the ctx owns the string)
     ctx->last_launches++;
     launch_ok(e);
 }
@@ -576,17 +605,8 @@ int emgpu_sample_dbn_device(emgpu_ctx *ctx, const emgpu_model *h, const emgpu_sa
     fill_run(ctx, u, h->m, p, A);
     bind_outputs(A, h->m, p, out);
     const EmgpuPresets *presets = nullptr;
-    if (p->start || out->log_weight) {   // a start grid / per-sample log-weights: a small block of device memory the kernel reads them through
-        EmgpuPresets Q;
-        memset(&Q, 0, sizeof Q);
-        Q.start = p->start; Q.log_weight = out->log_weight;
-        if (Q.log_weight) { ensure_logp(ctx, u, h->m); Q.logp = u.d_logp; memcpy(Q.lp_off, u.lp_off, sizeof Q.lp_off); }
-        if (!ctx->d_presets) HIP_OK(hipMalloc((void **)&ctx->d_presets, sizeof(EmgpuPresets)));
-        HIP_OK(hipStreamSynchronize(ctx->stream));   // (an earlier launch may still read the block)
-        HIP_OK(hipMemcpyAsync(ctx->d_presets, &Q, sizeof Q, hipMemcpyHostToDevice, ctx->stream));
-        HIP_OK(hipStreamSynchronize(ctx->stream));   // Q is a local
-        presets = ctx->d_presets;
-    }
+    // a start grid / per-sample log-weights: a small block of device memory the kernel reads them through
+    if (p->start || out->log_weight) presets = upload_presets(ctx, u, h->m, p->start, out->log_weight, nullptr);
     ctx->last_launches = 0;
     launch_dbn(ctx, u, A, nullptr, presets);
     return EMGPU_OK;
@@ -1360,7 +1380,9 @@ int emgpu_uncor_dynamic_limits(const emgpu_model *h, const emgpu_utrack_params *
 }
 
 // The rounds of UncorEncounterModel.m:419-471 (see the header).  d_*: device outputs (any may be null).
-static int track_uncor_rounds(emgpu_ctx *ctx, const emgpu_model *h, const emgpu_utrack_params *p, double *d_tracks, double *d_limits, int32_t *d_attempts) {
+// d_start: the call's start grid [p->n][n_initial] on the device, or null.
+static int track_uncor_rounds(emgpu_ctx *ctx, const emgpu_model *h, const emgpu_utrack_params *p, const int32_t *d_start, double *d_tracks, double *d_limits,
+                              int32_t *d_attempts) {
     const Model &m = h->m;
     if (p->n < 0 || p->sample_time < 1 || p->sample_time > 65535) throw Error(EMGPU_ERR_ARG, "n < 0 or sample_time outside 1..65535");
     if (p->max_track_attempts < 1 || p->max_attempts < 1 || p->record_stride < 1 || (10 * p->sample_time) % p->record_stride)
@@ -1421,7 +1443,9 @@ static int track_uncor_rounds(emgpu_ctx *ctx, const emgpu_model *h, const emgpu_
         EmgpuRun A;
         fill_run(ctx, u, m, &sp, A);
         A.init_val = d_iv; A.dyn_val = d_dv; A.ld = (int64_t)count;
-        launch_dbn(ctx, u, A);                                            // :424  self.sample(1, sample_time, 'seed', seed)
+        // a start grid: round 0 reads row i for lane i, a later round the rows of the trajectories it redraws (its slot list)
+        const EmgpuPresets *presets = d_start ? upload_presets(ctx, u, m, d_start, nullptr, j ? d_slot[cur] : nullptr) : nullptr;
+        launch_dbn(ctx, u, A, nullptr, presets);                          // :424  self.sample(1, sample_time, 'seed', seed)
         const std::string sampler = ctx->last_kernel;
         R.n = (int64_t)count; R.ld = (int64_t)count;
         auto row = [&](int idx) -> const float * { return idx > 0 ? d_iv + (size_t)(idx - 1) * count : nullptr; };
@@ -1439,16 +1463,24 @@ static int track_uncor_rounds(emgpu_ctx *ctx, const emgpu_model *h, const emgpu_
     return rc;
 }
 
-int emgpu_track_uncor_device(emgpu_ctx *ctx, const emgpu_model *h, const emgpu_utrack_params *p, double *tracks, double *limits, int32_t *attempts) {
+int emgpu_track_uncor_grid_device(emgpu_ctx *ctx, const emgpu_model *h, const emgpu_utrack_params *p, const int32_t *start, double *tracks, double *limits,
+                                  int32_t *attempts) {
     EMGPU_TRY
     if (!ctx || !h || !p) return fail(EMGPU_ERR_ARG, "null argument");
     CTX_LOCK(ctx);
     HIP_OK(hipSetDevice(ctx->device));
-    return track_uncor_rounds(ctx, h, p, tracks, limits, attempts);
+    return track_uncor_rounds(ctx, h, p, start, tracks, limits, attempts);
     EMGPU_CATCH
+}
+int emgpu_track_uncor_device(emgpu_ctx *ctx, const emgpu_model *h, const emgpu_utrack_params *p, double *tracks, double *limits, int32_t *attempts) {
+    return emgpu_track_uncor_grid_device(ctx, h, p, nullptr, tracks, limits, attempts);
 }
 
 int emgpu_track_uncor_host(emgpu_ctx *ctx, const emgpu_model *h, const emgpu_utrack_params *p, double *tracks, double *limits, int32_t *attempts) {
+    return emgpu_track_uncor_grid_host(ctx, h, p, nullptr, tracks, limits, attempts);
+}
+int emgpu_track_uncor_grid_host(emgpu_ctx *ctx, const emgpu_model *h, const emgpu_utrack_params *p, const int32_t *start, double *tracks, double *limits,
+                                int32_t *attempts) {
     EMGPU_TRY
     if (!ctx || !h || !p) return fail(EMGPU_ERR_ARG, "null argument");
     CTX_LOCK(ctx);
@@ -1460,7 +1492,14 @@ int emgpu_track_uncor_host(emgpu_ctx *ctx, const emgpu_model *h, const emgpu_utr
     double *dt = tracks ? b.alloc<double>(n * S * 8 * sizeof(double) + 8) : nullptr;
     double *dl = limits ? b.alloc<double>(n * 3 * sizeof(double) + 8) : nullptr;
     int32_t *da = b.alloc<int32_t>(n * 4 + 4);
-    const int rc = track_uncor_rounds(ctx, h, p, dt, dl, da);
+    int32_t *ds = nullptr;
+    if (start && n) {
+        const size_t bytes = n * (size_t)h->m.n_initial * sizeof(int32_t);
+        ds = b.alloc<int32_t>(bytes);
+        b.up(ds, start, bytes);
+        HIP_OK(hipStreamSynchronize(ctx->stream));   // start is caller memory
+    }
+    const int rc = track_uncor_rounds(ctx, h, p, ds, dt, dl, da);
     if (rc == EMGPU_OK || rc == EMGPU_ERR_REJECT_CAP) {
         const std::string msg = g_err;
         b.down(tracks, dt, n * S * 8 * sizeof(double));

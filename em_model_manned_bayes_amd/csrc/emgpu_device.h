@@ -250,18 +250,22 @@ __device__ __forceinline__ int32_t init_network(const EmgpuPlan &P, const EmgpuR
 }
 
 // The same with the lane's presets possibly coming from a start grid (Q->start, row `lane`) and its log-weight wanted (Q->log_weight):
-// k_dbn_generic (Q null: the model's own start, like init_network).
+// k_dbn_generic and the +start instances of the fast kernel (Q null: the model's own start, like init_network).  The lane's row of the grid
+// is Q->row[lane] (lane itself without a row list).  live = false: a lane outside the run (the fast kernel keeps those alive as workers of
+// their wave) -- it reads no row and writes no weight, and draws under the model's own start.
 template <int NI>
-__device__ __forceinline__ int32_t init_network_ps(const EmgpuPlan &P, const EmgpuRun &A, const EmgpuPresets *Qp, Rng &rng, int (&bin)[NI], double (&val)[NI], int64_t lane) {
+__device__ __forceinline__ int32_t init_network_ps(const EmgpuPlan &P, const EmgpuRun &A, const EmgpuPresets *Qp, Rng &rng, int (&bin)[NI], double (&val)[NI], int64_t lane,
+                                                   bool live = true) {
     constexpr bool PS = true;
     int32_t attempts_used = -1;
     const bool no_dedisc = (A.flags & EMGPU_FLAG_NO_DEDISC) != 0;
     int sp[NI];
     if constexpr (PS) {
-        if (Qp) {
+        if (Qp && live) {
             const EmgpuPresets &Q = *Qp;
-            const double lw = lane_presets<NI>(P, Q.start ? Q.start + (size_t)lane * (size_t)P.ni : nullptr, Q.log_weight ? Q.logp : nullptr, Q.lp_off, A.status, sp);
-            if (Q.log_weight) Q.log_weight[lane] = lw;
+            const int64_t row = Q.row ? Q.row[lane] : lane;
+            const double lw = lane_presets<NI>(P, Q.start ? Q.start + (size_t)row * (size_t)P.ni : nullptr, Q.log_weight ? Q.logp : nullptr, Q.lp_off, A.status, sp);
+            if (Q.log_weight) Q.log_weight[row] = lw;
         } else {
 #pragma unroll
             for (int p = 0; p < NI; p++) sp[p] = p < P.ni ? (int)P.i_start[p] : 0;

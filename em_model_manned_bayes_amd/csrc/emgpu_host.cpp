@@ -732,6 +732,13 @@ int emgpu_host_stats(const emgpu_ctx *ctx, emgpu_host_stats_t *out) {
 }
 
 // ================================================================================================ the host path
+// The start grid of a host-pointer call is caller (host) memory: uploaded once into the ctx's scratch, every chunk reads its own rows.
+static const int32_t *upload_start_grid(emgpu_ctx *ctx, const int32_t *start, size_t n, size_t ni) {
+    int32_t *ds = (int32_t *)ctx_scratch(ctx, 0, n * ni * sizeof(int32_t));
+    HIP_OK(hipMemcpyAsync(ds, start, n * ni * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
+    return ds;
+}
+
 int emgpu_sample_dbn_host(emgpu_ctx *ctx, const emgpu_model *h, const emgpu_sample_params *p, const emgpu_sample_out *out) {
     EMGPU_TRY
     if (!ctx || !h || !p || !out) return fail(EMGPU_ERR_ARG, "null argument");
@@ -781,9 +788,7 @@ int emgpu_sample_dbn_host(emgpu_ctx *ctx, const emgpu_model *h, const emgpu_samp
 
     emgpu_sample_params pd = *p;
     if (p->start) {     // the start grid and the index list are caller (host) memory here: uploaded once, every chunk reads its rows
-        int32_t *ds = (int32_t *)ctx_scratch(ctx, 0, n * ni * sizeof(int32_t));
-        HIP_OK(hipMemcpyAsync(ds, p->start, n * ni * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
-        pd.start = ds;
+        pd.start = upload_start_grid(ctx, p->start, n, ni);
     }
     if (p->indices) {
         uint64_t *di = (uint64_t *)ctx_scratch(ctx, 1, n * sizeof(uint64_t));
@@ -883,7 +888,7 @@ int emgpu_sample_uncor_host(emgpu_ctx *ctx, const emgpu_model *h, const emgpu_sa
         return fail(EMGPU_ERR_ARG, "inits, ev_count, events, ctrl_count, controls and totals are required");
     if (p->event_cap < 1) return fail(EMGPU_ERR_ARG, "event_cap must be >= 1");
     if (out->events_cap < 0 || out->controls_cap < 0) return fail(EMGPU_ERR_ARG, "events_cap and controls_cap must be >= 0");
-    if (p->start || p->indices) return fail(EMGPU_ERR_ARG, "emgpu_sample_uncor_host: start grids and index lists are not supported");
+    if (p->indices) return fail(EMGPU_ERR_ARG, "emgpu_sample_uncor_host: index lists are not supported");
     if (p->n < 0 || p->sample_time < 1 || p->sample_time > 65535) return fail(EMGPU_ERR_ARG, "n < 0 or sample_time outside 1..65535");
     const Model &m = h->m;
     for (int k = 0; k < 3; k++)
@@ -926,6 +931,8 @@ int emgpu_sample_uncor_host(emgpu_ctx *ctx, const emgpu_model *h, const emgpu_sa
     for (Arr *a : {&a_ev, &a_ctl}) if (a->staged) { a->stg_off = so; so = round_up(so + C * cap * a->elem, 256); }
     const size_t stage_bytes = std::max<size_t>(so, 256);
     if (!provision(ctx, P.nchunks, dev_bytes, stage_bytes)) return fail(EMGPU_ERR_HIP, "emgpu_sample_uncor_host: out of device memory");
+    const int32_t *d_start = nullptr;
+    if (p->start) { d_start = upload_start_grid(ctx, p->start, n, ni); HIP_OK(hipStreamSynchronize(ctx->stream)); }
 
     emgpu_host_stats_t st{};
     size_t rows[2][2] = {{0, 0}, {0, 0}}, base[2][2] = {{0, 0}, {0, 0}};   // per buffer: event / control rows of its chunk and their first row in the call
@@ -936,6 +943,7 @@ int emgpu_sample_uncor_host(emgpu_ctx *ctx, const emgpu_model *h, const emgpu_sa
         emgpu_sample_params q = *p;
         q.n = (int64_t)c;
         q.first_index = p->first_index + (uint64_t)k0;
+        if (d_start) q.start = d_start + k0 * ni;
         emgpu_sample_out d{};
         d.ld = (int64_t)Cp;
         d.init_val = (float *)(dev + o_iv);
@@ -1018,7 +1026,7 @@ int emgpu_sample_text_host(emgpu_ctx *ctx, const emgpu_model *h, const emgpu_sam
     if (!ctx || !h || !p || !out) return fail(EMGPU_ERR_ARG, "null argument");
     if (!out->initial || !out->transition || !out->totals) return fail(EMGPU_ERR_ARG, "initial, transition and totals are required");
     if (out->initial_cap < 0 || out->transition_cap < 0) return fail(EMGPU_ERR_ARG, "initial_cap and transition_cap must be >= 0");
-    if (p->start || p->indices) return fail(EMGPU_ERR_ARG, "emgpu_sample_text_host: start grids and index lists are not supported");
+    if (p->indices) return fail(EMGPU_ERR_ARG, "emgpu_sample_text_host: index lists are not supported");
     if (p->n < 0 || p->sample_time < 1) return fail(EMGPU_ERR_ARG, "n < 0 or sample_time < 1");
     if (out->id_first < 0 || out->id_first > ((int64_t)1 << 53) - p->n) return fail(EMGPU_ERR_ARG, "id_first < 0 or id_first + n > 2^53");
     CTX_LOCK(ctx);
@@ -1063,6 +1071,8 @@ int emgpu_sample_text_host(emgpu_ctx *ctx, const emgpu_model *h, const emgpu_sam
     for (Txt &t : tx) if (t.staged) { t.stg_off = so; so = round_up(so + C * t.per, 256); }
     const size_t stage_bytes = std::max<size_t>(so, 256);
     if (!provision(ctx, P.nchunks, dev_bytes, stage_bytes)) return fail(EMGPU_ERR_HIP, "emgpu_sample_text_host: out of device memory");
+    const int32_t *d_start = nullptr;
+    if (p->start) { d_start = upload_start_grid(ctx, p->start, n, ni); HIP_OK(hipStreamSynchronize(ctx->stream)); }
 
     emgpu_host_stats_t st{};
     size_t bytes[2][2] = {{0, 0}, {0, 0}}, base[2][2] = {{0, 0}, {0, 0}}, total[2] = {0, 0};   // per buffer: the chunk's bytes and their place in the call's
@@ -1072,6 +1082,7 @@ int emgpu_sample_text_host(emgpu_ctx *ctx, const emgpu_model *h, const emgpu_sam
         emgpu_sample_params q = *p;
         q.n = (int64_t)c;
         q.first_index = p->first_index + (uint64_t)k0;
+        if (d_start) q.start = d_start + k0 * ni;
         emgpu_sample_out d{};
         d.ld = (int64_t)Cp;
         d.init_val = (float *)(dev + a_iv.dev_off);

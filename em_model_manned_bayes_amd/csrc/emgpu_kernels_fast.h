@@ -529,8 +529,11 @@ __device__ __forceinline__ uint16_t *evu_lds(int wave) {
 }
 // EVW: the event list of a model with more rated variables than the eight streams of EV hold (haa_v1): emgpu_events.h "WIDE lists"
 // (1: result slots + a row loop per lane, any outputs; 2, 3: events only, the rows built by the wave -- "ROWS BY THE WAVE")
-template <int NI, int M0, int M1, int M2, bool MIXED = false, bool EV = false, bool IDX = false, int EVW = 0>
-__device__ __forceinline__ void uncor_fast_body(const EmgpuPlan &P, const EmgpuRun &A, const FastArgs &F, const int64_t i0 /* trajectory of lane 0: wave-uniform, may be < 0 */) {
+// PS: the lane's presets may come from its row of a start grid (Q->start), its log-weight may be wanted (Q->log_weight): the +start
+// instances of emgpu_kernels_fast_ps.hip.  Only the initial network differs; the frozen parent columns follow from the preset bins.
+template <int NI, int M0, int M1, int M2, bool MIXED = false, bool EV = false, bool IDX = false, int EVW = 0, bool PS = false>
+__device__ __forceinline__ void uncor_fast_body(const EmgpuPlan &P, const EmgpuRun &A, const FastArgs &F, const int64_t i0 /* trajectory of lane 0: wave-uniform, may be < 0 */,
+                                                const EmgpuPresets *Q = nullptr /* PS only */) {
     // workers look the bin of a request up in LDS (the owner does not encode it into the request): -1.8 % on the
     // <7,4,6,6> instance too since the packed compare pass freed its registers
     constexpr bool LB = true;
@@ -558,11 +561,16 @@ __device__ __forceinline__ void uncor_fast_body(const EmgpuPlan &P, const EmgpuR
     double val[NI];
 #pragma unroll
     for (int p = 0; p < NI; p++) { bin[p] = 0; val[p] = 0.0; }
+    int32_t attempts_used;
+    if constexpr (PS) {   // a lane outside the run reads no row of the grid (valid), like the index list above
+        attempts_used = init_network_ps<NI>(P, A, Q, rng, bin, val, i, valid);
+    } else {
 #ifdef EMGPU_FAST_INIT_KARG   // measuring variant (HISTORY.md section 9): -1.9 % vector instructions, judged in both box states
-    const int32_t attempts_used = init_network_karg<NI>((KargPlan)__builtin_amdgcn_kernarg_segment_ptr(), A, rng, bin, val);
+        attempts_used = init_network_karg<NI>((KargPlan)__builtin_amdgcn_kernarg_segment_ptr(), A, rng, bin, val);
 #else
-    const int32_t attempts_used = init_network<NI>(P, A, rng, bin, val);
+        attempts_used = init_network<NI>(P, A, rng, bin, val);
 #endif
+    }
     if (valid) {
         if (attempts_used < 0) atomicOr(A.status, 1u);
         if (A.attempts) A.attempts[i] = attempts_used;

@@ -10,6 +10,11 @@ hipError_t launch_bn(const EmgpuPlan &P, const EmgpuBnRun &A, hipStream_t s, con
 // Returns false when the (plan, run) pair is outside what the specialised kernel covers.
 bool fast_uncor_eligible(const EmgpuPlan &P, const EmgpuRun &A);
 hipError_t launch_uncor_fast(const EmgpuPlan &P, const EmgpuRun &A, hipStream_t s, const char **name);
+// The same with a start grid / per-sample log-weights (emgpu_kernels_fast_ps.hip).  uncor_fast_start_form: 0 = this fast-eligible call has
+// no +start instance (the list and the dense trace together: k_dbn_generic), 1 = dense, 2 = the list alone.  name: room for 64 characters,
+// receives the name of the instance whose body runs; the caller appends "+start".
+int uncor_fast_start_form(const EmgpuPlan &P, const EmgpuRun &A);
+hipError_t launch_uncor_fast_start(const EmgpuPlan &P, const EmgpuRun &A, const EmgpuPresets *presets, hipStream_t s, char *name);
 // Mixed-model batch in one launch: nb <= EMGPU_MAX_MIXED blocks whose plans are fast-eligible and share the instance
 // uncor_fast_shape().  A model's plan lives in device memory (plan_f_bytes() bytes filled by plan_f_fill on the host, then uploaded).
 int uncor_fast_shape(const EmgpuPlan &P);

@@ -223,6 +223,39 @@ std::vector<double> initial_log_prob(const Model &m, uint32_t off[EMGPU_MAX_NI])
     return lp;
 }
 
+void start_grid_log_weight(const Model &m, const int32_t *start, int64_t n, double *out) {
+    const int ni = m.n_initial;
+    if (ni > EMGPU_MAX_NI) throw Error(EMGPU_ERR_UNSUPPORTED, "more initial variables than EMGPU_MAX_NI");
+    uint32_t off[EMGPU_MAX_NI];
+    const std::vector<double> lp = initial_log_prob(m, off);
+    std::vector<int> bin((size_t)ni);   // by variable id: the accepted preset (1-based) or 0
+    for (int64_t i = 0; i < n; i++) {
+        const int32_t *row = start + (size_t)i * (size_t)ni;
+        std::fill(bin.begin(), bin.end(), 0);
+        double lw = 0.0;
+        for (int p = 0; p < ni; p++) {       // topological order: a node's parents come before it
+            const int v = m.order_initial[(size_t)p] - 1, r = m.r_initial[(size_t)v];
+            int s = row[v];
+            if (s == 0 && !m.start.empty()) s = m.start[(size_t)v];
+            if (s == 0) continue;
+            bool ok = s >= 1 && s <= r;
+            int64_t col = 0, stride = 1;
+            for (int q = 0; q < ni; q++) {   // asub2ind.m:13-14 over the parents in ascending index
+                if (!m.G_initial[(size_t)q * ni + v]) continue;
+                if (bin[(size_t)q] == 0) ok = false;
+                col += stride * (bin[(size_t)q] - 1);
+                stride *= m.r_initial[(size_t)q];
+            }
+            if (!ok)
+                throw Error(EMGPU_ERR_PRESET, "Attempt to preset a dependent variable: row " + std::to_string(i) + " of the start grid presets variable " +
+                                                  std::to_string(v + 1) + " without its parents, or to a bin outside 1.." + std::to_string(r));
+            bin[(size_t)v] = s;
+            lw += lp[off[p] + (size_t)col * (size_t)r + (size_t)(s - 1)];
+        }
+        out[i] = lw;
+    }
+}
+
 void Model::set_transition_stay_prior(double prior) {
     // setTransitionPriors.m:12-33
     for (auto &tm : temporal_map) {

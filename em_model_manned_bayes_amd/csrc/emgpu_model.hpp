@@ -99,6 +99,9 @@ UncorLimits build_uncor_limits(const Model &m, const UncorTrackVars &tv);
 // column-normalised N + alpha; an all-zero column draws bin 1 with certainty (select_random.m:17-20: sthres = 0).  The table behind the
 // per-sample log-weights of a start grid (InitStartTerminal.m:57-90).
 std::vector<double> initial_log_prob(const Model &m, uint32_t off[EMGPU_MAX_NI]);
+// out[i] = the log-weight of row i of a start grid [n][n_initial] (0 = unset: the model's own start): the table above summed in the order
+// of lane_presets (emgpu_device.h).  Throws EMGPU_ERR_PRESET naming the first row that breaks one of lane_presets' two rules.
+void start_grid_log_weight(const Model &m, const int32_t *start, int64_t n, double *out);
 
 // Quantile thresholds of one CPT column (r weights): out[r-1].
 void column_thresholds(const double *w, int r, uint32_t *out);

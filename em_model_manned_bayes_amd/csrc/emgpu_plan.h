@@ -145,13 +145,16 @@ struct EmgpuRun {
     const uint64_t *indices; // optional: global index of lane i (instead of first_index + i); every DBN kernel but the round-1 k_dbn_step
 };
 // per-sample presets (a start GRID in one launch: InitStartTerminal.m:57-90, UncorEncounterModel.m:204): a block of device memory handed to
-// k_dbn_generic as an argument of its own.  NOT part of EmgpuRun: the benchmark kernel sits at the edge of its scalar registers, and a
-// pointer it never reads cost it 45 more spill reloads in its loops (+3.7 % vector instructions, measured).
+// k_dbn_generic and the +start instances of the fast kernel (emgpu_kernels_fast_ps.hip) as an argument of its own.  NOT part of EmgpuRun:
+// the benchmark kernel sits at the edge of its scalar registers, and a pointer it never reads cost it 45 more spill reloads in its loops
+// (+3.7 % vector instructions, measured).  The block itself lives in device memory: growing it costs no kernel an argument.
 struct EmgpuPresets {
-    const int32_t *start;    // [n][ni] by variable id, 0 = unset (then the model's own start applies); null: the model's start for every lane
-    double *log_weight;      // [n] sum over the lane's preset nodes of log P(preset | parents); null: not wanted
+    const int32_t *start;    // [rows][ni] by variable id, 0 = unset (then the model's own start applies); null: the model's start for every lane
+    double *log_weight;      // [rows] sum over the lane's preset nodes of log P(preset | parents); null: not wanted
     const double *logp;      // log of the column-normalised (N + alpha) of the initial network, node after node (by position), column after column
     uint32_t lp_off[EMGPU_MAX_NI];
+    const int64_t *row;      // [n] the row of start / log_weight that lane i reads and writes; null: row i (the later rounds of
+                             // UncorEncounterModel.track hand their slot list in: lane i redraws trajectory row[i] of the call)
 };
 
 struct EmgpuBnRun {

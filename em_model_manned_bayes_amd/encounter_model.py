@@ -313,6 +313,43 @@ class EncounterModel:
         log-weight of every sample drawn with this start distribution (0.0 without presets)."""
         return self.native.start_log_weight()
 
+    def _start_grid(self, start_grid, n):
+        """A start grid as the library takes it: [n, n_initial] int32 by variable id, None / NaN / 0 = unset."""
+        grid = np.array([[0 if (v is None or (isinstance(v, float) and np.isnan(v))) else int(v) for v in row] for row in start_grid], dtype=np.int32)
+        if grid.shape != (int(n), self.n_initial):
+            raise ValueError("start_grid must have nSamples rows of n_initial entries")
+        return grid
+
+    def makeStartGrid(self, values, nSamples=1):
+        """A start grid for sample(start_grid=...) / track(start_grid=...) / em_sample(start_grid=...): `values` maps a label of the initial
+        network to the bins it is preset to in turn, e.g. {"G": [1], "A": [1, 2, 3, 4], "L": [1, 2, 3, 4]} (RUN_uncor.m:35-47 fixes G, A and
+        L before it samples).  The Cartesian product in the order of InitStartTerminal.m:57-90 (the first label varies slowest, the last
+        fastest), every combination repeated nSamples times in a row.  Returns (grid [n_combinations * nSamples, n_initial] int32 with 0 =
+        unset, comb [rows] = the 0-based number of each row's combination)."""
+        import itertools
+        labs = [lab.replace('"', "") for lab in self.labels_initial]
+        cols, bins = [], []
+        for name, b in values.items():
+            name = str(name).replace('"', "")
+            if name not in labs:
+                raise ValueError("makeStartGrid: no initial variable is labelled %r" % name)
+            b = [int(x) for x in np.atleast_1d(b)]
+            r = int(self.r_initial[labs.index(name)])
+            if not b or min(b) < 1 or max(b) > r:
+                raise ValueError("makeStartGrid: the bins of %r must lie in 1..%d" % (name, r))
+            cols.append(labs.index(name))
+            bins.append(b)
+        if len(set(cols)) != len(cols):
+            raise ValueError("makeStartGrid: a label is named twice")
+        combos = np.array(list(itertools.product(*bins)), dtype=np.int32).reshape(-1, len(cols))
+        per = int(nSamples)
+        if per < 1:
+            raise ValueError("makeStartGrid: nSamples must be >= 1")
+        comb = np.repeat(np.arange(combos.shape[0], dtype=np.int64), per)
+        grid = np.zeros((comb.size, self.n_initial), dtype=np.int32)
+        grid[:, cols] = combos[comb]
+        return grid, comb
+
     def _push_prior(self):
         if self._native is not None:
             self._native.set_prior(self._prior)
@@ -381,9 +418,15 @@ class UncorEncounterModel(EncounterModel):
         self.isRotorcraft = "rotorcraft" in os.path.basename(str(parameters_filename))  # :181-185
 
     def sample(self, n_samples, sample_time, seed=None, isQuantize500=False, layers=None,
-               transition_mode=L.TRANSITION_REFERENCE_AUTO, max_attempts=1000, first_index=None, ctx=None, lazy=False):
+               transition_mode=L.TRANSITION_REFERENCE_AUTO, max_attempts=1000, first_index=None, ctx=None, lazy=False,
+               start_grid=None, return_log_weight=False):
         """[out_inits, out_events, out_samples, out_EME] = sample(self, n_samples, sample_time, 'seed', s,
         'isQuantize500', b, 'layers', L)   (UncorEncounterModel.m:192-313).
+
+        start_grid: [n_samples, n_initial] preset bins by variable id, one row per sample (0 / None = unset: the model's own `start`, else
+        the variable is drawn) -- the strata a loop over `start` values (RUN_uncor.m:35-47) draws in as many calls, in ONE; sample i is
+        what `self.start = row i; self.sample(1, ..., first_index=i)` gives.  makeStartGrid builds one.  return_log_weight: a fifth output,
+        log P(presets of row i) per sample (importance weights; start_log_weight for every sample without a grid).
 
         lazy=True: the same four outputs, bit for bit, with out_samples and the controls built on the GPU (emgpu_sample_uncor_host) and
         out_events / out_samples / out_EME handed out as LazyEvents / LazySamples / LazyControls: sequences that build sample i's object when
@@ -406,10 +449,18 @@ class UncorEncounterModel(EncounterModel):
         flags = L.FLAG_QUANTIZE500 if isQuantize500 else 0
         n_samples = int(n_samples)
         ni, T = self.n_initial, int(sample_time)
+        grid = self._start_grid(start_grid, n_samples) if start_grid is not None else None
+        # the weights come from the host function the device's own weights are bit-equal to: the device-formatted call has no weight output
+        log_weight = None
+        if return_log_weight:
+            log_weight = native.start_grid_log_weight(m, grid if grid is not None else np.zeros((n_samples, ni), dtype=np.int32))
+        elif grid is not None:
+            native.start_grid_log_weight(m, grid)   # a bad row is reported with its number, before anything is drawn
         out_inits = np.zeros((n_samples, ni))
         out_events, out_samples, out_EME = [None] * n_samples, [None] * n_samples, [None] * n_samples
         if lazy:
-            return self._sample_lazy(ctx, n_samples, T, s, first, flags, layers, transition_mode, max_attempts, idxL, idxV, idxDH, idxDPsi, idxDV)
+            out = self._sample_lazy(ctx, n_samples, T, s, first, flags, layers, transition_mode, max_attempts, idxL, idxV, idxDH, idxDPsi, idxDV, grid)
+            return out + (log_weight,) if return_log_weight else out
         tm = self.temporal_map
         idxEME = [int(np.nonzero(tm[:, 0] == v)[0][0]) + 1 for v in (idxDH, idxDPsi, idxDV)]  # :291
         vars_dyn = tm[:, 0].astype(np.int64) - 1
@@ -422,7 +473,8 @@ class UncorEncounterModel(EncounterModel):
             try:
                 res = native.sample_dbn_host(ctx, m, nn, T, s, first_index=first + pos, want_dense=False, want_events=True,
                                              event_cap=cap, flags=flags, layers=layers, transition_mode=transition_mode,
-                                             max_attempts=max_attempts, idx_L=idxL, idx_v=idxV, idx_dh=idxDH)
+                                             max_attempts=max_attempts, idx_L=idxL, idx_v=idxV, idx_dh=idxDH,
+                                             start=None if grid is None else grid[pos: pos + nn])
             except L.EmgpuError as e:
                 if e.code == L.ERR_EVENT_CAP:   # longest event list did not fit: retry this chunk with more room
                     cap *= 2
@@ -478,9 +530,11 @@ class UncorEncounterModel(EncounterModel):
         tm["total_s"] = _time.perf_counter() - t_call
         tm["format_s"] = tm["total_s"] - tm["native_s"]
         self.last_sample_timing = tm
+        if return_log_weight:
+            return out_inits, out_events, out_samples, out_EME, log_weight
         return out_inits, out_events, out_samples, out_EME
 
-    def _sample_lazy(self, ctx, n, T, s, first, flags, layers, transition_mode, max_attempts, idxL, idxV, idxDH, idxDPsi, idxDV):
+    def _sample_lazy(self, ctx, n, T, s, first, flags, layers, transition_mode, max_attempts, idxL, idxV, idxDH, idxDPsi, idxDV, grid=None):
         """sample(..., lazy=True): one library call builds the four outputs on the device; out_EME's columns are the variables of idxEME
         (:291) in that order, dh, dpsi, dv."""
         import time as _time
@@ -491,7 +545,7 @@ class UncorEncounterModel(EncounterModel):
             try:
                 res = native.sample_uncor_host(ctx, self.native, n, T, s, (idxDH, idxDPsi, idxDV), event_cap=cap, first_index=first,
                                                flags=flags, layers=layers, transition_mode=transition_mode, max_attempts=max_attempts,
-                                               idx_L=idxL, idx_v=idxV, idx_dh=idxDH)
+                                               idx_L=idxL, idx_v=idxV, idx_dh=idxDH, start=grid)
             except L.EmgpuError as e:
                 tm["native_s"] += _time.perf_counter() - t_nat
                 if e.code != L.ERR_EVENT_CAP or e.ev_count.max(initial=0) <= cap:
@@ -515,10 +569,13 @@ class UncorEncounterModel(EncounterModel):
     TRACK_FIELDS = ("time_s", "north_ft", "east_ft", "up_ft", "speed_ft_s", "phi_rad", "theta_rad", "psi_rad")
 
     def track(self, nSamples, sample_time, initialSeed=None, isQuantize500=False, coordSys="NEU", max_track_attempts=200,
-              record_stride=1, first_index=None, ctx=None, return_info=False):
+              record_stride=1, first_index=None, ctx=None, return_info=False, start_grid=None, return_log_weight=False):
         """out_results = track(self, nSamples, sample_time, 'initialSeed', s, 'isQuantize500', b, 'coordSys', 'NEU')
         (UncorEncounterModel.m:318-471).  Each result is a dict of 1-D arrays with the columns of the reference's timetable
         (time_s instead of the row times), sampled at 10 Hz (record_stride=1) like results.time.
+
+        start_grid: as for sample -- every attempt of track i is drawn under row i, so track i is what `self.start = row i;
+        self.track(1, ..., first_index=i)` gives.  return_log_weight: log P(presets of row i) per track, as the last output.
 
         Runs on the GPU end to end: per round the still-rejected trajectories are sampled (attempt j with the key
         initialSeed + j, :424-428), integrated and tested against getDynamicLimits (:459-470) on the device.
@@ -536,11 +593,20 @@ class UncorEncounterModel(EncounterModel):
         s, first = _take(initialSeed, nSamples)
         if first_index is not None:
             first = int(first_index)
+        grid = self._start_grid(start_grid, nSamples) if start_grid is not None else None
+        log_weight = None
+        if return_log_weight:
+            log_weight = native.start_grid_log_weight(self.native, grid if grid is not None else np.zeros((int(nSamples), self.n_initial), dtype=np.int32))
+        elif grid is not None:
+            native.start_grid_log_weight(self.native, grid)   # a bad row is reported with its number, before anything is drawn
         res = native.track_uncor_host(ctx or native.default_context(), self.native, int(nSamples), int(sample_time), s, first_index=first,
                                       is_quantize500=isQuantize500, is_rotorcraft=self.isRotorcraft, max_track_attempts=max_track_attempts,
-                                      record_stride=record_stride)
+                                      record_stride=record_stride, start=grid)
         out_results = [{f: res["tracks"][i, :, k].copy() for k, f in enumerate(self.TRACK_FIELDS)} for i in range(int(nSamples))]
-        return (out_results, res) if return_info else out_results
+        out = (out_results, res) if return_info else (out_results,)
+        if return_log_weight:
+            out = out + (log_weight,)
+        return out if len(out) > 1 else out[0]
 
     def getDynamicLimits(self, initial, results, idx_G=None, idx_A=None, idx_L=None, idx_V=None, idx_DH=None, is_discretized=None):
         """dynamiclimits = getDynamicLimits(self, initial, results, ...)  (@UncorEncounterModel/getDynamicLimits.m).  The index
@@ -645,9 +711,7 @@ class CorTerminalModel(EncounterModel):
         nSamples must then equal its length.  return_log_weight: also return log P(presets of the row) per sample (importance weights)."""
         grid = None
         if start_grid is not None:
-            grid = np.array([[0 if (v is None or (isinstance(v, float) and np.isnan(v))) else int(v) for v in row] for row in start_grid], dtype=np.int32)
-            if grid.shape != (int(nSamples), self.n_initial):
-                raise ValueError("start_grid must have nSamples rows of n_initial entries")
+            grid = self._start_grid(start_grid, nSamples)
         s, first = _take(seed, nSamples)
         if first_index is not None:
             first = int(first_index)

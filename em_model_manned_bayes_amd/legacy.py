@@ -41,7 +41,7 @@ def _g(x):
 
 def em_sample(parameters_filename, initial_output_filename=None, transition_output_filename=None, num_initial_samples=100,
               num_transition_samples=60, start=None, isOverwriteZeroBoundaries=False, idxZeroBoundaries=(1, 2, 3),
-              rng_seed=42, prior=0, ctx=None, text="host", return_arrays=True, id_first=1, text_batch=None):
+              rng_seed=42, prior=0, ctx=None, text="host", return_arrays=True, id_first=1, text_batch=None, start_grid=None):
     """em_sample(parameters_filename, 'initial_output_filename', ..., 'num_initial_samples', 100,
     'num_transition_samples', 60, 'start', {}, 'rng_seed', 42)  (em_sample.m:1-104).
 
@@ -54,7 +54,10 @@ def em_sample(parameters_filename, initial_output_filename=None, transition_outp
     text: "host" formats every row in Python ("%g" per value); "device" writes the same two files from rows formatted on the GPU
     (native.sample_text_host), in batches of text_batch trajectories (default: as many as keep the pinned text buffers near 256 MiB, by
     native.text_bound), so host memory stays bounded whatever num_initial_samples is.  Device writer only: return_arrays=False returns
-    (None, None) and keeps no array of the run; id_first is the id of the first trajectory (a run continued from an earlier file)."""
+    (None, None) and keeps no array of the run; id_first is the id of the first trajectory (a run continued from an earlier file).
+
+    start_grid: [num_initial_samples, n_initial] preset bins by variable id, one row per trajectory (0 / None = unset: `start`, else the
+    variable is drawn): the strata of a loop over `start` values in one pair of files, under either writer."""
     if text not in ("host", "device"):
         raise ValueError("em_sample: text must be 'host' or 'device', not %r" % (text,))
     if text == "host" and (not return_arrays or int(id_first) != 1 or text_batch is not None):
@@ -67,6 +70,12 @@ def em_sample(parameters_filename, initial_output_filename=None, transition_outp
     dt = bn_dirichlet_prior(parms["N_transition"], prior)
     m = _model_of(parms, di, dt, start)
     n, T = int(num_initial_samples), int(num_transition_samples)
+    grid = None
+    if start_grid is not None:
+        grid = np.array([[0 if (v is None or (isinstance(v, float) and np.isnan(v))) else int(v) for v in row] for row in start_grid], dtype=np.int32)
+        if grid.shape != (n, m.n_initial):
+            raise ValueError("em_sample: start_grid must have num_initial_samples rows of n_initial entries")
+        native.start_grid_log_weight(m, grid)   # a bad row is reported with its number, before a file is touched
     seed, first = _take(rng_seed, n)
     tm = np.asarray(parms["temporal_map"]).reshape(-1, 2)
     header_initial = "id " + "".join("%s " % s for s in parms["labels_initial"]) + "\n"                                         # :64-68
@@ -76,10 +85,10 @@ def em_sample(parameters_filename, initial_output_filename=None, transition_outp
             os.makedirs(os.path.dirname(f), exist_ok=True)
     if text == "device":
         return _em_sample_device_text(ctx or native.default_context(), m, n, T, seed, first, initial_output_filename, transition_output_filename,
-                                      header_initial, header_transition, return_arrays, int(id_first), text_batch)
+                                      header_initial, header_transition, return_arrays, int(id_first), text_batch, grid)
     # dbn_hierarchical_sample + events2samples (em_sample.m:78-82): no rejection test, dense trace
     res = native.sample_dbn_host(ctx or native.default_context(), m, n, T, seed, first_index=first, want_dense=True,
-                                 max_attempts=1)
+                                 max_attempts=1, start=grid)
     initial = res["init_val"].astype(np.float64)
     trace = res["dyn_val"].astype(np.float64)
     with open(initial_output_filename, "w", encoding="utf-8", newline="\n") as f:
@@ -97,7 +106,7 @@ def em_sample(parameters_filename, initial_output_filename=None, transition_outp
 
 
 def _em_sample_device_text(ctx, m, n, T, seed, first, initial_filename, transition_filename, header_initial, header_transition, return_arrays,
-                           id_first, text_batch):
+                           id_first, text_batch, grid=None):
     """em_sample's files from rows formatted on the device: batch after batch of trajectories through native.sample_text_host into one pair of
     pinned buffers, each batch's bytes appended to the files.  last_text_stats says where the time went."""
     st = {"calls": 0, "batch": 0, "library_ms": 0.0, "kernel_ms": 0.0, "d2h_ms": 0.0, "scatter_ms": 0.0, "write_ms": 0.0, "bytes": 0}
@@ -113,7 +122,7 @@ def _em_sample_device_text(ctx, m, n, T, seed, first, initial_filename, transiti
         for b0 in range(0, n, batch):
             c = min(batch, n - b0)
             res = native.sample_text_host(ctx, m, c, T, seed, id_first=id_first + b0, want_arrays=return_arrays, buffers=buffers,
-                                          first_index=first + b0, max_attempts=1)
+                                          first_index=first + b0, max_attempts=1, start=None if grid is None else grid[b0:b0 + c])
             t0 = time.perf_counter()
             fi.write(res["initial"].data)
             ft.write(res["transition"].data)

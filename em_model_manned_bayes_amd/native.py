@@ -360,19 +360,20 @@ def shard_range(n_total, rank, world):
     return int(lo.value), int(hi.value)
 
 
-def _sample_out(init_bin=0, init_val=0, dyn_bin=0, dyn_val=0, ev_count=0, events=0, attempts=0, ld=0, col_offset=0):
+def _sample_out(init_bin=0, init_val=0, dyn_bin=0, dyn_val=0, ev_count=0, events=0, attempts=0, ld=0, col_offset=0, log_weight=0):
     o = L.SampleOut()
     o.init_bin, o.init_val, o.dyn_bin, o.dyn_val = init_bin or None, init_val or None, dyn_bin or None, dyn_val or None
-    o.ev_count, o.events, o.attempts = ev_count or None, events or None, attempts or None
+    o.ev_count, o.events, o.attempts, o.log_weight = ev_count or None, events or None, attempts or None, log_weight or None
     o.ld, o.col_offset = int(ld), int(col_offset)
     return o
 
 
 def sample_dbn_device(ctx, model, params, init_bin=0, init_val=0, dyn_bin=0, dyn_val=0, ev_count=0, events=0, attempts=0,
-                      ld=0, col_offset=0):
+                      ld=0, col_offset=0, log_weight=0):
     """Asynchronous launch with raw device pointers (ints, 0 = skip).  ld / col_offset: write this call's
-    trajectories into columns [col_offset, col_offset + n) of buffers dimensioned for ld trajectories."""
-    o = _sample_out(init_bin, init_val, dyn_bin, dyn_val, ev_count, events, attempts, ld, col_offset)
+    trajectories into columns [col_offset, col_offset + n) of buffers dimensioned for ld trajectories.  log_weight: [n] f64, not
+    offset by col_offset (a start grid goes in through make_params(start=device pointer))."""
+    o = _sample_out(init_bin, init_val, dyn_bin, dyn_val, ev_count, events, attempts, ld, col_offset, log_weight)
     L.check(L.lib().emgpu_sample_dbn_device(ctx._h, model._h, C.byref(params), C.byref(o)))
 
 
@@ -478,7 +479,8 @@ def sample_uncor_host(ctx, model, n, sample_time, seed, ctrl_var, event_cap=256,
     numpy arrays, filled through the library's staging buffers.  The packed rows go into arrays of events_cap / controls_cap rows (default
     n * event_cap: pinned when `pinned` and a capacity is given, else pageable, whose untouched pages cost nothing) and are returned trimmed.
     A list longer than event_cap, or rows beyond a capacity, raise EmgpuError(ERR_EVENT_CAP) with `.totals` (the rows needed, see emgpu.h)
-    and `.ev_count` set: a retry with that much room gives the same draws."""
+    and `.ev_count` set: a retry with that much room gives the same draws.
+    start= (make_params): a start grid [n, n_initial]; the weights of its rows: start_grid_log_weight."""
     ni, T, n = model.n_initial, int(sample_time), int(n)
     p, keep = make_params(n, T, seed, event_cap=int(event_cap), **kw)
     empty = ctx.pinned_empty if pinned else (lambda shape, dt: np.empty(shape, dtype=dt))
@@ -520,7 +522,7 @@ def sample_text_host(ctx, model, n, sample_time, seed, id_first=1, want_arrays=T
     them), kernel, host_stats.  id_first: the id of trajectory 0.  pinned: the buffers come from the context's pinned pool, else pageable numpy
     arrays.  initial_cap / transition_cap: bytes of the buffers (default: text_bound); buffers: (initial, transition) uint8 arrays of a caller
     who makes several calls.  Text that outgrows a buffer raises EmgpuError(ERR_EVENT_CAP) with `.totals` (the bytes needed): a retry with
-    that room gives the same bytes."""
+    that room gives the same bytes.  start= (make_params): a start grid [n, n_initial], trajectory i drawn under row i."""
     ni, nd, T, n = model.n_initial, model.n_dyn, int(sample_time), int(n)
     p, keep = make_params(n, T, seed, **kw)
     empty = ctx.pinned_empty if pinned else (lambda shape, dt: np.empty(shape, dtype=dt))
@@ -703,24 +705,43 @@ def utrack_params(model, n, sample_time, seed, first_index=0, is_quantize500=Fal
     return p
 
 
-def track_uncor_host(ctx, model, n, sample_time, seed, want_tracks=True, **kw):
+def start_grid_log_weight(model, grid):
+    """emgpu_start_grid_log_weight (host only, no GPU needed): log P(presets of row i) for every row of a start grid [n, n_initial]
+    (0 = unset: the model's own start) -- bit for bit the log_weight a sampling call returns for that row.  EmgpuError(ERR_PRESET) names the
+    first row that presets a node without its parents or to a bin outside 1..r."""
+    g = np.ascontiguousarray(grid, dtype=np.int32)
+    if g.ndim != 2 or g.shape[1] != model.n_initial:
+        raise ValueError("a start grid has n_initial columns")
+    out = np.zeros(g.shape[0], dtype=np.float64)
+    L.check(L.lib().emgpu_start_grid_log_weight(model._h, _p(g), g.shape[0], _p(out)))
+    return out
+
+
+def track_uncor_host(ctx, model, n, sample_time, seed, want_tracks=True, start=None, **kw):
     """emgpu_track_uncor_host: UncorEncounterModel.track on the GPU (sample -> point-mass dynamics -> rejection rounds).
-    Returns dict: tracks [n, S, 8] (time north east up speed phi theta psi), limits [n, 3], attempts [n], kernel."""
+    Returns dict: tracks [n, S, 8] (time north east up speed phi theta psi), limits [n, 3], attempts [n], kernel.
+    start: a start grid [n, n_initial] of preset bins (0 = unset), every attempt of track i drawn under row i (emgpu_track_uncor_grid_host)."""
     p = utrack_params(model, n, sample_time, seed, **kw)
     S = 10 * int(sample_time) // p.record_stride + 1
     tracks = np.zeros((n, S, 8)) if want_tracks else None
     limits = np.zeros((n, 3))
     attempts = np.zeros(n, dtype=np.int32)
-    L.check(L.lib().emgpu_track_uncor_host(ctx._h, model._h, C.byref(p), _p(tracks), _p(limits), _p(attempts)))
+    if start is not None:
+        st = np.ascontiguousarray(start, dtype=np.int32)
+        assert st.shape == (int(n), model.n_initial)
+        L.check(L.lib().emgpu_track_uncor_grid_host(ctx._h, model._h, C.byref(p), _p(st), _p(tracks), _p(limits), _p(attempts)))
+    else:
+        L.check(L.lib().emgpu_track_uncor_host(ctx._h, model._h, C.byref(p), _p(tracks), _p(limits), _p(attempts)))
     return {"tracks": tracks, "limits": limits, "attempts": attempts, "kernel": ctx.last_kernel()}
 
 
-def track_uncor_device(ctx, model, n, sample_time, seed, tracks=0, limits=0, attempts=0, **kw):
+def track_uncor_device(ctx, model, n, sample_time, seed, tracks=0, limits=0, attempts=0, start=0, **kw):
     """emgpu_track_uncor_device: track_uncor_host into the caller's device buffers (raw pointers, ints, 0 = skip): tracks [n, S, 8] f64,
-    limits [n, 3] f64, attempts [n] i32, in the layouts of track_uncor_host.  Returns the kernel names."""
+    limits [n, 3] f64, attempts [n] i32, in the layouts of track_uncor_host; start: a start grid [n, n_initial] i32 on the device
+    (emgpu_track_uncor_grid_device).  Returns the kernel names."""
     p = utrack_params(model, n, sample_time, seed, **kw)
-    L.check(L.lib().emgpu_track_uncor_device(ctx._h, model._h, C.byref(p), C.c_void_p(tracks or None), C.c_void_p(limits or None),
-                                             C.c_void_p(attempts or None)))
+    L.check(L.lib().emgpu_track_uncor_grid_device(ctx._h, model._h, C.byref(p), C.c_void_p(start or None), C.c_void_p(tracks or None),
+                                                  C.c_void_p(limits or None), C.c_void_p(attempts or None)))
     return ctx.last_kernel()
 
 

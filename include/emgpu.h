@@ -140,6 +140,12 @@ int emgpu_model_set_start(emgpu_model *m, const int32_t *start, int32_t n);
  * A start GRID (one row of presets per sample) with per-sample weights: emgpu_sample_params.start / emgpu_sample_out.log_weight and
  * emgpu_bn_params.start / .log_weight. */
 int emgpu_model_start_log_weight(const emgpu_model *m, double *out);
+/* The same per row of a start grid, on the host (no ctx): out[i] = the log-weight of a sample drawn with row i of start [n][n_initial]
+ * (by variable id; 0 = unset: the model's own `start` then applies) -- bit for bit what emgpu_sample_out.log_weight receives for that row
+ * (the same table of log P, summed over the preset nodes in topological order).  EMGPU_ERR_PRESET, naming the first offending row, under the
+ * sampler's two rules: a bin outside 1..r, or a preset node with a parent that is not preset.  What the entry points without a weight output
+ * (emgpu_sample_uncor_host, emgpu_sample_text_host, emgpu_track_uncor_grid_*) leave to the caller. */
+int emgpu_start_grid_log_weight(const emgpu_model *m, const int32_t *start, int64_t n, double *out);
 /* EncounterModel.zero_bins (EncounterModel.m:40; derived once by em_read.m:110-114,143-156 and, like in
  * the reference, NOT re-derived when boundaries are replaced): n_initial entries, 0 = none. */
 int emgpu_model_set_zero_bins(emgpu_model *m, const int32_t *zero_bins, int32_t n);
@@ -198,7 +204,10 @@ typedef struct {
                                 (UncorEncounterModel.m:204, bn_sample.m:44-50) does in as many calls, in ONE.  A device pointer for
                                 *_device calls, a host pointer for *_host.  A row that presets a node without presetting its parents,
                                 or a bin outside 1..r, is reported as EMGPU_ERR_PRESET (by emgpu_ctx_sync for *_device calls).
-                                Calls with a start grid or log-weights run on the general kernel.                                   */
+                                A fast-branch model (what runs on k_uncor_fast without a grid) is served at that kernel's pace by its
+                                +start instances when the call asks for the dense outputs alone (with or without `indices`) or for
+                                the event list alone; the list and the dense trace together, and every other model, run on the
+                                general kernel.  The same holds for calls that ask for log-weights.                                */
 } emgpu_sample_params;
 
 /* Event row (8 bytes): what one row [dt var value] of out_events{i} carries. */
@@ -259,7 +268,8 @@ int emgpu_sample_dbn_host(emgpu_ctx *ctx, const emgpu_model *m, const emgpu_samp
  * Both lists are packed over the call: list i's rows start at the sum of the counts before it.  The draws are those of emgpu_sample_dbn_host
  * with the same params (counter-based: chunking and capacities do not change them), and ctx's last kernel is the sampler's.
  * EMGPU_ERR_EVENT_CAP when a list outgrows event_cap (totals: the rows the lists need in full, for both totals) or the rows outgrow events_cap /
- * controls_cap (totals: exact); a retry with that room gives the same draws.  params.start and params.indices are not supported. */
+ * controls_cap (totals: exact); a retry with that room gives the same draws.  params.start (a HOST pointer: uploaded once, every chunk reads
+ * its own rows; the weights: emgpu_start_grid_log_weight) is honoured; params.indices is not supported. */
 typedef struct {
     double *inits;          /* [n][n_initial] row-major: out_inits                                                               */
     uint32_t *ev_count;     /* [n] rows of list i (> event_cap => EMGPU_ERR_EVENT_CAP)                                          */
@@ -288,7 +298,8 @@ int emgpu_sample_uncor_host(emgpu_ctx *ctx, const emgpu_model *m, const emgpu_sa
  * outgrows its capacity (totals: exact, the buffer's content undefined); a retry with that room gives the same bytes.  Pinned buffers
  * (emgpu_host_alloc) are written by the copy engine, pageable ones through the library's staging buffers.  emgpu_text_bound gives capacities
  * that always suffice: bytes[0] = n (21 + 13 n_initial), bytes[1] = n sample_time 13 (2 + n_dyn) -- a "%g" is at most 12 characters, an id
- * through "%d" at most 20, and one character follows each.  params.start and params.indices are not supported; id_first >= 0 and
+ * through "%d" at most 20, and one character follows each.  params.start (a HOST pointer, n rows: a trajectory's own row wins over the model's
+ * `start`) is honoured; params.indices is not supported; id_first >= 0 and
  * id_first + n <= 2^53 (beyond, an id is no longer a double).  emgpu_host_stats describes the call. */
 typedef struct {
     char *initial;          /* [initial_cap] bytes                                                                               */
@@ -626,6 +637,15 @@ int emgpu_track_uncor_host(emgpu_ctx *ctx, const emgpu_model *m, const emgpu_utr
                            double *tracks, double *limits, int32_t *attempts);
 int emgpu_track_uncor_device(emgpu_ctx *ctx, const emgpu_model *m, const emgpu_utrack_params *p,
                              double *tracks, double *limits, int32_t *attempts);
+/* The same with a start GRID: start [p->n][n_initial] as emgpu_sample_params.start (a HOST pointer for _host, a DEVICE pointer for _device;
+ * NULL: exactly the functions above).  Every attempt of trajectory i is drawn under row i: round 0 reads row i for lane i, a later round
+ * reads the rows of the trajectories it redraws.  Keys and indices are unchanged: attempt j of trajectory i has key seed + j and global index
+ * first_index + i.  A fast-branch model's sampler runs on the +start instance of k_uncor_fast_idx in every round.  EMGPU_ERR_PRESET as for
+ * emgpu_sample_dbn_*; the weights: emgpu_start_grid_log_weight. */
+int emgpu_track_uncor_grid_host(emgpu_ctx *ctx, const emgpu_model *m, const emgpu_utrack_params *p, const int32_t *start,
+                                double *tracks, double *limits, int32_t *attempts);
+int emgpu_track_uncor_grid_device(emgpu_ctx *ctx, const emgpu_model *m, const emgpu_utrack_params *p, const int32_t *start,
+                                  double *tracks, double *limits, int32_t *attempts);
 /* getDynamicLimits.m:1-130 for one trajectory on the host (what the table of the track kernel holds): initial = the
  * n_initial sampled values (bins for categorical variables), the extrema over the 10 Hz result in ft and ft/s. */
 int emgpu_uncor_dynamic_limits(const emgpu_model *m, const emgpu_utrack_params *vars, const double *initial,
