@@ -556,12 +556,17 @@ static void launch_dbn(emgpu_ctx *ctx, const Uploaded &u, const EmgpuRun &A, hip
     const char *name = "";
     hipError_t e;
     if (!stream) stream = ctx->stream;
-    char ps_name[64];
+    char ps_name[96];
     std::string suffix;
     // a start grid / per-sample log-weights: the +start instances of the fast kernel serve the dense outputs alone and the list alone of a
-    // fast-branch model; the list and the dense trace together, and every other model, run on the general kernel
+    // fast-branch model, those of the per-timestep kernel the same two forms of every other model it takes; the list and the dense trace
+    // together, an index list off the fast kernel, and what neither kernel takes run on the general kernel
     if (presets && emgpu::fast_uncor_eligible(u.cp.plan, A) && emgpu::uncor_fast_start_form(u.cp.plan, A) != 0) {
         e = emgpu::launch_uncor_fast_start(u.cp.plan, A, presets, stream, ps_name);
+        name = ps_name; suffix = "+start";
+    }
+    else if (presets && emgpu::step2_eligible(u.cp.plan, A) && emgpu::step2_start_form(u.cp.plan, A) != 0) {
+        e = emgpu::launch_dbn_step2_start(u.cp.plan, A, presets, stream, ps_name);
         name = ps_name; suffix = "+start";
     }
     else if (presets) e = emgpu::launch_dbn_generic(u.cp.plan, A, stream, &name, presets);

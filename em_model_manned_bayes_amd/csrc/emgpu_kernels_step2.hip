@@ -89,6 +89,34 @@ static bool launch_masked(const EmgpuPlan &P, const EmgpuRun &A, const Step2Args
     return false;
 }
 
+// the instances' names by shape (<7,3>, <9,3>, <16,4>) and form (w4 reg, w8 reg, reg, general), and the general frozen instance's
+static const char *const kStep2Names[3][4] = {
+    {"k_dbn_step2<7,3,w4,reg>", "k_dbn_step2<7,3,w8,reg>", "k_dbn_step2<7,3,reg>", "k_dbn_step2<7,3>"},
+    {"k_dbn_step2<9,3,w4,reg>", "k_dbn_step2<9,3,w8,reg>", "k_dbn_step2<9,3,reg>", "k_dbn_step2<9,3>"},
+    {"k_dbn_step2<16,4,w4,reg>", "k_dbn_step2<16,4,w8,reg>", "k_dbn_step2<16,4,reg>", "k_dbn_step2<16,4>"}};
+static const char *const kStep2FrozenName = "k_dbn_step2<16,4>[frozen]";
+
+Step2Args step2_args_of(const EmgpuPlan &P, bool *all_res, int *wmode) {
+    Step2Args F{};
+    *all_res = true;
+    *wmode = P.d_pw[0];
+    for (int k = 0; k < P.nd; k++) {
+        F.slot[k] = P.d_row[k];
+        for (int a = 0; a < P.nact; a++)
+            if (P.a_dyn[a] == k) F.Rk[k] = P.a_R[a];
+        F.RR1[k] = ((F.Rk[k] >> 16) + 1u) * 0x00010001u;
+        *all_res = *all_res && F.Rk[k] != 0u;
+        if (P.d_pw[k] != *wmode) *wmode = 0;
+    }
+    return F;
+}
+
+const char *step2_general_name(const EmgpuPlan &P, const EmgpuRun &A, int *shape) {
+    if (!(P.depend || A.per_step)) { *shape = 3; return kStep2FrozenName; }
+    *shape = (P.ni <= 7 && P.nd <= 3) ? 0 : ((P.ni <= 9 && P.nd <= 3) ? 1 : 2);
+    return kStep2Names[*shape][3];
+}
+
 static hipError_t launch_dbn_step2_inner(const EmgpuPlan &P, const EmgpuRun &A, hipStream_t s, const char **name);
 hipError_t launch_dbn_step2(const EmgpuPlan &P0, const EmgpuRun &A, hipStream_t s, const char **name) {
     EmgpuPlan P = P0;
@@ -103,24 +131,13 @@ hipError_t launch_dbn_step2(const EmgpuPlan &P0, const EmgpuRun &A, hipStream_t 
 }
 static hipError_t launch_dbn_step2_inner(const EmgpuPlan &P, const EmgpuRun &A, hipStream_t s, const char **name) {
     if (A.n <= 0) return hipSuccess;
-    Step2Args F{};
     const bool frozen = !(P.depend || A.per_step);
     bool all_res = true;
-    int wmode = P.d_pw[0];
-    for (int k = 0; k < P.nd; k++) {
-        F.slot[k] = P.d_row[k];
-        for (int a = 0; a < P.nact; a++)
-            if (P.a_dyn[a] == k) F.Rk[k] = P.a_R[a];
-        F.RR1[k] = ((F.Rk[k] >> 16) + 1u) * 0x00010001u;
-        all_res = all_res && F.Rk[k] != 0u;
-        if (P.d_pw[k] != wmode) wmode = 0;
-    }
+    int wmode = 0;
+    const Step2Args F = step2_args_of(P, &all_res, &wmode);
     // (Staging the tables in LDS was measured and dropped: random 16-byte gathers from LDS pay bank
     // conflicts and the extra LDS costs a workgroup of occupancy -- cor_v1 36.9 ms staged, 28.9 ms through L1/L2.)
-    static const char *names[3][4] = {
-        {"k_dbn_step2<7,3,w4,reg>", "k_dbn_step2<7,3,w8,reg>", "k_dbn_step2<7,3,reg>", "k_dbn_step2<7,3>"},
-        {"k_dbn_step2<9,3,w4,reg>", "k_dbn_step2<9,3,w8,reg>", "k_dbn_step2<9,3,reg>", "k_dbn_step2<9,3>"},
-        {"k_dbn_step2<16,4,w4,reg>", "k_dbn_step2<16,4,w8,reg>", "k_dbn_step2<16,4,reg>", "k_dbn_step2<16,4>"}};
+    const char *const(&names)[3][4] = kStep2Names;
     const int shape = (P.ni <= 7 && P.nd <= 3) ? 0 : ((P.ni <= 9 && P.nd <= 3) ? 1 : 2);
     const bool reg = all_res && P.nd == (shape == 2 ? 4 : 3);
     if (frozen) {   // fast branch: four dynamic variables, or fewer than three
@@ -132,7 +149,7 @@ static hipError_t launch_dbn_step2_inner(const EmgpuPlan &P, const EmgpuRun &A, 
             *name = "k_dbn_step2<16,4,w4,reg>[frozen]";   // littoral_cor_v1: every variable's only dynamic parent is its own current bin
             EMGPU_S2_LAUNCH(16, 4, 4, true, 0x8421u, 0u, true);
         } else {
-            *name = "k_dbn_step2<16,4>[frozen]";
+            *name = kStep2FrozenName;
             EMGPU_S2_LAUNCH(16, 4, 0, false, kCurAll4, 0u, true);
         }
         return hipGetLastError();

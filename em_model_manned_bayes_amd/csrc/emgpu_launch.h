@@ -30,6 +30,12 @@ bool step2_eligible(const EmgpuPlan &P, const EmgpuRun &A);
 // bit 4k+q of cur_mask: the time-t node of dynamic variable q is a parent of (t+1) node k; of new_mask: its (t+1) node is (q < k)
 void step_parent_masks(const EmgpuPlan &P, uint32_t *cur_mask, uint32_t *new_mask);
 hipError_t launch_dbn_step2(const EmgpuPlan &P, const EmgpuRun &A, hipStream_t s, const char **name);
+// The same with a start grid / per-sample log-weights (emgpu_kernels_step2_ps.hip): the +start twin of the general instance of the call's
+// shape.  step2_start_form: 0 = this step2-eligible call has no +start instance (the list and the dense trace together, or
+// EMGPU_DEBUG_EVENT_ROWS set: k_dbn_generic), 1 = dense, 2 = the list alone with its rows built by the wave.  name: room for 96 characters,
+// receives the name the general instance reports for this form; the caller appends "+start".
+int step2_start_form(const EmgpuPlan &P, const EmgpuRun &A);
+hipError_t launch_dbn_step2_start(const EmgpuPlan &P, const EmgpuRun &A, const EmgpuPresets *presets, hipStream_t s, char *name);
 hipError_t launch_terminal_propagate(const EmgpuPlan &P, const EmgpuTermRun &A, hipStream_t s, const char **name);
 int terminal_debug_counters(unsigned long long *out, int n);   // -DEMGPU_TERM_COUNTERS builds: the loop's path counters (0: not such a build)
 // createEncounter.m:88-89 through the stand-in of EMGPU_FLAG_LOCAL_SMOOTH: v_ft_s (5 s) and z_ft (15 s) of n2 joined tracks, in place

@@ -426,7 +426,9 @@ class UncorEncounterModel(EncounterModel):
         start_grid: [n_samples, n_initial] preset bins by variable id, one row per sample (0 / None = unset: the model's own `start`, else
         the variable is drawn) -- the strata a loop over `start` values (RUN_uncor.m:35-47) draws in as many calls, in ONE; sample i is
         what `self.start = row i; self.sample(1, ..., first_index=i)` gives.  makeStartGrid builds one.  return_log_weight: a fifth output,
-        log P(presets of row i) per sample (importance weights; start_log_weight for every sample without a grid).
+        log P(presets of row i) per sample (importance weights; start_log_weight for every sample without a grid).  A grid keeps the call on
+        the kernel it would run on without one (ctx.last_kernel() ends in "+start"): k_uncor_fast's +start instances for a fast-branch model,
+        k_dbn_step2's for the dependent-branch models (gliders, uncor_1200code_v1, ...) and under EMGPU_TRANSITION_PER_STEP.
 
         lazy=True: the same four outputs, bit for bit, with out_samples and the controls built on the GPU (emgpu_sample_uncor_host) and
         out_events / out_samples / out_EME handed out as LazyEvents / LazySamples / LazyControls: sequences that build sample i's object when
@@ -575,7 +577,9 @@ class UncorEncounterModel(EncounterModel):
         (time_s instead of the row times), sampled at 10 Hz (record_stride=1) like results.time.
 
         start_grid: as for sample -- every attempt of track i is drawn under row i, so track i is what `self.start = row i;
-        self.track(1, ..., first_index=i)` gives.  return_log_weight: log P(presets of row i) per track, as the last output.
+        self.track(1, ..., first_index=i)` gives.  return_log_weight: log P(presets of row i) per track, as the last output.  Round 0 runs on
+        the +start instance of the model's sampler (k_uncor_fast_idx or k_dbn_step2); the later rounds of a model outside the fast branch
+        redraw their index lists on k_dbn_generic.
 
         Runs on the GPU end to end: per round the still-rejected trajectories are sampled (attempt j with the key
         initialSeed + j, :424-428), integrated and tested against getDynamicLimits (:459-470) on the device.

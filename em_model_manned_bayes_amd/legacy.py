@@ -57,7 +57,8 @@ def em_sample(parameters_filename, initial_output_filename=None, transition_outp
     (None, None) and keeps no array of the run; id_first is the id of the first trajectory (a run continued from an earlier file).
 
     start_grid: [num_initial_samples, n_initial] preset bins by variable id, one row per trajectory (0 / None = unset: `start`, else the
-    variable is drawn): the strata of a loop over `start` values in one pair of files, under either writer."""
+    variable is drawn): the strata of a loop over `start` values in one pair of files, under either writer.  The sampler is the +start instance
+    of the kernel the model runs on without a grid (k_uncor_fast_idx, or k_dbn_step2 for cor_v1 and the other models outside the fast branch)."""
     if text not in ("host", "device"):
         raise ValueError("em_sample: text must be 'host' or 'device', not %r" % (text,))
     if text == "host" and (not return_arrays or int(id_first) != 1 or text_batch is not None):

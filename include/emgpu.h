@@ -206,7 +206,10 @@ typedef struct {
                                 or a bin outside 1..r, is reported as EMGPU_ERR_PRESET (by emgpu_ctx_sync for *_device calls).
                                 A fast-branch model (what runs on k_uncor_fast without a grid) is served at that kernel's pace by its
                                 +start instances when the call asks for the dense outputs alone (with or without `indices`) or for
-                                the event list alone; the list and the dense trace together, and every other model, run on the
+                                the event list alone.  Every other model the per-timestep kernel takes (cor_v1, littoral_cor_v1, the
+                                dependent-branch family, EMGPU_TRANSITION_PER_STEP) is served the same two forms, without `indices`,
+                                by the +start instances of k_dbn_step2 (the general instance of the model's shape).  The list and the
+                                dense trace together, `indices` outside the fast branch, and what neither kernel takes run on the
                                 general kernel.  The same holds for calls that ask for log-weights.                                */
 } emgpu_sample_params;
 
@@ -640,7 +643,8 @@ int emgpu_track_uncor_device(emgpu_ctx *ctx, const emgpu_model *m, const emgpu_u
 /* The same with a start GRID: start [p->n][n_initial] as emgpu_sample_params.start (a HOST pointer for _host, a DEVICE pointer for _device;
  * NULL: exactly the functions above).  Every attempt of trajectory i is drawn under row i: round 0 reads row i for lane i, a later round
  * reads the rows of the trajectories it redraws.  Keys and indices are unchanged: attempt j of trajectory i has key seed + j and global index
- * first_index + i.  A fast-branch model's sampler runs on the +start instance of k_uncor_fast_idx in every round.  EMGPU_ERR_PRESET as for
+ * first_index + i.  A fast-branch model's sampler runs on the +start instance of k_uncor_fast_idx in every round; any other model's round 0
+ * on the +start instance of k_dbn_step2 and its later rounds (index lists) on the general kernel.  EMGPU_ERR_PRESET as for
  * emgpu_sample_dbn_*; the weights: emgpu_start_grid_log_weight. */
 int emgpu_track_uncor_grid_host(emgpu_ctx *ctx, const emgpu_model *m, const emgpu_utrack_params *p, const int32_t *start,
                                 double *tracks, double *limits, int32_t *attempts);

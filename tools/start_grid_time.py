@@ -1,6 +1,11 @@
-"""tools/start_grid_time.py [--parent DIR] [--n N] [--T T] -- a start grid in one launch, device-resident outputs, on one GPU: 1 M trajectories x 240 s
-of uncor_1200code_v2p1 and uncor_1200only_fwse_v1p2 under a 16-row G x A grid (row i % 16 for trajectory i), the dense outputs alone and the event
-list alone, 3 warm-up + 10 timed launches each, beside the same two calls without a grid (the ceiling: k_uncor_fast_idx / k_uncor_fast_evu).
+"""tools/start_grid_time.py [--parent DIR] [--models A,B,..] [--n N] [--T T] -- a start grid in one launch, device-resident outputs, on one GPU:
+1 M trajectories x 240 s of uncor_1200code_v2p1 and uncor_1200only_fwse_v1p2 under a 16-row G x A grid (row i % 16 for trajectory i), the dense
+outputs alone and the event list alone, 3 warm-up + 10 timed launches each, beside the same two calls without a grid (the ceiling:
+k_uncor_fast_idx / k_uncor_fast_evu).
+
+--models: the models to time instead (comma-separated).  The two variables the 16-row grid spans come from GRID_VARS (bins 1-4 of each; any other
+model: its variables 1 and 2, which must then be a closed set).  For the models k_uncor_fast does not take -- cor_v1, uncor_1200code_v1, glider_v1 -- the grid
+calls run on the +start instances of k_dbn_step2 and the call without a grid on the model's family instance ([cor], [chain,w884], ...).
 
 --parent DIR: a checkout of another commit with its library built (tools/ab_checkout.sh <commit> parent -> tools/ab/parent) is timed first, in a
 process of its own with its own Python package, on the same GPU in the same run: before the +start instances its calls ran on k_dbn_generic, the
@@ -16,9 +21,12 @@ import tempfile
 
 HERE = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 MODELS = ["uncor_1200code_v2p1", "uncor_1200only_fwse_v1p2"]
+# the two variables of the 4 x 4 grid, by label (bins 1-4 of each; a preset variable's parents must be preset: both pairs are closed)
+GRID_VARS = {"uncor_1200code_v2p1": ("G", "A"), "uncor_1200only_fwse_v1p2": ("G", "A"), "cor_v1": ("A", "L"), "uncor_1200code_v1": ("A", "L"),
+             "glider_v1": ("L", "v")}
 
 
-def child(pkg_root, n, T, warmup, launches):
+def child(pkg_root, n, T, warmup, launches, models):
     sys.path.insert(0, pkg_root)
     import numpy as np
     import torch
@@ -28,13 +36,13 @@ def child(pkg_root, n, T, warmup, launches):
     ctx = native.Context(0, stream=stream.cuda_stream)
     out = {"lib": L.lib().emgpu_version().decode(), "device": torch.cuda.get_device_name(0), "n": n, "T": T, "calls": {}}
     rows = np.array([[g, a] for g in (1, 2, 3, 4) for a in (1, 2, 3, 4)], dtype=np.int32)
-    for name in MODELS:
+    for name in models:
         nm = native.NativeModel.load_txt(em_io.materialize_model(name, tempfile.mkdtemp()))
         labs = nm.get_labels(L.F_LABELS_INITIAL)
-        idx = {k: labs.index('"%s"' % v) + 1 for k, v in (("idx_L", "L"), ("idx_v", "v"), ("idx_dh", "\\dot h"))}
+        idx = {k: (labs.index('"%s"' % v) + 1 if '"%s"' % v in labs else 0) for k, v in (("idx_L", "L"), ("idx_v", "v"), ("idx_dh", "\\dot h"))}
         ni, nd, G4, cap = nm.n_initial, nm.n_dyn, (T + 3) // 4, 512
         grid = np.zeros((n, ni), dtype=np.int32)
-        grid[:, [labs.index('"G"'), labs.index('"A"')]] = rows[np.arange(n) % 16]
+        grid[:, [labs.index('"%s"' % v) for v in GRID_VARS[name]] if name in GRID_VARS else [0, 1]] = rows[np.arange(n) % 16]
         d_grid = torch.from_numpy(grid).to(dev)
         ib = torch.empty((ni, n), dtype=torch.uint8, device=dev)
         iv = torch.empty((ni, n), dtype=torch.float32, device=dev)
@@ -64,7 +72,7 @@ def child(pkg_root, n, T, warmup, launches):
 
 def run_child(pkg_root, args):
     cmd = [sys.executable, os.path.abspath(__file__), "--child", pkg_root, "--n", str(args.n), "--T", str(args.T), "--warmup", str(args.warmup),
-           "--launches", str(args.launches)]
+           "--launches", str(args.launches), "--models", args.models]
     txt = subprocess.run(cmd, check=True, capture_output=True, text=True, timeout=600).stdout
     return json.loads([ln for ln in txt.splitlines() if ln.startswith("RESULT ")][-1][7:])
 
@@ -77,9 +85,10 @@ def main():
     ap.add_argument("--T", type=int, default=240)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--launches", type=int, default=10)
+    ap.add_argument("--models", default=",".join(MODELS))
     args = ap.parse_args()
     if args.child:
-        return child(args.child, args.n, args.T, args.warmup, args.launches)
+        return child(args.child, args.n, args.T, args.warmup, args.launches, args.models.split(","))
     base = run_child(os.path.abspath(args.parent), args) if args.parent else None
     tree = run_child(HERE, args)
     print(json.dumps({"parent": base, "tree": tree}))
