@@ -165,7 +165,7 @@ SYMBOLS = [
     "emgpu_model_set_zero_bins", "emgpu_shard_range", "emgpu_device_count", "emgpu_mixed_blocks",
     "emgpu_sample_dbn_blocks_device", "emgpu_sample_dbn_multi_host", "emgpu_sample_dbn_multi_device",
     "emgpu_track_uncor_host", "emgpu_track_uncor_device", "emgpu_uncor_dynamic_limits", "emgpu_model_start_log_weight",
-    "emgpu_track_terminal_host", "emgpu_debug_parent_masks", "emgpu_last_launch_count", "emgpu_debug_pk_column", "emgpu_debug_terminal_counters", "emgpu_debug_uncor_dynamics_host", "emgpu_model_save_bin", "emgpu_model_load_bin", "emgpu_philox_rounds", "emgpu_ctx_trim",
+    "emgpu_track_terminal_host", "emgpu_debug_parent_masks", "emgpu_debug_kernel_choice", "emgpu_last_launch_count", "emgpu_debug_pk_column", "emgpu_debug_terminal_counters", "emgpu_debug_uncor_dynamics_host", "emgpu_model_save_bin", "emgpu_model_load_bin", "emgpu_philox_rounds", "emgpu_ctx_trim",
     "emgpu_slot_map_revision", "emgpu_trace_alloc", "emgpu_trace_out", "emgpu_trace_report", "emgpu_trace_free", "emgpu_host_alloc", "emgpu_host_free", "emgpu_host_stats",
     "emgpu_device_alloc", "emgpu_device_free", "emgpu_sample_uncor_host",
     "emgpu_sample_text_host", "emgpu_text_bound", "emgpu_format_g_host", "emgpu_debug_format_paths",
@@ -316,6 +316,7 @@ def lib():
     L.emgpu_debug_pk_column.argtypes = [C.c_void_p, C.c_int32, C.c_int64, C.c_void_p]
     L.emgpu_debug_bernoulli_threshold.restype = C.c_uint32
     L.emgpu_debug_parent_masks.argtypes = [C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
+    L.emgpu_debug_kernel_choice.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_char_p, C.c_int32]
     for f in (L.emgpu_propagate_terminal_device, L.emgpu_propagate_terminal_host):
         f.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(TermParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     L.emgpu_philox_rounds.restype = C.c_int32

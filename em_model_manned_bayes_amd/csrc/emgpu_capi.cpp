@@ -553,30 +553,17 @@ static const EmgpuPresets *upload_presets(emgpu_ctx *ctx, Uploaded &u, const Mod
 }
 
 static void launch_dbn(emgpu_ctx *ctx, const Uploaded &u, const EmgpuRun &A, hipStream_t stream = nullptr, const EmgpuPresets *presets = nullptr) {
-    const char *name = "";
-    hipError_t e;
     if (!stream) stream = ctx->stream;
-    char ps_name[96];
-    std::string suffix;
-    // a start grid / per-sample log-weights: the +start instances of the fast kernel serve the dense outputs alone and the list alone of a
-    // fast-branch model, those of the per-timestep kernel the same two forms of every other model it takes; the list and the dense trace
-    // together, an index list off the fast kernel, and what neither kernel takes run on the general kernel
-    if (presets && emgpu::fast_uncor_eligible(u.cp.plan, A) && emgpu::uncor_fast_start_form(u.cp.plan, A) != 0) {
-        e = emgpu::launch_uncor_fast_start(u.cp.plan, A, presets, stream, ps_name);
-        name = ps_name; suffix = "+start";
-    }
-    else if (presets && emgpu::step2_eligible(u.cp.plan, A) && emgpu::step2_start_form(u.cp.plan, A) != 0) {
-        e = emgpu::launch_dbn_step2_start(u.cp.plan, A, presets, stream, ps_name);
-        name = ps_name; suffix = "+start";
-    }
-    else if (presets) e = emgpu::launch_dbn_generic(u.cp.plan, A, stream, &name, presets);
-    else if (emgpu::fast_uncor_eligible(u.cp.plan, A)) e = emgpu::launch_uncor_fast(u.cp.plan, A, stream, &name);
-    else if (emgpu::step2_eligible(u.cp.plan, A)) e = emgpu::launch_dbn_step2(u.cp.plan, A, stream, &name);
-    else if (emgpu::step_eligible(u.cp.plan, A)) e = emgpu::launch_dbn_step(u.cp.plan, A, stream, &name);
-    else e = emgpu::launch_dbn_generic(u.cp.plan, A, stream, &name);
-    ctx->last_kernel = name + suffix;   // (the ctx owns the string)
+    const EmgpuPlan &P = u.cp.plan;
+    const emgpu::DbnChoice c = emgpu::choose_dbn(P, A, presets != nullptr);
+    ctx->last_kernel = c.name;
     ctx->last_launches++;
-    launch_ok(e);
+    switch (c.family) {
+    case emgpu::DbnFamily::Fast: launch_ok(emgpu::launch_uncor_fast(P, A, c, presets, stream)); break;
+    case emgpu::DbnFamily::Step2: launch_ok(emgpu::launch_dbn_step2(P, A, c, presets, stream)); break;
+    case emgpu::DbnFamily::Step: launch_ok(emgpu::launch_dbn_step(P, A, c, stream)); break;
+    case emgpu::DbnFamily::Generic: launch_ok(emgpu::launch_dbn_generic(P, A, c, presets, stream)); break;
+    }
 }
 
 // Run fn(d) for d = 0..n-1 on one host thread per device and fold the results: the first
@@ -685,7 +672,8 @@ int emgpu_sample_dbn_blocks_device(emgpu_ctx *ctx, const emgpu_model *const *mod
         bind_outputs(L.A, h->m, &q, &o, col);
         // (event lists: k_uncor_fast_ev, one launch per block -- the shared launch writes the dense trace only)
         // (... and stores both dense outputs unconditionally)
-        L.shape = (emgpu::fast_uncor_eligible(u.cp.plan, L.A) && L.A.ev_count == nullptr && L.A.dyn_bin != nullptr && L.A.dyn_val != nullptr) ? emgpu::uncor_fast_shape(u.cp.plan) : -1;
+        const emgpu::DbnChoice c = emgpu::choose_dbn(u.cp.plan, L.A, false);
+        L.shape = (c.family == emgpu::DbnFamily::Fast && c.form == emgpu::FastForm::Dense) ? c.shape : -1;
         live.push_back(L);
     }
     ctx->last_launches = 0;
@@ -755,9 +743,8 @@ int emgpu_sample_dbn_blocks_device(emgpu_ctx *ctx, const emgpu_model *const *mod
         q0.n = L0.A.n;   // bind_outputs checks col + n against ld: column 0 with the first member's n always fits
         bind_outputs(A, models[0]->m, &q0, &o, 0);
         A.ld = L0.A.ld;
-        const char *name = "";
-        hipError_t e = emgpu::launch_uncor_fast_mixed(A, (int)G.members.size(), planf, first, nn, col, G.shape, st, &name);
-        ctx->last_kernel = name;
+        hipError_t e = emgpu::launch_uncor_fast_mixed(A, (int)G.members.size(), planf, first, nn, col, G.shape, st);
+        ctx->last_kernel = emgpu::uncor_fast_mixed_name(G.shape);
         ctx->last_launches++;
         launch_ok(e);
     }
@@ -966,6 +953,23 @@ int emgpu_debug_parent_masks(const emgpu_model *m, uint32_t *cur_mask, uint32_t 
     if (!m || !cur_mask || !new_mask) return fail(EMGPU_ERR_ARG, "null argument");
     const std::shared_ptr<const emgpu::CompiledPlan> cp_keep = emgpu::plan_of(m->m); const emgpu::CompiledPlan &cp = *cp_keep;
     emgpu::step_parent_masks(cp.plan, cur_mask, new_mask);
+    return EMGPU_OK;
+    EMGPU_CATCH
+}
+
+int emgpu_debug_kernel_choice(const emgpu_model *m, const emgpu_sample_params *p, const emgpu_sample_out *out, char *name, int32_t cap) {
+    EMGPU_TRY
+    if (!m || !p || !out || !name) return fail(EMGPU_ERR_ARG, "null argument");
+    const std::shared_ptr<const emgpu::CompiledPlan> cp_keep = emgpu::plan_of(m->m);
+    EmgpuRun A;   // what choose_dbn reads of fill_run's and bind_outputs' run: which outputs are asked for, never where they are
+    memset(&A, 0, sizeof A);
+    A.n = p->n; A.per_step = p->transition_mode == EMGPU_TRANSITION_PER_STEP; A.flags = p->flags; A.event_cap = p->event_cap;
+    A.indices = p->indices;
+    A.dyn_bin = out->dyn_bin; A.dyn_val = out->dyn_val; A.ev_count = out->ev_count;
+    A.events = reinterpret_cast<uint64_t *>(out->events);
+    const emgpu::DbnChoice c = emgpu::choose_dbn(cp_keep->plan, A, p->start != nullptr || out->log_weight != nullptr);
+    if (cap < 1 || strlen(c.name) >= (size_t)cap) return fail(EMGPU_ERR_ARG, "name does not fit cap");
+    strcpy(name, c.name);
     return EMGPU_OK;
     EMGPU_CATCH
 }

@@ -112,14 +112,6 @@ __device__ __forceinline__ EvState ev_state_of(const EmgpuPlan &P, const EmgpuRu
         if (b < P.nact && P.a_dyn[b] < 0) S.sbins |= (uint64_t)(uint32_t)(pick<NI>(bin, P.a_pos[b]) + 1) << (8 * b);
     return S;
 }
-// host side: can a plan's event list be written by the block kernels?  At most 8 - nd variables with a rate, every rate below
-// the packed compare's limit
-inline bool ev_plan_ok(const EmgpuPlan &P, const EmgpuRun &A) {
-    if (P.nact > 8 - P.nd || P.nact > 5 || A.event_cap < 1) return false;
-    for (int a = 0; a < P.nact; a++)
-        if (P.a_R[a] >= 0xFFFF0000u) return false;
-    return true;
-}
 
 // dediscretize.m:33-39 for a resample row whose draw the cooperative pass did not make (a static variable, or a row hidden by a
 // transition of the same second): slot (DEDISC_RES, variable, second c), made by the lane itself
@@ -268,12 +260,6 @@ __device__ __forceinline__ EvStateW ev_state_w_of(const EmgpuPlan &P, const Emgp
 __device__ __forceinline__ uint64_t ev_interleave_bytes(uint32_t a, uint32_t c) {
     const uint32_t hi = __builtin_amdgcn_perm(a, c, 0x07030602u), lo = __builtin_amdgcn_perm(a, c, 0x05010400u);
     return ((uint64_t)hi << 32) | lo;
-}
-inline bool ev_plan_wide_ok(const EmgpuPlan &P, const EmgpuRun &A) {
-    if (P.nact > 16 - P.nd || A.event_cap < 1) return false;
-    for (int a = 0; a < P.nact; a++)
-        if (P.a_R[a] >= 0xFFFF0000u) return false;
-    return true;
 }
 // the rows of one block as a 128-bit mask in list order: bit 63 - (16 j + b) of `hi` = (second j < 4, stream b), `lo` the same for seconds 4-7
 template <int ND>

@@ -286,14 +286,15 @@ static hipError_t launch_generic_t(const EmgpuPlan &P, const EmgpuRun &A, const 
     return hipGetLastError();
 }
 
-hipError_t launch_dbn_generic(const EmgpuPlan &P, const EmgpuRun &A, hipStream_t s, const char **name, const EmgpuPresets *Q) {
+hipError_t launch_dbn_generic(const EmgpuPlan &P, const EmgpuRun &A, const DbnChoice &c, const EmgpuPresets *Q, hipStream_t s) {
     if (A.n <= 0) return hipSuccess;
-    if (P.ni <= 7 && P.nd <= 3 && P.nact <= 4) { *name = "k_dbn_generic<7,3,4>"; return launch_generic_t<7, 3, 4>(P, A, Q, s); }
-    if (P.ni <= 7 && P.nd <= 3 && P.nact <= 7) { *name = "k_dbn_generic<7,3,7>"; return launch_generic_t<7, 3, 7>(P, A, Q, s); }
-    if (P.ni <= 9 && P.nd <= 3 && P.nact <= 9) { *name = "k_dbn_generic<9,3,9>"; return launch_generic_t<9, 3, 9>(P, A, Q, s); }
-    if (P.nact <= 4) { *name = "k_dbn_generic<16,4,4>"; return launch_generic_t<16, 4, 4>(P, A, Q, s); }
-    *name = "k_dbn_generic<16,4,16>";
-    return launch_generic_t<16, 4, 16>(P, A, Q, s);
+    switch (c.shape) {
+    case 0: return launch_generic_t<7, 3, 4>(P, A, Q, s);
+    case 1: return launch_generic_t<7, 3, 7>(P, A, Q, s);
+    case 2: return launch_generic_t<9, 3, 9>(P, A, Q, s);
+    case 3: return launch_generic_t<16, 4, 4>(P, A, Q, s);
+    default: return launch_generic_t<16, 4, 16>(P, A, Q, s);
+    }
 }
 
 hipError_t launch_bn(const EmgpuPlan &P, const EmgpuBnRun &A, hipStream_t s, const char **name) {

@@ -1,5 +1,5 @@
 // emgpu_kernels_fast.h -- the benchmarked kernel (templates; launched from emgpu_kernels_fast.hip, the event-list forms from
-// emgpu_kernels_fast_ev.hip): uncorrelated DBN, REFERENCE_AUTO semantics on a
+// emgpu_kernels_fast_ev.hip, the +start forms from emgpu_kernels_fast_ps.hip): uncorrelated DBN, REFERENCE_AUTO semantics on a
 // "fast-branch" model (dbn_sample.m:95-166: parent configuration frozen at the initial state),
 // compact dense trace output.  One lane = one trajectory, 3 dynamic variables, 8 seconds per
 // loop iteration.
@@ -781,20 +781,24 @@ __global__ void __launch_bounds__(256, EMGPU_FAST_WAVES) k_uncor_fast_mixed(cons
     uncor_fast_body<NI, M0, M1, M2, true>(E.P, A, E.F, (int64_t)(blockIdx.x - H.wg_begin[b]) * 256 - ((H.A.col0 + B.col) & 255));
 }
 
-// Kernel instances by the number of DISTINCT thresholds per column of the three dynamic variables
-// (EmgpuPlan::d_meff).  A model runs on the first instance that covers it.
-struct FastShape { int ni, m0, m1, m2; };
-static const FastShape kFastShapes[] = {
-    {7, 2, 2, 2}, {7, 2, 4, 2}, {7, 2, 4, 4}, {7, 4, 2, 4}, {7, 4, 6, 4}, {7, 4, 6, 6}, {7, 6, 6, 6}, {9, 6, 6, 6},
-};
-
-static inline int fast_shape_of(const EmgpuPlan &P) {
-    for (size_t q = 0; q < sizeof kFastShapes / sizeof kFastShapes[0]; q++) {
-        const FastShape &f = kFastShapes[q];
-        if (P.ni <= f.ni && P.d_meff[0] <= f.m0 && P.d_meff[1] <= f.m1 && P.d_meff[2] <= f.m2) return (int)q;
+// ---- launching: KERNEL<NI, M0, M1, M2> of shape index `shape` (EMGPU_FAST_SHAPES, emgpu_dispatch.h)
+template <int NI_, int M0_, int M1_, int M2_>
+struct FastTag { static constexpr int NI = NI_, M0 = M0_, M1 = M1_, M2 = M2_; };
+template <class F>
+static inline hipError_t with_fast_shape(int shape, F &&f) {
+    switch (shape) {
+#define EMGPU_X(Q, NI, M0, M1, M2) case Q: return f(FastTag<NI, M0, M1, M2>{});
+    EMGPU_FAST_SHAPES(EMGPU_X)
+#undef EMGPU_X
+    default: return hipErrorNotSupported;
     }
-    return -1;
 }
+#define EMGPU_FAST_LAUNCH(KERNEL, shape, blocks, lds, stream, ...)                                                                      \
+    with_fast_shape(shape, [&](auto t_) {                                                                                               \
+        using S_ = decltype(t_);                                                                                                        \
+        hipLaunchKernelGGL((KERNEL<S_::NI, S_::M0, S_::M1, S_::M2>), dim3(blocks), dim3(256), lds, stream, __VA_ARGS__);                \
+        return hipGetLastError();                                                                                                       \
+    })
 
 static inline FastArgs fast_args_of(const EmgpuPlan &P) {
     FastArgs F{};

@@ -9,67 +9,15 @@
 
 namespace emgpu {
 
-template <int NI, int M0, int M1, int M2>
-static hipError_t launch_ev_t(const EmgpuPlan &P, const EmgpuRun &A, const FastArgs &F, hipStream_t s) {
-    const int64_t blocks = (A.n + (A.col0 & 255) + 255) / 256;
-    hipLaunchKernelGGL((k_uncor_fast_ev<NI, M0, M1, M2>), dim3((unsigned)blocks), dim3(256), 0, s, P, A, F);
-    return hipGetLastError();
-}
-template <int NI, int M0, int M1, int M2>
-static hipError_t launch_evu_t(const EmgpuPlan &P, const EmgpuRun &A, const FastArgs &F, hipStream_t s) {
-    const int64_t blocks = (A.n + (A.col0 & 255) + 255) / 256;
-    hipLaunchKernelGGL((k_uncor_fast_evu<NI, M0, M1, M2>), dim3((unsigned)blocks), dim3(256), 0, s, P, A, F);
-    return hipGetLastError();
-}
-
-hipError_t launch_uncor_fast_events(const EmgpuPlan &P, const EmgpuRun &A, const FastArgs &F, hipStream_t s, const char **name) {
-    // EMGPU_DEBUG_EVENT_ROWS (tests, A/B runs): "lane" = the list alone also takes the per-lane row loops (k_uncor_fast_ev / _evw),
-    // "wide" = every list takes k_uncor_fast_evw (its instance holds any fast-branch shape), "long" = every list alone takes k_uncor_fast_evu_long
-    static const char *rows_env = getenv("EMGPU_DEBUG_EVENT_ROWS");
-    const bool force_long = rows_env != nullptr && rows_env[0] == 'l' && rows_env[1] == 'o';
-    const bool force_lane = rows_env != nullptr && rows_env[0] == 'l' && !force_long, force_wide = rows_env != nullptr && rows_env[0] == 'w' && rows_env[1] == 'i';
-    const bool list_alone = A.dyn_bin == nullptr && A.dyn_val == nullptr;
-    const bool plain = (A.flags & (EMGPU_FLAG_NO_RESAMPLE | EMGPU_FLAG_NO_DEDISC)) != 0;   // (only eligible as a list alone: fast_uncor_eligible)
-    if (list_alone && ((!force_lane && !force_wide) || plain) && ev_plan_wide_ok(P, A)) {
-        // rows expected per wave and 8-second block from the resample rates alone (transition rows come on top): several hundred of them
-        // (haa_v1: 1.27 per second and lane -> 650) would take the short queue's 254 requests per round three or four rounds per block
-        double rate = 0.0;
-        if (!(A.flags & EMGPU_FLAG_NO_RESAMPLE))
-            for (int a = 0; a < P.nact; a++) rate += (double)P.a_R[a] * (1.0 / 4294967296.0);
-        if (rate * 512.0 > 300.0 || (force_long && P.ni <= 9)) {
-            const int64_t blocks = (A.n + (A.col0 & 255) + 255) / 256;
-            *name = "k_uncor_fast_evu_long<9,6,6,6>";
-            hipLaunchKernelGGL((k_uncor_fast_evu_long<9, 6, 6, 6>), dim3((unsigned)blocks), dim3(256), 0, s, P, A, F);
-            return hipGetLastError();
-        }
-        switch (fast_shape_of(P)) {
-        case 0: *name = "k_uncor_fast_evu<7,2,2,2>"; return launch_evu_t<7, 2, 2, 2>(P, A, F, s);
-        case 1: *name = "k_uncor_fast_evu<7,2,4,2>"; return launch_evu_t<7, 2, 4, 2>(P, A, F, s);
-        case 2: *name = "k_uncor_fast_evu<7,2,4,4>"; return launch_evu_t<7, 2, 4, 4>(P, A, F, s);
-        case 3: *name = "k_uncor_fast_evu<7,4,2,4>"; return launch_evu_t<7, 4, 2, 4>(P, A, F, s);
-        case 4: *name = "k_uncor_fast_evu<7,4,6,4>"; return launch_evu_t<7, 4, 6, 4>(P, A, F, s);
-        case 5: *name = "k_uncor_fast_evu<7,4,6,6>"; return launch_evu_t<7, 4, 6, 6>(P, A, F, s);
-        case 6: *name = "k_uncor_fast_evu<7,6,6,6>"; return launch_evu_t<7, 6, 6, 6>(P, A, F, s);
-        case 7: *name = "k_uncor_fast_evu<9,6,6,6>"; return launch_evu_t<9, 6, 6, 6>(P, A, F, s);
-        default: *name = "none"; return hipErrorNotSupported;
-        }
-    }
-    if (!ev_plan_ok(P, A) || (force_wide && ev_plan_wide_ok(P, A))) {   // more rated variables than eight streams hold: the wide list, on the widest instance
-        const int64_t blocks = (A.n + (A.col0 & 255) + 255) / 256;
-        *name = "k_uncor_fast_evw<9,6,6,6>";
-        hipLaunchKernelGGL((k_uncor_fast_evw<9, 6, 6, 6>), dim3((unsigned)blocks), dim3(256), 0, s, P, A, F);
-        return hipGetLastError();
-    }
-    switch (fast_shape_of(P)) {
-    case 0: *name = "k_uncor_fast_ev<7,2,2,2>"; return launch_ev_t<7, 2, 2, 2>(P, A, F, s);
-    case 1: *name = "k_uncor_fast_ev<7,2,4,2>"; return launch_ev_t<7, 2, 4, 2>(P, A, F, s);
-    case 2: *name = "k_uncor_fast_ev<7,2,4,4>"; return launch_ev_t<7, 2, 4, 4>(P, A, F, s);
-    case 3: *name = "k_uncor_fast_ev<7,4,2,4>"; return launch_ev_t<7, 4, 2, 4>(P, A, F, s);
-    case 4: *name = "k_uncor_fast_ev<7,4,6,4>"; return launch_ev_t<7, 4, 6, 4>(P, A, F, s);
-    case 5: *name = "k_uncor_fast_ev<7,4,6,6>"; return launch_ev_t<7, 4, 6, 6>(P, A, F, s);
-    case 6: *name = "k_uncor_fast_ev<7,6,6,6>"; return launch_ev_t<7, 6, 6, 6>(P, A, F, s);
-    case 7: *name = "k_uncor_fast_ev<9,6,6,6>"; return launch_ev_t<9, 6, 6, 6>(P, A, F, s);
-    default: *name = "none"; return hipErrorNotSupported;
+// c.form: Evu / EvuLong / Evw / Ev (choose_dbn); Evw and EvuLong have the widest instance alone
+hipError_t launch_uncor_fast_events(const EmgpuPlan &P, const EmgpuRun &A, const FastArgs &F, const DbnChoice &c, hipStream_t s) {
+    const unsigned blocks = fast_blocks(A.n, A.col0);
+    switch (c.form) {
+    case FastForm::EvuLong: hipLaunchKernelGGL((k_uncor_fast_evu_long<9, 6, 6, 6>), dim3(blocks), dim3(256), 0, s, P, A, F); return hipGetLastError();
+    case FastForm::Evu: return EMGPU_FAST_LAUNCH(k_uncor_fast_evu, c.shape, blocks, 0, s, P, A, F);
+    case FastForm::Evw: hipLaunchKernelGGL((k_uncor_fast_evw<9, 6, 6, 6>), dim3(blocks), dim3(256), 0, s, P, A, F); return hipGetLastError();
+    case FastForm::Ev: return EMGPU_FAST_LAUNCH(k_uncor_fast_ev, c.shape, blocks, 0, s, P, A, F);
+    default: return hipErrorNotSupported;
     }
 }
 

@@ -162,44 +162,18 @@ __global__ void __launch_bounds__(256, 2) k_dbn_step(const EmgpuPlan P, const Em
     }
 }
 
-bool step_eligible(const EmgpuPlan &P, const EmgpuRun &A) {
-    if (A.indices != nullptr) return false; // an index list goes through the generic kernel
-    if (P.nd < 1 || P.nd > 4) return false;
-    if (!(P.depend || A.per_step)) return false;
-    if (A.ev_count != nullptr || A.events != nullptr) return false;
-    if (A.flags & (EMGPU_FLAG_NO_RESAMPLE | EMGPU_FLAG_NO_DEDISC)) return false;
-    for (int k = 0; k < P.nd; k++) {
-        if (P.d_nb[k] == 0 || P.d_nb[k] > 16 || P.d_r[k] > 9) return false;
-        for (int a = 0; a < P.nact; a++)
-            if (P.a_dyn[a] == k && P.a_R[a] == 0xFFFFFFFFu) return false;
-    }
-    return true;
-}
-
-static bool step_compact(const EmgpuPlan &P) {
-    static const bool off = getenv("EMGPU_DEBUG_STEP_NO_COMPACT") != nullptr;
-    if (off) return false;
-    for (int k = 0; k < P.nd; k++)
-        if (P.d_meff[k] == 0) return false;
-    return true;
-}
-static size_t step_table_bytes(const EmgpuPlan &P) {
-    return (size_t)(step_compact(P) ? P.cthr_total : P.thr_total - P.d_off[0]) * sizeof(uint32_t);
-}
-
+// c.lds: the dynamic tables staged in LDS (c.lds_bytes of them); c.compact: read in their compact form (choose_dbn)
 template <int NI, int ND, int RM1>
-static hipError_t launch_t(const EmgpuPlan &P, const EmgpuRun &A, const StepArgs &F, hipStream_t s, bool lds) {
-    const int64_t blocks = (A.n + 255) / 256;
-    const bool ct = step_compact(P);
-    const size_t bytes = lds ? step_table_bytes(P) : 0;
-    if (lds && ct) hipLaunchKernelGGL((k_dbn_step<NI, ND, RM1, true, true>), dim3((unsigned)blocks), dim3(256), bytes, s, P, A, F);
-    else if (lds) hipLaunchKernelGGL((k_dbn_step<NI, ND, RM1, true, false>), dim3((unsigned)blocks), dim3(256), bytes, s, P, A, F);
-    else if (ct) hipLaunchKernelGGL((k_dbn_step<NI, ND, RM1, false, true>), dim3((unsigned)blocks), dim3(256), 0, s, P, A, F);
-    else hipLaunchKernelGGL((k_dbn_step<NI, ND, RM1, false, false>), dim3((unsigned)blocks), dim3(256), 0, s, P, A, F);
+static hipError_t launch_t(const EmgpuPlan &P, const EmgpuRun &A, const StepArgs &F, const DbnChoice &c, hipStream_t s) {
+    const dim3 g((unsigned)((A.n + 255) / 256)), b(256);
+    if (c.lds && c.compact) hipLaunchKernelGGL((k_dbn_step<NI, ND, RM1, true, true>), g, b, c.lds_bytes, s, P, A, F);
+    else if (c.lds) hipLaunchKernelGGL((k_dbn_step<NI, ND, RM1, true, false>), g, b, c.lds_bytes, s, P, A, F);
+    else if (c.compact) hipLaunchKernelGGL((k_dbn_step<NI, ND, RM1, false, true>), g, b, 0, s, P, A, F);
+    else hipLaunchKernelGGL((k_dbn_step<NI, ND, RM1, false, false>), g, b, 0, s, P, A, F);
     return hipGetLastError();
 }
 
-hipError_t launch_dbn_step(const EmgpuPlan &P, const EmgpuRun &A, hipStream_t s, const char **name) {
+hipError_t launch_dbn_step(const EmgpuPlan &P, const EmgpuRun &A, const DbnChoice &c, hipStream_t s) {
     if (A.n <= 0) return hipSuccess;
     StepArgs F{};
     for (int k = 0; k < P.nd; k++) {
@@ -207,13 +181,9 @@ hipError_t launch_dbn_step(const EmgpuPlan &P, const EmgpuRun &A, hipStream_t s,
         for (int a = 0; a < P.nact; a++)
             if (P.a_dyn[a] == k) F.Rk[k] = P.a_R[a];
     }
-    // stage the dynamic tables in LDS when two workgroups per CU still fit beside the cooperative area
-    static const bool no_lds = getenv("EMGPU_DEBUG_STEP_NO_LDS") != nullptr;
-    const bool lds = !no_lds && step_table_bytes(P) <= 32768;
-    if (P.ni <= 7 && P.nd <= 3) { *name = lds ? "k_dbn_step<7,3,8,lds>" : "k_dbn_step<7,3,8>"; return launch_t<7, 3, 8>(P, A, F, s, lds); }
-    if (P.ni <= 9 && P.nd <= 3) { *name = lds ? "k_dbn_step<9,3,8,lds>" : "k_dbn_step<9,3,8>"; return launch_t<9, 3, 8>(P, A, F, s, lds); }
-    *name = lds ? "k_dbn_step<16,4,8,lds>" : "k_dbn_step<16,4,8>";
-    return launch_t<16, 4, 8>(P, A, F, s, lds);
+    if (c.shape == 0) return launch_t<7, 3, 8>(P, A, F, c, s);
+    if (c.shape == 1) return launch_t<9, 3, 8>(P, A, F, c, s);
+    return launch_t<16, 4, 8>(P, A, F, c, s);
 }
 
 } // namespace emgpu

@@ -17,7 +17,6 @@
 // Bound: VALU issue (Philox + ~16 instructions per draw, 84 % of the cycles on cor_v1) and one exposed L1/L2 round trip per second.
 #include <hip/hip_runtime.h>
 
-#include <cstdio>
 #include <cstdlib>
 
 #include "emgpu_coop.h"
@@ -186,28 +185,25 @@ __global__ void __launch_bounds__(256, step2_waves(NI, ND, WMODE, FRZ, EV)) k_db
 // every parent / the full chain of dependencies: the instance any model can run on
 constexpr uint32_t kCurAll3 = 0x0777u, kNewAll3 = 0x0310u, kCurAll4 = 0xFFFFu, kNewAll4 = 0x7310u;
 
-// one instance, with or without the event list
+// one instance, with or without the event list (c: the call's DbnChoice)
 #define EMGPU_S2_LAUNCH(NI_, ND_, W_, REG_, C_, N_, FRZ_)                                                                      \
     do {                                                                                                                       \
-        if (A.ev_count != nullptr && step2_rows_by_wave(P, A)) hipLaunchKernelGGL((k_dbn_step2<NI_, ND_, W_, REG_, C_, N_, FRZ_, 2>), g, b, step2_extra_lds(), s, P, A, F); \
-        else if (A.ev_count != nullptr) hipLaunchKernelGGL((k_dbn_step2<NI_, ND_, W_, REG_, C_, N_, FRZ_, 1>), g, b, step2_extra_lds(), s, P, A, F); \
+        if (c.ev == 2) hipLaunchKernelGGL((k_dbn_step2<NI_, ND_, W_, REG_, C_, N_, FRZ_, 2>), g, b, step2_extra_lds(), s, P, A, F); \
+        else if (c.ev == 1) hipLaunchKernelGGL((k_dbn_step2<NI_, ND_, W_, REG_, C_, N_, FRZ_, 1>), g, b, step2_extra_lds(), s, P, A, F); \
         else hipLaunchKernelGGL((k_dbn_step2<NI_, ND_, W_, REG_, C_, N_, FRZ_, 0>), g, b, step2_extra_lds(), s, P, A, F);                        \
     } while (0)
 
 
-// a list asked for alone: its rows are built by the wave (EMGPU_DEBUG_EVENT_ROWS=lane: tests keep the per-lane row loop reachable)
-inline bool step2_rows_by_wave(const EmgpuPlan &P, const EmgpuRun &A) {
-    static const char *rows_env = getenv("EMGPU_DEBUG_EVENT_ROWS");
-    return A.dyn_bin == nullptr && A.dyn_val == nullptr && rows_env == nullptr && ev_plan_wide_ok(P, A);
-}
+// the per-variable arguments of a plan (the call's step2_plan)
+Step2Args step2_args_of(const EmgpuPlan &P);
 
-// launch_dbn_step2's set-up, shared with the +start instances (emgpu_kernels_step2_ps.hip): the per-variable arguments of a plan (all_res:
-// every dynamic variable has a rate; wmode: the width all columns share, or 0), and the name the general instance -- not "reg", widths
-// left to run time, every parent -- of the call's shape reports (shape: 0 <7,3>, 1 <9,3>, 2 <16,4>, 3 <16,4>[frozen])
-Step2Args step2_args_of(const EmgpuPlan &P, bool *all_res, int *wmode);
-const char *step2_general_name(const EmgpuPlan &P, const EmgpuRun &A, int *shape);
+// entries of EMGPU_S2_CASES_ND4: DbnChoice::mask_case counts on through EMGPU_S2_CASES_ND3 from here
+#define EMGPU_S2_CASE(NI_, ND_, W_, C_, N_, TAG_) +1
+constexpr int kStep2CasesNd4 = 0 EMGPU_S2_CASES_ND4;
+#undef EMGPU_S2_CASE
 
-// the instances built for the 3-variable families (emgpu_kernels_step2b.hip)
-bool launch_masked3(const EmgpuPlan &P, const EmgpuRun &A, const Step2Args &F, hipStream_t s, uint32_t cur, uint32_t nw, const char **tag);
+// the instances built for the 3-variable families (emgpu_kernels_step2b.hip) and the +start instances (emgpu_kernels_step2_ps.hip)
+hipError_t launch_masked3(const EmgpuPlan &P, const EmgpuRun &A, const Step2Args &F, const DbnChoice &c, hipStream_t s);
+hipError_t launch_dbn_step2_start(const EmgpuPlan &P, const EmgpuRun &A, const Step2Args &F, const DbnChoice &c, const EmgpuPresets *Q, hipStream_t s);
 
 } // namespace emgpu

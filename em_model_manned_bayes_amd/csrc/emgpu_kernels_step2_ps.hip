@@ -9,8 +9,6 @@
 // The list AND the dense trace with a start grid stay on k_dbn_generic, and so does an index list (not step2_eligible).
 // The presets pointer is an argument of these kernels alone: EmgpuPlan, EmgpuRun and Step2Args are what every other instance gets, and the
 // plan is still at offset 0 of the kernel-argument segment.
-#include <stdio.h>
-
 #include "emgpu_kernels_step2.h"
 
 namespace emgpu {
@@ -28,46 +26,21 @@ __global__ void __launch_bounds__(256, ND == 4 ? 3 : 4) k_dbn_step2_ps(const Emg
 #include "emgpu_kernels_step2_body.h"
 }
 
-// 0: none (the call stays on k_dbn_generic), 1: dense, 2: list alone.  The (plan, run) pair is step2_eligible.
-int step2_start_form(const EmgpuPlan &P0, const EmgpuRun &A) {
-    if (A.ev_count == nullptr) return 1;
-    EmgpuPlan P = P0;
-    if (A.flags & EMGPU_FLAG_NO_RESAMPLE) P.nact = 0;   // (launch_dbn_step2's rule)
-    return step2_rows_by_wave(P, A) ? 2 : 0;
-}
-
 template <int NI, int ND, uint32_t CUR, uint32_t NEW, bool FRZ>
-static hipError_t launch_ps_t(int form, const EmgpuPlan &P, const EmgpuRun &A, const Step2Args &F, const EmgpuPresets *Q, hipStream_t s) {
+static hipError_t launch_ps_t(const EmgpuPlan &P, const EmgpuRun &A, const Step2Args &F, const DbnChoice &c, const EmgpuPresets *Q, hipStream_t s) {
     const dim3 g((unsigned)((A.n + 255) / 256)), b(256);
-    if (form == 1) hipLaunchKernelGGL((k_dbn_step2_ps<NI, ND, CUR, NEW, FRZ, 0>), g, b, step2_extra_lds(), s, P, A, F, Q);
+    if (c.ev == 0) hipLaunchKernelGGL((k_dbn_step2_ps<NI, ND, CUR, NEW, FRZ, 0>), g, b, step2_extra_lds(), s, P, A, F, Q);
     else hipLaunchKernelGGL((k_dbn_step2_ps<NI, ND, CUR, NEW, FRZ, 2>), g, b, step2_extra_lds(), s, P, A, F, Q);
     return hipGetLastError();
 }
 
-// name: room for 96 characters; receives the name the general instance of the call's shape reports for this form (without the "+start")
-hipError_t launch_dbn_step2_start(const EmgpuPlan &P0, const EmgpuRun &A, const EmgpuPresets *Q, hipStream_t s, char *name) {
-    name[0] = 0;
-    if (A.n <= 0) return hipSuccess;
-    const int form = step2_start_form(P0, A);
-    if (form == 0 || Q == nullptr) return hipErrorNotSupported;
-    EmgpuPlan P = P0;
-    if (A.flags & EMGPU_FLAG_NO_RESAMPLE) P.nact = 0;   // no variable has a rate: no resample stream, no resample pass
-    bool all_res;
-    int wmode, shape;
-    const Step2Args F = step2_args_of(P, &all_res, &wmode);
-    snprintf(name, 96, "%s%s", step2_general_name(P, A, &shape), form == 2 ? "+rows-by-wave+events" : "");
-    switch (shape) {
-    case 0: return launch_ps_t<7, 3, kCurAll3, kNewAll3, false>(form, P, A, F, Q, s);
-    case 1: return launch_ps_t<9, 3, kCurAll3, kNewAll3, false>(form, P, A, F, Q, s);
-    case 2: return launch_ps_t<16, 4, kCurAll4, kNewAll4, false>(form, P, A, F, Q, s);
-    case 3: {
-        uint32_t cur, nw;
-        step_parent_masks(P, &cur, &nw);
-        if (nw != 0u) return hipErrorNotSupported;   // (cannot be: is_dynvar_depend would be set)
-        return launch_ps_t<16, 4, kCurAll4, 0u, true>(form, P, A, F, Q, s);
-    }
-    default: return hipErrorNotSupported;
-    }
+// P, F: the call's step2_plan and its arguments; c.ev: 0 or 2 (choose_dbn)
+hipError_t launch_dbn_step2_start(const EmgpuPlan &P, const EmgpuRun &A, const Step2Args &F, const DbnChoice &c, const EmgpuPresets *Q, hipStream_t s) {
+    if (Q == nullptr || c.ev == 1) return hipErrorNotSupported;
+    if (c.shape == 0) return launch_ps_t<7, 3, kCurAll3, kNewAll3, false>(P, A, F, c, Q, s);
+    if (c.shape == 1) return launch_ps_t<9, 3, kCurAll3, kNewAll3, false>(P, A, F, c, Q, s);
+    if (!c.frozen) return launch_ps_t<16, 4, kCurAll4, kNewAll4, false>(P, A, F, c, Q, s);
+    return launch_ps_t<16, 4, kCurAll4, 0u, true>(P, A, F, c, Q, s);
 }
 
 } // namespace emgpu

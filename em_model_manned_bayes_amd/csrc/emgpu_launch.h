@@ -2,40 +2,22 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include "emgpu_dispatch.h"
 #include "emgpu_plan.h"
 
 namespace emgpu {
-hipError_t launch_dbn_generic(const EmgpuPlan &P, const EmgpuRun &A, hipStream_t s, const char **name, const EmgpuPresets *presets = nullptr);
+// The sampler's kernels: c = choose_dbn(P, A, presets != nullptr) names the instance, the launcher launches it.
+hipError_t launch_dbn_generic(const EmgpuPlan &P, const EmgpuRun &A, const DbnChoice &c, const EmgpuPresets *presets, hipStream_t s);
+hipError_t launch_uncor_fast(const EmgpuPlan &P, const EmgpuRun &A, const DbnChoice &c, const EmgpuPresets *presets, hipStream_t s);
+hipError_t launch_dbn_step2(const EmgpuPlan &P, const EmgpuRun &A, const DbnChoice &c, const EmgpuPresets *presets, hipStream_t s);
+hipError_t launch_dbn_step(const EmgpuPlan &P, const EmgpuRun &A, const DbnChoice &c, hipStream_t s);
 hipError_t launch_bn(const EmgpuPlan &P, const EmgpuBnRun &A, hipStream_t s, const char **name);
-// Returns false when the (plan, run) pair is outside what the specialised kernel covers.
-bool fast_uncor_eligible(const EmgpuPlan &P, const EmgpuRun &A);
-hipError_t launch_uncor_fast(const EmgpuPlan &P, const EmgpuRun &A, hipStream_t s, const char **name);
-// The same with a start grid / per-sample log-weights (emgpu_kernels_fast_ps.hip).  uncor_fast_start_form: 0 = this fast-eligible call has
-// no +start instance (the list and the dense trace together: k_dbn_generic), 1 = dense, 2 = the list alone.  name: room for 64 characters,
-// receives the name of the instance whose body runs; the caller appends "+start".
-int uncor_fast_start_form(const EmgpuPlan &P, const EmgpuRun &A);
-hipError_t launch_uncor_fast_start(const EmgpuPlan &P, const EmgpuRun &A, const EmgpuPresets *presets, hipStream_t s, char *name);
-// Mixed-model batch in one launch: nb <= EMGPU_MAX_MIXED blocks whose plans are fast-eligible and share the instance
-// uncor_fast_shape().  A model's plan lives in device memory (plan_f_bytes() bytes filled by plan_f_fill on the host, then uploaded).
-int uncor_fast_shape(const EmgpuPlan &P);
+// Mixed-model batch in one launch: nb <= EMGPU_MAX_MIXED blocks whose choice is the dense fast kernel at the same shape
+// (uncor_fast_mixed_name).  A model's plan lives in device memory (plan_f_bytes() bytes filled by plan_f_fill on the host, then uploaded).
 size_t plan_f_bytes();
 void plan_f_fill(const EmgpuPlan &P, void *host_buf);
 hipError_t launch_uncor_fast_mixed(const EmgpuRun &A, int nb, const void *const *d_planf, const uint64_t *first, const int64_t *n, const int64_t *col,
-                                   int shape, hipStream_t s, const char **name);
-// The per-timestep DBN with dense output (dependent-branch models, EMGPU_TRANSITION_PER_STEP).
-bool step_eligible(const EmgpuPlan &P, const EmgpuRun &A);
-hipError_t launch_dbn_step(const EmgpuPlan &P, const EmgpuRun &A, hipStream_t s, const char **name);
-bool step2_eligible(const EmgpuPlan &P, const EmgpuRun &A);
-// which dynamic variables are parents of which in the transition network, as the per-timestep kernel's instances see it:
-// bit 4k+q of cur_mask: the time-t node of dynamic variable q is a parent of (t+1) node k; of new_mask: its (t+1) node is (q < k)
-void step_parent_masks(const EmgpuPlan &P, uint32_t *cur_mask, uint32_t *new_mask);
-hipError_t launch_dbn_step2(const EmgpuPlan &P, const EmgpuRun &A, hipStream_t s, const char **name);
-// The same with a start grid / per-sample log-weights (emgpu_kernels_step2_ps.hip): the +start twin of the general instance of the call's
-// shape.  step2_start_form: 0 = this step2-eligible call has no +start instance (the list and the dense trace together, or
-// EMGPU_DEBUG_EVENT_ROWS set: k_dbn_generic), 1 = dense, 2 = the list alone with its rows built by the wave.  name: room for 96 characters,
-// receives the name the general instance reports for this form; the caller appends "+start".
-int step2_start_form(const EmgpuPlan &P, const EmgpuRun &A);
-hipError_t launch_dbn_step2_start(const EmgpuPlan &P, const EmgpuRun &A, const EmgpuPresets *presets, hipStream_t s, char *name);
+                                   int shape, hipStream_t s);
 hipError_t launch_terminal_propagate(const EmgpuPlan &P, const EmgpuTermRun &A, hipStream_t s, const char **name);
 int terminal_debug_counters(unsigned long long *out, int n);   // -DEMGPU_TERM_COUNTERS builds: the loop's path counters (0: not such a build)
 // createEncounter.m:88-89 through the stand-in of EMGPU_FLAG_LOCAL_SMOOTH: v_ft_s (5 s) and z_ft (15 s) of n2 joined tracks, in place

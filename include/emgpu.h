@@ -738,6 +738,12 @@ int emgpu_debug_terminal_counters(emgpu_ctx *ctx, uint64_t *out, int32_t n);
  * dependent branch; q < k by the topological order).  The per-timestep kernel picks its instance by these masks. */
 int emgpu_debug_parent_masks(const emgpu_model *m, uint32_t *cur_mask, uint32_t *new_mask);
 
+/* Which kernel instance emgpu_sample_dbn_device / _host would run this call on: the name emgpu_last_kernel_name reports after it (the
+ * instance, then "+rows-by-wave+events" / "+events" for an event list and "+start" for a start grid or log-weights), written to
+ * name[0..cap).  Host only, no ctx: only WHICH pointers of p and out are null is read (p->start or out->log_weight: presets), never
+ * what they point to.  EMGPU_ERR_ARG when the name does not fit cap. */
+int emgpu_debug_kernel_choice(const emgpu_model *m, const emgpu_sample_params *p, const emgpu_sample_out *out, char *name, int32_t cap);
+
 /* Host helpers that mirror small reference functions (used by the class layer and tests). */
 int32_t emgpu_discretize_bayes(double x, const double *thresholds, int32_t n); /* discretize_bayes.m:14-22 */
 int64_t emgpu_asub2ind(const int32_t *siz, const int32_t *x, int32_t n);       /* asub2ind.m:13-14        */

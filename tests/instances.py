@@ -14,8 +14,10 @@ Each row of ROWS:
   per_step -- EMGPU_TRANSITION_PER_STEP
   env      -- debug variables the library reads once per process (getenv cached in a static): the row runs in a child process
 
-The completeness test (test_instances.py) extracts every kernel name literal and EMGPU_S2_CASE / EMGPU_S2_CASE_W tag from the launcher
-sources and fails on one that no row reaches and that neither COVERED_ELSEWHERE nor UNREACHABLE lists.
+The completeness test (test_instances.py) extracts every kernel name literal and EMGPU_S2_CASE / EMGPU_S2_CASE_W tag from the sources (the
+name tables of csrc/emgpu_dispatch.cpp and the case lists of csrc/emgpu_dispatch.h, where the dispatcher keeps them; the single-instance
+launchers' own literals) and fails on one that no row reaches and that neither COVERED_ELSEWHERE nor UNREACHABLE lists.
+test_dispatch.py predicts every row's kernel on the CPU through emgpu_debug_kernel_choice; test_gpu_instances.py runs it.
 """
 
 RATE_AT_EDGE = 1.0 - 2.0 ** -16               # Bernoulli threshold exactly 0xFFFF0000: RR1 = (R >> 16) + 1 does not fit 16 bits, the

@@ -8,14 +8,12 @@ import pytest
 
 import oracle as O
 from em_model_manned_bayes_amd import native, _lib as L
+from parity_models import DEP_MODELS, FAST_MODELS
 from util import load_pair, uncor_indices, assert_uncor_parity, assert_parting_only_on_a_threshold, assert_f32_of_f64
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
-FAST_MODELS = ["uncor_1200code_v2p1", "uncor_1200only_fwse_v1p2", "uncor_1200exclude_rotorcraft_v1p2",
-               "uncor_allcode_fwmulti_v1", "dueregard_v1", "haa_v1", "blimp_v1"]
-DEP_MODELS = ["uncor_1200code_v1", "littoral_uncor_v1", "glider_v1", "paraglider_v1", "fai1_v1", "paramotor_v1", "skydiving_v1"]
 
 
 @pytest.mark.parametrize("name", FAST_MODELS + DEP_MODELS)
