@@ -1054,16 +1054,64 @@ static const Uploaded *terminal_tables(emgpu_ctx *ctx, const emgpu_model *const 
     return first;
 }
 
-// k_terminal_propagate's run over the tables terminal_tables published in ctx->d_thr_base
-static EmgpuTermRun term_run(emgpu_ctx *ctx, uint64_t seed, uint64_t first_index, int64_t n, const double *geo, const int32_t *model_of,
-                             double tmax_s, int32_t max_resample, int32_t cap, const double (&dyn_limits)[2][5], float *traj, int32_t *rows) {
+// One terminal encounter chain for `count` encounters: geometry draw (sample.m:29-77) -> createEncounter.m:21-49 -> PropagateTrajectory x 4
+// (:52-72) -> local_smooth (:88-89) under EMGPU_FLAG_LOCAL_SMOOTH.  geom == null: geo and model_of are the caller's, and only the
+// propagate + smooth tail runs (emgpu_propagate_terminal_device).
+struct TerminalChain {
+    const Model *gm; const Uploaded *geom;   // the geometry model and its upload
+    const Uploaded *first;                   // the trajectory tables terminal_tables published in ctx->d_thr_base
+    uint64_t seed, first_index;
+    int64_t count;
+    const uint64_t *indices;                 // the encounters' global indices (a later rejection round), or null: first_index + lane
+    int quiet;                               // a re-draw cap voids the track without raising the ctx status
+    int32_t max_attempts; const double *bounds_sample; const int32_t *idx; const double (*dyn_limits)[5];
+    double tmax_s; int32_t max_resample, cap; uint32_t flags;
+    uint8_t *geom_bin; float *geom_val; int32_t *attempts;   // the accepted geometry sample [n_i][count]
+    const double *geo_in; const int32_t *model_of_in;        // geom == null: the tail's inputs
+    double *geo; int32_t *model_of; float *traj; int32_t *rows;
+};
+// the geometry model and the ten trajectory models of a chain, uploaded, and the trajectory tables published
+static void upload_terminal(emgpu_ctx *ctx, const emgpu_model *gm, const emgpu_model *const *traj_models, int32_t n_traj_models, TerminalChain &c) {
+    std::set<uint64_t> pinned{gm->m.uid};   // the trajectory tables' pointers are published before the geometry model's upload
+    for (int i = 0; i < n_traj_models; i++) if (traj_models[i]) pinned.insert(traj_models[i]->m.uid);
+    c.first = terminal_tables(ctx, traj_models, n_traj_models, &pinned);
+    c.gm = &gm->m; c.geom = &get_uploaded(ctx, gm, &pinned);
+}
+struct TerminalNames { const char *bn = "", *propagate = "", *smooth = ""; };   // what ran (smooth: " + k_terminal_smooth" or nothing)
+static TerminalNames terminal_chain(emgpu_ctx *ctx, const TerminalChain &c) {
+    // k_terminal_smooth keeps a track's block in one workgroup's registers: refused before anything is launched
+    if ((c.flags & EMGPU_FLAG_LOCAL_SMOOTH) && EMGPU_TERMINAL_BLOCK_ROWS(c.cap) > 256) throw Error(EMGPU_ERR_UNSUPPORTED, "EMGPU_FLAG_LOCAL_SMOOTH: cap above 128");
+    TerminalNames ran;
+    if (c.geom) {
+        emgpu_bn_params bp;
+        memset(&bp, 0, sizeof bp);
+        bp.seed = c.seed; bp.first_index = c.first_index; bp.n = c.count;
+        bp.max_attempts = c.max_attempts; bp.bounds_sample = c.bounds_sample;
+        bp.idx_own_speed = c.idx[3]; bp.idx_int_speed = c.idx[9];
+        bp.min_vel1 = c.dyn_limits[0][0]; bp.max_vel1 = c.dyn_limits[0][1]; bp.min_vel2 = c.dyn_limits[1][0]; bp.max_vel2 = c.dyn_limits[1][1];
+        EmgpuBnRun B;
+        fill_bn(ctx, *c.geom, *c.gm, &bp, B);
+        B.out_bin = c.geom_bin; B.out_val = c.geom_val; B.attempts = c.attempts; B.indices = c.indices;
+        launch_ok(emgpu::launch_bn(c.geom->cp.plan, B, ctx->stream, &ran.bn));
+        EmgpuTGeoRun G;
+        memset(&G, 0, sizeof G);
+        G.n = c.count; G.val = c.geom_val; G.geo = c.geo; G.model_of = c.model_of;
+        for (int k = 0; k < 12; k++) G.idx[k] = c.idx[k] - 1;
+        launch_ok(emgpu::launch_terminal_geo(G, ctx->stream));
+    }
     EmgpuTermRun A;
     memset(&A, 0, sizeof A);
-    A.seed = seed; A.first_index = first_index; A.n = n; A.geo = geo; A.model_of = model_of; A.thr_base = ctx->d_thr_base;
-    A.tmax_s = tmax_s; A.max_resample = max_resample; A.cap = cap;
-    memcpy(A.dl, dyn_limits, sizeof A.dl);
-    A.traj = traj; A.rows = rows; A.status = ctx->d_status; A.queue = ctx->d_queue;
-    return A;
+    A.seed = c.seed; A.first_index = c.first_index; A.n = c.count; A.thr_base = ctx->d_thr_base;
+    A.geo = c.geom ? c.geo : c.geo_in; A.model_of = c.geom ? c.model_of : c.model_of_in;
+    A.tmax_s = c.tmax_s; A.max_resample = c.max_resample; A.cap = c.cap; A.indices = c.indices; A.quiet = c.quiet;
+    memcpy(A.dl, c.dyn_limits, sizeof A.dl);
+    A.traj = c.traj; A.rows = c.rows; A.status = ctx->d_status; A.queue = ctx->d_queue;
+    launch_ok(emgpu::launch_terminal_propagate(c.first->cp.plan, A, ctx->stream, &ran.propagate));
+    if (c.flags & EMGPU_FLAG_LOCAL_SMOOTH) {
+        launch_ok(emgpu::launch_terminal_smooth(c.traj, c.rows, 2 * c.count, c.cap, ctx->stream));
+        ran.smooth = " + k_terminal_smooth";
+    }
+    return ran;
 }
 
 int emgpu_propagate_terminal_device(emgpu_ctx *ctx, const emgpu_model *const *models, int32_t n_models,
@@ -1075,17 +1123,13 @@ int emgpu_propagate_terminal_device(emgpu_ctx *ctx, const emgpu_model *const *mo
     if (p->n >= ((int64_t)1 << 29)) return fail(EMGPU_ERR_ARG, "more than 2^29 encounters in one call");
     CTX_LOCK(ctx);
     HIP_OK(hipSetDevice(ctx->device));
-    const Uploaded *first = terminal_tables(ctx, models, n_models);
-    const EmgpuTermRun A = term_run(ctx, p->seed, p->first_index, p->n, geo, model_of, p->tmax_s, p->max_resample, p->cap, p->dyn_limits, traj, rows);
-    const char *name = "";
-    if ((p->flags & EMGPU_FLAG_LOCAL_SMOOTH) && EMGPU_TERMINAL_BLOCK_ROWS(p->cap) > 256) return fail(EMGPU_ERR_UNSUPPORTED, "EMGPU_FLAG_LOCAL_SMOOTH: cap above 128");
-    hipError_t e = emgpu::launch_terminal_propagate(first->cp.plan, A, ctx->stream, &name);
-    ctx->last_kernel = name;
-    if (e == hipSuccess && (p->flags & EMGPU_FLAG_LOCAL_SMOOTH)) {
-        e = emgpu::launch_terminal_smooth(traj, rows, 2 * p->n, p->cap, ctx->stream);
-        ctx->last_kernel += " + k_terminal_smooth";
-    }
-    launch_ok(e);
+    TerminalChain c{};
+    c.first = terminal_tables(ctx, models, n_models);
+    c.seed = p->seed; c.first_index = p->first_index; c.count = p->n;
+    c.dyn_limits = p->dyn_limits; c.tmax_s = p->tmax_s; c.max_resample = p->max_resample; c.cap = p->cap; c.flags = p->flags;
+    c.geo_in = geo; c.model_of_in = model_of; c.traj = traj; c.rows = rows;
+    const TerminalNames ran = terminal_chain(ctx, c);
+    ctx->last_kernel = std::string(ran.propagate) + ran.smooth;
     return EMGPU_OK;
     EMGPU_CATCH
 }
@@ -1130,63 +1174,67 @@ int emgpu_sample_terminal_device(emgpu_ctx *ctx, const emgpu_model *gm, const em
     CTX_LOCK(ctx);
     HIP_OK(hipSetDevice(ctx->device));
     if (p->n == 0) return EMGPU_OK;
-    std::set<uint64_t> pinned{gm->m.uid};   // the trajectory tables' pointers are published before the geometry model's upload
-    for (int i = 0; i < n_traj_models; i++) if (traj_models[i]) pinned.insert(traj_models[i]->m.uid);
-    const Uploaded *first = terminal_tables(ctx, traj_models, n_traj_models, &pinned);
-    Uploaded &ug = get_uploaded(ctx, gm, &pinned);
-    // geometry draw (sample.m:29-77)
-    emgpu_bn_params bp;
-    memset(&bp, 0, sizeof bp);
-    bp.seed = p->seed; bp.first_index = p->first_index; bp.n = p->n;
-    bp.max_attempts = p->max_attempts; bp.bounds_sample = p->bounds_sample;
-    bp.idx_own_speed = p->idx[3]; bp.idx_int_speed = p->idx[9];
-    bp.min_vel1 = p->dyn_limits[0][0]; bp.max_vel1 = p->dyn_limits[0][1]; bp.min_vel2 = p->dyn_limits[1][0]; bp.max_vel2 = p->dyn_limits[1][1];
-    EmgpuBnRun B;
-    fill_bn(ctx, ug, g, &bp, B);
-    B.out_bin = geom_bin; B.out_val = geom_val; B.attempts = attempts;
-    const char *name = "";
-    launch_ok(emgpu::launch_bn(ug.cp.plan, B, ctx->stream, &name));
-    std::string kernels = name;
-    // createEncounter.m:21-49
-    EmgpuTGeoRun G;
-    memset(&G, 0, sizeof G);
-    G.n = p->n; G.val = geom_val; G.geo = geo; G.model_of = model_of;
-    for (int k = 0; k < 12; k++) G.idx[k] = p->idx[k] - 1;
-    launch_ok(emgpu::launch_terminal_geo(G, ctx->stream));
-    kernels += " + k_terminal_geo";
-    // PropagateTrajectory x 4 (createEncounter.m:52-72)
-    const EmgpuTermRun A = term_run(ctx, p->seed, p->first_index, p->n, geo, model_of, p->tmax_s, p->max_resample, p->cap, p->dyn_limits, traj, rows);
-    launch_ok(emgpu::launch_terminal_propagate(first->cp.plan, A, ctx->stream, &name));
-    ctx->last_kernel = kernels + " + " + name;
-    ctx->last_launches = 3;
-    if (p->flags & EMGPU_FLAG_LOCAL_SMOOTH) {
-        launch_ok(emgpu::launch_terminal_smooth(traj, rows, 2 * p->n, p->cap, ctx->stream));
-        ctx->last_kernel = kernels + " + k_terminal_smooth + " + name;   // (the dominant kernel stays last in the list)
-        ctx->last_launches = 4;
-    }
+    TerminalChain c{};
+    upload_terminal(ctx, gm, traj_models, n_traj_models, c);
+    c.seed = p->seed; c.first_index = p->first_index; c.count = p->n;
+    c.max_attempts = p->max_attempts; c.bounds_sample = p->bounds_sample; c.idx = p->idx; c.dyn_limits = p->dyn_limits;
+    c.tmax_s = p->tmax_s; c.max_resample = p->max_resample; c.cap = p->cap; c.flags = p->flags;
+    c.geom_bin = geom_bin; c.geom_val = geom_val; c.attempts = attempts; c.geo = geo; c.model_of = model_of; c.traj = traj; c.rows = rows;
+    const TerminalNames ran = terminal_chain(ctx, c);
+    ctx->last_kernel = std::string(ran.bn) + " + k_terminal_geo" + ran.smooth + " + " + ran.propagate;   // (the dominant kernel stays last in the list)
+    ctx->last_launches = *ran.smooth ? 4 : 3;
     return EMGPU_OK;
     EMGPU_CATCH
 }
 
-// Synchronizes a stream when the scope ends, however it ends: the round drivers' launches read their scratch and the caller's buffers.
-struct StreamSyncOnExit {
-    hipStream_t s;
-    ~StreamSyncOnExit() { (void)hipStreamSynchronize(s); }
-};
+// The rejection rounds of a track call over n lanes: round j redraws what round j - 1 rejected, with attempt number j + 1, until nothing is
+// left or max_rounds have run.  Owns the accepted flags, the two (global index, output slot) list pairs -- round j reads pair j & 1 (round 0
+// none: lane i is global index first_index + i and slot i) and next() writes the other -- and the compaction's scratch.
+class RejectionRounds {
+  public:
+    RejectionRounds(emgpu_ctx *ctx, RoundScratch &mem, size_t n, uint64_t first_index, int max_rounds)
+        : ctx_(ctx), first_index_(first_index), max_(max_rounds), count_(n) {
+        accepted_ = mem.alloc<uint8_t>(n);
+        for (auto &q : gidx_) q = mem.alloc<uint64_t>(n * 8);
+        for (auto &q : slot_) q = mem.alloc<int64_t>(n * 8);
+        d_count_ = mem.alloc<uint32_t>(4 * emgpu::compact_scratch_words((int64_t)n));
+    }
+    bool more() const { return j_ < max_ && count_ > 0; }
+    int round() const { return j_; }
+    size_t count() const { return count_; }   // lanes of this round
+    const uint64_t *indices() const { return j_ ? gidx_[j_ & 1] : nullptr; }
+    const int64_t *slots() const { return j_ ? slot_[j_ & 1] : nullptr; }
+    uint8_t *accepted() const { return accepted_; }
+    int attempt_no() const { return j_ + 1; }
+    int last_round() const { return j_ + 1 == max_; }
+    // the end of a round: the lanes it rejected, in lane order, become the next round's lists
+    void next() {
+        const int cur = j_ & 1;
+        HIP_OK(hipMemsetAsync(d_count_, 0, 4, ctx_->stream));
+        launch_ok(emgpu::launch_compact_rejected((int64_t)count_, first_index_, accepted_, indices(), slots(), gidx_[cur ^ 1], slot_[cur ^ 1], d_count_, ctx_->stream));
+        uint32_t hc = 0;
+        HIP_OK(hipMemcpyAsync(&hc, d_count_, 4, hipMemcpyDeviceToHost, ctx_->stream));
+        HIP_OK(hipStreamSynchronize(ctx_->stream));
+        count_ = hc;
+        j_++;
+    }
+    // after the last round: the draws' own deferred status (their rejection cap), then the lanes the rounds left rejected
+    int status(const char *who, const char *what) const {
+        const int rc = emgpu_ctx_sync(ctx_);
+        if (rc != EMGPU_OK || count_ == 0) return rc;
+        return fail(EMGPU_ERR_REJECT_CAP, std::string(who) + ": " + std::to_string(count_) + " " + what + " were still rejected after max_track_attempts");
+    }
 
-// The end of rejection round j: the lanes it rejected, in lane order, become the next round's (global index, output slot) lists
-// d_gidx / d_slot[(j & 1) ^ 1] (round j read [j & 1], round 0 none).  Returns how many.
-static size_t compact_rejected(emgpu_ctx *ctx, int j, size_t count, uint64_t first_index, const uint8_t *d_acc, uint64_t *const d_gidx[2],
-                               int64_t *const d_slot[2], uint32_t *d_count) {
-    const int cur = j & 1;
-    HIP_OK(hipMemsetAsync(d_count, 0, 4, ctx->stream));
-    launch_ok(emgpu::launch_compact_rejected((int64_t)count, first_index, d_acc, j ? d_gidx[cur] : nullptr, j ? d_slot[cur] : nullptr,
-                                             d_gidx[cur ^ 1], d_slot[cur ^ 1], d_count, ctx->stream));
-    uint32_t hc = 0;
-    HIP_OK(hipMemcpyAsync(&hc, d_count, 4, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_OK(hipStreamSynchronize(ctx->stream));
-    return hc;
-}
+  private:
+    emgpu_ctx *ctx_;
+    uint64_t first_index_;
+    int max_, j_ = 0;
+    size_t count_;
+    uint8_t *accepted_;
+    uint64_t *gidx_[2];
+    int64_t *slot_[2];
+    uint32_t *d_count_;
+};
 
 int emgpu_track_terminal_host(emgpu_ctx *ctx, const emgpu_model *gm, const emgpu_model *const *traj_models, int32_t n_traj_models,
                               const emgpu_ttrack_params *p, double *sample, double *traj, int32_t cap2, int32_t *len,
@@ -1205,83 +1253,45 @@ int emgpu_track_terminal_host(emgpu_ctx *ctx, const emgpu_model *gm, const emgpu
     const size_t n = (size_t)p->n, ni = (size_t)g.n_initial;
     if (n == 0) return EMGPU_OK;
     const int cap = (int)p->tmax_s + 3;
-    size_t slot = 0;
-    auto dalloc = [&](size_t bytes) { return ctx_scratch(ctx, slot++, bytes ? bytes : 1); };   // kept by the ctx between calls
-    const StreamSyncOnExit drain{ctx->stream};
-    float *d_val = (float *)dalloc(ni * n * 4);
-    double *d_geo = (double *)dalloc(n * 12 * 8);
-    int32_t *d_mo = (int32_t *)dalloc(4 * n * 4), *d_rows = (int32_t *)dalloc(4 * n * 4);
-    float *d_out = (float *)dalloc((size_t)2 * n * (size_t)EMGPU_TERMINAL_BLOCK_ROWS(cap) * 5 * 4);
-    uint8_t *d_acc = (uint8_t *)dalloc(n);
-    uint64_t *d_gidx[2] = {(uint64_t *)dalloc(n * 8), (uint64_t *)dalloc(n * 8)};
-    int64_t *d_slot[2] = {(int64_t *)dalloc(n * 8), (int64_t *)dalloc(n * 8)};
-    uint32_t *d_count = (uint32_t *)dalloc(4 * emgpu::compact_scratch_words((int64_t)n));
-    double *d_sample = sample ? (double *)dalloc(n * ni * 8) : nullptr;
-    double *d_traj = traj ? (double *)dalloc(n * 2 * (size_t)cap2 * 6 * 8) : nullptr;
-    int32_t *d_len = len ? (int32_t *)dalloc(n * 2 * 4) : nullptr;
-    double *d_meta = meta ? (double *)dalloc(n * 4 * 8) : nullptr;
-    int32_t *d_att = (int32_t *)dalloc(n * 4);
-    std::set<uint64_t> pinned{gm->m.uid};   // the trajectory tables' pointers are published before the geometry model's upload
-    for (int i = 0; i < n_traj_models; i++) if (traj_models[i]) pinned.insert(traj_models[i]->m.uid);
-    const Uploaded *first = terminal_tables(ctx, traj_models, n_traj_models, &pinned);
-    Uploaded &ug = get_uploaded(ctx, gm, &pinned);
-    emgpu_bn_params bp;
-    memset(&bp, 0, sizeof bp);
-    bp.max_attempts = p->max_attempts; bp.bounds_sample = p->bounds_sample;
-    bp.idx_own_speed = p->idx[3]; bp.idx_int_speed = p->idx[9];
-    bp.min_vel1 = p->dyn_limits[0][0]; bp.max_vel1 = p->dyn_limits[0][1]; bp.min_vel2 = p->dyn_limits[1][0]; bp.max_vel2 = p->dyn_limits[1][1];
-    size_t count = n;
-    std::string kernels;
-    for (int j = 0; j < p->max_track_attempts && count > 0; j++) {
-        const int cur = j & 1;
-        const uint64_t seed = p->seed + (uint64_t)j;
-        const uint64_t *ind = j ? d_gidx[cur] : nullptr;
-        // geometry draw (sample.m:29-77)
-        bp.seed = seed; bp.first_index = p->first_index; bp.n = (int64_t)count;
-        EmgpuBnRun B;
-        fill_bn(ctx, ug, g, &bp, B);
-        B.out_val = d_val; B.ld = (int64_t)count; B.indices = ind;
+    RoundScratch mem(ctx);
+    float *d_val = mem.alloc<float>(ni * n * 4);
+    double *d_geo = mem.alloc<double>(n * 12 * 8);
+    int32_t *d_mo = mem.alloc<int32_t>(4 * n * 4), *d_rows = mem.alloc<int32_t>(4 * n * 4);
+    float *d_out = mem.alloc<float>((size_t)2 * n * (size_t)EMGPU_TERMINAL_BLOCK_ROWS(cap) * 5 * 4);
+    RejectionRounds rounds(ctx, mem, n, p->first_index, p->max_track_attempts);
+    double *d_sample = sample ? mem.alloc<double>(n * ni * 8) : nullptr;
+    double *d_traj = traj ? mem.alloc<double>(n * 2 * (size_t)cap2 * 6 * 8) : nullptr;
+    int32_t *d_len = len ? mem.alloc<int32_t>(n * 2 * 4) : nullptr;
+    double *d_meta = meta ? mem.alloc<double>(n * 4 * 8) : nullptr;
+    int32_t *d_att = mem.alloc<int32_t>(n * 4);
+    TerminalChain c{};
+    upload_terminal(ctx, gm, traj_models, n_traj_models, c);
+    c.first_index = p->first_index; c.quiet = 1;
+    c.max_attempts = p->max_attempts; c.bounds_sample = p->bounds_sample; c.idx = p->idx; c.dyn_limits = p->dyn_limits;
+    c.tmax_s = p->tmax_s; c.max_resample = p->max_resample; c.cap = cap; c.flags = p->flags;   // (smoothed: the filters read the smoothed speed and altitude)
+    c.geom_val = d_val; c.geo = d_geo; c.model_of = d_mo; c.traj = d_out; c.rows = d_rows;
+    // the filters (track.m:62-145)
+    EmgpuTFilterRun F;
+    memset(&F, 0, sizeof F);
+    F.tracks = d_out; F.rows = d_rows; F.cap = cap; F.geo = d_geo; F.val = d_val; F.n_i = (int32_t)ni;
+    memcpy(F.dl, p->dyn_limits, sizeof F.dl);
+    for (int a = 0; a < 2; a++) { F.max_cum_turn[a] = p->max_cum_turn_deg[a]; F.pitch[a] = p->pitch_deg[a]; }
+    F.min_enc_time_s = p->min_enc_time_s; F.thres_dist_ft = p->thres_dist_ft; F.thres_alt_low_ft = p->thres_alt_low_ft; F.thres_vertrate_ft_s = p->thres_vertrate_ft_s;
+    F.accepted = rounds.accepted();
+    F.sample = d_sample; F.traj = d_traj; F.cap2 = cap2; F.len = d_len; F.meta = d_meta; F.attempts = d_att;
+    for (; rounds.more(); rounds.next()) {
+        c.seed = p->seed + (uint64_t)rounds.round(); c.count = (int64_t)rounds.count(); c.indices = rounds.indices();
+        const TerminalNames ran = terminal_chain(ctx, c);
+        F.n = c.count; F.slot = rounds.slots(); F.attempt_no = rounds.attempt_no(); F.last_round = rounds.last_round();
         const char *name = "";
-        launch_ok(emgpu::launch_bn(ug.cp.plan, B, ctx->stream, &name));
-        kernels = name;
-        // createEncounter.m:21-49
-        EmgpuTGeoRun G;
-        memset(&G, 0, sizeof G);
-        G.n = (int64_t)count; G.val = d_val; G.geo = d_geo; G.model_of = d_mo;
-        for (int k = 0; k < 12; k++) G.idx[k] = p->idx[k] - 1;
-        launch_ok(emgpu::launch_terminal_geo(G, ctx->stream));
-        // PropagateTrajectory x 4 (createEncounter.m:52-72)
-        EmgpuTermRun A = term_run(ctx, seed, p->first_index, (int64_t)count, d_geo, d_mo, p->tmax_s, p->max_resample, cap, p->dyn_limits, d_out, d_rows);
-        A.indices = ind; A.quiet = 1;
-        launch_ok(emgpu::launch_terminal_propagate(first->cp.plan, A, ctx->stream, &name));
-        kernels += std::string(" + ") + name;
-        if (p->flags & EMGPU_FLAG_LOCAL_SMOOTH) {   // createEncounter.m:88-89 (stand-in): the filters read the smoothed speed and altitude
-            launch_ok(emgpu::launch_terminal_smooth(d_out, d_rows, 2 * (int64_t)count, cap, ctx->stream));
-            kernels += " + k_terminal_smooth";
-        }
-        // the filters (track.m:62-145)
-        EmgpuTFilterRun F;
-        memset(&F, 0, sizeof F);
-        F.n = (int64_t)count; F.tracks = d_out; F.rows = d_rows; F.cap = cap; F.geo = d_geo; F.val = d_val; F.n_i = (int32_t)ni;
-        memcpy(F.dl, p->dyn_limits, sizeof F.dl);
-        for (int a = 0; a < 2; a++) { F.max_cum_turn[a] = p->max_cum_turn_deg[a]; F.pitch[a] = p->pitch_deg[a]; }
-        F.min_enc_time_s = p->min_enc_time_s; F.thres_dist_ft = p->thres_dist_ft; F.thres_alt_low_ft = p->thres_alt_low_ft; F.thres_vertrate_ft_s = p->thres_vertrate_ft_s;
-        F.slot = j ? d_slot[cur] : nullptr; F.accepted = d_acc;
-        F.sample = d_sample; F.traj = d_traj; F.cap2 = cap2; F.len = d_len; F.meta = d_meta; F.attempts = d_att;
-        F.attempt_no = j + 1; F.last_round = (j + 1 == p->max_track_attempts);
         launch_ok(emgpu::launch_terminal_filter(F, ctx->stream, &name));
-        ctx->last_kernel = kernels + " + " + name;
-        count = compact_rejected(ctx, j, count, p->first_index, d_acc, d_gidx, d_slot, d_count);
+        ctx->last_kernel = std::string(ran.bn) + " + " + ran.propagate + ran.smooth + " + " + name;
     }
-    int rc = emgpu_ctx_sync(ctx);   // the geometry draw's own rejection cap
-    std::string msg = g_err;
-    auto back = [&](void *dst, const void *src, size_t bytes) { if (dst && bytes) HIP_OK(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, ctx->stream)); };
-    back(sample, d_sample, n * ni * 8); back(traj, d_traj, n * 2 * (size_t)cap2 * 6 * 8); back(len, d_len, n * 2 * 4);
-    back(meta, d_meta, n * 4 * 8); back(attempts, d_att, n * 4);
-    HIP_OK(hipStreamSynchronize(ctx->stream));
-    if (rc != EMGPU_OK) g_err = msg;
-    else if (count > 0) rc = fail(EMGPU_ERR_REJECT_CAP, "terminal track: " + std::to_string(count) + " encounters were still rejected after max_track_attempts");
-    return rc;
+    return copy_back_accepted(ctx, rounds.status("terminal track", "encounters"), [&] {
+        auto back = [&](void *dst, const void *src, size_t bytes) { if (dst && bytes) HIP_OK(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, ctx->stream)); };
+        back(sample, d_sample, n * ni * 8); back(traj, d_traj, n * 2 * (size_t)cap2 * 6 * 8); back(len, d_len, n * 2 * 4);
+        back(meta, d_meta, n * 4 * 8); back(attempts, d_att, n * 4);
+    });
     EMGPU_CATCH
 }
 
@@ -1302,8 +1312,7 @@ int emgpu_sample2track_device(emgpu_ctx *ctx, const emgpu_track_params *p, const
     HIP_OK(hipSetDevice(ctx->device));
     EmgpuTrackRun A{};
     A.n = p->n; A.T = p->T;
-    A.ur_speed = p->ur_speed; A.ur_vertrate = p->ur_vertrate; A.ur_heading = p->ur_heading;
-    A.min_speed = p->min_speed; A.max_speed = p->max_speed;
+    set_track_units(A, p);
     A.alt0_f = alt0; A.speed0_f = speed0; A.dyn_val = dyn_val;
     A.nd = p->nd; A.s_vr = p->slot_vertrate; A.s_acc = p->slot_acc; A.s_tr = p->slot_turnrate;
     A.xyz = xyz; A.flags = flags; A.vmm = speed_minmax;
@@ -1338,8 +1347,7 @@ int emgpu_sample2track_host(emgpu_ctx *ctx, const emgpu_track_params *p, const d
     b.up(d_in + planar.size() + n, speed0, n * sizeof(double));
     EmgpuTrackRun A{};
     A.n = p->n; A.T = p->T;
-    A.ur_speed = p->ur_speed; A.ur_vertrate = p->ur_vertrate; A.ur_heading = p->ur_heading;
-    A.min_speed = p->min_speed; A.max_speed = p->max_speed;
+    set_track_units(A, p);
     A.upd = d_in; A.alt0_d = d_in + planar.size(); A.speed0_d = d_in + planar.size() + n;
     A.xyz = d_xyz; A.flags = d_fl; A.vmm = d_vmm;
     const char *name = "";
@@ -1412,15 +1420,10 @@ static int track_uncor_rounds(emgpu_ctx *ctx, const emgpu_model *h, const emgpu_
     const int sDV = row_of(p->idx_dv), sDH = row_of(p->idx_dh), sDPsi = row_of(p->idx_dpsi);
     const size_t n = (size_t)p->n, ni = (size_t)m.n_initial, nd = (size_t)m.n_dyn(), T = (size_t)p->sample_time, G4 = (T + 3) / 4;
     if (n == 0) return EMGPU_OK;
-    size_t slot = 0;
-    auto dalloc = [&](size_t bytes) { return ctx_scratch(ctx, slot++, bytes ? bytes : 1); };   // kept by the ctx between calls
-    const StreamSyncOnExit drain{ctx->stream};
-    float *d_iv = (float *)dalloc(ni * n * 4), *d_dv = (float *)dalloc(G4 * nd * n * 16);
-    double *d_lim = (double *)dalloc(L.table.size() * 8);
-    uint8_t *d_acc = (uint8_t *)dalloc(n);
-    uint64_t *d_gidx[2] = {(uint64_t *)dalloc(n * 8), (uint64_t *)dalloc(n * 8)};
-    int64_t *d_slot[2] = {(int64_t *)dalloc(n * 8), (int64_t *)dalloc(n * 8)};
-    uint32_t *d_count = (uint32_t *)dalloc(4 * emgpu::compact_scratch_words((int64_t)n));
+    RoundScratch mem(ctx);
+    float *d_iv = mem.alloc<float>(ni * n * 4), *d_dv = mem.alloc<float>(G4 * nd * n * 16);
+    double *d_lim = mem.alloc<double>(L.table.size() * 8);
+    RejectionRounds rounds(ctx, mem, n, p->first_index, p->max_track_attempts);
     HIP_OK(hipMemcpyAsync(d_lim, L.table.data(), L.table.size() * 8, hipMemcpyHostToDevice, ctx->stream));
     HIP_OK(hipStreamSynchronize(ctx->stream)); // L.table is a local
     Uploaded &u = get_uploaded(ctx, h);
@@ -1438,38 +1441,34 @@ static int track_uncor_rounds(emgpu_ctx *ctx, const emgpu_model *h, const emgpu_
     R.ordered = L.ordered; R.rG = L.rG; R.rA = L.rA; R.rL = L.rL; R.rV = L.rV; R.ncL = L.ncL; R.ncV = L.ncV; R.discL = L.discL; R.discV = L.discV;
     memcpy(R.cutL, L.cutL, sizeof R.cutL); memcpy(R.cutV, L.cutV, sizeof R.cutV);
     R.lim = d_lim; R.tracks = d_tracks; R.S = (int64_t)(10 * T / (size_t)p->record_stride + 1); R.limits = d_limits;
-    R.accepted = d_acc; R.attempts = d_attempts;
-    size_t count = n;
-    for (int j = 0; j < p->max_track_attempts && count > 0; j++) {
-        const int cur = j & 1;
+    R.accepted = rounds.accepted(); R.attempts = d_attempts;
+    for (; rounds.more(); rounds.next()) {
+        const size_t count = rounds.count();
         emgpu_sample_params sp;
         memset(&sp, 0, sizeof sp);
-        sp.seed = p->seed + (uint64_t)j;                                  // :428  seed = seed + 1
+        sp.seed = p->seed + (uint64_t)rounds.round();                     // :428  seed = seed + 1
         sp.first_index = p->first_index; sp.n = (int64_t)count; sp.sample_time = p->sample_time;
         sp.flags = p->flags & EMGPU_FLAG_QUANTIZE500; sp.max_attempts = p->max_attempts;
         sp.idx_L = p->idx_L; sp.idx_v = p->idx_v; sp.idx_dh = p->idx_dh;
-        sp.indices = j ? d_gidx[cur] : nullptr;
+        sp.indices = rounds.indices();
         EmgpuRun A;
         fill_run(ctx, u, m, &sp, A);
         A.init_val = d_iv; A.dyn_val = d_dv; A.ld = (int64_t)count;
         // a start grid: round 0 reads row i for lane i, a later round the rows of the trajectories it redraws (its slot list)
-        const EmgpuPresets *presets = d_start ? upload_presets(ctx, u, m, d_start, nullptr, j ? d_slot[cur] : nullptr) : nullptr;
+        const EmgpuPresets *presets = d_start ? upload_presets(ctx, u, m, d_start, nullptr, rounds.slots()) : nullptr;
         launch_dbn(ctx, u, A, nullptr, presets);                          // :424  self.sample(1, sample_time, 'seed', seed)
         const std::string sampler = ctx->last_kernel;
         R.n = (int64_t)count; R.ld = (int64_t)count;
         auto row = [&](int idx) -> const float * { return idx > 0 ? d_iv + (size_t)(idx - 1) * count : nullptr; };
         R.iG = row(p->idx_G); R.iA = row(p->idx_A); R.iL = row(p->idx_L); R.iV = row(p->idx_v);
         R.iDV = row(p->idx_dv); R.iDH = row(p->idx_dh); R.iDPsi = row(p->idx_dpsi);
-        R.dyn_val = d_dv; R.slot = j ? d_slot[cur] : nullptr;
-        R.attempt_no = j + 1; R.last_round = (j + 1 == p->max_track_attempts);
+        R.dyn_val = d_dv; R.slot = rounds.slots();
+        R.attempt_no = rounds.attempt_no(); R.last_round = rounds.last_round();
         const char *name = "";
         launch_ok(emgpu::launch_uncor_track(R, ctx->stream, &name));
         ctx->last_kernel = sampler + " + " + name;
-        count = compact_rejected(ctx, j, count, p->first_index, d_acc, d_gidx, d_slot, d_count);
     }
-    int rc = emgpu_ctx_sync(ctx);   // the sampler's own rejection cap
-    if (rc == EMGPU_OK && count > 0) rc = fail(EMGPU_ERR_REJECT_CAP, "track: " + std::to_string(count) + " trajectories were still rejected after max_track_attempts");
-    return rc;
+    return rounds.status("track", "trajectories");
 }
 
 int emgpu_track_uncor_grid_device(emgpu_ctx *ctx, const emgpu_model *h, const emgpu_utrack_params *p, const int32_t *start, double *tracks, double *limits,
@@ -1508,16 +1507,11 @@ int emgpu_track_uncor_grid_host(emgpu_ctx *ctx, const emgpu_model *h, const emgp
         b.up(ds, start, bytes);
         HIP_OK(hipStreamSynchronize(ctx->stream));   // start is caller memory
     }
-    const int rc = track_uncor_rounds(ctx, h, p, ds, dt, dl, da);
-    if (rc == EMGPU_OK || rc == EMGPU_ERR_REJECT_CAP) {
-        const std::string msg = g_err;
+    return copy_back_accepted(ctx, track_uncor_rounds(ctx, h, p, ds, dt, dl, da), [&] {
         b.down(tracks, dt, n * S * 8 * sizeof(double));
         b.down(limits, dl, n * 3 * sizeof(double));
         b.down(attempts, da, n * 4);
-        HIP_OK(hipStreamSynchronize(ctx->stream));
-        if (rc != EMGPU_OK) g_err = msg;
-    }
-    return rc;
+    });
     EMGPU_CATCH
 }
 

@@ -1362,7 +1362,7 @@ int emgpu_tracks_text_host(emgpu_ctx *ctx, const emgpu_track_params *p, const em
         B.up(d_xoff, xoff.data(), (n + 1) * 8);
         emgpu::EmgpuTrackTableRun A{};
         A.n = (int64_t)n;
-        A.ur_speed = p->ur_speed; A.ur_vertrate = p->ur_vertrate; A.ur_heading = p->ur_heading; A.min_speed = p->min_speed; A.max_speed = p->max_speed;
+        set_track_units(A, p);
         A.alt0 = d_in + n; A.speed0 = d_in + 2 * n;
         A.table = T.d; A.ncol = ncol; A.c_vr = in->col_vertrate; A.c_acc = in->col_acc; A.c_tr = in->col_turnrate;
         A.first = d_first; A.len = d_len; A.rowidx = d_rowidx; A.xoff = d_xoff; A.xyz = d_xyz; A.flags = d_flags; A.vmm = d_vmm;

@@ -113,9 +113,20 @@ struct emgpu_ctx {
 };
 
 // emgpu_capi.cpp
-void *ctx_scratch(emgpu_ctx *ctx, size_t slot, size_t bytes);   // slot-th scratch buffer of the ctx, at least `bytes` long
+// slot-th scratch buffer of the ctx, at least `bytes` long.  Two users share the slots: the host-path sampling entry points of emgpu_host.cpp
+// take slot 0 (the start grid) and slot 1 (the index list) by number, and the round drivers of emgpu_capi.cpp (RoundScratch) take 0 ... k in
+// request order.  They never meet in one call: a host-path entry point samples through the *_device entry points and never enters a round
+// driver, a round driver draws through launch_dbn / launch_bn and never enters the host path, and CTX_LOCK lets one call at a time use a ctx.
+void *ctx_scratch(emgpu_ctx *ctx, size_t slot, size_t bytes);
 // emgpu_host.cpp
 void ctx_release_host_side(emgpu_ctx *ctx, bool everything);    // trim (false: pools and staging) / free (true: streams and events too)
+
+// sample2track.m:113-139: the unit ratios and the speed limits of a track call, into the kernel argument struct of either track kernel
+// (EmgpuTrackRun, EmgpuTrackTableRun)
+template <typename Run> void set_track_units(Run &A, const emgpu_track_params *p) {
+    A.ur_speed = p->ur_speed; A.ur_vertrate = p->ur_vertrate; A.ur_heading = p->ur_heading;
+    A.min_speed = p->min_speed; A.max_speed = p->max_speed;
+}
 
 #define CTX_LOCK(ctx) std::lock_guard<std::recursive_mutex> _ctx_lock((ctx)->mu)
 
@@ -147,3 +158,28 @@ class CallBuffers {
     std::vector<void *> ptrs_;
 };
 
+// The device scratch of one round-driver call: the ctx's scratch blocks 0, 1, ... in request order (kept by the ctx between calls).  The
+// stream is synchronized when the scope ends, however it ends: the rounds' launches read this scratch and the caller's buffers.
+class RoundScratch {
+  public:
+    explicit RoundScratch(emgpu_ctx *ctx) : ctx_(ctx) {}
+    RoundScratch(const RoundScratch &) = delete;
+    RoundScratch &operator=(const RoundScratch &) = delete;
+    ~RoundScratch() { (void)hipStreamSynchronize(ctx_->stream); }
+    template <typename T> T *alloc(size_t bytes) { return static_cast<T *>(ctx_scratch(ctx_, slot_++, bytes ? bytes : 1)); }
+
+  private:
+    emgpu_ctx *ctx_;
+    size_t slot_ = 0;
+};
+
+// What a round driver's host wrapper does with the rounds' status: under EMGPU_OK or EMGPU_ERR_REJECT_CAP (the accepted lanes are valid, the
+// others carry attempts -1) copy() brings the outputs back, and the rounds' message survives whatever the copies do to the thread's.
+template <typename Copy> int copy_back_accepted(emgpu_ctx *ctx, int rc, Copy copy) {
+    if (rc != EMGPU_OK && rc != EMGPU_ERR_REJECT_CAP) return rc;
+    const std::string msg = g_err;
+    copy();
+    HIP_OK(hipStreamSynchronize(ctx->stream));
+    if (rc != EMGPU_OK) g_err = msg;
+    return rc;
+}

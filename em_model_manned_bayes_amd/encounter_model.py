@@ -417,6 +417,27 @@ class UncorEncounterModel(EncounterModel):
                          isOverwriteZeroBoundaries=isOverwriteZeroBoundaries)
         self.isRotorcraft = "rotorcraft" in os.path.basename(str(parameters_filename))  # :181-185
 
+    def _track_variables(self):
+        """The 1-based ids of L, v, \\dot v, \\dot h, \\dot \\psi by label (0: the model has none); without the three rates: dynvar:empty
+        (UncorEncounterModel.m:231-234)."""
+        labs = self.labels_initial
+        idx = [labs.index('"%s"' % name) + 1 if '"%s"' % name in labs else 0 for name in ("L", "v", "\\dot v", "\\dot h", "\\dot \\psi")]
+        if not all(idx[2:]):
+            e = L.EmgpuError(L.ERR_ARG, "Model does not have a dynamic variable for either acceleration, vertical rate, or turn rate")
+            e.identifier = "dynvar:empty"
+            raise e
+        return idx
+
+    def _grid_and_log_weight(self, start_grid, n, return_log_weight):
+        """(the start grid or None, log P(presets of row i) per sample or None).  The weights come from the host function the device's own
+        weights are bit-equal to (the device-formatted call has no weight output); a grid whose weights nobody asked for goes through it as
+        well: a bad row is reported with its number, before anything is drawn."""
+        grid = self._start_grid(start_grid, n) if start_grid is not None else None
+        if return_log_weight or grid is not None:
+            w = native.start_grid_log_weight(self.native, grid if grid is not None else np.zeros((n, self.n_initial), dtype=np.int32))
+            return grid, (w if return_log_weight else None)
+        return grid, None
+
     def sample(self, n_samples, sample_time, seed=None, isQuantize500=False, layers=None,
                transition_mode=L.TRANSITION_REFERENCE_AUTO, max_attempts=1000, first_index=None, ctx=None, lazy=False,
                start_grid=None, return_log_weight=False):
@@ -433,16 +454,7 @@ class UncorEncounterModel(EncounterModel):
         lazy=True: the same four outputs, bit for bit, with out_samples and the controls built on the GPU (emgpu_sample_uncor_host) and
         out_events / out_samples / out_EME handed out as LazyEvents / LazySamples / LazyControls: sequences that build sample i's object when
         it is accessed."""
-        labs = self.labels_initial
-
-        def find(name):
-            q = '"%s"' % name
-            return labs.index(q) + 1 if q in labs else 0
-        idxL, idxV, idxDV, idxDH, idxDPsi = find("L"), find("v"), find("\\dot v"), find("\\dot h"), find("\\dot \\psi")
-        if not (idxDV and idxDH and idxDPsi):  # :231-234
-            e = L.EmgpuError(L.ERR_ARG, "Model does not have a dynamic variable for either acceleration, vertical rate, or turn rate")
-            e.identifier = "dynvar:empty"
-            raise e
+        idxL, idxV, idxDV, idxDH, idxDPsi = self._track_variables()
         s, first = _take(seed, n_samples)
         if first_index is not None:
             first = int(first_index)
@@ -451,13 +463,7 @@ class UncorEncounterModel(EncounterModel):
         flags = L.FLAG_QUANTIZE500 if isQuantize500 else 0
         n_samples = int(n_samples)
         ni, T = self.n_initial, int(sample_time)
-        grid = self._start_grid(start_grid, n_samples) if start_grid is not None else None
-        # the weights come from the host function the device's own weights are bit-equal to: the device-formatted call has no weight output
-        log_weight = None
-        if return_log_weight:
-            log_weight = native.start_grid_log_weight(m, grid if grid is not None else np.zeros((n_samples, ni), dtype=np.int32))
-        elif grid is not None:
-            native.start_grid_log_weight(m, grid)   # a bad row is reported with its number, before anything is drawn
+        grid, log_weight = self._grid_and_log_weight(start_grid, n_samples, return_log_weight)
         out_inits = np.zeros((n_samples, ni))
         out_events, out_samples, out_EME = [None] * n_samples, [None] * n_samples, [None] * n_samples
         if lazy:
@@ -589,20 +595,11 @@ class UncorEncounterModel(EncounterModel):
         if str(coordSys).lower() != "neu":
             raise NotImplementedError("coordSys 'geodetic' needs a DEM, the digital obstacle file and em-core's placeTrack "
                                       "(UncorEncounterModel.m:480-540): out of scope, use 'NEU'")
-        for lab in ('"\\dot v"', '"\\dot h"', '"\\dot \\psi"'):
-            if lab not in self.labels_initial:
-                e = L.EmgpuError(L.ERR_ARG, "Model does not have a dynamic variable for either acceleration, vertical rate, or turn rate")
-                e.identifier = "dynvar:empty"
-                raise e
+        self._track_variables()
         s, first = _take(initialSeed, nSamples)
         if first_index is not None:
             first = int(first_index)
-        grid = self._start_grid(start_grid, nSamples) if start_grid is not None else None
-        log_weight = None
-        if return_log_weight:
-            log_weight = native.start_grid_log_weight(self.native, grid if grid is not None else np.zeros((int(nSamples), self.n_initial), dtype=np.int32))
-        elif grid is not None:
-            native.start_grid_log_weight(self.native, grid)   # a bad row is reported with its number, before anything is drawn
+        grid, log_weight = self._grid_and_log_weight(start_grid, int(nSamples), return_log_weight)
         res = native.track_uncor_host(ctx or native.default_context(), self.native, int(nSamples), int(sample_time), s, first_index=first,
                                       is_quantize500=isQuantize500, is_rotorcraft=self.isRotorcraft, max_track_attempts=max_track_attempts,
                                       record_stride=record_stride, start=grid)

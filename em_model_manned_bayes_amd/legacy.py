@@ -12,6 +12,7 @@ native.sample2track_device (it reads the sampler's dense trace in place).
 import os
 import re
 import time
+import types
 
 import numpy as np
 
@@ -177,6 +178,56 @@ def _matlab_round(x):
     return np.sign(x) * np.floor(np.abs(x) + 0.5)
 
 
+UR_SPEED, UR_VERTRATE, UR_HEADING = FT_PER_NM / 3600.0, 1.0 / 60.0, 1.0        # sample2track.m:113-123 (both branches)
+
+
+def _altitude_grid(min_alt, max_alt):
+    """The edges of the altitude directories, step 100 ft (sample2track.m:150-158)."""
+    first = np.floor(min_alt - 50.0) if min_alt % 100.0 != 0 else min_alt
+    Lgrid = np.arange(first, max_alt + 200.0 + 1e-9, 100.0)
+    if Lgrid[0] < 0:
+        Lgrid[0] = 0.0
+    return Lgrid
+
+
+def _make_directories(out_dir_parent, Lgrid, geo=None, air=None):
+    """Every altitude directory, under every G<g>/A<a> of the initial table for an uncor model that has both (sample2track.m:161-178)."""
+    os.makedirs(out_dir_parent, exist_ok=True)
+    tops = [()] if geo is None else [("G%i" % g, "A%i" % a) for g in np.unique(geo) for a in np.unique(air)]
+    for top in tops:
+        for l in Lgrid:
+            os.makedirs(os.path.join(out_dir_parent, *top, "%ift" % l), exist_ok=True)
+
+
+def _track_file_name(rows, track_no, z0, v0):
+    """sample2track.m:249 (round: half away from zero)."""
+    return "BAYES_t%i_id%i_alt%i_speed%i.csv" % (rows, track_no, _matlab_round(z0), _matlab_round(v0))
+
+
+def _altitude_directory(Lgrid, z0):
+    """The directory of discretize(z0, L) (sample2track.m:263): bin k holds [L(k), L(k + 1)), the last one its top edge as well."""
+    k = int(np.searchsorted(Lgrid, z0, side="right")) - 1
+    if z0 == Lgrid[-1]:
+        k = len(Lgrid) - 2
+    if k < 0 or k >= len(Lgrid) - 1:
+        raise ValueError("sample2track: initial altitude %g ft is outside the altitude directories" % z0)
+    return "%ift" % Lgrid[k]
+
+
+def _host_csv(xyz):
+    """A track's file as the host formats it (sample2track.m:274-279)."""
+    return ("time_s,x_ft,y_ft,z_ft\n" + "".join("%i,%0.0f,%0.0f,%0.0f\n" % (t, xyz[t, 0], xyz[t, 1], xyz[t, 2]) for t in range(xyz.shape[0]))).encode("utf-8")
+
+
+def _t_initial(Ti, names_i, c):
+    """T_initial as a dict of columns, speed, acceleration and vertical rate in the tracks' units (sample2track.m:126-128)."""
+    T_initial = {name: Ti[:, k].copy() for k, name in enumerate(names_i)}
+    for k, ur in ((c.spd, UR_SPEED), (c.acc, UR_SPEED), (c.vr, UR_VERTRATE)):
+        if k is not None:
+            T_initial[names_i[k]] *= ur
+    return T_initial
+
+
 def sample2track(parameters_filename, initial_filename, transition_filename, num_max_tracks=10000, out_dir_parent=None,
                  label_initial_geographic="G", label_initial_airspace="A", label_initial_altitude="L", label_initial_speed="v",
                  label_initial_acceleration="dotV", label_initial_vertrate="dotH", label_initial_turnrate="dotPsi",
@@ -204,39 +255,68 @@ def sample2track(parameters_filename, initial_filename, transition_filename, num
     labels_trans = [make_valid_name(_erase(parameters["labels_transition"][int(r[1]) - 1])) for r in tm]  # :64
     names_i = ["id"] + labels_init
     names_t = ["id", "t"] + labels_trans
-    if text == "device":
-        return _sample2track_device_text(ctx or native.default_context(), parameters, parameters_filename, initial_filename, transition_filename,
-                                         names_i, names_t, labels_init, int(num_max_tracks), out_dir_parent,
-                                         (label_initial_geographic, label_initial_airspace, label_initial_altitude, label_initial_speed,
-                                          label_initial_acceleration, label_initial_vertrate),
-                                         (label_transition_speed, label_transition_altitude, label_transition_heading),
-                                         int(rng_seed), write_files, verbose)
-    Ti = _read_table(initial_filename, len(names_i))
-    Tt = _read_table(transition_filename, len(names_t))
-    if Ti.shape[0] > num_max_tracks:                                                                       # :75-77
-        keep = np.random.RandomState(int(rng_seed)).permutation(Ti.shape[0])[: int(num_max_tracks)]
-        Ti = Ti[keep]
-    num_tracks = Ti.shape[0]
 
-    def col(names, label):
-        return names.index(label) if label in names else None
+    def prepare(Ti):
+        """What either reader does with the initial table once both files are read: the selection, the columns, the limits."""
+        c = types.SimpleNamespace(rows_read=Ti.shape[0])
+        if Ti.shape[0] > num_max_tracks:                                                                   # :75-77
+            Ti = Ti[np.random.RandomState(int(rng_seed)).permutation(Ti.shape[0])[: int(num_max_tracks)]]
+        c.Ti = Ti
+        col = lambda names, label: names.index(label) if label in names else None
+        c.geo, c.air, c.alt, c.spd, c.acc, c.vr = (col(names_i, l) for l in (
+            label_initial_geographic, label_initial_airspace, label_initial_altitude, label_initial_speed, label_initial_acceleration, label_initial_vertrate))
+        c.u_acc, c.u_vr, c.u_tr = (col(names_t, l) for l in (label_transition_speed, label_transition_altitude, label_transition_heading))
+        for what, k in (("altitude", c.alt), ("speed", c.spd), ("transition speed", c.u_acc), ("transition altitude", c.u_vr),
+                        ("transition heading", c.u_tr)):
+            if k is None:
+                raise ValueError("sample2track: no %s column with the given label" % what)
+        b_alt = np.asarray(parameters["boundaries"][labels_init.index(label_initial_altitude)], dtype=np.float64)
+        b_spd = np.asarray(parameters["boundaries"][labels_init.index(label_initial_speed)], dtype=np.float64)
+        c.min_alt, c.max_alt = float(b_alt[0]), float(b_alt[-1])                                           # :100-101
+        c.min_speed, c.max_speed = float(b_spd[0]), float(b_spd[-1])                                       # :104-105
+        return c
 
-    ci_geo, ci_air = col(names_i, label_initial_geographic), col(names_i, label_initial_airspace)
-    ci_alt, ci_spd = col(names_i, label_initial_altitude), col(names_i, label_initial_speed)
-    ci_acc, ci_vr = col(names_i, label_initial_acceleration), col(names_i, label_initial_vertrate)
-    cu_acc, cu_vr, cu_tr = col(names_t, label_transition_speed), col(names_t, label_transition_altitude), col(names_t, label_transition_heading)
-    for what, c in (("altitude", ci_alt), ("speed", ci_spd), ("transition speed", cu_acc), ("transition altitude", cu_vr),
-                    ("transition heading", cu_tr)):
-        if c is None:
-            raise ValueError("sample2track: no %s column with the given label" % what)
-    b_alt = np.asarray(parameters["boundaries"][labels_init.index(label_initial_altitude)], dtype=np.float64)
-    b_spd = np.asarray(parameters["boundaries"][labels_init.index(label_initial_speed)], dtype=np.float64)
-    min_alt, max_alt = float(b_alt[0]), float(b_alt[-1])                                                   # :100-101
-    min_speed, max_speed = float(b_spd[0]), float(b_spd[-1])                                               # :104-105
-    base = os.path.basename(parameters_filename)
-    ur_speed, ur_vertrate, ur_heading = FT_PER_NM / 3600.0, 1.0 / 60.0, 1.0                                # :113-123 (both branches)
-    is_uncor = "uncor_" in base
+    reader = _sample2track_device_text if text == "device" else _sample2track_host_text
+    c, flags, vmm, lengths, file_bytes, st = reader(ctx, initial_filename, transition_filename, len(names_i), len(names_t), prepare, write_files)
+    Ti, num_tracks = c.Ti, c.Ti.shape[0]
+    is_good = flags == 0                                                                                   # :243
+    Lgrid = _altitude_grid(c.min_alt, c.max_alt)
+    is_geo, is_air = c.geo is not None, c.air is not None
+    t0 = time.perf_counter()
+    if write_files:
+        both = "uncor_" in os.path.basename(parameters_filename) and is_geo and is_air
+        _make_directories(out_dir_parent, Lgrid, Ti[:, c.geo] if both else None, Ti[:, c.air] if both else None)
+    made = set()
+    for i in range(num_tracks):
+        if not is_good[i]:
+            if verbose:
+                print("Reject i=%i, CFIT = %i, v = [%0.3f, %0.3f]" % (i + 1, int(flags[i] & 1), vmm[i, 0], vmm[i, 1]))   # :284
+            continue
+        if not write_files:
+            continue
+        z0, v0 = Ti[i, c.alt], Ti[i, c.spd] * UR_SPEED
+        parts = (["G%i" % Ti[i, c.geo]] if is_geo else []) + (["A%i" % Ti[i, c.air]] if is_air else [])   # :253-260
+        out_dir = os.path.join(out_dir_parent, *parts, _altitude_directory(Lgrid, z0))
+        if out_dir not in made:
+            os.makedirs(out_dir, exist_ok=True)
+            made.add(out_dir)
+        with open(os.path.join(out_dir, _track_file_name(lengths[i], i + 1, z0, v0)), "wb") as f:          # :274-279
+            f.write(file_bytes(i))
+    if st is not None:                                      # the device reader's account of the call
+        st = dict(st[0], write_ms=(time.perf_counter() - t0) * 1e3, **st[1])
+        st.update(tracks=int(num_tracks), accepted=int(is_good.sum()))
+        last_track_stats.clear()
+        last_track_stats.update(st)
+    return is_good, _t_initial(Ti, names_i, c)
 
+
+def _sample2track_host_text(ctx, initial_filename, transition_filename, ncol_i, ncol_t, prepare, write_files):
+    """sample2track(text="host"): both files through numpy.loadtxt, the transition rows grouped on the host, one launch per distinct track
+    length (native.sample2track_host); a track's file is formatted in Python from its positions."""
+    Ti = _read_table(initial_filename, ncol_i)
+    Tt = _read_table(transition_filename, ncol_t)
+    c = prepare(Ti)
+    Ti, num_tracks = c.Ti, c.Ti.shape[0]
     # group the transition rows by id, in file order (:192-193)
     T_of = {}
     order = np.argsort(Tt[:, 0], kind="stable") if Tt.shape[0] else np.zeros(0, dtype=np.int64)
@@ -255,72 +335,18 @@ def sample2track(parameters_filename, initial_filename, transition_filename, num
         sel = np.flatnonzero(lens == T)
         if T == 0:
             for i in sel:                           # no transition rows: the track is its initial point (:196 never runs)
-                z0, v0 = Ti[i, ci_alt], Ti[i, ci_spd] * ur_speed
+                z0, v0 = Ti[i, c.alt], Ti[i, c.spd] * UR_SPEED
                 xyz_all[i] = np.array([[0.0, 0.0, z0]])
-                flags[i] = (1 if z0 < 0 else 0) | (2 if (v0 <= min_speed * ur_speed or v0 >= max_speed * ur_speed) else 0)
+                flags[i] = (1 if z0 < 0 else 0) | (2 if (v0 <= c.min_speed * UR_SPEED or v0 >= c.max_speed * UR_SPEED) else 0)
                 vmm[i] = (v0, v0)
             continue
-        upd = np.stack([Tt[T_of[Ti[i, 0]]][:, [cu_vr, cu_acc, cu_tr]] for i in sel])
-        x, f, v = native.sample2track_host(context, Ti[sel, ci_alt], Ti[sel, ci_spd], upd, ur_speed, ur_vertrate, ur_heading,
-                                           min_speed, max_speed)
+        upd = np.stack([Tt[T_of[Ti[i, 0]]][:, [c.u_vr, c.u_acc, c.u_tr]] for i in sel])
+        x, f, v = native.sample2track_host(context, Ti[sel, c.alt], Ti[sel, c.spd], upd, UR_SPEED, UR_VERTRATE, UR_HEADING,
+                                           c.min_speed, c.max_speed)
         for q, i in enumerate(sel):
             xyz_all[i] = x[q]
         flags[sel], vmm[sel] = f, v
-    is_good = flags == 0                                                                                   # :243
-
-    # altitude directories, step 100 ft (:150-158)
-    if min_alt % 100.0 != 0:
-        Lgrid = np.arange(np.floor(min_alt - 50.0), max_alt + 200.0 + 1e-9, 100.0)
-    else:
-        Lgrid = np.arange(min_alt, max_alt + 200.0 + 1e-9, 100.0)
-    if Lgrid[0] < 0:
-        Lgrid[0] = 0.0
-    is_geo, is_air = ci_geo is not None, ci_air is not None
-    if write_files:
-        os.makedirs(out_dir_parent, exist_ok=True)
-        if is_uncor and is_geo and is_air:                                                                # :161-173
-            for g in np.unique(Ti[:, ci_geo]):
-                for a in np.unique(Ti[:, ci_air]):
-                    for l in Lgrid:
-                        os.makedirs(os.path.join(out_dir_parent, "G%i" % g, "A%i" % a, "%ift" % l), exist_ok=True)
-        else:                                                                                              # :175-178
-            for l in Lgrid:
-                os.makedirs(os.path.join(out_dir_parent, "%ift" % l), exist_ok=True)
-
-    for i in range(num_tracks):
-        xyz = xyz_all[i]
-        if not is_good[i]:
-            if verbose:
-                print("Reject i=%i, CFIT = %i, v = [%0.3f, %0.3f]" % (i + 1, int(flags[i] & 1), vmm[i, 0], vmm[i, 1]))   # :284
-            continue
-        if not write_files:
-            continue
-        z0, v0 = xyz[0, 2], Ti[i, ci_spd] * ur_speed
-        out_name = "BAYES_t%i_id%i_alt%i_speed%i.csv" % (xyz.shape[0] - 1, i + 1, _matlab_round(z0), _matlab_round(v0))     # :249
-        k = int(np.searchsorted(Lgrid, z0, side="right")) - 1                                              # discretize(z0, L), :263
-        if z0 == Lgrid[-1]:
-            k = len(Lgrid) - 2
-        if k < 0 or k >= len(Lgrid) - 1:
-            raise ValueError("sample2track: initial altitude %g ft is outside the altitude directories" % z0)
-        parts = []
-        if is_geo:
-            parts.append("G%i" % Ti[i, ci_geo])                                                            # :253-255
-        if is_air:
-            parts.append("A%i" % Ti[i, ci_air])                                                            # :258-260
-        parts.append("%ift" % Lgrid[k])
-        out_dir = os.path.join(out_dir_parent, *parts)
-        os.makedirs(out_dir, exist_ok=True)
-        with open(os.path.join(out_dir, out_name), "w", encoding="utf-8", newline="\n") as f:              # :274-279
-            f.write("time_s,x_ft,y_ft,z_ft\n")
-            f.write("".join("%i,%0.0f,%0.0f,%0.0f\n" % (t, xyz[t, 0], xyz[t, 1], xyz[t, 2]) for t in range(xyz.shape[0])))
-
-    T_initial = {name: Ti[:, c].copy() for c, name in enumerate(names_i)}
-    T_initial[names_i[ci_spd]] *= ur_speed                                                                 # :126-128
-    if ci_acc is not None:
-        T_initial[names_i[ci_acc]] *= ur_speed
-    if ci_vr is not None:
-        T_initial[names_i[ci_vr]] *= ur_vertrate
-    return is_good, T_initial
+    return c, flags, vmm, lens, lambda i: _host_csv(xyz_all[i]), None
 
 
 def _read_rows(filename, ctx=None):
@@ -337,47 +363,28 @@ def _read_rows(filename, ctx=None):
     return data[head:], head
 
 
-def _sample2track_device_text(ctx, parameters, parameters_filename, initial_filename, transition_filename, names_i, names_t, labels_init,
-                              num_max_tracks, out_dir_parent, labels_i, labels_t, rng_seed, write_files, verbose):
-    """sample2track(text="device"): the steps of sample2track above with both tables parsed, the tracks integrated and the CSV rows formatted
-    on the device; selection, directories and file names are computed here from the initial table, as there."""
+def _sample2track_device_text(ctx, initial_filename, transition_filename, ncol_i, ncol_t, prepare, write_files):
+    """sample2track(text="device"): both tables parsed, the tracks integrated and the CSV rows formatted on the device (native.parse_table,
+    native.tracks_text_host); a track's file is its slice of the device's CSV text, or the host's formatting of its positions where the
+    device does not format a coordinate.  Also returns the call's account for last_track_stats, the parts before and after write_ms."""
+    ctx = ctx or native.default_context()
     st = {}
     t0 = time.perf_counter()
     rows_i, _ = _read_rows(initial_filename)
-    Ti = native.parse_table(ctx, rows_i, len(names_i), header_lines=1)
+    Ti = native.parse_table(ctx, rows_i, ncol_i, header_lines=1)
     rows_t, _ = _read_rows(transition_filename, ctx)
     st["read_ms"] = (time.perf_counter() - t0) * 1e3
-    n_initial_rows = Ti.shape[0]
-    if Ti.shape[0] > num_max_tracks:                                                                       # :75-77
-        keep = np.random.RandomState(rng_seed).permutation(Ti.shape[0])[:num_max_tracks]
-        Ti = Ti[keep]
-    num_tracks = Ti.shape[0]
-
-    def col(names, label):
-        return names.index(label) if label in names else None
-
-    ci_geo, ci_air, ci_alt, ci_spd, ci_acc, ci_vr = (col(names_i, l) for l in labels_i)
-    cu_acc, cu_vr, cu_tr = (col(names_t, l) for l in labels_t)
-    for what, c in (("altitude", ci_alt), ("speed", ci_spd), ("transition speed", cu_acc), ("transition altitude", cu_vr),
-                    ("transition heading", cu_tr)):
-        if c is None:
-            raise ValueError("sample2track: no %s column with the given label" % what)
-    b_alt = np.asarray(parameters["boundaries"][labels_init.index(labels_i[2])], dtype=np.float64)
-    b_spd = np.asarray(parameters["boundaries"][labels_init.index(labels_i[3])], dtype=np.float64)
-    min_alt, max_alt = float(b_alt[0]), float(b_alt[-1])                                                   # :100-101
-    min_speed, max_speed = float(b_spd[0]), float(b_spd[-1])                                               # :104-105
-    ur_speed, ur_vertrate, ur_heading = FT_PER_NM / 3600.0, 1.0 / 60.0, 1.0                                # :113-123
-    is_uncor = "uncor_" in os.path.basename(parameters_filename)
-
+    c = prepare(Ti)
+    Ti, num_tracks = c.Ti, c.Ti.shape[0]
     # the CSV buffer: sized from the look of the file's first rows, and from the library's exact total when that was too little
     csv_cap = None
     if write_files:
         head = rows_t[: 1 << 20]
         per_line = head.size / max(int(np.count_nonzero(head == 10)), 1)
-        share = num_tracks / max(n_initial_rows, 1)
+        share = num_tracks / max(c.rows_read, 1)
         csv_cap = int(num_tracks * 64 + rows_t.size / max(per_line, 1.0) * share * 30) + (1 << 16)
-    args = (ctx, rows_t, len(names_t), (cu_vr, cu_acc, cu_tr), Ti[:, 0], Ti[:, ci_alt], Ti[:, ci_spd], ur_speed, ur_vertrate, ur_heading,
-            min_speed, max_speed)
+    args = (ctx, rows_t, ncol_t, (c.u_vr, c.u_acc, c.u_tr), Ti[:, 0], Ti[:, c.alt], Ti[:, c.spd], UR_SPEED, UR_VERTRATE, UR_HEADING,
+            c.min_speed, c.max_speed)
     t0 = time.perf_counter()
     try:
         res = native.tracks_text_host(*args, want_csv=write_files, csv_cap=csv_cap)
@@ -389,75 +396,12 @@ def _sample2track_device_text(ctx, parameters, parameters_filename, initial_file
     if write_files and res["totals"]["host_formatted"]:     # coordinates the device does not format: those files are written as the host path writes them
         host_xyz = native.tracks_text_host(*args, want_csv=False, want_xyz=True)["xyz"]
     st["library_ms"] = (time.perf_counter() - t0) * 1e3
-    flags, vmm, lengths = res["flags"], res["speed_minmax"], res["lengths"]
-    is_good = flags == 0                                                                                   # :243
-
-    # altitude directories, step 100 ft (:150-158)
-    if min_alt % 100.0 != 0:
-        Lgrid = np.arange(np.floor(min_alt - 50.0), max_alt + 200.0 + 1e-9, 100.0)
-    else:
-        Lgrid = np.arange(min_alt, max_alt + 200.0 + 1e-9, 100.0)
-    if Lgrid[0] < 0:
-        Lgrid[0] = 0.0
-    is_geo, is_air = ci_geo is not None, ci_air is not None
-    t0 = time.perf_counter()
-    if write_files:
-        os.makedirs(out_dir_parent, exist_ok=True)
-        if is_uncor and is_geo and is_air:                                                                # :161-173
-            for g in np.unique(Ti[:, ci_geo]):
-                for a in np.unique(Ti[:, ci_air]):
-                    for l in Lgrid:
-                        os.makedirs(os.path.join(out_dir_parent, "G%i" % g, "A%i" % a, "%ift" % l), exist_ok=True)
-        else:                                                                                              # :175-178
-            for l in Lgrid:
-                os.makedirs(os.path.join(out_dir_parent, "%ift" % l), exist_ok=True)
+    after = {"library_call_ms": res["host_stats"]["total_ms"], "bytes_transition": int(rows_t.size)}
+    after.update({k + "_ms": v for k, v in res["phase_ms"].items()})
+    after.update(res["totals"])
     csv = res["csv"]
     offs = res["offsets"].astype(np.int64).tolist() if write_files else None
-    made = set()
-    for i in range(num_tracks):
-        if not is_good[i]:
-            if verbose:
-                print("Reject i=%i, CFIT = %i, v = [%0.3f, %0.3f]" % (i + 1, int(flags[i] & 1), vmm[i, 0], vmm[i, 1]))   # :284
-            continue
-        if not write_files:
-            continue
-        z0, v0 = Ti[i, ci_alt], Ti[i, ci_spd] * ur_speed
-        out_name = "BAYES_t%i_id%i_alt%i_speed%i.csv" % (lengths[i], i + 1, _matlab_round(z0), _matlab_round(v0))               # :249
-        k = int(np.searchsorted(Lgrid, z0, side="right")) - 1                                              # discretize(z0, L), :263
-        if z0 == Lgrid[-1]:
-            k = len(Lgrid) - 2
-        if k < 0 or k >= len(Lgrid) - 1:
-            raise ValueError("sample2track: initial altitude %g ft is outside the altitude directories" % z0)
-        parts = []
-        if is_geo:
-            parts.append("G%i" % Ti[i, ci_geo])                                                            # :253-255
-        if is_air:
-            parts.append("A%i" % Ti[i, ci_air])                                                            # :258-260
-        parts.append("%ift" % Lgrid[k])
-        out_dir = os.path.join(out_dir_parent, *parts)
-        if out_dir not in made:
-            os.makedirs(out_dir, exist_ok=True)
-            made.add(out_dir)
-        if offs[i + 1] > offs[i]:
-            with open(os.path.join(out_dir, out_name), "wb") as f:                                         # :274-279
-                f.write(csv[offs[i]:offs[i + 1]].data)
-        else:
-            xyz = host_xyz[i]
-            with open(os.path.join(out_dir, out_name), "w", encoding="utf-8", newline="\n") as f:
-                f.write("time_s,x_ft,y_ft,z_ft\n")
-                f.write("".join("%i,%0.0f,%0.0f,%0.0f\n" % (t, xyz[t, 0], xyz[t, 1], xyz[t, 2]) for t in range(xyz.shape[0])))
-    st["write_ms"] = (time.perf_counter() - t0) * 1e3
-    st.update({"library_call_ms": res["host_stats"]["total_ms"], "bytes_transition": int(rows_t.size), "tracks": int(num_tracks),
-               "accepted": int(is_good.sum())})
-    st.update({k + "_ms": v for k, v in res["phase_ms"].items()})
-    st.update(res["totals"])
-    last_track_stats.clear()
-    last_track_stats.update(st)
 
-    T_initial = {name: Ti[:, c].copy() for c, name in enumerate(names_i)}
-    T_initial[names_i[ci_spd]] *= ur_speed                                                                 # :126-128
-    if ci_acc is not None:
-        T_initial[names_i[ci_acc]] *= ur_speed
-    if ci_vr is not None:
-        T_initial[names_i[ci_vr]] *= ur_vertrate
-    return is_good, T_initial
+    def file_bytes(i):
+        return csv[offs[i]:offs[i + 1]].data if offs[i + 1] > offs[i] else _host_csv(host_xyz[i])
+    return c, res["flags"], res["speed_minmax"], res["lengths"], file_bytes, (st, after)

@@ -469,6 +469,15 @@ def sample_dbn_host(ctx, model, n, sample_time, seed, want_dense=True, want_even
     return out
 
 
+def _event_cap_error(rc, totals, ev_count=None):
+    """The EmgpuError of ERR_EVENT_CAP with the library's message, `.totals` (the room a retry needs) and `.ev_count` where there is one."""
+    e = L.EmgpuError(rc, L.lib().emgpu_last_error().decode("utf-8", "replace"))
+    e.totals = totals
+    if ev_count is not None:
+        e.ev_count = np.array(ev_count)
+    return e
+
+
 def sample_uncor_host(ctx, model, n, sample_time, seed, ctrl_var, event_cap=256, events_cap=None, controls_cap=None, want_samples=True,
                       pinned=True, **kw):
     """emgpu_sample_uncor_host: UncorEncounterModel.sample's arrays built on the device.  Returns a dict:
@@ -498,9 +507,7 @@ def sample_uncor_host(ctx, model, n, sample_time, seed, ctrl_var, event_cap=256,
     o.ctrl_var[:] = [int(v) for v in ctrl_var]
     rc = L.lib().emgpu_sample_uncor_host(ctx._h, model._h, C.byref(p), C.byref(o))
     if rc == L.ERR_EVENT_CAP:
-        e = L.EmgpuError(rc, L.lib().emgpu_last_error().decode("utf-8", "replace"))
-        e.totals, e.ev_count = (int(totals[0]), int(totals[1])), np.array(ec)
-        raise e
+        raise _event_cap_error(rc, (int(totals[0]), int(totals[1])), ev_count=ec)
     L.check(rc)
     return {"inits": inits, "ev_count": ec, "events": ev[: int(totals[0])], "ctrl_count": cc, "controls": ctl[: int(totals[1])],
             "samples": smp, "attempts": att, "kernel": ctx.last_kernel(), "host_stats": ctx.host_stats()}
@@ -546,9 +553,7 @@ def sample_text_host(ctx, model, n, sample_time, seed, id_first=1, want_arrays=T
             o.dyn_val = _p(dv)
     rc = L.lib().emgpu_sample_text_host(ctx._h, model._h, C.byref(p), C.byref(o))
     if rc == L.ERR_EVENT_CAP:
-        e = L.EmgpuError(rc, L.lib().emgpu_last_error().decode("utf-8", "replace"))
-        e.totals = (int(totals[0]), int(totals[1]))
-        raise e
+        raise _event_cap_error(rc, (int(totals[0]), int(totals[1])))
     L.check(rc)
     out = {"initial": bi[: int(totals[0])], "transition": bt[: int(totals[1])], "totals": (int(totals[0]), int(totals[1])),
            "init_val": None, "dyn_val": None, "kernel": ctx.last_kernel(), "host_stats": ctx.host_stats()}
@@ -757,14 +762,11 @@ def uncor_dynamic_limits(model, initial, up_min, up_max, speed_min, speed_max, i
 TERMINAL_GEO_FIELDS = ("distance", "bearing", "alt", "speed", "heading", "intent")
 
 
-def terminal_sample_params(geom_model, n, seed, dyn_limits, first_index=0, tmax_s=120.0, cap=None, bounds_sample=None,
-                           max_attempts=100000, max_resample=100000, local_smooth=False):
-    """emgpu_tsample_params for emgpu_sample_terminal_device; returns (params, keep-alive) -- the variable ids are looked up by label like
-    @CorTerminalModel/sample.m:56-62 / createEncounter.m:45-49."""
+def _fill_terminal(p, geom_model, n, seed, first_index, tmax_s, dyn_limits, bounds_sample, max_attempts, max_resample, local_smooth):
+    """The fields emgpu_tsample_params and emgpu_ttrack_params share, into either; returns the keep-alive of bounds_sample."""
     labels = [s.strip('"') for s in geom_model.get_labels(L.F_LABELS_INITIAL)]
-    p = L.TSampleParams()
     p.seed, p.first_index, p.n, p.tmax_s = int(seed) & (2**64 - 1), int(first_index), int(n), float(tmax_s)
-    p.max_resample, p.cap, p.max_attempts = int(max_resample), int(cap or (int(tmax_s) + 3)), int(max_attempts)
+    p.max_resample, p.max_attempts = int(max_resample), int(max_attempts)
     p.flags = L.FLAG_LOCAL_SMOOTH if local_smooth else 0
     for i, v in enumerate(np.asarray(dyn_limits, dtype=np.float64).reshape(10)):
         p.dyn_limits[i] = float(v)
@@ -775,7 +777,16 @@ def terminal_sample_params(geom_model, n, seed, dyn_limits, first_index=0, tmax_
     for a, pre in enumerate(("own", "int")):
         for k, f in enumerate(TERMINAL_GEO_FIELDS):
             p.idx[6 * a + k] = labels.index(pre + "_" + f) + 1
-    return p, bs
+    return bs
+
+
+def terminal_sample_params(geom_model, n, seed, dyn_limits, first_index=0, tmax_s=120.0, cap=None, bounds_sample=None,
+                           max_attempts=100000, max_resample=100000, local_smooth=False):
+    """emgpu_tsample_params for emgpu_sample_terminal_device; returns (params, keep-alive) -- the variable ids are looked up by label like
+    @CorTerminalModel/sample.m:56-62 / createEncounter.m:45-49."""
+    p = L.TSampleParams()
+    p.cap = int(cap or (int(tmax_s) + 3))
+    return p, _fill_terminal(p, geom_model, n, seed, first_index, tmax_s, dyn_limits, bounds_sample, max_attempts, max_resample, local_smooth)
 
 
 def sample_terminal_device(ctx, geom_model, traj_models, p, geom_val, geo, model_of, traj, rows, geom_bin=0, attempts=0):
@@ -799,23 +810,12 @@ def track_terminal_host(ctx, geom_model, traj_models, n, seed, dyn_limits, max_c
     CorTerminalModel.createEncounter default to True; PropagateTrajectory (createEncounter.m:93-265) does not smooth, so
     propagate_terminal_host / _joined_host default to False.  The C ABI has no defaults (a zeroed `flags` field is off: set
     EMGPU_FLAG_LOCAL_SMOOTH).  The smoother itself is the library's documented stand-in for em-core's un-vendored local_smooth: UNPINNED."""
-    labels = [s.strip('"') for s in geom_model.get_labels(L.F_LABELS_INITIAL)]
     p = L.TTrackParams()
-    p.seed, p.first_index, p.n, p.tmax_s = int(seed) & (2**64 - 1), int(first_index), int(n), float(tmax_s)
-    p.max_resample, p.max_track_attempts, p.max_attempts = int(max_resample), int(max_track_attempts), int(max_attempts)
-    p.flags = L.FLAG_LOCAL_SMOOTH if local_smooth else 0
-    for i, v in enumerate(np.asarray(dyn_limits, dtype=np.float64).reshape(10)):
-        p.dyn_limits[i] = float(v)
+    bs = _fill_terminal(p, geom_model, n, seed, first_index, tmax_s, dyn_limits, bounds_sample, max_attempts, max_resample, local_smooth)   # (bs: alive through the call)
+    p.max_track_attempts = int(max_track_attempts)
     for a in range(2):
         p.max_cum_turn_deg[a], p.pitch_deg[a] = float(max_cum_turn_deg[a]), float(pitch_deg[a])
     p.min_enc_time_s, p.thres_dist_ft, p.thres_alt_low_ft, p.thres_vertrate_ft_s = float(min_enc_time_s), float(thres_dist_ft), float(thres_alt_low_ft), float(thres_vertrate_ft_s)
-    bs = None
-    if bounds_sample is not None:
-        bs = np.ascontiguousarray(np.asarray(bounds_sample, dtype=np.float64).reshape(geom_model.n_initial, 2))
-        p.bounds_sample = _p(bs)
-    for a, pre in enumerate(("own", "int")):
-        for k, f in enumerate(TERMINAL_GEO_FIELDS):
-            p.idx[6 * a + k] = labels.index(pre + "_" + f) + 1
     ni, cap2 = geom_model.n_initial, 2 * (int(tmax_s) + 3)
     sample = np.zeros((n, ni)); traj = np.zeros((n, 2, cap2, 6)) if want_traj else None; ln = np.zeros((n, 2), dtype=np.int32)
     meta = np.zeros((n, 4)); att = np.zeros(n, dtype=np.int32)
@@ -960,9 +960,7 @@ def tracks_text_host(ctx, text, ncol, cols, ids, alt0, speed0, ur_speed, ur_vert
         if rc == L.ERR_PARSE:
             raise _parse_error(rc, int(header_lines), "tracks_text_host")
         if rc == L.ERR_EVENT_CAP:
-            e = L.EmgpuError(rc, L.lib().emgpu_last_error().decode("utf-8", "replace"))
-            e.totals = totals.copy()
-            raise e
+            raise _event_cap_error(rc, totals.copy())
         L.check(rc)
 
     xyz_buf = None

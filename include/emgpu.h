@@ -503,7 +503,9 @@ int emgpu_propagate_terminal_host(emgpu_ctx *ctx, const emgpu_model *const *mode
  * rejection cap or a re-draw cap).  geom_model: the 15-variable geometry network; traj_models[10] in CorTerminalModel.m:84-100 order with
  * the stay prior set.  DEVICE pointers:
  *   geom_bin [n_i][n] u8 (may be NULL), geom_val [n_i][n] f32: the accepted geometry sample;  attempts [n] i32 (may be NULL)
- *   geo [n][12] f64, model_of [4n] i32: the inputs of createEncounter (outputs here);  traj, rows: as emgpu_propagate_terminal_device */
+ *   geo [n][12] f64, model_of [4n] i32: the inputs of createEncounter (outputs here);  traj, rows: as emgpu_propagate_terminal_device
+ * EMGPU_FLAG_LOCAL_SMOOTH with EMGPU_TERMINAL_BLOCK_ROWS(cap) > 256 is refused with EMGPU_ERR_UNSUPPORTED before anything is launched, like
+ * emgpu_propagate_terminal_device refuses it (it used to run three launches and fail in the smoother's launcher with EMGPU_ERR_HIP). */
 typedef struct {
     uint64_t seed, first_index;
     int64_t n;

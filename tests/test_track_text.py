@@ -5,6 +5,7 @@ import inspect
 import os
 import re
 
+import numpy as np
 import pytest
 
 from em_model_manned_bayes_amd import _lib as L, legacy, native
@@ -90,3 +91,25 @@ def test_the_host_reader_never_calls_the_new_bindings(monkeypatch, tmp_path, mod
     assert seen == ["ctx"]                     # both files were read and grouped by the host code; nothing new was touched
     with pytest.raises(AssertionError, match="called"):
         legacy.sample2track(path, str(fi), str(ft), out_dir_parent=str(tmp_path / "out"), verbose=False, text="device", ctx=object())
+
+
+def test_the_epilogue_helpers_give_sample2track_ms_directories_and_names():
+    """The pieces both readers share, against answers worked out by hand from sample2track.m.
+    :150-158: the model's altitude limits 50 and 5000 ft are no multiples of 100, so the edges are floor(50 - 50) : 100 : 5000 + 200, i.e.
+    0, 100, ..., 5200; a first edge below zero becomes 0 (limits 20 .. 1000: -30, 70, 170, ... -> 0, 70, 170, ...).
+    :263: discretize(z0, L) puts z0 into [L(k), L(k + 1)) and the last edge into the last bin; outside the edges it gives NaN, an error here.
+    :249: sprintf('%i', round(x)) with MATLAB's round, half away from zero: 2500.5 -> 2501, 202.5 -> 203 (numpy and Python give 202)."""
+    g = legacy._altitude_grid(50.0, 5000.0)
+    assert g[0] == 0 and g[-1] == 5200 and len(g) == 53 and np.all(np.diff(g) == 100)
+    assert legacy._altitude_grid(0.0, 5000.0).tolist() == list(range(0, 5201, 100))       # limits on the grid: min : 100 : max + 200
+    low = legacy._altitude_grid(20.0, 1000.0)
+    assert low[0] == 0 and low[1] == 70 and low[2] == 170
+    assert legacy._altitude_directory(g, 1500.0) == "1500ft" and legacy._altitude_directory(g, 1499.9) == "1400ft"
+    assert legacy._altitude_directory(g, 5200.0) == "5100ft"
+    with pytest.raises(ValueError, match="outside the altitude directories"):
+        legacy._altitude_directory(g, 5201.0)
+    with pytest.raises(ValueError, match="outside the altitude directories"):
+        legacy._altitude_directory(g, -1.0)
+    assert legacy._track_file_name(12, 2, 2500.5, 202.5) == "BAYES_t12_id2_alt2501_speed203.csv"
+    assert legacy._track_file_name(0, 1, 1499.4, 99.5) == "BAYES_t0_id1_alt1499_speed100.csv"
+    assert legacy._host_csv(np.array([[0.0, 0.0, 1500.0], [168.8, -0.4, 1501.5]])) == b"time_s,x_ft,y_ft,z_ft\n0,0,0,1500\n1,169,-0,1502\n"
