@@ -791,7 +791,7 @@ int emgpu_sample_dbn_multi_host(emgpu_ctx *const *ctxs, int32_t n_ctx, const emg
     EMGPU_CATCH
 }
 
-// (emgpu_sample_dbn_host, the trace pool and the pinned pool: emgpu_host.cpp)
+// (emgpu_sample_dbn_host: emgpu_host.cpp; the trace pool and the pinned pool: emgpu_memory.cpp)
 
 static void fill_bn(emgpu_ctx *ctx, const Uploaded &u, const Model &m, const emgpu_bn_params *p, EmgpuBnRun &A) {
     memset(&A, 0, sizeof A);

@@ -1,230 +1,19 @@
-// emgpu_host.cpp -- the parts of the C ABI that own memory on behalf of the caller (round 6):
-//   * the trace pool: emgpu_trace_alloc / _out / _report / _free -- device memory for the sampler's outputs whose PLACEMENT has been
-//     measured with the caller's own launch (profiles/r05_placement_probe.txt: the same launch writes one 36 GB allocation in 6.0 ms
-//     and another in 7.1 ms);
-//   * the pinned pool: emgpu_host_alloc / _free;
-//   * emgpu_sample_dbn_host, emgpu_sample_uncor_host (UncorEncounterModel.sample's samples and controls built on the device) and
-//     emgpu_sample_text_host (em_sample's two text files formatted on the device, em_sample.m:85-99): one driver, run_chunks, pipelines all three -- chunk k's launches | chunk k-1's copy over PCIe | chunk k-2's copy into the caller's arrays.
+// emgpu_host.cpp -- the chunked sampling path of the C ABI: emgpu_sample_dbn_host, emgpu_sample_uncor_host (UncorEncounterModel.sample's
+// samples and controls built on the device) and emgpu_sample_text_host (em_sample's two text files formatted on the device,
+// em_sample.m:85-99).  One driver, run_chunks, pipelines all three -- chunk k's launches | chunk k-1's copy over PCIe | chunk k-2's copy
+// into the caller's arrays.  The chunk buffers, the staging buffers and the pinned pool are emgpu_memory.cpp's (emgpu_hostmem.hpp).
 // Reference semantics: the loop over samples of UncorEncounterModel.m:244-300 and the host arrays it returns (:283-300).
 #include <algorithm>
-#include <chrono>
 #include <cstdlib>
 #include <cstring>
-#include <map>
-#include <mutex>
 #include <system_error>
 #include <thread>
 
-#include "emgpu_internal.hpp"
+#include "emgpu_hostmem.hpp"
 
-struct emgpu_trace {
-    emgpu_ctx::TraceBlock blk;
-    emgpu_sample_out out{};
-    emgpu_trace_report_t rep{};
-};
+using namespace emgpu_detail;
 
 namespace {
-using Clock = std::chrono::steady_clock;
-double ms_since(Clock::time_point t0) { return std::chrono::duration<double, std::milli>(Clock::now() - t0).count(); }
-size_t round_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
-
-// ------------------------------------------------------------------------------------------------ device blocks
-// How a block of the trace pool is obtained (round 6, tools/placement_probe5.py, profiles/r06_placement_probe.txt).  The same launch writes a
-// 36 GB trace in 5.9, 6.6 or 7.0 ms depending on the allocation.  Blocks that hipMalloc hands out are mostly of the 6.6 ms kind, now and then
-// of the others; ONE ADDRESS RANGE BACKED BY SEPARATELY CREATED 1 GiB PHYSICAL CHUNKS (hipMemAddressReserve + hipMemCreate + hipMemMap) is of the
-// 5.9 ms kind four to six times out of six, of the 7.0 ms kind the rest (chunks of 256 MiB - 2 GiB alike, 4 GiB chunks like hipMalloc; where the
-// range starts -- on a 1 GiB boundary or 2 MiB off one -- makes no difference: measured both ways).  Why is not known; the allocator does not need
-// to know: blocks of 1 GiB and more are built that way (falling back to hipMalloc where the virtual-memory calls fail), smaller ones come from
-// hipMalloc, and emgpu_trace_alloc MEASURES its candidates -- candidate 0 a plain hipMalloc block, so that the report shows what a caller's own
-// allocation would have got.
-// EMGPU_TRACE_ALLOC (read once; experiments) = "plain": hipMalloc only; "contiguous": hipExtMallocWithFlags(hipDeviceMallocContiguous);
-// "vmm:<chunk MiB>": another chunk size.
-struct VmmBlock { size_t bytes = 0, chunk = 0; std::vector<hipMemGenericAllocationHandle_t> handles; };
-std::mutex g_vmm_mu;
-std::map<void *, VmmBlock> g_vmm;
-struct AllocMode { int mode; size_t chunk; };
-const AllocMode &alloc_mode_once() {
-    static const AllocMode am = [] {   // (a function-local static: initialised once, also when several host threads come here together)
-        AllocMode a{3, (size_t)1 << 30};   // automatic: a range over 1 GiB chunks for blocks of 1 GiB and more, hipMalloc below (and as the fallback)
-        const char *e = getenv("EMGPU_TRACE_ALLOC");
-        if (e && !strncmp(e, "plain", 5)) a.mode = 0;
-        if (e && !strncmp(e, "contiguous", 10)) a.mode = 1;
-        if (e && !strncmp(e, "vmm", 3)) {
-            a.mode = 2;
-            if (e[3] == ':' && atol(e + 4) > 0) a.chunk = (size_t)atol(e + 4) << 20;
-        }
-        return a;
-    }();
-    return am;
-}
-int alloc_mode(size_t *chunk) {
-    const AllocMode &a = alloc_mode_once();
-    if (chunk) *chunk = a.chunk;
-    return a.mode;
-}
-bool vmm_block(size_t bytes, void **p) {
-    size_t chunk = 0;
-    (void)alloc_mode(&chunk);
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) return false;
-    hipMemAllocationProp prop;
-    memset(&prop, 0, sizeof prop);
-    prop.type = hipMemAllocationTypePinned;
-    prop.location.type = hipMemLocationTypeDevice;
-    prop.location.id = dev;
-    size_t gran = 0;
-    if (hipMemGetAllocationGranularity(&gran, &prop, hipMemAllocationGranularityRecommended) != hipSuccess || !gran) { (void)hipGetLastError(); return false; }
-    chunk = round_up(chunk, gran);
-    const size_t total = round_up(bytes, chunk);
-    void *va = nullptr;   // (hipMemAddressReserve returns 2 MiB-aligned ranges whatever alignment it is asked for: tools/ubench/vmm_repro.hip)
-    if (hipMemAddressReserve(&va, total, 0, nullptr, 0) != hipSuccess) { (void)hipGetLastError(); return false; }
-    VmmBlock B;
-    B.bytes = total; B.chunk = chunk;
-    bool ok = true;
-    for (size_t o = 0; o < total && ok; o += chunk) {
-        hipMemGenericAllocationHandle_t hnd;
-        if (hipMemCreate(&hnd, chunk, &prop, 0) != hipSuccess) { ok = false; break; }
-        B.handles.push_back(hnd);
-        if (hipMemMap((char *)va + o, chunk, 0, hnd, 0) != hipSuccess) { ok = false; break; }
-    }
-    if (ok) {
-        hipMemAccessDesc acc;
-        memset(&acc, 0, sizeof acc);
-        acc.location = prop.location;
-        acc.flags = hipMemAccessFlagsProtReadWrite;
-        ok = hipMemSetAccess(va, total, &acc, 1) == hipSuccess;
-    }
-    if (!ok) {
-        (void)hipGetLastError();
-        for (size_t i = 0; i < B.handles.size(); i++) { (void)hipMemUnmap((char *)va + i * chunk, chunk); (void)hipMemRelease(B.handles[i]); }
-        (void)hipMemAddressFree(va, total);
-        (void)hipGetLastError();
-        return false;
-    }
-    std::lock_guard<std::mutex> lk(g_vmm_mu);
-    g_vmm[va] = std::move(B);
-    *p = va;
-    return true;
-}
-bool device_block(size_t bytes, void **p, bool plain = false) {   // an allocation that reports failure instead of throwing (a candidate too many is not an error)
-    *p = nullptr;
-    const int mode = plain ? 0 : alloc_mode(nullptr);
-    if (mode == 2) return vmm_block(bytes, p);
-    if (mode == 3 && bytes >= ((size_t)1 << 30) && vmm_block(bytes, p)) return true;
-    const hipError_t e = mode == 1 ? hipExtMallocWithFlags(p, bytes, hipDeviceMallocContiguous) : hipMalloc(p, bytes);
-    if (e == hipSuccess) return true;
-    (void)hipGetLastError();
-    *p = nullptr;
-    return false;
-}
-void device_release(void *p) {
-    if (!p) return;
-    {
-        std::lock_guard<std::mutex> lk(g_vmm_mu);
-        auto it = g_vmm.find(p);
-        if (it != g_vmm.end()) {
-            VmmBlock &B = it->second;
-            for (size_t i = 0; i < B.handles.size(); i++) { (void)hipMemUnmap((char *)p + i * B.chunk, B.chunk); (void)hipMemRelease(B.handles[i]); }
-            // The physical chunks go back; the ADDRESS RANGE does not (unless EMGPU_VMM_FREE_VA is set).  A HIP runtime (the 7.0 build PyTorch wheels
-            // bundle) crashes in hipMemMap -- VirtualGPU::submitVirtualMap -- when a new range overlaps one whose block had been the source of
-            // hipMemcpyAsync calls before it was released (tools/copy_placement_probe.py; the 7.2 system runtime does not).  A reservation costs
-            // address space only (47 bits of it: a thousand 36 GB traces are 36 TiB), so ranges are simply never handed back for re-use.
-            static const bool free_va = getenv("EMGPU_VMM_FREE_VA") != nullptr;
-            if (free_va) (void)hipMemAddressFree(p, B.bytes);
-            g_vmm.erase(it);
-            return;
-        }
-    }
-    (void)hipFree(p);
-}
-void pool_release(emgpu_ctx *ctx) {
-    for (auto &b : ctx->trace_pool) device_release(b.p);
-    ctx->trace_pool.clear();
-}
-// a free block of the pool that fits (and is not more than a quarter too large), or a fresh allocation; {nullptr} when neither exists
-emgpu_ctx::TraceBlock pool_take(emgpu_ctx *ctx, size_t bytes, bool *from_pool, bool plain = false) {
-    int best = -1;
-    for (int i = 0; i < (int)ctx->trace_pool.size(); i++) {
-        const auto &b = ctx->trace_pool[(size_t)i];
-        if (b.bytes >= bytes && b.bytes <= bytes + bytes / 4 + (1u << 20) && (best < 0 || b.bytes < ctx->trace_pool[(size_t)best].bytes)) best = i;
-    }
-    if (from_pool) *from_pool = best >= 0;
-    if (best >= 0) {
-        emgpu_ctx::TraceBlock b = ctx->trace_pool[(size_t)best];
-        ctx->trace_pool.erase(ctx->trace_pool.begin() + best);
-        return b;
-    }
-    emgpu_ctx::TraceBlock b;
-    if (!device_block(bytes, &b.p, plain)) {   // out of memory: give the pool's idle blocks back and try once more
-        HIP_OK(hipStreamSynchronize(ctx->stream));
-        pool_release(ctx);
-        if (!device_block(bytes, &b.p, plain)) return b;
-    }
-    b.bytes = bytes;
-    return b;
-}
-
-// ------------------------------------------------------------------------------------------------ trace layout
-struct TraceLayout {
-    size_t o_ib = 0, o_iv = 0, o_db = 0, o_dv = 0, o_ec = 0, o_ev = 0, o_at = 0, bytes = 0;
-    int64_t ld = 0;
-};
-TraceLayout trace_layout(const Model &m, const emgpu_sample_params *p, uint32_t want) {
-    constexpr size_t kA = 2u << 20;   // every array of a trace starts on a 2 MiB boundary
-    TraceLayout L;
-    L.ld = (int64_t)round_up((size_t)std::max<int64_t>(p->n, 1), 1024);
-    const size_t ld = (size_t)L.ld, ni = (size_t)m.n_initial, nd = (size_t)m.n_dyn(), G4 = ((size_t)p->sample_time + 3) / 4;
-    size_t o = 0;
-    auto put = [&](size_t bytes) { const size_t at = o; o = round_up(o + std::max<size_t>(bytes, 1), kA); return at; };
-    if (want & EMGPU_TRACE_DENSE) { L.o_dv = put(G4 * nd * ld * 16); L.o_db = put(G4 * nd * ld * 4); }
-    if (want & EMGPU_TRACE_INIT) { L.o_iv = put(ni * ld * 4); L.o_ib = put(ni * ld); }
-    if (want & EMGPU_TRACE_EVENTS) { L.o_ev = put(ld * (size_t)p->event_cap * 8); L.o_ec = put(ld * 4); }
-    if (want & EMGPU_TRACE_ATTEMPTS) L.o_at = put(ld * 4);
-    L.bytes = std::max<size_t>(o, kA);
-    return L;
-}
-void trace_bind(const TraceLayout &L, uint32_t want, void *base, emgpu_sample_out *o) {
-    char *b = (char *)base;
-    memset(o, 0, sizeof *o);
-    if (want & EMGPU_TRACE_DENSE) { o->dyn_val = (float *)(b + L.o_dv); o->dyn_bin = (uint32_t *)(b + L.o_db); }
-    if (want & EMGPU_TRACE_INIT) { o->init_val = (float *)(b + L.o_iv); o->init_bin = (uint8_t *)(b + L.o_ib); }
-    if (want & EMGPU_TRACE_EVENTS) { o->events = (emgpu_event *)(b + L.o_ev); o->ev_count = (uint32_t *)(b + L.o_ec); }
-    if (want & EMGPU_TRACE_ATTEMPTS) o->attempts = (int32_t *)(b + L.o_at);
-    o->ld = L.ld;
-    o->col_offset = 0;
-}
-
-struct Events {   // a few HIP events, destroyed on every path out
-    std::vector<hipEvent_t> e;
-    explicit Events(int n) : e((size_t)n, nullptr) { for (auto &x : e) HIP_OK(hipEventCreate(&x)); }
-    ~Events() { for (auto x : e) if (x) (void)hipEventDestroy(x); }
-    hipEvent_t operator[](int i) const { return e[(size_t)i]; }
-};
-
-// `timed` launches of the caller's call into `o` after `warm` untimed ones: ms per launch (HIP events on the ctx stream)
-float time_launches(emgpu_ctx *ctx, const emgpu_model *m, const emgpu_sample_params *p, const emgpu_sample_out *o, int warm, int timed, const Events &ev) {
-    auto launch = [&]() {
-        const int rc = emgpu_sample_dbn_device(ctx, m, p, o);
-        if (rc != EMGPU_OK) throw Error(rc, g_err);
-    };
-    for (int i = 0; i < warm; i++) launch();
-    HIP_OK(hipEventRecord(ev[0], ctx->stream));
-    for (int i = 0; i < timed; i++) launch();
-    HIP_OK(hipEventRecord(ev[1], ctx->stream));
-    HIP_OK(hipEventSynchronize(ev[1]));
-    float ms = 0.f;
-    HIP_OK(hipEventElapsedTime(&ms, ev[0], ev[1]));
-    return ms / (float)timed;
-}
-
-bool is_pinned(const void *p) {
-    if (!p) return false;
-    hipPointerAttribute_t a;
-    memset(&a, 0, sizeof a);
-    if (hipPointerGetAttributes(&a, p) != hipSuccess) { (void)hipGetLastError(); return false; }
-    return a.type == hipMemoryTypeHost;
-}
-
 int host_threads() {
     static const int n = [] {
         const char *e = getenv("EMGPU_HOST_THREADS");
@@ -251,8 +40,7 @@ struct ChunkPlan { size_t n, C, Cp, nchunks; };   // n trajectories in chunks of
 // `bpt` device bytes per trajectory; chunks of equal size, and with event lists (event_cap > 0: rows per list) or text rows (bytes per
 // trajectory at most) a chunk's packed rows / bytes counted in 32 bits
 ChunkPlan chunk_plan(size_t n, size_t bpt, bool direct, size_t event_cap) {
-    size_t target = (size_t)(direct ? 1024 : 256) << 20;   // pinned outputs: larger pieces (the copy engine writes row by row into the caller's pitch)
-    if (const char *e = getenv("EMGPU_HOST_CHUNK_MB")) { const long v = atol(e); if (v > 0) target = (size_t)v << 20; }
+    const size_t target = host_chunk_target((size_t)(direct ? 1024 : 256) << 20);   // pinned outputs: larger pieces (the copy engine writes row by row into the caller's pitch)
     size_t C = std::max<size_t>(1024, target / std::max<size_t>(bpt, 1) / 1024 * 1024);
     if (event_cap) C = std::min(C, std::max<size_t>(1024, ((size_t)0xFFFF0000u / event_cap) / 1024 * 1024));
     if (C >= n) C = n;
@@ -261,32 +49,6 @@ ChunkPlan chunk_plan(size_t n, size_t bpt, bool direct, size_t event_cap) {
         C = std::min(C, round_up((n + k - 1) / k, 1024));
     }
     return {n, C, round_up(C, 256), (n + C - 1) / C};
-}
-
-// chunk buffers (blocks of the trace pool's allocator, unprobed) and pinned staging buffers of these sizes, one of each for a single chunk, two
-// otherwise; the copy stream and h_total.  false: out of device memory
-bool provision(emgpu_ctx *ctx, size_t nchunks, size_t dev_bytes, size_t stage_bytes) {
-    const size_t nbuf = nchunks == 1 ? 1 : 2;
-    for (size_t q = 0; q < nbuf; q++) {
-        emgpu_ctx::TraceBlock &b = ctx->chunk_buf[q];
-        if (b.bytes >= dev_bytes) continue;
-        HIP_OK(hipStreamSynchronize(ctx->stream));
-        if (b.p) { device_release(b.p); b = emgpu_ctx::TraceBlock(); }
-        // (plain hipMalloc blocks: these buffers are the SOURCE of copies, which is all their placement could matter for -- measured: it does not)
-        b = pool_take(ctx, dev_bytes + dev_bytes / 8, nullptr, /*plain=*/true);   // (some headroom: batch sizes that wobble do not reallocate)
-        if (!b.p) return false;
-    }
-    if (ctx->h_stage_cap < stage_bytes) {
-        const size_t want_cap = stage_bytes + stage_bytes / 8;
-        for (auto &s : ctx->h_stage) { if (s) HIP_OK(hipHostFree(s)); s = nullptr; }
-        ctx->h_stage_cap = 0;
-        for (size_t b = 0; b < nbuf; b++) HIP_OK(hipHostMalloc(&ctx->h_stage[b], want_cap, hipHostMallocDefault));
-        ctx->h_stage_cap = want_cap;
-    }
-    if (nbuf == 2 && !ctx->h_stage[1]) HIP_OK(hipHostMalloc(&ctx->h_stage[1], ctx->h_stage_cap, hipHostMallocDefault));
-    if (!ctx->copy_stream) HIP_OK(hipStreamCreateWithFlags(&ctx->copy_stream, hipStreamNonBlocking));
-    if (!ctx->h_total) HIP_OK(hipHostMalloc((void **)&ctx->h_total, 4 * sizeof(uint64_t), hipHostMallocDefault));
-    return true;
 }
 
 // Launch k / drain k-1 over the chunks: launch(k0, c, b) on the ctx stream and copy(k0, c, b) on the copy stream behind it for trajectories
@@ -353,383 +115,7 @@ int sample_nothing(emgpu_ctx *ctx, const emgpu_model *h, const emgpu_sample_para
 }
 } // namespace
 
-void ctx_release_host_side(emgpu_ctx *ctx, bool everything) {
-    pool_release(ctx);
-    if (everything) { for (void *p : ctx->device_blocks) device_release(p); ctx->device_blocks.clear(); }
-    for (auto &b : ctx->chunk_buf) { device_release(b.p); b = emgpu_ctx::TraceBlock(); }
-    for (auto &s : ctx->h_stage) { if (s) (void)hipHostFree(s); s = nullptr; }
-    ctx->h_stage_cap = 0;
-    for (auto it = ctx->host_pool.begin(); it != ctx->host_pool.end();) {
-        if (!it->in_use || everything) { (void)hipHostFree(it->p); it = ctx->host_pool.erase(it); }
-        else ++it;
-    }
-    if (everything) {
-        if (ctx->h_total) (void)hipHostFree(ctx->h_total);
-        ctx->h_total = nullptr;
-        if (ctx->copy_stream) (void)hipStreamDestroy(ctx->copy_stream);
-        ctx->copy_stream = nullptr;
-    }
-}
-
-// ------------------------------------------------------------------------------------------------ the file pipeline's text tables, parsed on the device
-namespace {
-size_t env_size(const char *name, size_t dflt) {
-    const char *e = getenv(name);
-    const long long v = e ? atoll(e) : 0;
-    return v > 0 ? (size_t)v : dflt;
-}
-
-struct DeviceTable {   // the parsed table: a block of the traces' allocator, released on every path out
-    double *d = nullptr;
-    int64_t rows = 0, cap_rows = 0;
-    uint64_t hard = 0;
-    int32_t chunks = 0;
-    double h2d_ms = 0, kernel_ms = 0, host_ms = 0;
-    DeviceTable() = default;
-    DeviceTable(const DeviceTable &) = delete;
-    DeviceTable &operator=(const DeviceTable &) = delete;
-    ~DeviceTable() { if (d) { (void)hipDeviceSynchronize(); device_release(d); } }
-};
-
-int64_t line_of(const char *text, size_t off) {   // 1-based line of byte off
-    int64_t line = 1;
-    for (const char *q = text, *e = text + off; q < e && (q = (const char *)memchr(q, '\n', (size_t)(e - q))) != nullptr; q++) line++;
-    return line;
-}
-
-// text [nbytes] -> T.d [T.rows][ncol] on the device.  The text goes up in chunks cut behind a newline (EMGPU_HOST_CHUNK_MB, or
-// EMGPU_DEBUG_PARSE_CHUNK_BYTES for tests that want the cuts at every position of a row), chunk k + 1's copy on the copy stream behind chunk k's
-// parse; pageable text through the pinned staging buffers.  Offsets within a chunk are 32-bit, offsets into the text and rows 64-bit.
-// Hard tokens (emgpu_kernels_parse.hip) are finished here with strtod; a chunk with more of them than the list holds (EMGPU_DEBUG_PARSE_HARD_CAP
-// entries, default 65 536) is parsed again with a list of the counted size.  Throws Error(EMGPU_ERR_PARSE) naming the first malformed line.
-void parse_to_device(emgpu_ctx *ctx, const char *what, const char *text, size_t nbytes, int ncol, DeviceTable &T) {
-    T.cap_rows = (int64_t)(nbytes / (2 * (size_t)ncol)) + 1;   // a row of ncol numbers is at least 2 ncol - 1 bytes and what ends its line
-    const size_t table_bytes = std::max<size_t>((size_t)T.cap_rows * (size_t)ncol * 8, 256);
-    void *tp = nullptr;
-    if (!device_block(table_bytes, &tp)) {
-        HIP_OK(hipStreamSynchronize(ctx->stream));
-        pool_release(ctx);
-        if (!device_block(table_bytes, &tp))
-            throw Error(EMGPU_ERR_HIP, std::string(what) + ": the parsed table (" + std::to_string(table_bytes) + " bytes) does not fit the device's memory");
-    }
-    T.d = (double *)tp;
-    if (!nbytes) return;
-    // ---- the cuts
-    size_t target = (size_t)256 << 20;
-    if (const char *e = getenv("EMGPU_HOST_CHUNK_MB")) { const long v = atol(e); if (v > 0) target = (size_t)v << 20; }
-    target = std::min<size_t>(env_size("EMGPU_DEBUG_PARSE_CHUNK_BYTES", target), (size_t)0xC0000000u);
-    std::vector<size_t> cut{0};
-    size_t maxc = 0;
-    while (cut.back() < nbytes) {
-        const size_t a = cut.back();
-        size_t b = nbytes;
-        if (nbytes - a > target) {
-            const void *q = memrchr(text + a, '\n', target);
-            if (!q) q = memchr(text + a + target, '\n', nbytes - a - target);   // a line longer than a chunk: the chunk ends with it
-            b = q ? (size_t)((const char *)q - text) + 1 : nbytes;
-        }
-        if (b - a > (size_t)0xFFFFFF00u) throw Error(EMGPU_ERR_ARG, std::string(what) + ": a line of more than 4 GB: a chunk's offsets would not fit 32 bits");
-        maxc = std::max(maxc, b - a);
-        cut.push_back(b);
-    }
-    const size_t nchunks = cut.size() - 1;
-    T.chunks = (int32_t)nchunks;
-    const size_t tiles_max = (maxc + emgpu::kParseTile - 1) / emgpu::kParseTile;
-    const size_t hard_cap = env_size("EMGPU_DEBUG_PARSE_HARD_CAP", 65536);
-    size_t o = 0;
-    auto put = [&](size_t bytes) { const size_t at = o; o = round_up(o + std::max<size_t>(bytes, 1), 256); return at; };
-    const size_t o_text = put(maxc + 8), o_cnt = put(tiles_max * 4), o_scr = put(emgpu::pack_scratch_words((int64_t)tiles_max) * 4);
-    const size_t o_hard = put(hard_cap * sizeof(emgpu::EmgpuHardToken)), o_val = put(hard_cap * 8), o_misc = put(16);   // misc: err (u64), hard count (u32)
-    const bool pinned = is_pinned(text);
-    if (!provision(ctx, nchunks, o, pinned ? 256 : maxc)) throw Error(EMGPU_ERR_HIP, std::string(what) + ": out of device memory");
-    Events ev(8);   // per buffer b: 4b + {copy start, copy end, parse start, parse end}
-    auto upload = [&](size_t k) {
-        const int b = (int)(k & 1);
-        const char *src = text + cut[k];
-        const size_t len = cut[k + 1] - cut[k];
-        if (!pinned) { const auto t0 = Clock::now(); memcpy(ctx->h_stage[b], src, len); src = (const char *)ctx->h_stage[b]; T.host_ms += ms_since(t0); }
-        HIP_OK(hipEventRecord(ev[4 * b], ctx->copy_stream));
-        HIP_OK(hipMemcpyAsync((char *)ctx->chunk_buf[b].p + o_text, src, len, hipMemcpyHostToDevice, ctx->copy_stream));
-        HIP_OK(hipEventRecord(ev[4 * b + 1], ctx->copy_stream));
-    };
-    struct Extra { void *p = nullptr; ~Extra() { if (p) (void)hipFree(p); } };
-    try {
-        HIP_OK(hipStreamSynchronize(ctx->stream));   // (the chunk buffers may still be read by an earlier call's copies)
-        HIP_OK(hipStreamSynchronize(ctx->copy_stream));
-        upload(0);
-        for (size_t k = 0; k < nchunks; k++) {
-            const int b = (int)(k & 1);
-            char *dev = (char *)ctx->chunk_buf[b].p;
-            const size_t len = cut[k + 1] - cut[k];
-            emgpu::EmgpuParseRun P{};
-            P.text = (const uint8_t *)(dev + o_text); P.nbytes = (uint32_t)len; P.ncol = ncol;
-            P.cnt = (uint32_t *)(dev + o_cnt); P.scratch = (uint32_t *)(dev + o_scr);
-            P.table = T.d; P.row_base = T.rows; P.table_rows = T.cap_rows;
-            P.hard = (emgpu::EmgpuHardToken *)(dev + o_hard); P.hard_cap = (uint32_t)hard_cap;
-            P.err = (unsigned long long *)(dev + o_misc); P.hard_count = (uint32_t *)(dev + o_misc + 8);
-            HIP_OK(hipStreamWaitEvent(ctx->stream, ev[4 * b + 1], 0));
-            HIP_OK(hipEventRecord(ev[4 * b + 2], ctx->stream));
-            HIP_OK(hipMemsetAsync(dev + o_misc, 0xFF, 8, ctx->stream));
-            HIP_OK(hipMemsetAsync(dev + o_misc + 8, 0, 8, ctx->stream));
-            launch_ok(emgpu::launch_parse_count(P, ctx->stream));
-            HIP_OK(hipMemcpyAsync(&ctx->h_total[2 * b], P.scratch, 8, hipMemcpyDeviceToHost, ctx->stream));
-            if (k + 1 < nchunks) upload(k + 1);   // (its buffer's last reader, chunk k - 1's parse, has been waited for)
-            HIP_OK(hipStreamSynchronize(ctx->stream));
-            const uint64_t rows = ctx->h_total[2 * b];
-            P.rows = (uint32_t)rows;
-            launch_ok(emgpu::launch_parse_rows(P, ctx->stream));
-            HIP_OK(hipMemcpyAsync(&ctx->h_total[2 * b], dev + o_misc, 16, hipMemcpyDeviceToHost, ctx->stream));
-            HIP_OK(hipEventRecord(ev[4 * b + 3], ctx->stream));
-            HIP_OK(hipStreamSynchronize(ctx->stream));
-            const uint64_t err = ctx->h_total[2 * b];
-            if (err != ~0ull)
-                throw Error(EMGPU_ERR_PARSE, std::string(what) + ": line " + std::to_string(line_of(text, cut[k] + (size_t)err)) + " is not a row of " +
-                                                 std::to_string(ncol) + " numbers");
-            if (T.rows + (int64_t)rows > T.cap_rows) throw Error(EMGPU_ERR_PARSE, std::string(what) + ": more rows than the text has room for");
-            const uint32_t nh = (uint32_t)ctx->h_total[2 * b + 1];
-            Extra extra;
-            const emgpu::EmgpuHardToken *d_list = P.hard;
-            double *d_val = (double *)(dev + o_val);
-            if (nh > hard_cap) {   // the list was too small: once more with one of the counted size (the values written meanwhile are the same)
-                HIP_OK(hipMalloc(&extra.p, (size_t)nh * 24));
-                P.hard = (emgpu::EmgpuHardToken *)extra.p; P.hard_cap = nh;
-                d_list = P.hard; d_val = (double *)((char *)extra.p + (size_t)nh * 16);
-                HIP_OK(hipMemsetAsync(dev + o_misc + 8, 0, 8, ctx->stream));
-                launch_ok(emgpu::launch_parse_rows(P, ctx->stream));
-                HIP_OK(hipStreamSynchronize(ctx->stream));
-            }
-            if (nh) {
-                const auto t0 = Clock::now();
-                std::vector<emgpu::EmgpuHardToken> list(nh);
-                std::vector<double> val(nh);
-                HIP_OK(hipMemcpy(list.data(), d_list, (size_t)nh * 16, hipMemcpyDeviceToHost));
-                std::string tok;
-                for (uint32_t i = 0; i < nh; i++) {
-                    const char *q = text + cut[k] + list[i].off, *e = text + cut[k + 1], *r = q;
-                    while (r < e && *r != ' ' && *r != '\t' && *r != '\n' && *r != '\r') r++;
-                    tok.assign(q, r);
-                    val[i] = strtod(tok.c_str(), nullptr);
-                }
-                HIP_OK(hipMemcpyAsync(d_val, val.data(), (size_t)nh * 8, hipMemcpyHostToDevice, ctx->stream));
-                launch_ok(emgpu::launch_parse_patch(T.d, d_list, d_val, nh, ctx->stream));
-                HIP_OK(hipStreamSynchronize(ctx->stream));
-                T.host_ms += ms_since(t0);
-            }
-            float ms = 0.f;
-            HIP_OK(hipEventElapsedTime(&ms, ev[4 * b], ev[4 * b + 1])); T.h2d_ms += ms;
-            HIP_OK(hipEventElapsedTime(&ms, ev[4 * b + 2], ev[4 * b + 3])); T.kernel_ms += ms;
-            T.rows += (int64_t)rows;
-            T.hard += nh;
-        }
-    } catch (...) {
-        (void)hipStreamSynchronize(ctx->stream);
-        if (ctx->copy_stream) (void)hipStreamSynchronize(ctx->copy_stream);
-        throw;
-    }
-}
-} // namespace
-
 extern "C" {
-
-// ================================================================================================ the trace pool
-int emgpu_trace_alloc(emgpu_ctx *ctx, const emgpu_model *h, const emgpu_sample_params *p, uint32_t want, int32_t candidates, emgpu_trace **out) {
-    EMGPU_TRY
-    if (!ctx || !h || !p || !out) return fail(EMGPU_ERR_ARG, "null argument");
-    if (p->n < 0 || p->sample_time < 1) return fail(EMGPU_ERR_ARG, "n < 0 or sample_time < 1");
-    if (!(want & (EMGPU_TRACE_INIT | EMGPU_TRACE_DENSE | EMGPU_TRACE_EVENTS | EMGPU_TRACE_ATTEMPTS)) || (want & ~15u)) return fail(EMGPU_ERR_ARG, "want: a combination of EMGPU_TRACE_*");
-    if ((want & EMGPU_TRACE_EVENTS) && p->event_cap < 1) return fail(EMGPU_ERR_ARG, "EMGPU_TRACE_EVENTS needs event_cap >= 1");
-    if (candidates < 0 || candidates > 8) return fail(EMGPU_ERR_ARG, "candidates outside 0..8");
-    CTX_LOCK(ctx);
-    HIP_OK(hipSetDevice(ctx->device));
-    const TraceLayout L = trace_layout(h->m, p, want);
-    std::unique_ptr<emgpu_trace> t(new emgpu_trace());
-    t->rep.bytes = (int64_t)L.bytes;
-    t->rep.ld = L.ld;
-    const bool automatic = candidates == 0;
-    int target = automatic ? (L.bytes < ((size_t)1 << 30) ? 1 : 6) : candidates;   // (no early stop: a candidate costs a quarter of a second, and two
-    if (p->n == 0) target = 1;                                                      //  medium ones that agree say nothing about a fast one further on)
-
-    bool from_pool = false;
-    std::vector<emgpu_ctx::TraceBlock> cands;
-    // candidate 0 of a probe is what hipMalloc hands a caller (the report's first_allocation_ms); the others are the library's own kind
-    cands.push_back(pool_take(ctx, L.bytes, &from_pool, /*plain=*/target > 1));
-    if (!cands[0].p) return fail(EMGPU_ERR_HIP, "emgpu_trace_alloc: out of device memory (" + std::to_string(L.bytes) + " bytes)");
-    auto give_up = [&]() { for (auto &c : cands) device_release(c.p); cands.clear(); };
-    try {
-        if (from_pool && (cands[0].probed || target == 1)) {   // placed by an earlier call (or the caller does not want a probe): take it as it is
-            t->rep.candidates = 1;
-            t->rep.reused = 1;
-            t->rep.kept_ms = cands[0].ms;
-        } else if (target == 1) {
-            t->rep.candidates = 1;
-        } else {
-            auto room_for_one_more = [&]() {
-                size_t fr = 0, tot = 0;
-                if (hipMemGetInfo(&fr, &tot) != hipSuccess) { (void)hipGetLastError(); return false; }
-                return fr >= L.bytes + ((size_t)4 << 30);
-            };
-            auto one_more = [&]() {
-                if (!room_for_one_more()) return false;
-                emgpu_ctx::TraceBlock b;
-                if (!device_block(L.bytes, &b.p)) return false;   // (another process took the memory meanwhile)
-                b.bytes = L.bytes;
-                cands.push_back(b);
-                return true;
-            };
-            while ((int)cands.size() < target && one_more()) {}
-            if (cands.size() == 1) {
-                t->rep.candidates = 1;   // no memory for a second candidate
-            } else {
-                Events ev(2);
-                std::vector<emgpu_sample_out> outs(cands.size());
-                for (size_t i = 0; i < cands.size(); i++) trace_bind(L, want, cands[i].p, &outs[i]);
-                // the allocations above left the device idle and its clocks fell: load it first
-                const auto t0 = Clock::now();
-                while (ms_since(t0) < 500.0) (void)time_launches(ctx, h, p, &outs.back(), 0, 4, ev);
-                std::vector<float> ms(cands.size(), 1e30f);
-                for (int round = 0; round < 2; round++)   // a b c a b c: what is left of a ramp does not favour the last one
-                    for (size_t i = 0; i < cands.size(); i++) ms[i] = std::min(ms[i], time_launches(ctx, h, p, &outs[i], 2, 5, ev));
-                const size_t kept = (size_t)(std::min_element(ms.begin(), ms.end()) - ms.begin());
-                t->rep.candidates = (int32_t)cands.size();
-                t->rep.kept = (int32_t)kept;
-                for (size_t i = 0; i < cands.size() && i < 8; i++) t->rep.ms[i] = ms[i];
-                t->rep.first_allocation_ms = ms[0];
-                t->rep.kept_ms = ms[kept];
-                // the probe's launches may have left deferred per-trajectory bits (a rejection cap ...): the caller's own call will raise them again
-                const int rc = emgpu_ctx_sync(ctx);
-                if (rc == EMGPU_ERR_HIP) throw Error(rc, g_err);
-                for (size_t i = 0; i < cands.size(); i++)
-                    if (i != kept) device_release(cands[i].p);
-                emgpu_ctx::TraceBlock k = cands[kept];
-                k.probed = true;
-                k.ms = ms[kept];
-                cands.assign(1, k);
-            }
-        }
-    } catch (...) {
-        (void)hipStreamSynchronize(ctx->stream);
-        give_up();
-        throw;
-    }
-    t->blk = cands[0];
-    trace_bind(L, want, t->blk.p, &t->out);
-    *out = t.release();
-    return EMGPU_OK;
-    EMGPU_CATCH
-}
-
-int emgpu_trace_out(const emgpu_trace *t, emgpu_sample_out *out) {
-    if (!t || !out) return fail(EMGPU_ERR_ARG, "null argument");
-    *out = t->out;
-    return EMGPU_OK;
-}
-
-int emgpu_trace_report(const emgpu_trace *t, emgpu_trace_report_t *out) {
-    if (!t || !out) return fail(EMGPU_ERR_ARG, "null argument");
-    *out = t->rep;
-    return EMGPU_OK;
-}
-
-int emgpu_trace_free(emgpu_ctx *ctx, emgpu_trace *t) {
-    EMGPU_TRY
-    if (!t) return EMGPU_OK;
-    if (!ctx) return fail(EMGPU_ERR_ARG, "null ctx");
-    CTX_LOCK(ctx);
-    HIP_OK(hipSetDevice(ctx->device));
-    HIP_OK(hipStreamSynchronize(ctx->stream));   // nothing in flight may still write the block when somebody else takes it
-    ctx->trace_pool.push_back(t->blk);
-    delete t;
-    return EMGPU_OK;
-    EMGPU_CATCH
-}
-
-// Plain device memory from the same allocator as the traces (no probe): for outputs that are not a DBN trace -- the joined tracks of
-// emgpu_sample_terminal_device, a consumer's own buffers.
-int emgpu_device_alloc(emgpu_ctx *ctx, uint64_t bytes, void **out) {
-    EMGPU_TRY
-    if (!ctx || !out) return fail(EMGPU_ERR_ARG, "null argument");
-    CTX_LOCK(ctx);
-    HIP_OK(hipSetDevice(ctx->device));
-    void *p = nullptr;
-    const size_t need = std::max<size_t>((size_t)bytes, 256);
-    if (!device_block(need, &p)) {
-        HIP_OK(hipStreamSynchronize(ctx->stream));
-        pool_release(ctx);
-        if (!device_block(need, &p)) return fail(EMGPU_ERR_HIP, "emgpu_device_alloc: out of device memory (" + std::to_string(need) + " bytes)");
-    }
-    ctx->device_blocks.insert(p);
-    *out = p;
-    return EMGPU_OK;
-    EMGPU_CATCH
-}
-
-int emgpu_device_free(emgpu_ctx *ctx, void *p) {
-    EMGPU_TRY
-    if (!p) return EMGPU_OK;
-    if (!ctx) return fail(EMGPU_ERR_ARG, "null ctx");
-    CTX_LOCK(ctx);
-    if (!ctx->device_blocks.erase(p)) return fail(EMGPU_ERR_ARG, "emgpu_device_free: not a block of this ctx");
-    HIP_OK(hipSetDevice(ctx->device));
-    HIP_OK(hipStreamSynchronize(ctx->stream));
-    device_release(p);
-    return EMGPU_OK;
-    EMGPU_CATCH
-}
-
-// ================================================================================================ the pinned pool
-int emgpu_host_alloc(emgpu_ctx *ctx, uint64_t bytes, void **out) {
-    EMGPU_TRY
-    if (!ctx || !out) return fail(EMGPU_ERR_ARG, "null argument");
-    CTX_LOCK(ctx);
-    HIP_OK(hipSetDevice(ctx->device));
-    const size_t need = std::max<size_t>((size_t)bytes, 64);   // (portable: emgpu_sample_dbn_multi_host hands one caller array to the contexts of several devices)
-    emgpu_ctx::HostBlock *best = nullptr;
-    for (auto &b : ctx->host_pool)
-        if (!b.in_use && b.bytes >= need && b.bytes <= need + need / 2 + (1u << 20) && (!best || b.bytes < best->bytes)) best = &b;
-    if (best) {
-        best->in_use = true;
-        *out = best->p;
-        return EMGPU_OK;
-    }
-    void *p = nullptr;
-    if (hipHostMalloc(&p, need, hipHostMallocPortable) != hipSuccess) {
-        (void)hipGetLastError();
-        for (auto it = ctx->host_pool.begin(); it != ctx->host_pool.end();)   // the pool's idle blocks first, then once more
-            if (!it->in_use) { (void)hipHostFree(it->p); it = ctx->host_pool.erase(it); } else ++it;
-        HIP_OK(hipHostMalloc(&p, need, hipHostMallocPortable));
-    }
-    ctx->host_pool.push_back({p, need, true});
-    *out = p;
-    return EMGPU_OK;
-    EMGPU_CATCH
-}
-
-int emgpu_host_free(emgpu_ctx *ctx, void *p) {
-    if (!p) return EMGPU_OK;
-    if (!ctx) return fail(EMGPU_ERR_ARG, "null ctx");
-    CTX_LOCK(ctx);
-    for (auto &b : ctx->host_pool)
-        if (b.p == p) {
-            if (!b.in_use) return fail(EMGPU_ERR_ARG, "emgpu_host_free: block freed twice");
-            b.in_use = false;
-            // the pool keeps at most 16 GiB of idle pinned memory (callers that wander through many sizes would pin the host's RAM away)
-            size_t idle = 0;
-            for (const auto &q : ctx->host_pool) idle += q.in_use ? 0 : q.bytes;
-            if (idle > ((size_t)16 << 30)) {
-                (void)hipSetDevice(ctx->device);
-                for (auto it = ctx->host_pool.begin(); it != ctx->host_pool.end();)
-                    if (!it->in_use && it->p != p) { (void)hipHostFree(it->p); it = ctx->host_pool.erase(it); } else ++it;
-            }
-            return EMGPU_OK;
-        }
-    return fail(EMGPU_ERR_ARG, "emgpu_host_free: not a block of this ctx");
-}
-
-int emgpu_host_stats(const emgpu_ctx *ctx, emgpu_host_stats_t *out) {
-    if (!ctx || !out) return fail(EMGPU_ERR_ARG, "null argument");
-    *out = ctx->host_stats;
-    return EMGPU_OK;
-}
 
 // ================================================================================================ the host path
 // The start grid of a host-pointer call is caller (host) memory: uploaded once into the ctx's scratch, every chunk reads its own rows.
@@ -1142,295 +528,10 @@ int emgpu_sample_text_host(emgpu_ctx *ctx, const emgpu_model *h, const emgpu_sam
     EMGPU_CATCH
 }
 
-int emgpu_format_g_host(emgpu_ctx *ctx, const float *x, int64_t n, char *out, int64_t cap, uint64_t *offsets) {
-    EMGPU_TRY
-    if (!ctx || !offsets || (n > 0 && !x) || (cap > 0 && !out)) return fail(EMGPU_ERR_ARG, "null argument");
-    if (n < 0 || cap < 0) return fail(EMGPU_ERR_ARG, "n < 0 or cap < 0");
-    CTX_LOCK(ctx);
-    HIP_OK(hipSetDevice(ctx->device));
-    offsets[0] = 0;
-    if (n == 0) return EMGPU_OK;
-    const size_t C = (size_t)std::min<int64_t>(n, (int64_t)1 << 22);   // values per pass: their text is counted in 32 bits (12 C bytes)
-    uint64_t total = 0, paths[2] = {0, 0};
-    {
-        CallBuffers B(ctx);
-        float *d_x = B.alloc<float>(C * 4);
-        uint32_t *d_cnt = B.alloc<uint32_t>(C * 4), *d_scr = B.alloc<uint32_t>(emgpu::pack_scratch_words((int64_t)C) * 4);
-        char *d_text = B.alloc<char>(C * 12);
-        uint64_t *d_off = B.alloc<uint64_t>(C * 8);
-        unsigned long long *d_paths = B.alloc<unsigned long long>(16);
-        HIP_OK(hipMemsetAsync(d_paths, 0, 16, ctx->stream));
-        for (size_t k0 = 0; k0 < (size_t)n; k0 += C) {
-            const size_t c = std::min(C, (size_t)n - k0);
-            B.up(d_x, x + k0, c * 4);
-            launch_ok(emgpu::launch_format_g(d_x, (int64_t)c, d_cnt, d_scr, d_text, total, d_off, d_paths, ctx->stream));
-            uint64_t bytes = 0;
-            B.down(&bytes, d_scr, sizeof bytes);
-            B.down(offsets + k0, d_off, c * 8);
-            HIP_OK(hipStreamSynchronize(ctx->stream));
-            if (bytes > c * 12) throw Error(EMGPU_ERR_HIP, "emgpu_format_g_host: a pass's text outgrew its bound");
-            if (total + bytes <= (uint64_t)cap) { B.down(out + total, d_text, (size_t)bytes); HIP_OK(hipStreamSynchronize(ctx->stream)); }
-            total += bytes;
-        }
-        B.down(paths, d_paths, sizeof paths);
-        HIP_OK(hipStreamSynchronize(ctx->stream));
-    }
-    ctx->format_paths[0] += paths[0];
-    ctx->format_paths[1] += paths[1];
-    offsets[n] = total;
-    if (total > (uint64_t)cap) return fail(EMGPU_ERR_EVENT_CAP, "emgpu_format_g_host: the text has " + std::to_string(total) + " bytes, cap is " + std::to_string(cap));
-    return EMGPU_OK;
-    EMGPU_CATCH
-}
-
-int emgpu_debug_format_paths(emgpu_ctx *ctx, uint64_t out[2]) {
+int emgpu_host_stats(const emgpu_ctx *ctx, emgpu_host_stats_t *out) {
     if (!ctx || !out) return fail(EMGPU_ERR_ARG, "null argument");
-    CTX_LOCK(ctx);
-    out[0] = ctx->format_paths[0]; out[1] = ctx->format_paths[1];
-    ctx->format_paths[0] = ctx->format_paths[1] = 0;
+    *out = ctx->host_stats;
     return EMGPU_OK;
-}
-
-// ================================================================================================ sample2track's files
-int64_t emgpu_csv_bound(int64_t n, int64_t rows) { return n < 0 || rows < 0 ? -1 : 22 * n + 74 * rows; }
-
-int emgpu_parse_table_host(emgpu_ctx *ctx, const char *text, int64_t nbytes, int32_t ncol, double *out, int64_t rows_cap, int64_t *rows, uint64_t *hard_tokens) {
-    EMGPU_TRY
-    if (!ctx || !rows || (nbytes > 0 && !text) || (rows_cap > 0 && !out)) return fail(EMGPU_ERR_ARG, "null argument");
-    if (nbytes < 0 || rows_cap < 0 || ncol < 1 || ncol > 4096) return fail(EMGPU_ERR_ARG, "nbytes < 0, rows_cap < 0 or ncol outside 1..4096");
-    CTX_LOCK(ctx);
-    HIP_OK(hipSetDevice(ctx->device));
-    *rows = 0;
-    if (hard_tokens) *hard_tokens = 0;
-    DeviceTable T;
-    parse_to_device(ctx, "emgpu_parse_table_host", text, (size_t)nbytes, ncol, T);
-    *rows = T.rows;
-    if (hard_tokens) *hard_tokens = T.hard;
-    if (T.rows > rows_cap) return fail(EMGPU_ERR_EVENT_CAP, "emgpu_parse_table_host: the text has " + std::to_string(T.rows) + " rows, rows_cap is " + std::to_string(rows_cap));
-    if (T.rows) HIP_OK(hipMemcpy(out, T.d, (size_t)T.rows * (size_t)ncol * 8, hipMemcpyDeviceToHost));
-    return EMGPU_OK;
-    EMGPU_CATCH
-}
-
-int emgpu_format_f0_host(emgpu_ctx *ctx, const double *x, int64_t n, char *out, int64_t cap, uint64_t *offsets) {
-    EMGPU_TRY
-    if (!ctx || !offsets || (n > 0 && !x) || (cap > 0 && !out)) return fail(EMGPU_ERR_ARG, "null argument");
-    if (n < 0 || cap < 0) return fail(EMGPU_ERR_ARG, "n < 0 or cap < 0");
-    CTX_LOCK(ctx);
-    HIP_OK(hipSetDevice(ctx->device));
-    offsets[0] = 0;
-    if (n == 0) return EMGPU_OK;
-    const size_t C = (size_t)std::min<int64_t>(n, (int64_t)1 << 22);   // values per pass: their text is counted in 32 bits (20 C bytes)
-    uint64_t total = 0;
-    {
-        CallBuffers B(ctx);
-        double *d_x = B.alloc<double>(C * 8);
-        uint32_t *d_cnt = B.alloc<uint32_t>(C * 4), *d_scr = B.alloc<uint32_t>(emgpu::pack_scratch_words((int64_t)C) * 4);
-        char *d_text = B.alloc<char>(C * 20);
-        uint64_t *d_off = B.alloc<uint64_t>(C * 8);
-        for (size_t k0 = 0; k0 < (size_t)n; k0 += C) {
-            const size_t c = std::min(C, (size_t)n - k0);
-            B.up(d_x, x + k0, c * 8);
-            launch_ok(emgpu::launch_format_f0(d_x, (int64_t)c, d_cnt, d_scr, d_text, total, d_off, ctx->stream));
-            uint64_t bytes = 0;
-            B.down(&bytes, d_scr, sizeof bytes);
-            B.down(offsets + k0, d_off, c * 8);
-            HIP_OK(hipStreamSynchronize(ctx->stream));
-            if (bytes > c * 20) throw Error(EMGPU_ERR_HIP, "emgpu_format_f0_host: a pass's text outgrew its bound");
-            if (total + bytes <= (uint64_t)cap) { B.down(out + total, d_text, (size_t)bytes); HIP_OK(hipStreamSynchronize(ctx->stream)); }
-            total += bytes;
-        }
-    }
-    offsets[n] = total;
-    if (total > (uint64_t)cap) return fail(EMGPU_ERR_EVENT_CAP, "emgpu_format_f0_host: the text has " + std::to_string(total) + " bytes, cap is " + std::to_string(cap));
-    return EMGPU_OK;
-    EMGPU_CATCH
-}
-
-int emgpu_tracks_text_host(emgpu_ctx *ctx, const emgpu_track_params *p, const emgpu_tracks_text_in *in, const emgpu_tracks_text_out *out) {
-    EMGPU_TRY
-    if (!ctx || !p || !in || !out) return fail(EMGPU_ERR_ARG, "null argument");
-    if (!out->totals || !out->flags) return fail(EMGPU_ERR_ARG, "flags and totals are required");
-    if (p->n < 0 || in->nbytes < 0 || (in->nbytes > 0 && !in->text)) return fail(EMGPU_ERR_ARG, "n < 0, or no text");
-    if (p->n > 0 && (!in->id || !in->alt0 || !in->speed0)) return fail(EMGPU_ERR_ARG, "id, alt0 and speed0 are required");
-    if (p->n > 0x7FFFFFFF) return fail(EMGPU_ERR_ARG, "more than 2^31 - 1 tracks in one call");
-    if (in->ncol < 2 || in->ncol > 4096) return fail(EMGPU_ERR_ARG, "ncol outside 2..4096");
-    for (int32_t c : {in->col_vertrate, in->col_acc, in->col_turnrate})
-        if (c < 0 || c >= in->ncol) return fail(EMGPU_ERR_ARG, "an update column outside 0..ncol-1");
-    if (out->csv_cap < 0 || out->xyz_cap < 0 || (out->csv && !out->offsets)) return fail(EMGPU_ERR_ARG, "csv_cap / xyz_cap < 0, or csv without offsets");
-    CTX_LOCK(ctx);
-    HIP_OK(hipSetDevice(ctx->device));
-    const auto t_call = Clock::now();
-    const size_t n = (size_t)p->n;
-    const int ncol = in->ncol;
-    for (int k = 0; k < 5; k++) out->totals[k] = 0;
-    emgpu_host_stats_t st{};
-    double phase[6] = {0, 0, 0, 0, 0, 0};   // upload, parse kernels, grouping + track kernels, CSV kernels, download, host work
-    DeviceTable T;
-    parse_to_device(ctx, "emgpu_tracks_text_host", in->text, (size_t)in->nbytes, ncol, T);
-    const int64_t R = T.rows;
-    out->totals[1] = R;
-    out->totals[2] = (int64_t)T.hard;
-    phase[0] = T.h2d_ms; phase[1] = T.kernel_ms; phase[5] = T.host_ms;
-    st.chunks = T.chunks; st.threads = 1; st.direct = (is_pinned(in->text) && (!out->csv || is_pinned(out->csv))) ? 1 : 0;
-    int rc = EMGPU_OK;
-    uint64_t csv_total = 0, xyz_rows = 0;
-    {
-        CallBuffers B(ctx);
-        Events ev(6);
-        const size_t n1 = std::max<size_t>(n, 1);
-        double *d_in = B.alloc<double>(3 * n1 * 8), *d_vmm = B.alloc<double>(2 * n1 * 8);
-        int64_t *d_first = B.alloc<int64_t>(n1 * 8);
-        int32_t *d_len = B.alloc<int32_t>(n1 * 4);
-        uint8_t *d_flags = B.alloc<uint8_t>(n1);
-        uint64_t *d_xoff = B.alloc<uint64_t>((n1 + 1) * 8);
-        B.up(d_in, in->id, n * 8); B.up(d_in + n, in->alt0, n * 8); B.up(d_in + 2 * n, in->speed0, n * 8);
-        // ---- the runs of equal ids, and every wanted id's run
-        HIP_OK(hipEventRecord(ev[0], ctx->stream));
-        emgpu::EmgpuRunTable G{};
-        G.table = T.d; G.ncol = ncol; G.R = R;
-        G.cnt = B.alloc<uint32_t>(std::max<size_t>((size_t)R, 1) * 4);
-        G.scratch = B.alloc<uint32_t>(emgpu::pack_scratch_words(R) * 4);
-        launch_ok(emgpu::launch_run_mark(G, ctx->stream));
-        uint64_t runs = 0;
-        B.down(&runs, G.scratch, 8);
-        HIP_OK(hipStreamSynchronize(ctx->stream));
-        if (runs >= 0x7FFFFFFFull) return fail(EMGPU_ERR_ARG, "emgpu_tracks_text_host: more than 2^31 - 1 runs of ids");
-        size_t H = 16;
-        while (H < 2 * runs) H <<= 1;
-        G.run_id = B.alloc<double>(std::max<size_t>(runs, 1) * 8); G.run_first = B.alloc<int64_t>(std::max<size_t>(runs, 1) * 8);
-        G.keys = B.alloc<unsigned long long>(H * 8); G.vals = B.alloc<uint32_t>(H * 4); G.mask = (uint32_t)(H - 1);
-        G.dup = B.alloc<uint32_t>(4);
-        HIP_OK(hipMemsetAsync(G.keys, 0xFF, H * 8, ctx->stream));
-        HIP_OK(hipMemsetAsync(G.dup, 0, 4, ctx->stream));
-        launch_ok(emgpu::launch_run_fill(G, ctx->stream));
-        launch_ok(emgpu::launch_run_match(G, (uint32_t)runs, (int64_t)n, d_in, d_first, d_len, ctx->stream));
-        uint32_t dup = 0;
-        std::vector<int32_t> len(n);
-        B.down(&dup, G.dup, 4);
-        B.down(len.data(), d_len, n * 4);
-        HIP_OK(hipStreamSynchronize(ctx->stream));
-        const int64_t *d_rowidx = nullptr;
-        if (dup) {   // an id owns more than one run: the reference's selection (every row with that id, in file order) through a stable sort on the host
-            const auto t0 = Clock::now();
-            out->totals[4] = 1;
-            std::vector<double> ids((size_t)R);
-            HIP_OK(hipMemcpy2D(ids.data(), 8, T.d, (size_t)ncol * 8, 8, (size_t)R, hipMemcpyDeviceToHost));
-            std::vector<int64_t> order;
-            order.reserve((size_t)R);
-            for (int64_t r = 0; r < R; r++) if (ids[(size_t)r] == ids[(size_t)r]) order.push_back(r);
-            std::stable_sort(order.begin(), order.end(), [&](int64_t a, int64_t b) { return ids[(size_t)a] < ids[(size_t)b]; });
-            std::vector<int64_t> first(n), rowidx;
-            for (size_t i = 0; i < n; i++) {
-                const double id = in->id[i];
-                first[i] = (int64_t)rowidx.size();
-                if (id == id) {
-                    auto lo = std::lower_bound(order.begin(), order.end(), id, [&](int64_t a, double v) { return ids[(size_t)a] < v; });
-                    for (; lo != order.end() && ids[(size_t)*lo] == id; ++lo) rowidx.push_back(*lo);
-                }
-                const int64_t l = (int64_t)rowidx.size() - first[i];
-                if (l > 0x7FFFFFFF) return fail(EMGPU_ERR_ARG, "emgpu_tracks_text_host: a track of more than 2^31 - 1 rows");
-                len[i] = (int32_t)l;
-            }
-            int64_t *d_ri = B.alloc<int64_t>(std::max<size_t>(rowidx.size(), 1) * 8);
-            B.up(d_ri, rowidx.data(), rowidx.size() * 8);
-            B.up(d_first, first.data(), n * 8);
-            B.up(d_len, len.data(), n * 4);
-            HIP_OK(hipStreamSynchronize(ctx->stream));   // (the vectors go out of scope)
-            d_rowidx = d_ri;
-            phase[5] += ms_since(t0);
-        }
-        std::vector<uint64_t> xoff(n + 1, 0);
-        for (size_t i = 0; i < n; i++) {
-            if (len[i] > 50000000) return fail(EMGPU_ERR_ARG, "emgpu_tracks_text_host: a track of more than 50 000 000 rows: its file would not fit 32 bits");
-            xoff[i + 1] = xoff[i] + (uint64_t)len[i] + 1;
-        }
-        xyz_rows = xoff[n];
-        if (out->lengths) memcpy(out->lengths, len.data(), n * 4);
-        // ---- the tracks
-        const bool want_csv = out->offsets != nullptr, want_xyz = want_csv || out->xyz;
-        double *d_xyz = nullptr;
-        if (want_xyz) {
-            void *q = nullptr;
-            if (hipMalloc(&q, std::max<size_t>((size_t)xyz_rows * 24, 256)) != hipSuccess) {
-                (void)hipGetLastError();
-                return fail(EMGPU_ERR_HIP, "emgpu_tracks_text_host: the positions (" + std::to_string(xyz_rows * 24) + " bytes) do not fit the device's memory");
-            }
-            d_xyz = (double *)q;
-        }
-        struct Free { void *p; ~Free() { if (p) { (void)hipDeviceSynchronize(); (void)hipFree(p); } } } free_xyz{d_xyz};
-        B.up(d_xoff, xoff.data(), (n + 1) * 8);
-        emgpu::EmgpuTrackTableRun A{};
-        A.n = (int64_t)n;
-        set_track_units(A, p);
-        A.alt0 = d_in + n; A.speed0 = d_in + 2 * n;
-        A.table = T.d; A.ncol = ncol; A.c_vr = in->col_vertrate; A.c_acc = in->col_acc; A.c_tr = in->col_turnrate;
-        A.first = d_first; A.len = d_len; A.rowidx = d_rowidx; A.xoff = d_xoff; A.xyz = d_xyz; A.flags = d_flags; A.vmm = d_vmm;
-        const char *name = "";
-        const hipError_t e = emgpu::launch_sample2track_table(A, ctx->stream, &name);
-        ctx->last_kernel = name;
-        launch_ok(e);
-        HIP_OK(hipEventRecord(ev[1], ctx->stream));
-        B.down(out->flags, d_flags, n);
-        B.down(out->speed_minmax, d_vmm, 2 * n * 8);
-        // ---- the files
-        std::vector<uint64_t> off(n + 1, 0);
-        struct Free free_csv{nullptr};
-        if (want_csv) {
-            emgpu::EmgpuCsvRun C{};
-            C.n = (int64_t)n; C.flags = d_flags; C.len = d_len; C.xoff = d_xoff; C.xyz = d_xyz;
-            C.cnt = B.alloc<uint32_t>(n1 * 4); C.hostfmt = B.alloc<uint8_t>(n1);
-            HIP_OK(hipEventRecord(ev[2], ctx->stream));
-            launch_ok(emgpu::launch_csv_len(C, ctx->stream));
-            HIP_OK(hipEventRecord(ev[3], ctx->stream));
-            std::vector<uint32_t> cnt(n);
-            std::vector<uint8_t> hostfmt(n);
-            B.down(cnt.data(), C.cnt, n * 4);
-            B.down(hostfmt.data(), C.hostfmt, n);
-            HIP_OK(hipStreamSynchronize(ctx->stream));
-            for (size_t i = 0; i < n; i++) { off[i + 1] = off[i] + cnt[i]; out->totals[3] += hostfmt[i]; }
-            csv_total = off[n];
-            memcpy(out->offsets, off.data(), (n + 1) * 8);
-            float ms = 0.f;
-            HIP_OK(hipEventElapsedTime(&ms, ev[2], ev[3])); phase[3] += ms;
-            if (out->csv && csv_total && csv_total <= (uint64_t)out->csv_cap) {
-                void *q = nullptr;
-                if (hipMalloc(&q, (size_t)csv_total + 8) != hipSuccess) {
-                    (void)hipGetLastError();
-                    return fail(EMGPU_ERR_HIP, "emgpu_tracks_text_host: the CSV text (" + std::to_string(csv_total) + " bytes) does not fit the device's memory");
-                }
-                free_csv.p = q;
-                uint64_t *d_off = B.alloc<uint64_t>(n1 * 8);
-                B.up(d_off, off.data(), n * 8);
-                C.off = d_off; C.csv = (char *)q;
-                HIP_OK(hipEventRecord(ev[2], ctx->stream));
-                launch_ok(emgpu::launch_csv_emit(C, ctx->stream));
-                HIP_OK(hipEventRecord(ev[3], ctx->stream));
-                HIP_OK(hipEventRecord(ev[4], ctx->stream));
-                B.down(out->csv, q, (size_t)csv_total);
-                HIP_OK(hipEventRecord(ev[5], ctx->stream));
-                HIP_OK(hipStreamSynchronize(ctx->stream));
-                HIP_OK(hipEventElapsedTime(&ms, ev[2], ev[3])); phase[3] += ms;
-                HIP_OK(hipEventElapsedTime(&ms, ev[4], ev[5])); phase[4] += ms;
-                st.bytes_d2h += (int64_t)csv_total;
-            }
-        }
-        out->totals[0] = (int64_t)csv_total;
-        if (out->xyz && xyz_rows <= (uint64_t)out->xyz_cap) { B.down(out->xyz, d_xyz, (size_t)xyz_rows * 24); st.bytes_d2h += (int64_t)xyz_rows * 24; }
-        rc = emgpu_ctx_sync(ctx);
-        float ms = 0.f;
-        HIP_OK(hipEventElapsedTime(&ms, ev[0], ev[1])); phase[2] = ms;
-    }
-    st.kernel_ms = phase[1] + phase[2] + phase[3]; st.d2h_ms = phase[4]; st.scatter_ms = phase[5];
-    st.total_ms = ms_since(t_call);
-    ctx->host_stats = st;
-    if (out->phase_ms) memcpy(out->phase_ms, phase, sizeof phase);
-    if (rc == EMGPU_OK && out->csv && csv_total > (uint64_t)out->csv_cap)
-        return fail(EMGPU_ERR_EVENT_CAP, "emgpu_tracks_text_host: the CSV text has " + std::to_string(csv_total) + " bytes, csv_cap is " + std::to_string(out->csv_cap));
-    if (rc == EMGPU_OK && out->xyz && xyz_rows > (uint64_t)out->xyz_cap)
-        return fail(EMGPU_ERR_EVENT_CAP, "emgpu_tracks_text_host: the tracks have " + std::to_string(xyz_rows) + " position rows, xyz_cap is " + std::to_string(out->xyz_cap));
-    return rc;
-    EMGPU_CATCH
 }
 
 } // extern "C"

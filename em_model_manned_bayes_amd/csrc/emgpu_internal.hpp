@@ -94,7 +94,7 @@ struct emgpu_ctx {
     std::map<std::array<uint64_t, 3>, emgpu::UncorLimits> limits_cache;
     hipStream_t side[kSide] = {nullptr, nullptr, nullptr};
     hipEvent_t ev_fork = nullptr, ev_join[kSide] = {nullptr, nullptr, nullptr};
-    // ---- the trace pool (emgpu_trace_alloc / emgpu_trace_free, emgpu_host.cpp): device blocks whose PLACEMENT has been measured.  A block
+    // ---- the trace pool (emgpu_trace_alloc / emgpu_trace_free, emgpu_memory.cpp): device blocks whose PLACEMENT has been measured.  A block
     // given back stays here and the next request it fits takes it without a new probe; emgpu_ctx_trim / emgpu_ctx_free release them.
     struct TraceBlock { void *p = nullptr; size_t bytes = 0; float ms = 0.f; bool probed = false; };
     std::vector<TraceBlock> trace_pool;
@@ -118,7 +118,7 @@ struct emgpu_ctx {
 // request order.  They never meet in one call: a host-path entry point samples through the *_device entry points and never enters a round
 // driver, a round driver draws through launch_dbn / launch_bn and never enters the host path, and CTX_LOCK lets one call at a time use a ctx.
 void *ctx_scratch(emgpu_ctx *ctx, size_t slot, size_t bytes);
-// emgpu_host.cpp
+// emgpu_memory.cpp
 void ctx_release_host_side(emgpu_ctx *ctx, bool everything);    // trim (false: pools and staging) / free (true: streams and events too)
 
 // sample2track.m:113-139: the unit ratios and the speed limits of a track call, into the kernel argument struct of either track kernel
@@ -145,6 +145,14 @@ class CallBuffers {
         ptrs_.push_back(nullptr);   // (the slot first: nothing can throw between the hipMalloc and the record)
         HIP_OK(hipMalloc(&ptrs_.back(), bytes));
         return static_cast<T *>(ptrs_.back());
+    }
+    // alloc for a block whose failure the caller reports in words of its own: null, with HIP's error cleared and the slot dropped
+    template <typename T> T *try_alloc(size_t bytes) {
+        ptrs_.push_back(nullptr);
+        if (hipMalloc(&ptrs_.back(), bytes) == hipSuccess) return static_cast<T *>(ptrs_.back());
+        (void)hipGetLastError();
+        ptrs_.pop_back();
+        return nullptr;
     }
     void up(void *dst, const void *src, size_t bytes) {
         if (bytes && src) HIP_OK(hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, ctx_->stream));

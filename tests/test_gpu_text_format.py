@@ -135,6 +135,44 @@ def test_format_g_capacity_protocol(gpu_ctx):
     assert native.format_g(gpu_ctx, np.zeros(0, dtype=np.float32)) == []
 
 
+def test_a_second_pass_continues_the_first(gpu_ctx):
+    """emgpu_format_g_host and emgpu_format_f0_host format 2^22 values per pass.  n = 2^22 + 5 is the smallest call with a second pass, which
+    starts at a total that is not zero and writes offsets from k0 = 2^22 on: text and offsets are those of two calls, on the first 2^22 values
+    and on the last 5, put together.  With a cap that holds the first pass only (exactly, or all but the last byte of the call) the status is
+    EMGPU_ERR_EVENT_CAP, the message and offsets[n] name the full total, the first pass's text has arrived and nothing was written behind it.
+    Through ctypes: no list of four million strings is built."""
+    n1 = 2 ** 22
+    n = n1 + 5
+    rs = np.random.RandomState(20261018)
+    cases = [("emgpu_format_g_host", f32(rs.randint(0, 2 ** 32, size=n, dtype=np.uint64).astype(np.uint32)), 12),
+             ("emgpu_format_f0_host", rs.uniform(-1e6, 1e6, n), 20)]     # (inside +-2^63: every value is formatted on the device)
+    for name, x, per in cases:
+        fn = getattr(L.lib(), name)
+
+        def call(v, cap):
+            v = np.ascontiguousarray(v)
+            out = np.full(cap + 64, 0xA5, dtype=np.uint8)                # (0xA5: no byte of a number's text)
+            offs = np.zeros(v.size + 1, dtype=np.uint64)
+            return fn(gpu_ctx._h, native._p(v), v.size, native._p(out), cap, native._p(offs)), out, offs
+
+        rc1, out1, o1 = call(x[:n1], per * n1)
+        rc2, out2, o2 = call(x[n1:], per * 5)
+        t1, t2 = int(o1[n1]), int(o2[5])
+        assert rc1 == 0 and rc2 == 0 and np.all(np.diff(o1.astype(np.int64)) > 0) and np.all(np.diff(o2.astype(np.int64)) > 0), name
+        want = np.concatenate([out1[:t1], out2[:t2]])
+        want_offs = np.concatenate([o1, o2[1:] + np.uint64(t1)])
+        rc, out, o = call(x, per * n)
+        assert rc == 0 and int(o[n]) == t1 + t2, (name, rc, int(o[n]), t1, t2)
+        assert np.array_equal(o[:n1 + 1], o1) and np.array_equal(o[n1:], o2 + np.uint64(t1)), name
+        assert np.array_equal(out[:t1 + t2], want) and np.all(out[t1 + t2:] == 0xA5), name
+        for cap in (t1, t1 + t2 - 1):
+            rc, out, o = call(x, cap)
+            msg = L.lib().emgpu_last_error().decode()
+            assert rc == L.ERR_EVENT_CAP and name in msg and str(t1 + t2) in msg, (name, cap, rc, msg)
+            assert int(o[n]) == t1 + t2 and np.array_equal(o, want_offs), (name, cap)
+            assert np.array_equal(out[:t1], out1[:t1]) and np.all(out[t1:] == 0xA5), (name, cap)
+
+
 # ------------------------------------------------------------------------------------------------ whole files
 def run_both(path, tmp_path, n, T, ctx, tag="", device_kw=None, **kw):
     """em_sample with the host writer and with the device writer: the four file names and the two results"""

@@ -1,4 +1,4 @@
-// tools/ubench/vmm_repro.hip -- the HIP virtual-memory calls the trace pool uses (csrc/emgpu_host.cpp), alone: K blocks of A GiB are built (address range on a
+// tools/ubench/vmm_repro.hip -- the HIP virtual-memory calls the trace pool uses (csrc/emgpu_memory.cpp), alone: K blocks of A GiB are built (address range on a
 // 1 GiB boundary, 1 GiB chunks), released, then one block of B GiB is built.  Prints every step (a crash names its call).
 #include <hip/hip_runtime.h>
 #include <cstdio>
