@@ -143,6 +143,10 @@ class TracksTextOut(C.Structure):   # emgpu_tracks_text_out
                 ("offsets", C.c_void_p), ("totals", C.c_void_p), ("xyz", C.c_void_p), ("xyz_cap", C.c_int64), ("phase_ms", C.c_void_p)]
 
 
+class ScoreParams(C.Structure):     # emgpu_score_params
+    _fields_ = [("n", C.c_int64), ("sample_time", C.c_int32), ("transition_mode", C.c_int32), ("ld", C.c_int64), ("col_offset", C.c_int64)]
+
+
 class BnParams(C.Structure):
     _fields_ = [("seed", C.c_uint64), ("first_index", C.c_uint64), ("n", C.c_int64), ("flags", C.c_uint32),
                 ("max_attempts", C.c_int32), ("bounds_sample", C.c_void_p),
@@ -171,6 +175,7 @@ SYMBOLS = [
     "emgpu_sample_text_host", "emgpu_text_bound", "emgpu_format_g_host", "emgpu_debug_format_paths",
     "emgpu_parse_table_host", "emgpu_format_f0_host", "emgpu_csv_bound", "emgpu_tracks_text_host",
     "emgpu_start_grid_log_weight", "emgpu_track_uncor_grid_host", "emgpu_track_uncor_grid_device",
+    "emgpu_model_log_prob", "emgpu_score_dbn_device", "emgpu_score_dbn_host", "emgpu_device_upload", "emgpu_device_download",
 ]
 
 _lib = None
@@ -347,6 +352,12 @@ def lib():
     L.emgpu_csv_bound.argtypes = [C.c_int64, C.c_int64]
     L.emgpu_csv_bound.restype = C.c_int64
     L.emgpu_tracks_text_host.argtypes = [C.c_void_p, C.POINTER(TrackParams), C.POINTER(TracksTextIn), C.POINTER(TracksTextOut)]
+    L.emgpu_model_log_prob.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int64]
+    L.emgpu_model_log_prob.restype = C.c_int64
+    for f in (L.emgpu_device_upload, L.emgpu_device_download):
+        f.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64]
+    for f in (L.emgpu_score_dbn_device, L.emgpu_score_dbn_host):
+        f.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(ScoreParams)] + [C.c_void_p] * 4
     _lib = L
     return L
 

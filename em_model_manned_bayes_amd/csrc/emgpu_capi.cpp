@@ -226,6 +226,13 @@ int64_t emgpu_model_get_f64(const emgpu_model *h, int32_t field, int32_t node, d
     return fail(EMGPU_ERR_ARG, "node out of range");
 }
 
+int64_t emgpu_model_log_prob(const emgpu_model *h, int32_t network, int32_t node, double *out, int64_t cap) {
+    EMGPU_TRY
+    if (!h) return fail(EMGPU_ERR_ARG, "null model");
+    return copy_out(emgpu::node_log_prob(h->m, network, node), out, cap);
+    EMGPU_CATCH
+}
+
 int64_t emgpu_model_get_text(const emgpu_model *h, int32_t field, char *out, int64_t cap) {
     if (!h) return fail(EMGPU_ERR_ARG, "null model");
     const std::vector<std::string> *v = field == EMGPU_F_LABELS_INITIAL ? &h->m.labels_initial
@@ -337,11 +344,11 @@ int emgpu_ctx_create(int32_t device, emgpu_ctx **out) {
     HIP_OK(hipSetDevice(device));
     HIP_OK(hipStreamCreateWithFlags(&c->own_stream, hipStreamNonBlocking));
     c->stream = c->own_stream;
-    HIP_OK(hipMalloc((void **)&c->d_status, sizeof(uint32_t)));
-    HIP_OK(hipMemset(c->d_status, 0, sizeof(uint32_t)));
+    HIP_OK(hipMalloc((void **)&c->d_status, 2 * sizeof(uint32_t)));   // word 1: k_score_dbn's "a bin outside 1..r" (a plain store, no atomic)
+    HIP_OK(hipMemset(c->d_status, 0, 2 * sizeof(uint32_t)));
     HIP_OK(hipMalloc((void **)&c->d_queue, sizeof(uint32_t)));
-    HIP_OK(hipHostMalloc((void **)&c->h_status, sizeof(uint32_t), hipHostMallocDefault));
-    *c->h_status = 0;
+    HIP_OK(hipHostMalloc((void **)&c->h_status, 2 * sizeof(uint32_t), hipHostMallocDefault));
+    c->h_status[0] = c->h_status[1] = 0;
     *out = c.release();
     return EMGPU_OK;
     EMGPU_CATCH
@@ -359,13 +366,18 @@ int emgpu_ctx_sync(emgpu_ctx *ctx) {
     if (!ctx) return fail(EMGPU_ERR_ARG, "null ctx");
     CTX_LOCK(ctx);
     HIP_OK(hipSetDevice(ctx->device));
-    HIP_OK(hipMemcpyAsync(ctx->h_status, ctx->d_status, sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
-    HIP_OK(hipMemsetAsync(ctx->d_status, 0, sizeof(uint32_t), ctx->stream));
+    HIP_OK(hipMemcpyAsync(ctx->h_status, ctx->d_status, 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_OK(hipMemsetAsync(ctx->d_status, 0, sizeof(uint32_t), ctx->stream));   // (word 1 stays until it is the one reported)
     HIP_OK(hipStreamSynchronize(ctx->stream));
-    const uint32_t st = *ctx->h_status;
+    const uint32_t st = ctx->h_status[0];
     if (st & 1u) return fail(EMGPU_ERR_REJECT_CAP, "rejection loop reached max_attempts for at least one trajectory");
     if (st & 4u) return fail(EMGPU_ERR_PRESET, "Attempt to preset a dependent variable (a row of the start grid presets a node without its parents, or a bin outside 1..r)");
     if (st & 2u) return fail(EMGPU_ERR_EVENT_CAP, "an event list did not fit event_cap rows");
+    if (ctx->h_status[1]) {   // one error per call: a bad-bin report behind a sampler's error above is kept for the next sync
+        HIP_OK(hipMemsetAsync(ctx->d_status + 1, 0, sizeof(uint32_t), ctx->stream));
+        HIP_OK(hipStreamSynchronize(ctx->stream));
+        return fail(EMGPU_ERR_ARG, emgpu_detail::kScoreBadBin);
+    }
     return EMGPU_OK;
     EMGPU_CATCH
 }
@@ -413,7 +425,7 @@ int32_t emgpu_last_launch_count(const emgpu_ctx *ctx) { return ctx ? ctx->last_l
 // argument list (terminal propagation, mixed batches) and must survive the eviction.
 // Entries outlive emgpu_model_free (a model does not know the contexts that uploaded it): they are
 // reclaimed by this LRU sweep or by emgpu_ctx_free; at most 48 + the models of one call stay resident.
-static Uploaded &get_uploaded(emgpu_ctx *ctx, const emgpu_model *h, const std::set<uint64_t> *pinned = nullptr) {
+Uploaded &get_uploaded(emgpu_ctx *ctx, const emgpu_model *h, const std::set<uint64_t> *pinned) {
     if (ctx->cache.size() > 48 && ctx->cache.find(h->m.uid) == ctx->cache.end()) {
         // models come and go (their tables stay uploaded): drop the least recently used half
         HIP_OK(hipStreamSynchronize(ctx->stream));
@@ -462,7 +474,7 @@ static Uploaded &get_uploaded(emgpu_ctx *ctx, const emgpu_model *h, const std::s
 
 // the log-probability table behind per-sample log-weights, uploaded on first use (with the model version it was built for: get_uploaded
 // frees every table when the model changes)
-static void ensure_logp(emgpu_ctx *ctx, Uploaded &u, const Model &m) {
+void ensure_logp(emgpu_ctx *ctx, Uploaded &u, const Model &m) {
     if (u.d_logp) return;
     const std::vector<double> lp = emgpu::initial_log_prob(m, u.lp_off);
     HIP_OK(hipMalloc((void **)&u.d_logp, (lp.size() + 1) * sizeof(double)));

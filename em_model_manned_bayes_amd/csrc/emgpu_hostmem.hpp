@@ -1,5 +1,5 @@
-// emgpu_hostmem.hpp -- what the three host-pointer units share: emgpu_memory.cpp (which defines all of it), emgpu_host.cpp (the chunked
-// sampling path) and emgpu_files.cpp (the text tables and files).  Nothing else includes it.
+// emgpu_hostmem.hpp -- what the host-pointer units share: emgpu_memory.cpp (which defines all of it), emgpu_host.cpp (the chunked
+// sampling path), emgpu_files.cpp (the text tables and files) and emgpu_score.cpp (the chunked scoring path).  Nothing else includes it.
 #pragma once
 #include <chrono>
 

@@ -59,9 +59,14 @@ struct Uploaded {
     void *d_planf = nullptr; // the plan itself (+ k_uncor_fast's resample thresholds) for launches that serve several models
     double *d_logp = nullptr; // log P of the initial network (emgpu::initial_log_prob), uploaded when a call first asks for log-weights
     uint32_t lp_off[EMGPU_MAX_NI] = {0};
+    // log P of the transition network (emgpu::transition_log_prob) for emgpu_score_dbn_*, uploaded when a call first scores (the initial
+    // network's is d_logp); like d_logp it belongs to `version`: get_uploaded frees every table when anything of the model has changed
+    double *d_logpt = nullptr;
+    uint32_t lpt_off[EMGPU_MAX_ND] = {0};   // by temporal-map row
     void free_tables() {
         (void)hipFree(d_thr); (void)hipFree(d_cthr); (void)hipFree(d_pthr); (void)hipFree(d_bnd); (void)hipFree(d_planf); (void)hipFree(d_logp);
-        d_thr = d_cthr = d_pthr = nullptr; d_bnd = nullptr; d_planf = nullptr; d_logp = nullptr;
+        (void)hipFree(d_logpt);
+        d_thr = d_cthr = d_pthr = nullptr; d_bnd = nullptr; d_planf = nullptr; d_logp = nullptr; d_logpt = nullptr;
     }
 };
 
@@ -70,10 +75,10 @@ struct emgpu_ctx {
     int device = 0;
     hipStream_t stream = nullptr;
     hipStream_t own_stream = nullptr;
-    uint32_t *d_status = nullptr;
+    uint32_t *d_status = nullptr;   // two words: the sampler's status bits, k_score_dbn's bad-bin word (emgpu_ctx_sync reads and clears both)
     uint32_t *d_queue = nullptr;  // k_terminal_propagate: the launch's track queue (one word, zeroed by the launcher)
     EmgpuPresets *d_presets = nullptr;   // the start grid / log-weight block of the last DBN call that had one
-    uint32_t *h_status = nullptr; // pinned
+    uint32_t *h_status = nullptr; // pinned, two words
     std::map<uint64_t, Uploaded> cache; // by Model::uid
     uint64_t use_clock = 0;
     std::string last_kernel;
@@ -113,6 +118,13 @@ struct emgpu_ctx {
 };
 
 // emgpu_capi.cpp
+// The model's tables on this ctx's device, uploaded (again) when the model's version is not the uploaded one.  `pinned`: uids that must survive
+// the eviction of old entries (the other models of the current call).
+Uploaded &get_uploaded(emgpu_ctx *ctx, const emgpu_model *h, const std::set<uint64_t> *pinned = nullptr);
+void ensure_logp(emgpu_ctx *ctx, Uploaded &u, const Model &m);   // u.d_logp / u.lp_off, uploaded on first use
+namespace emgpu_detail {
+constexpr const char *kScoreBadBin = "score: a bin outside 1..r in the trace (the log-likelihood of those trajectories is NaN)";
+}
 // slot-th scratch buffer of the ctx, at least `bytes` long.  Two users share the slots: the host-path sampling entry points of emgpu_host.cpp
 // take slot 0 (the start grid) and slot 1 (the index list) by number, and the round drivers of emgpu_capi.cpp (RoundScratch) take 0 ... k in
 // request order.  They never meet in one call: a host-path entry point samples through the *_device entry points and never enters a round

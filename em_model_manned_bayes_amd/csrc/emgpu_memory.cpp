@@ -405,6 +405,26 @@ int emgpu_device_free(emgpu_ctx *ctx, void *p) {
     EMGPU_CATCH
 }
 
+// plain copies between a caller's host array and device memory, on the ctx stream, complete when the call returns
+static int device_copy(emgpu_ctx *ctx, void *dst, const void *src, uint64_t bytes, hipMemcpyKind kind) {
+    EMGPU_TRY
+    if (!ctx) return fail(EMGPU_ERR_ARG, "null ctx");
+    if (bytes == 0) return EMGPU_OK;
+    if (!dst || !src) return fail(EMGPU_ERR_ARG, "null argument");
+    CTX_LOCK(ctx);
+    HIP_OK(hipSetDevice(ctx->device));
+    HIP_OK(hipMemcpyAsync(dst, src, (size_t)bytes, kind, ctx->stream));
+    HIP_OK(hipStreamSynchronize(ctx->stream));
+    return EMGPU_OK;
+    EMGPU_CATCH
+}
+int emgpu_device_upload(emgpu_ctx *ctx, void *dst_device, const void *src_host, uint64_t bytes) {
+    return device_copy(ctx, dst_device, src_host, bytes, hipMemcpyHostToDevice);
+}
+int emgpu_device_download(emgpu_ctx *ctx, void *dst_host, const void *src_device, uint64_t bytes) {
+    return device_copy(ctx, dst_host, src_device, bytes, hipMemcpyDeviceToHost);
+}
+
 // ================================================================================================ the pinned pool
 int emgpu_host_alloc(emgpu_ctx *ctx, uint64_t bytes, void **out) {
     EMGPU_TRY

@@ -204,21 +204,51 @@ double Model::start_log_weight() const {
     return lw;
 }
 
+// log of the column-normalised N + A of one node, appended to lp: column after column, r entries each.  tot is the column's entries added in
+// ascending bin order; an all-zero column is bin 1 with certainty (select_random.m:17-20).  The one definition behind both networks' tables.
+static void append_log_prob(std::vector<double> &lp, const std::vector<double> &N, const std::vector<double> &A, int r, int64_t q) {
+    for (int64_t c = 0; c < q; c++) {
+        double tot = 0.0;
+        for (int k = 0; k < r; k++) tot += N[(size_t)(c * r + k)] + A[(size_t)(c * r + k)];
+        for (int k = 0; k < r; k++) {
+            const double w = N[(size_t)(c * r + k)] + A[(size_t)(c * r + k)];
+            lp.push_back(tot > 0 ? std::log(w / tot) : (k == 0 ? 0.0 : -INFINITY));
+        }
+    }
+}
+
 std::vector<double> initial_log_prob(const Model &m, uint32_t off[EMGPU_MAX_NI]) {
     std::vector<double> lp;
     for (int p = 0; p < m.n_initial && p < EMGPU_MAX_NI; p++) {
-        const int v = m.order_initial[(size_t)p] - 1, r = m.r_initial[(size_t)v];
+        const int v = m.order_initial[(size_t)p] - 1;
         off[p] = (uint32_t)lp.size();
-        const std::vector<double> &N = m.N_initial[(size_t)v], &A = m.A_initial[(size_t)v];
-        const int64_t q = m.q_initial[(size_t)v];
-        for (int64_t c = 0; c < q; c++) {
-            double tot = 0.0;
-            for (int k = 0; k < r; k++) tot += N[(size_t)(c * r + k)] + A[(size_t)(c * r + k)];
-            for (int k = 0; k < r; k++) {
-                const double w = N[(size_t)(c * r + k)] + A[(size_t)(c * r + k)];
-                lp.push_back(tot > 0 ? std::log(w / tot) : (k == 0 ? 0.0 : -INFINITY));
-            }
-        }
+        append_log_prob(lp, m.N_initial[(size_t)v], m.A_initial[(size_t)v], m.r_initial[(size_t)v], m.q_initial[(size_t)v]);
+    }
+    return lp;
+}
+
+std::vector<double> transition_log_prob(const Model &m, uint32_t off[EMGPU_MAX_ND]) {
+    std::vector<double> lp;
+    for (int k = 0; k < m.n_dyn() && k < EMGPU_MAX_ND; k++) {
+        const int tv = m.temporal_map[(size_t)k][1] - 1;
+        off[k] = (uint32_t)lp.size();
+        if (tv < 0 || tv >= m.n_transition || m.N_transition[(size_t)tv].empty()) throw Error(EMGPU_ERR_ARG, "dynamic variable without a transition table");
+        append_log_prob(lp, m.N_transition[(size_t)tv], m.A_transition[(size_t)tv], m.r_transition[(size_t)tv], m.q_transition[(size_t)tv]);
+    }
+    return lp;
+}
+
+std::vector<double> node_log_prob(const Model &m, int network, int node) {
+    std::vector<double> lp;
+    if (network == 0) {
+        if (node < 1 || node > m.n_initial) throw Error(EMGPU_ERR_ARG, "node out of range");
+        append_log_prob(lp, m.N_initial[(size_t)node - 1], m.A_initial[(size_t)node - 1], m.r_initial[(size_t)node - 1], m.q_initial[(size_t)node - 1]);
+    } else if (network == 1) {
+        if (node < 1 || node > m.n_transition) throw Error(EMGPU_ERR_ARG, "node out of range");
+        if (!m.N_transition[(size_t)node - 1].empty())   // (the nodes of the first slice have no table: em_read.m:92)
+            append_log_prob(lp, m.N_transition[(size_t)node - 1], m.A_transition[(size_t)node - 1], m.r_transition[(size_t)node - 1], m.q_transition[(size_t)node - 1]);
+    } else {
+        throw Error(EMGPU_ERR_ARG, "network must be 0 (initial) or 1 (transition)");
     }
     return lp;
 }

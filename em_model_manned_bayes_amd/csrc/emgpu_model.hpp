@@ -99,6 +99,12 @@ UncorLimits build_uncor_limits(const Model &m, const UncorTrackVars &tv);
 // column-normalised N + alpha; an all-zero column draws bin 1 with certainty (select_random.m:17-20: sthres = 0).  The table behind the
 // per-sample log-weights of a start grid (InitStartTerminal.m:57-90).
 std::vector<double> initial_log_prob(const Model &m, uint32_t off[EMGPU_MAX_NI]);
+// The same for the transition network: the (t+1) node of temporal-map row k (ascending variable id, the k of dyn_bin), column after column in
+// the numbering of asub2ind over the node's parents (the plan's d_stride_*), r entries each; off[k] = the first entry of row k.  Entries are
+// computed by the one function initial_log_prob uses.  The table emgpu_score_dbn_* gathers from.
+std::vector<double> transition_log_prob(const Model &m, uint32_t off[EMGPU_MAX_ND]);
+// the r x q entries of one node (1-based variable id) of network 0 (initial) / 1 (transition), column-major; empty for a node without a table
+std::vector<double> node_log_prob(const Model &m, int network, int node);
 // out[i] = the log-weight of row i of a start grid [n][n_initial] (0 = unset: the model's own start): the table above summed in the order
 // of lane_presets (emgpu_device.h).  Throws EMGPU_ERR_PRESET naming the first row that breaks one of lane_presets' two rules.
 void start_grid_log_weight(const Model &m, const int32_t *start, int64_t n, double *out);

@@ -313,6 +313,14 @@ class EncounterModel:
         log-weight of every sample drawn with this start distribution (0.0 without presets)."""
         return self.native.start_log_weight()
 
+    def log_likelihood(self, init_bin, dyn_bin=None, transition_mode=L.TRANSITION_REFERENCE_AUTO, ctx=None):
+        """log P(trajectory | this model) of bins in the shapes native.sample_dbn_host returns: init_bin [n, n_initial], dyn_bin [n, T, n_dyn]
+        (None: the initial network alone).  Summed on the GPU in the order DESIGN.md fixes (initial nodes in topological order, then second after
+        second); the rejection loop's normalisation is not part of it.  Returns [n] float64."""
+        ctx = ctx or native.default_context()
+        T = 1 if dyn_bin is None else int(np.asarray(dyn_bin).shape[1])
+        return native.score_dbn_host(ctx, self.native, init_bin, dyn_bin, T, transition_mode)["log_lik"]
+
     def _start_grid(self, start_grid, n):
         """A start grid as the library takes it: [n, n_initial] int32 by variable id, None / NaN / 0 = unset."""
         grid = np.array([[0 if (v is None or (isinstance(v, float) and np.isnan(v))) else int(v) for v in row] for row in start_grid], dtype=np.int32)

@@ -162,6 +162,15 @@ class NativeModel:
         else:
             raise L.EmgpuError(L.ERR_PRIOR, "Second argument must be a char or double")
 
+    def log_prob(self, network, node):
+        """emgpu_model_log_prob: log P(bin | column) of one node (network 0 initial / 1 transition, node = 1-based variable id) as
+        [r, q] -- the entries start_grid_log_weight and score_dbn_* add up.  [0, 0] for a transition node without a table."""
+        n = L.check(L.lib().emgpu_model_log_prob(self._h, int(network), int(node), None, 0))
+        out = np.zeros(n, dtype=np.float64)
+        L.check(L.lib().emgpu_model_log_prob(self._h, int(network), int(node), _p(out), n))
+        r = int(self.get_i32(L.F_R_TRANSITION if network else L.F_R_INITIAL)[node - 1]) if n else 0
+        return out.reshape(-1, r).T if n else out.reshape(0, 0)
+
     def set_transition_stay_prior(self, prior):
         L.check(L.lib().emgpu_model_set_transition_stay_prior(self._h, float(prior)))
 
@@ -603,6 +612,158 @@ def unpack_dyn_val(dv, T):
     """[G4][nd][n][4] f32 -> [n, T, nd] f32."""
     G4, nd, n, _ = dv.shape
     return np.ascontiguousarray(dv.transpose(2, 0, 3, 1).reshape(n, G4 * 4, nd)[:, :T, :])
+
+
+def pack_dyn_bin(db):
+    """[n, T, nd] uint8 -> [G4][nd][n] uint32 (the inverse of unpack_dyn_bin; padding columns are 0)."""
+    db = np.asarray(db, dtype=np.uint8)
+    n, T, nd = db.shape
+    G4 = (T + 3) // 4
+    b = np.zeros((n, G4 * 4, nd), dtype=np.uint8)
+    b[:, :T, :] = db
+    return np.ascontiguousarray(b.reshape(n, G4, 4, nd).transpose(1, 3, 0, 2)).view(np.uint32).reshape(G4, nd, n)
+
+
+def score_params(n, sample_time, transition_mode=L.TRANSITION_REFERENCE_AUTO, ld=0, col_offset=0):
+    p = L.ScoreParams()
+    p.n, p.sample_time, p.transition_mode, p.ld, p.col_offset = int(n), int(sample_time), int(transition_mode), int(ld), int(col_offset)
+    return p
+
+
+def score_dbn_device(ctx, model, params, init_bin, dyn_bin=0, log_lik=0, initial=0):
+    """emgpu_score_dbn_device: asynchronous, raw device pointers (ints; dyn_bin 0 for sample_time 1 or a model without a transition network,
+    initial 0 = not wanted).  log_lik / initial [n] f64 are not offset by col_offset.  A bin outside 1..r makes its trajectory NaN and the
+    next ctx.sync() raise EmgpuError(ERR_ARG)."""
+    L.check(L.lib().emgpu_score_dbn_device(ctx._h, model._h, C.byref(params), C.c_void_p(init_bin or None), C.c_void_p(dyn_bin or None),
+                                           C.c_void_p(log_lik or None), C.c_void_p(initial or None)))
+
+
+def score_dbn_host(ctx, model, init_bin, dyn_bin, T, transition_mode=L.TRANSITION_REFERENCE_AUTO, raw=False, n=None, col_offset=0):
+    """log P(trajectory | model) of a host trace (emgpu_score_dbn_host; the definition is in include/emgpu.h).  raw=False: the user-facing
+    shapes sample_dbn_host returns (init_bin [n, n_i] u8, dyn_bin [n, T, n_d] u8 or None); raw=True: the library layout (init_bin [n_i, ld]
+    u8, dyn_bin [G4, n_d, ld] u32), of which columns col_offset .. col_offset + n are scored (n: default ld - col_offset).
+    Returns {"log_lik" [n], "initial" [n], "kernel"}.  The rejection loop's normalisation (altitude / speed / layers) is not part of the
+    number.  A bin outside 1..r raises EmgpuError(ERR_ARG) carrying .log_lik / .initial (NaN for exactly those trajectories)."""
+    if raw:
+        ib = np.ascontiguousarray(init_bin, dtype=np.uint8)
+        db = None if dyn_bin is None else np.ascontiguousarray(dyn_bin, dtype=np.uint32)
+    else:
+        ib = np.ascontiguousarray(np.asarray(init_bin, dtype=np.uint8).T)
+        db = None if dyn_bin is None else pack_dyn_bin(dyn_bin)
+    if ib.ndim != 2 or ib.shape[0] != model.n_initial:
+        raise ValueError("init_bin must hold n_initial entries per trajectory")
+    ld = ib.shape[1]
+    n = ld - int(col_offset) if n is None else int(n)
+    if db is not None and (db.ndim != 3 or db.shape != ((int(T) + 3) // 4, model.n_dyn, ld)):
+        raise ValueError("dyn_bin must hold T columns of n_dyn variables for the trajectories of init_bin")
+    p = score_params(n, T, transition_mode, ld, col_offset)
+    ll, ini = np.zeros(max(n, 0), dtype=np.float64), np.zeros(max(n, 0), dtype=np.float64)
+    rc = L.lib().emgpu_score_dbn_host(ctx._h, model._h, C.byref(p), _p(ib), _p(db), _p(ll), _p(ini))
+    if rc < 0:
+        e = L.EmgpuError(int(rc), L.lib().emgpu_last_error().decode("utf-8", "replace"))
+        e.log_lik, e.initial = ll, ini
+        raise e
+    return {"log_lik": ll, "initial": ini, "kernel": ctx.last_kernel()}
+
+
+def device_upload(ctx, addr, src):
+    """emgpu_device_upload: the numpy array `src` into device memory at addr, on the context's stream; complete on return."""
+    src = np.ascontiguousarray(src)
+    L.check(L.lib().emgpu_device_upload(ctx._h, C.c_void_p(int(addr)), _p(src), src.nbytes))
+
+
+def device_download(ctx, addr, out):
+    """emgpu_device_download: out.nbytes bytes of device memory at addr (an emgpu_device_alloc block, a trace) into the contiguous numpy
+    array `out`, behind the launches already issued on the context's stream; complete on return.  Returns out."""
+    assert out.flags["C_CONTIGUOUS"]
+    L.check(L.lib().emgpu_device_download(ctx._h, _p(out), C.c_void_p(int(addr)), out.nbytes))
+    return out
+
+
+def _same_shape(a, b):
+    tm_a, tm_b = a.get_i32(L.F_TEMPORAL_MAP).reshape(-1, 2), b.get_i32(L.F_TEMPORAL_MAP).reshape(-1, 2)
+    if a.n_initial != b.n_initial or not np.array_equal(a.get_i32(L.F_R_INITIAL), b.get_i32(L.F_R_INITIAL)):
+        return False
+    if not np.array_equal(tm_a, tm_b):
+        return False
+    return bool(np.array_equal(a.get_i32(L.F_R_TRANSITION)[tm_a[:, 1] - 1], b.get_i32(L.F_R_TRANSITION)[tm_b[:, 1] - 1])) if len(tm_a) else True
+
+
+def sample_weighted_host(ctx, proposal, target, n, T, seed, raw=False, want_log_weight=False, first_index=0,
+                         transition_mode=L.TRANSITION_REFERENCE_AUTO, flags=0, max_attempts=1000, idx_L=0, idx_v=0, idx_dh=0, layers=None,
+                         indices=None, start=None):
+    """Importance sampling between two models of one shape: draw n trajectories of T seconds under `proposal` into a
+    device-resident trace (emgpu_sample_dbn_device), score that trace under both models where it lies, and bring everything back.
+    The keywords are make_params' sampling keywords, with sample_dbn_host's meaning; `indices` [n] uint64 and `start` [n, n_initial] (a
+    start grid, 0 = unset) are numpy arrays, which this function copies to the device.  Returns a dict: init_bin, init_val, dyn_bin, dyn_val
+    and attempts -- equal to what sample_dbn_host(ctx, proposal, n, T, seed, <the same keywords>) returns under these names (raw: in the
+    library's layout) -- `kernel` (the sampler's) and `score_kernel`, log_weight (want_log_weight: the start grid's log-weights under the
+    proposal, as sample_dbn_host's), log_lik_proposal, log_lik_target and log_weight_model = log_lik_target - log_lik_proposal, subtracted
+    on the host.  No event lists and no host_stats: nothing goes through the chunked host path.
+    The weights are those of the networks alone: a rejection loop (idx_L / idx_v / idx_dh, layers) renormalises both models differently,
+    and that ratio is not part of them.  ValueError when the models differ in n_initial, r_initial, the temporal map or the dynamic
+    variables' r, or when `start` / `indices` are not arrays of the shapes above."""
+    if not _same_shape(proposal, target):
+        raise ValueError("sample_weighted_host: proposal and target differ in n_initial, r_initial, the temporal map or the dynamic variables' r")
+    ni, nd, T, n = proposal.n_initial, proposal.n_dyn, int(T), int(n)
+    G4 = (T + 3) // 4
+    # a host address in params.start / .indices would be read by the kernel: both go to the device block first
+    if start is not None:
+        if isinstance(start, int):
+            raise ValueError("sample_weighted_host: start is a numpy start grid [n, n_initial], not a device pointer")
+        start = np.ascontiguousarray(start, dtype=np.int32)
+        if start.shape != (n, ni):
+            raise ValueError("sample_weighted_host: start must be [n, n_initial]")
+    if indices is not None:
+        if isinstance(indices, int):
+            raise ValueError("sample_weighted_host: indices is a numpy array of n global indices, not a device pointer")
+        indices = np.ascontiguousarray(indices, dtype=np.uint64).reshape(-1)
+        if indices.size != n:
+            raise ValueError("sample_weighted_host: indices must hold n entries")
+    sizes = [("init_bin", ni * n), ("init_val", 4 * ni * n), ("dyn_bin", 4 * G4 * nd * n), ("dyn_val", 16 * G4 * nd * n), ("attempts", 4 * n),
+             ("ll_p", 8 * n), ("ll_t", 8 * n), ("lw", 8 * n), ("start", 4 * ni * n if start is not None else 0),
+             ("indices", 8 * n if indices is not None else 0)]
+    off, o = {}, 0
+    for name, b in sizes:
+        off[name] = o
+        o += (b + 255) // 256 * 256
+    base = ctx.device_alloc(max(o, 256))
+    try:
+        at = {k: base + v for k, v in off.items()}
+        if start is not None:
+            device_upload(ctx, at["start"], start)
+        if indices is not None:
+            device_upload(ctx, at["indices"], indices)
+        p, keep = make_params(n, T, seed, first_index=first_index, transition_mode=transition_mode, flags=flags, max_attempts=max_attempts,
+                              idx_L=idx_L, idx_v=idx_v, idx_dh=idx_dh, layers=layers, indices=at["indices"] if indices is not None else None,
+                              start=at["start"] if start is not None else None)
+        dense = nd > 0
+        sample_dbn_device(ctx, proposal, p, init_bin=at["init_bin"], init_val=at["init_val"], dyn_bin=at["dyn_bin"] if dense else 0,
+                          dyn_val=at["dyn_val"] if dense else 0, attempts=at["attempts"], log_weight=at["lw"] if want_log_weight else 0)
+        kernel = ctx.last_kernel()
+        sp = score_params(n, T, p.transition_mode)
+        score_dbn_device(ctx, proposal, sp, at["init_bin"], at["dyn_bin"] if dense else 0, at["ll_p"])
+        score_dbn_device(ctx, target, sp, at["init_bin"], at["dyn_bin"] if dense else 0, at["ll_t"])
+        out = {"kernel": kernel, "score_kernel": ctx.last_kernel()}
+        ctx.sync()                                  # the three launches' deferred errors
+        ib = device_download(ctx, at["init_bin"], np.zeros((ni, n), np.uint8))
+        iv = device_download(ctx, at["init_val"], np.zeros((ni, n), np.float32))
+        out["attempts"] = device_download(ctx, at["attempts"], np.zeros(n, np.int32))
+        out["init_bin"], out["init_val"] = (ib, iv) if raw else (ib.T.copy(), iv.T.copy())
+        if dense:
+            db = device_download(ctx, at["dyn_bin"], np.zeros((G4, nd, n), np.uint32))
+            dv = device_download(ctx, at["dyn_val"], np.zeros((G4, nd, n, 4), np.float32))
+            out["dyn_bin"] = db if raw else unpack_dyn_bin(db, T)
+            out["dyn_val"] = dv if raw else unpack_dyn_val(dv, T)
+        if want_log_weight:
+            out["log_weight"] = device_download(ctx, at["lw"], np.zeros(n, np.float64))
+        out["log_lik_proposal"] = device_download(ctx, at["ll_p"], np.zeros(n, np.float64))
+        out["log_lik_target"] = device_download(ctx, at["ll_t"], np.zeros(n, np.float64))
+        out["log_weight_model"] = out["log_lik_target"] - out["log_lik_proposal"]
+    finally:
+        ctx.device_free(base)
+    del keep
+    return out
 
 
 def sample_bn_host(ctx, model, n, seed, first_index=0, dediscretize=False, max_attempts=100000, bounds_sample=None,

@@ -146,6 +146,12 @@ int emgpu_model_start_log_weight(const emgpu_model *m, double *out);
  * sampler's two rules: a bin outside 1..r, or a preset node with a parent that is not preset.  What the entry points without a weight output
  * (emgpu_sample_uncor_host, emgpu_sample_text_host, emgpu_track_uncor_grid_*) leave to the caller. */
 int emgpu_start_grid_log_weight(const emgpu_model *m, const int32_t *start, int64_t n, double *out);
+/* log P(bin | column) of one node as the library computes it: P = N + alpha (alpha as set_prior / the stay prior left it), entry (b, j) =
+ * log(w / tot) with tot the column's entries added in ascending bin order; an all-zero column is 0.0 for bin 1 and -inf for the others
+ * (select_random.m:17-20).  network: 0 initial, 1 transition; node: 1-based variable id; r x q entries column-major, with the count and
+ * capacity conventions of emgpu_model_get_f64 (0 entries for a transition node without a table).  These are the entries
+ * emgpu_start_grid_log_weight and emgpu_score_dbn_* add up. */
+int64_t emgpu_model_log_prob(const emgpu_model *m, int32_t network, int32_t node, double *out, int64_t cap);
 /* EncounterModel.zero_bins (EncounterModel.m:40; derived once by em_read.m:110-114,143-156 and, like in
  * the reference, NOT re-derived when boundaries are replaced): n_initial entries, 0 = none. */
 int emgpu_model_set_zero_bins(emgpu_model *m, const int32_t *zero_bins, int32_t n);
@@ -371,6 +377,42 @@ int emgpu_trace_free(emgpu_ctx *ctx, emgpu_trace *t);
  * emgpu_sample_terminal_device (createEncounter.m:74-84), a consumer's own buffers.  Freed by emgpu_device_free, or with the ctx. */
 int emgpu_device_alloc(emgpu_ctx *ctx, uint64_t bytes, void **out);
 int emgpu_device_free(emgpu_ctx *ctx, void *p);
+/* Plain copies between a caller's host array and device memory (a block of emgpu_device_alloc, a trace), on the ctx stream behind the launches
+ * already issued; complete when the call returns.  They do not read the deferred status: emgpu_ctx_sync still reports it. */
+int emgpu_device_upload(emgpu_ctx *ctx, void *dst_device, const void *src_host, uint64_t bytes);
+int emgpu_device_download(emgpu_ctx *ctx, void *dst_host, const void *src_device, uint64_t bytes);
+
+/* ------------------------------------------------------------------------------------------------
+ * Scoring a trace: log P(trajectory | model) of every trajectory of a trace in the layout of emgpu_sample_out (init_bin [n_initial][ld],
+ * dyn_bin [G4][n_dyn][ld]; ld 0 = n; the call reads columns col_offset .. col_offset + n).  The outputs log_lik [n] and initial [n]
+ * (may be NULL) are NOT offset, like log_weight.
+ *   log_lik[i] is a double acc that starts at +0.0 and receives, one IEEE addition at a time, entries of emgpu_model_log_prob:
+ *   1. for the initial nodes in topological order (order_initial): the entry at the node's bin, in the column its parents' bins select
+ *      (asub2ind.m:13-14, parents in ascending index).  initial[i] = acc after this step;
+ *   2. for t = 1 .. sample_time-1, and within t for the rows k of the temporal map in ascending order (the k of dyn_bin): the entry of that
+ *      variable's (t+1) node at its bin in column t, in the column its parents select.
+ *   Parent bins: per step (dbn_sample.m:65-93; EMGPU_TRANSITION_PER_STEP, or REFERENCE_AUTO when is_dynvar_depend) a static parent's bin in
+ *   init_bin, a time-t node's bin in column t-1, a (t+1) node's bin in column t; frozen (dbn_sample.m:97-135; REFERENCE_AUTO otherwise)
+ *   every parent's bin at column 0 (static parents: init_bin), for all t.
+ * -inf entries make the sum -inf; valid bins never give NaN.  A bin outside 1..r among the bins the call reads (init_bin; for sample_time > 1
+ * columns 0 .. sample_time-1 of dyn_bin) makes THAT trajectory's log_lik NaN (initial: when the bin is one of init_bin); no read leaves the
+ * tables, and the call reports EMGPU_ERR_ARG: _host by its return value (the outputs are written), _device at the next emgpu_ctx_sync.
+ * The report of a _device call is a word of the ctx: it stays pending through later calls until an emgpu_ctx_sync returns it.  A sync that
+ * has a sampler's deferred error to return (rejection cap, preset, event cap) returns that one and keeps the bad-bin report for the next
+ * sync; a _host call reports its own trace only and leaves a pending _device report in place.
+ * dyn_bin may be NULL when sample_time == 1 or the model has no transition network.
+ * The number is the probability under the networks alone: the normalisation by the rejection loop of UncorEncounterModel.sample (altitude,
+ * speed, `layers`) is NOT part of it.  For importance weights between two models of one shape, subtract two scores of the same trace.
+ * _host works in chunks of EMGPU_HOST_CHUNK_MB device bytes (default 256) and needs no device memory proportional to n. */
+typedef struct {
+    int64_t n;
+    int32_t sample_time, transition_mode;
+    int64_t ld, col_offset;
+} emgpu_score_params;
+int emgpu_score_dbn_device(emgpu_ctx *ctx, const emgpu_model *m, const emgpu_score_params *p, const uint8_t *init_bin, const uint32_t *dyn_bin,
+                           double *log_lik, double *initial);
+int emgpu_score_dbn_host(emgpu_ctx *ctx, const emgpu_model *m, const emgpu_score_params *p, const uint8_t *init_bin, const uint32_t *dyn_bin,
+                         double *log_lik, double *initial);
 
 /* Pinned host memory for the outputs of the *_host entry points (hipHostMalloc, kept in a per-ctx pool: pinning gigabytes costs about as
  * much as copying them).  emgpu_sample_dbn_host recognises pinned output arrays and lets the copy engine write straight into them;
