@@ -176,6 +176,7 @@ SYMBOLS = [
     "emgpu_parse_table_host", "emgpu_format_f0_host", "emgpu_csv_bound", "emgpu_tracks_text_host",
     "emgpu_start_grid_log_weight", "emgpu_track_uncor_grid_host", "emgpu_track_uncor_grid_device",
     "emgpu_model_log_prob", "emgpu_score_dbn_device", "emgpu_score_dbn_host", "emgpu_device_upload", "emgpu_device_download",
+    "emgpu_count_layout", "emgpu_count_dbn_device", "emgpu_count_dbn_host",
 ]
 
 _lib = None
@@ -357,6 +358,9 @@ def lib():
     for f in (L.emgpu_device_upload, L.emgpu_device_download):
         f.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64]
     for f in (L.emgpu_score_dbn_device, L.emgpu_score_dbn_host):
+        f.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(ScoreParams)] + [C.c_void_p] * 4
+    L.emgpu_count_layout.argtypes = [C.c_void_p, C.c_int32, C.c_void_p]
+    for f in (L.emgpu_count_dbn_device, L.emgpu_count_dbn_host):
         f.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(ScoreParams)] + [C.c_void_p] * 4
     _lib = L
     return L

@@ -1,0 +1,178 @@
+// emgpu_count.cpp -- emgpu_count_layout / emgpu_count_dbn_device / emgpu_count_dbn_host: the sufficient statistics of a trace (k_count_dbn,
+// emgpu_kernels_count.hip; the definition is in emgpu_count.h and DESIGN.md).  The host entry point uploads and counts in chunks of
+// EMGPU_HOST_CHUNK_MB device bytes into device tables it keeps across the chunks, and adds them to the caller's once, at the end: it never
+// holds device memory proportional to n.
+#include <algorithm>
+#include <cstring>
+#include <utility>
+
+#include "emgpu_count.h"
+#include "emgpu_hostmem.hpp"
+
+using namespace emgpu_detail;
+
+namespace {
+constexpr const char *kCountBadBin = "count: a bin outside 1..r in the trace (the observations that read it were skipped)";
+
+// the first element of every node's table in a network's counts array, and the total behind the last: the element order and count of
+// emgpu_model_get_f64(EMGPU_F_N_INITIAL / EMGPU_F_N_TRANSITION, node), node after node
+std::vector<int64_t> layout(const Model &m, int network) {
+    const auto &N = network == 0 ? m.N_initial : m.N_transition;
+    std::vector<int64_t> off(N.size() + 1, 0);
+    for (size_t v = 0; v < N.size(); v++) off[v + 1] = off[v] + (int64_t)N[v].size();
+    return off;
+}
+
+int check_args(const emgpu_model *h, const emgpu_score_params *p, const void *init_bin, const void *dyn_bin, const void *ci, const void *ct) {
+    return emgpu::check_trace_args(h, p, init_bin, dyn_bin, ci || ct, "both counts arrays", ct != nullptr);
+}
+
+// the kernel's argument block but its buffers; want_i / want_t: the networks the call counts
+bool fill_count(const Model &m, const EmgpuPlan &P, const emgpu_score_params *p, bool want_i, bool want_t, EmgpuCountRun &A) {
+    const std::vector<int64_t> oi = layout(m, 0), ot = layout(m, 1);
+    if (oi.back() > 0xFFFFFFF0ll || ot.back() > 0xFFFFFFF0ll) throw Error(EMGPU_ERR_UNSUPPORTED, "count table too large (the kernel indexes it with 32 bits)");
+    uint32_t i_off[EMGPU_MAX_NI] = {0}, d_off[EMGPU_MAX_ND] = {0};
+    memset(&A, 0, sizeof A);
+    std::vector<std::pair<uint32_t, int>> small;   // (cells, position p | 64 + row k) of the counted tables
+    for (int q = 0; q < P.ni; q++) {
+        i_off[q] = (uint32_t)oi[P.i_var[q]];
+        A.i_cells[q] = (uint32_t)(oi[(size_t)P.i_var[q] + 1] - oi[P.i_var[q]]);
+        if (want_i) small.push_back({A.i_cells[q], q});
+    }
+    for (int k = 0; k < m.n_dyn() && k < EMGPU_MAX_ND; k++) {
+        const int tv = m.temporal_map[(size_t)k][1] - 1;
+        if (tv < 0 || tv >= m.n_transition || m.N_transition[(size_t)tv].empty()) throw Error(EMGPU_ERR_ARG, "dynamic variable without a transition table");
+        d_off[k] = (uint32_t)ot[(size_t)tv];
+        A.d_cells[k] = (uint32_t)(ot[(size_t)tv + 1] - ot[(size_t)tv]);
+        if (want_t) small.push_back({A.d_cells[k], 64 + k});
+    }
+    const bool per_step = emgpu::fill_trace_graph(P, p, i_off, d_off, A.G);
+    // the LDS partials: the smallest tables first, while they fit
+    for (auto &x : A.i_lds) x = EMGPU_COUNT_NO_LDS;
+    for (auto &x : A.d_lds) x = EMGPU_COUNT_NO_LDS;
+    std::sort(small.begin(), small.end());
+    for (const auto &s : small) {
+        if (A.lds_used + s.first > EMGPU_COUNT_LDS_CELLS) break;
+        (s.second >= 64 ? A.d_lds[s.second - 64] : A.i_lds[s.second]) = A.lds_used;
+        A.lds_used += s.first;
+    }
+    // whose bins an observation reads (a parent is a non-zero stride: a stride is a product of bin counts)
+    for (int q = 0; q < P.ni; q++) {
+        A.i_mask[q] = 1u << q;
+        for (int j = 0; j < q; j++) if (A.G.i_stride[q][j]) A.i_mask[q] |= 1u << j;
+    }
+    for (int k = 0; k < P.nd; k++) {
+        A.d_nmask[k] = 1u << k;
+        for (int q = 0; q < P.ni; q++) if (A.G.d_static[k][q]) A.d_smask[k] |= 1u << q;
+        for (int kp = 0; kp < P.nd; kp++) {
+            if (A.G.d_cur[k][kp]) A.d_cmask[k] |= 1u << kp;
+            if (A.G.d_new[k][kp]) A.d_nmask[k] |= 1u << kp;
+        }
+    }
+    return per_step;
+}
+
+void launch(emgpu_ctx *ctx, const EmgpuCountRun &A, bool per_step) {
+    const char *name = "";
+    launch_ok(emgpu::launch_count_dbn(A, per_step, ctx->stream, &name));
+    ctx->last_kernel = name;
+    ctx->last_launches++;
+}
+} // namespace
+
+extern "C" {
+
+int emgpu_count_layout(const emgpu_model *h, int32_t network, int64_t *offsets) {
+    EMGPU_TRY
+    if (!h || !offsets) return fail(EMGPU_ERR_ARG, "null argument");
+    if (network != 0 && network != 1) return fail(EMGPU_ERR_ARG, "network must be 0 (initial) or 1 (transition)");
+    const std::vector<int64_t> off = layout(h->m, network);
+    memcpy(offsets, off.data(), off.size() * sizeof(int64_t));
+    return EMGPU_OK;
+    EMGPU_CATCH
+}
+
+int emgpu_count_dbn_device(emgpu_ctx *ctx, const emgpu_model *h, const emgpu_score_params *p, const uint8_t *init_bin, const uint32_t *dyn_bin,
+                           uint64_t *counts_initial, uint64_t *counts_transition) {
+    EMGPU_TRY
+    if (const int rc = check_args(h, p, init_bin, dyn_bin, counts_initial, counts_transition)) return rc;
+    if (!ctx) return fail(EMGPU_ERR_ARG, "null ctx");
+    CTX_LOCK(ctx);
+    HIP_OK(hipSetDevice(ctx->device));
+    Uploaded &u = get_uploaded(ctx, h);
+    EmgpuCountRun A;
+    const bool per_step = fill_count(h->m, u.cp.plan, p, counts_initial != nullptr, counts_transition != nullptr, A);
+    const size_t off = (size_t)p->col_offset;
+    A.G.n = p->n; A.G.ld = p->ld ? p->ld : p->n;
+    A.G.init_bin = init_bin ? init_bin + off : nullptr;
+    A.G.dyn_bin = dyn_bin && p->sample_time > 1 ? dyn_bin + off : nullptr;
+    A.G.bad = ctx->d_status + 1;
+    A.counts_i = (unsigned long long *)counts_initial; A.counts_t = (unsigned long long *)counts_transition;
+    ctx->last_launches = 0;
+    launch(ctx, A, per_step);
+    return EMGPU_OK;
+    EMGPU_CATCH
+}
+
+int emgpu_count_dbn_host(emgpu_ctx *ctx, const emgpu_model *h, const emgpu_score_params *p, const uint8_t *init_bin, const uint32_t *dyn_bin,
+                         uint64_t *counts_initial, uint64_t *counts_transition) {
+    EMGPU_TRY
+    if (const int rc = check_args(h, p, init_bin, dyn_bin, counts_initial, counts_transition)) return rc;
+    if (!ctx) return fail(EMGPU_ERR_ARG, "null ctx");
+    CTX_LOCK(ctx);
+    HIP_OK(hipSetDevice(ctx->device));
+    Uploaded &u = get_uploaded(ctx, h);
+    EmgpuCountRun A;
+    const bool per_step = fill_count(h->m, u.cp.plan, p, counts_initial != nullptr, counts_transition != nullptr, A);
+    ctx->last_launches = 0;
+    ctx->last_kernel = per_step ? "k_count_dbn[per-step]" : "k_count_dbn[frozen]";
+    if (p->n == 0) return EMGPU_OK;
+    const int64_t ld = p->ld ? p->ld : p->n;
+    const bool dyn = counts_transition && dyn_bin && p->sample_time > 1;
+    const size_t ni = (size_t)A.G.ni, rows_d = dyn ? (size_t)((p->sample_time + 3) / 4) * (size_t)A.G.nd : 0;
+    // the device tables of this call: the model's size, whatever n is
+    const size_t cells_i = counts_initial ? (size_t)layout(h->m, 0).back() : 0, cells_t = counts_transition ? (size_t)layout(h->m, 1).back() : 0;
+    CallBuffers B(ctx);
+    uint64_t *d_counts = B.alloc<uint64_t>((cells_i + cells_t + 1) * sizeof(uint64_t));
+    HIP_OK(hipMemsetAsync(d_counts, 0, (cells_i + cells_t + 1) * sizeof(uint64_t), ctx->stream));
+    A.counts_i = counts_initial ? (unsigned long long *)d_counts : nullptr;
+    A.counts_t = counts_transition ? (unsigned long long *)(d_counts + cells_i) : nullptr;
+    // a chunk: c trajectories, c a multiple of 256 (the device arrays' trajectory dimension), of about host_chunk_target device bytes
+    const size_t per_lane = ni + 4 * rows_d;
+    const size_t target = host_chunk_target((size_t)256 << 20);
+    const int64_t c = (int64_t)std::min<size_t>(round_up((size_t)p->n, 256), std::max<size_t>(target / per_lane / 256 * 256, 256));
+    const size_t o_dyn = round_up(ni * (size_t)c, 256);
+    char *dev = (char *)device_block_or_trim(ctx, o_dyn + round_up(4 * rows_d * (size_t)c, 256) + 256, true);
+    if (!dev) return fail(EMGPU_ERR_HIP, "emgpu_count_dbn_host: out of device memory for one chunk");
+    struct Release { emgpu_ctx *ctx; void *p; ~Release() { (void)hipStreamSynchronize(ctx->stream); device_release(p); } } release{ctx, dev};
+    A.G.ld = c;
+    A.G.init_bin = (const uint8_t *)dev;
+    A.G.dyn_bin = rows_d ? (const uint32_t *)(dev + o_dyn) : nullptr;
+    A.G.bad = ctx->d_status + 1;
+    // the word may hold the report of an earlier _device call nobody has synchronized on yet: that one is not this call's (emgpu_score_dbn_host)
+    HIP_OK(hipMemcpyAsync(ctx->h_status + 1, ctx->d_status + 1, sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_OK(hipMemsetAsync(ctx->d_status + 1, 0, sizeof(uint32_t), ctx->stream));
+    HIP_OK(hipStreamSynchronize(ctx->stream));
+    const bool pending = ctx->h_status[1] != 0;
+    for (int64_t c0 = 0; c0 < p->n; c0 += c) {
+        const int64_t cn = std::min<int64_t>(c, p->n - c0);
+        const size_t src = (size_t)(p->col_offset + c0);
+        HIP_OK(hipMemcpy2DAsync(dev, (size_t)c, init_bin + src, (size_t)ld, (size_t)cn, ni, hipMemcpyHostToDevice, ctx->stream));
+        if (rows_d) HIP_OK(hipMemcpy2DAsync(dev + o_dyn, 4 * (size_t)c, dyn_bin + src, 4 * (size_t)ld, 4 * (size_t)cn, rows_d, hipMemcpyHostToDevice, ctx->stream));
+        A.G.n = cn;
+        launch(ctx, A, per_step);
+        HIP_OK(hipStreamSynchronize(ctx->stream));   // the next chunk overwrites the buffer; the caller's arrays are pageable
+    }
+    std::vector<uint64_t> got(cells_i + cells_t);
+    B.down(got.data(), d_counts, got.size() * sizeof(uint64_t));
+    HIP_OK(hipMemcpyAsync(ctx->h_status + 1, ctx->d_status + 1, sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_OK(hipMemsetAsync(ctx->d_status + 1, pending ? 1 : 0, sizeof(uint32_t), ctx->stream));   // (any non-zero word is a report)
+    HIP_OK(hipStreamSynchronize(ctx->stream));
+    for (size_t j = 0; j < cells_i; j++) counts_initial[j] += got[j];
+    for (size_t j = 0; j < cells_t; j++) counts_transition[j] += got[cells_i + j];
+    if (ctx->h_status[1]) return fail(EMGPU_ERR_ARG, kCountBadBin);
+    return EMGPU_OK;
+    EMGPU_CATCH
+}
+
+} // extern "C"

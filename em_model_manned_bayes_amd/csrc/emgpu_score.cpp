@@ -3,6 +3,7 @@
 // EMGPU_HOST_CHUNK_MB device bytes: it never holds device memory proportional to n.
 #include <algorithm>
 #include <cstring>
+#include <string>
 
 #include "emgpu_hostmem.hpp"
 #include "emgpu_score.h"
@@ -23,48 +24,15 @@ void ensure_score_tables(emgpu_ctx *ctx, Uploaded &u, const Model &m) {
     HIP_OK(hipStreamSynchronize(ctx->stream));   // lp is a local
 }
 
-// what can be said about a call without a device: EMGPU_OK, or the error (recorded)
-int check_args(const emgpu_model *h, const emgpu_score_params *p, const void *init_bin, const void *dyn_bin, const void *log_lik) {
-    if (!h || !p) return fail(EMGPU_ERR_ARG, "null argument");
-    if (p->n < 0 || p->sample_time < 1 || p->sample_time > 65535) return fail(EMGPU_ERR_ARG, "n < 0 or sample_time outside 1..65535");
-    if (p->transition_mode != EMGPU_TRANSITION_REFERENCE_AUTO && p->transition_mode != EMGPU_TRANSITION_PER_STEP)
-        return fail(EMGPU_ERR_ARG, "unknown transition_mode");
-    const int64_t ld = p->ld ? p->ld : p->n;
-    if (ld < 0 || p->col_offset < 0 || p->col_offset + p->n > ld) return fail(EMGPU_ERR_ARG, "col_offset + n exceeds ld");
-    if (h->m.n_initial > EMGPU_MAX_NI || h->m.n_dyn() > EMGPU_MAX_ND) return fail(EMGPU_ERR_UNSUPPORTED, "more variables than EMGPU_MAX_NI / EMGPU_MAX_ND");
-    if (p->n > 0 && (!init_bin || !log_lik)) return fail(EMGPU_ERR_ARG, "null init_bin or log_lik");
-    if (p->n > 0 && !dyn_bin && p->sample_time > 1 && h->m.n_dyn() > 0)
-        return fail(EMGPU_ERR_ARG, "null dyn_bin: only a call with sample_time 1, or a model without a transition network, has no transitions to score");
-    return EMGPU_OK;
-}
-
 // the kernel's argument block but its buffers
 bool fill_score(const Uploaded &u, const emgpu_score_params *p, EmgpuScoreRun &A) {
-    const EmgpuPlan &P = u.cp.plan;
-    memset(&A, 0, sizeof A);
-    A.T = p->sample_time; A.ni = P.ni; A.nd = P.nd;
+    const bool per_step = emgpu::fill_trace_graph(u.cp.plan, p, u.lp_off, u.lpt_off, A);
     A.logp_i = u.d_logp; A.logp_t = u.d_logpt;
-    memcpy(A.i_var, P.i_var, sizeof A.i_var);
-    memcpy(A.i_r, P.i_r, sizeof A.i_r);
-    memcpy(A.i_off, u.lp_off, sizeof A.i_off);
-    memcpy(A.i_stride, P.i_stride, sizeof A.i_stride);
-    for (int k = 0; k < P.nd; k++) {   // the plan numbers the dynamic variables in sampling order, the trace and the sum by temporal-map row
-        const int row = P.d_row[k];
-        A.d_r[row] = P.d_r[k];
-        A.d_off[row] = u.lpt_off[row];
-        memcpy(A.d_static[row], P.d_stride_static[k], sizeof A.d_static[row]);
-        for (int kp = 0; kp < P.nd; kp++) {
-            A.d_cur[row][P.d_row[kp]] = P.d_stride_cur[k][kp];
-            A.d_new[row][P.d_row[kp]] = P.d_stride_new[k][kp];
-        }
-    }
-    // padding: positions >= ni and rows >= nd repeat node 0 / row 0 with zero strides (the kernel loads them and keeps them out of the sum)
-    for (int q = P.ni; q < EMGPU_MAX_NI; q++) {
-        A.i_var[q] = A.i_var[0]; A.i_r[q] = A.i_r[0]; A.i_off[q] = A.i_off[0];
-        memset(A.i_stride[q], 0, sizeof A.i_stride[q]);
-    }
-    for (int k = P.nd; k < EMGPU_MAX_ND && P.nd > 0; k++) { A.d_r[k] = A.d_r[0]; A.d_off[k] = A.d_off[0]; }
-    return p->transition_mode == EMGPU_TRANSITION_PER_STEP || P.depend != 0;   // dbn_sample.m:55
+    return per_step;
+}
+
+int check_args(const emgpu_model *h, const emgpu_score_params *p, const void *init_bin, const void *dyn_bin, const void *log_lik) {
+    return emgpu::check_trace_args(h, p, init_bin, dyn_bin, log_lik != nullptr, "log_lik", true);
 }
 
 void launch(emgpu_ctx *ctx, const EmgpuScoreRun &A, bool per_step) {
@@ -74,6 +42,49 @@ void launch(emgpu_ctx *ctx, const EmgpuScoreRun &A, bool per_step) {
     ctx->last_launches++;
 }
 } // namespace
+
+namespace emgpu {
+int check_trace_args(const emgpu_model *h, const emgpu_score_params *p, const void *init_bin, const void *dyn_bin, bool have_out,
+                     const char *outputs, bool transitions) {
+    if (!h || !p) return fail(EMGPU_ERR_ARG, "null argument");
+    if (p->n < 0 || p->sample_time < 1 || p->sample_time > 65535) return fail(EMGPU_ERR_ARG, "n < 0 or sample_time outside 1..65535");
+    if (p->transition_mode != EMGPU_TRANSITION_REFERENCE_AUTO && p->transition_mode != EMGPU_TRANSITION_PER_STEP)
+        return fail(EMGPU_ERR_ARG, "unknown transition_mode");
+    const int64_t ld = p->ld ? p->ld : p->n;
+    if (ld < 0 || p->col_offset < 0 || p->col_offset + p->n > ld) return fail(EMGPU_ERR_ARG, "col_offset + n exceeds ld");
+    if (h->m.n_initial > EMGPU_MAX_NI || h->m.n_dyn() > EMGPU_MAX_ND) return fail(EMGPU_ERR_UNSUPPORTED, "more variables than EMGPU_MAX_NI / EMGPU_MAX_ND");
+    if (p->n > 0 && (!init_bin || !have_out)) return fail(EMGPU_ERR_ARG, std::string("null init_bin or ") + outputs);
+    if (p->n > 0 && !dyn_bin && transitions && p->sample_time > 1 && h->m.n_dyn() > 0)
+        return fail(EMGPU_ERR_ARG, "null dyn_bin: only a call with sample_time 1, or a model without a transition network, has no transitions to score");
+    return EMGPU_OK;
+}
+
+bool fill_trace_graph(const EmgpuPlan &P, const emgpu_score_params *p, const uint32_t *i_off, const uint32_t *d_off, EmgpuScoreRun &A) {
+    memset(&A, 0, sizeof A);
+    A.T = p->sample_time; A.ni = P.ni; A.nd = P.nd;
+    memcpy(A.i_var, P.i_var, sizeof A.i_var);
+    memcpy(A.i_r, P.i_r, sizeof A.i_r);
+    memcpy(A.i_off, i_off, sizeof A.i_off);
+    memcpy(A.i_stride, P.i_stride, sizeof A.i_stride);
+    for (int k = 0; k < P.nd; k++) {   // the plan numbers the dynamic variables in sampling order, the trace and the sum by temporal-map row
+        const int row = P.d_row[k];
+        A.d_r[row] = P.d_r[k];
+        A.d_off[row] = d_off[row];
+        memcpy(A.d_static[row], P.d_stride_static[k], sizeof A.d_static[row]);
+        for (int kp = 0; kp < P.nd; kp++) {
+            A.d_cur[row][P.d_row[kp]] = P.d_stride_cur[k][kp];
+            A.d_new[row][P.d_row[kp]] = P.d_stride_new[k][kp];
+        }
+    }
+    // padding: positions >= ni and rows >= nd repeat node 0 / row 0 with zero strides (the kernels load them and keep them out of the result)
+    for (int q = P.ni; q < EMGPU_MAX_NI; q++) {
+        A.i_var[q] = A.i_var[0]; A.i_r[q] = A.i_r[0]; A.i_off[q] = A.i_off[0];
+        memset(A.i_stride[q], 0, sizeof A.i_stride[q]);
+    }
+    for (int k = P.nd; k < EMGPU_MAX_ND && P.nd > 0; k++) { A.d_r[k] = A.d_r[0]; A.d_off[k] = A.d_off[0]; }
+    return p->transition_mode == EMGPU_TRANSITION_PER_STEP || P.depend != 0;   // dbn_sample.m:55
+}
+} // namespace emgpu
 
 extern "C" {
 

@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "../../include/emgpu.h"
 #include "emgpu_plan.h"
 
 // The definition (DESIGN.md "Scoring a trace"): acc starts at +0.0 and receives one IEEE double addition per node, in this order:
@@ -37,6 +38,15 @@ struct EmgpuScoreRun {
     uint32_t d_new[EMGPU_MAX_ND][EMGPU_MAX_ND];      // the (t+1) node of row k'
 };
 
+struct emgpu_model;
 namespace emgpu {
+// What can be said about a trace call (emgpu_score_dbn_*, emgpu_count_dbn_*) without a device: EMGPU_OK, or the error (recorded).  `have_out`:
+// the call's required output is there (`outputs` names it in the message); `transitions`: the call reads dyn_bin when the trace has any.
+int check_trace_args(const emgpu_model *h, const emgpu_score_params *p, const void *init_bin, const void *dyn_bin, bool have_out,
+                     const char *outputs, bool transitions);
+// The graph part of the argument block from the model's plan -- topological positions, strides by temporal-map row, padding positions and
+// rows -- with i_off / d_off [by temporal-map row] as the caller's tables are laid out; the buffers stay null.  The one owner of this
+// derivation: k_score_dbn and k_count_dbn (emgpu_count.h) index with it.  Returns whether the parents are read per step (dbn_sample.m:55).
+bool fill_trace_graph(const EmgpuPlan &P, const emgpu_score_params *p, const uint32_t *i_off, const uint32_t *d_off, EmgpuScoreRun &A);
 hipError_t launch_score_dbn(const EmgpuScoreRun &A, bool per_step, hipStream_t s, const char **name);
 }

@@ -321,6 +321,17 @@ class EncounterModel:
         T = 1 if dyn_bin is None else int(np.asarray(dyn_bin).shape[1])
         return native.score_dbn_host(ctx, self.native, init_bin, dyn_bin, T, transition_mode)["log_lik"]
 
+    def count(self, init_bin, dyn_bin=None, transition_mode=L.TRANSITION_REFERENCE_AUTO, ctx=None):
+        """The sufficient statistics of bins in the shapes native.sample_dbn_host returns (init_bin [n, n_initial], dyn_bin [n, T, n_dyn];
+        None: the initial network alone, N_transition all zero): how often every cell of this model's graph was observed, counted on the
+        GPU.  Returns (N_initial, N_transition, None, None), the argument order of setParameters, so m.setParameters(*m.count(ib, db))
+        makes the trace the model.  all_repeat and all_change are None: they describe continuous values inside a bin, which a bin trace
+        does not carry (updateResampleRates tolerates None).  An observation that reads a bin outside 1..r raises EmgpuError(ERR_ARG)."""
+        ctx = ctx or native.default_context()
+        T = 1 if dyn_bin is None else int(np.asarray(dyn_bin).shape[1])
+        got = native.count_dbn_host(ctx, self.native, init_bin, dyn_bin, T, transition_mode)
+        return got["N_initial"], got["N_transition"], None, None
+
     def _start_grid(self, start_grid, n):
         """A start grid as the library takes it: [n, n_initial] int32 by variable id, None / NaN / 0 = unset."""
         grid = np.array([[0 if (v is None or (isinstance(v, float) and np.isnan(v))) else int(v) for v in row] for row in start_grid], dtype=np.int32)

@@ -171,6 +171,13 @@ class NativeModel:
         r = int(self.get_i32(L.F_R_TRANSITION if network else L.F_R_INITIAL)[node - 1]) if n else 0
         return out.reshape(-1, r).T if n else out.reshape(0, 0)
 
+    def count_layout(self, network):
+        """emgpu_count_layout: the element offsets of the nodes' tables in a counts array of count_dbn_* (network 0 initial / 1 transition):
+        [n nodes + 1] int64, node v (1-based) at offsets[v - 1] : offsets[v], r x q column-major; the last entry is the array's length."""
+        off = np.zeros((self.n_transition if network else self.n_initial) + 1, dtype=np.int64)
+        L.check(L.lib().emgpu_count_layout(self._h, int(network), _p(off)))
+        return off
+
     def set_transition_stay_prior(self, prior):
         L.check(L.lib().emgpu_model_set_transition_stay_prior(self._h, float(prior)))
 
@@ -664,6 +671,110 @@ def score_dbn_host(ctx, model, init_bin, dyn_bin, T, transition_mode=L.TRANSITIO
         e.log_lik, e.initial = ll, ini
         raise e
     return {"log_lik": ll, "initial": ini, "kernel": ctx.last_kernel()}
+
+
+def count_dbn_device(ctx, model, params, init_bin, dyn_bin=0, counts_initial=0, counts_transition=0):
+    """emgpu_count_dbn_device: asynchronous, raw device pointers (ints; params: score_params).  counts_initial / counts_transition are uint64
+    arrays in the layout of model.count_layout(network), which the call ADDS to (the caller zeroes them); 0 = that network is not counted.
+    An observation that reads a bin outside 1..r is skipped, and the next ctx.sync() raises EmgpuError(ERR_ARG)."""
+    L.check(L.lib().emgpu_count_dbn_device(ctx._h, model._h, C.byref(params), C.c_void_p(init_bin or None), C.c_void_p(dyn_bin or None),
+                                           C.c_void_p(counts_initial or None), C.c_void_p(counts_transition or None)))
+
+
+def split_counts(model, raw):
+    """(u64 initial array, u64 transition array) in the library's layout -> (N_initial, N_transition): one [r, q] float64 per variable, (0, 0)
+    for a transition node without a table -- what NativeModel.from_arrays and EncounterModel.setParameters take.  Exact below 2**53."""
+    out = []
+    for network, a in enumerate(raw):
+        off = model.count_layout(network).tolist()
+        r = model.get_i32(L.F_R_TRANSITION if network else L.F_R_INITIAL)
+        out.append([a[s:e].astype(np.float64).reshape(-1, int(r[v])).T.copy() if e > s else np.zeros((0, 0))
+                    for v, (s, e) in enumerate(zip(off[:-1], off[1:]))])
+    return out[0], out[1]
+
+
+def _counts_arrays(model, counts):
+    """the two u64 arrays of a call: fresh zeros, or a previous result's `raw` (accumulated into, in place)"""
+    sizes = [int(model.count_layout(network)[-1]) for network in (0, 1)]
+    if counts is None:
+        return [np.zeros(max(s, 1), dtype=np.uint64)[:s] for s in sizes]
+    ci, ct = counts
+    for a, s in ((ci, sizes[0]), (ct, sizes[1])):
+        if not isinstance(a, np.ndarray) or a.dtype != np.uint64 or a.shape != (s,) or not a.flags["C_CONTIGUOUS"]:
+            raise ValueError("counts must be the `raw` pair of a count of this model: contiguous uint64 arrays of count_layout's lengths")
+    return [ci, ct]
+
+
+def count_dbn_host(ctx, model, init_bin, dyn_bin, T, transition_mode=L.TRANSITION_REFERENCE_AUTO, raw=False, n=None, col_offset=0, counts=None):
+    """The sufficient statistics of a host trace (emgpu_count_dbn_host; the definition is in include/emgpu.h): how often every cell of the
+    model's N_initial / N_transition was observed.  The trace is given as to score_dbn_host (raw=False: init_bin [n, n_i] u8, dyn_bin
+    [n, T, n_d] u8 or None; raw=True: the library layout and its window n / col_offset).
+    Returns {"N_initial": [r x q float64 per variable], "N_transition": [per node, (0, 0) where no table], "raw": (u64 initial, u64
+    transition), "kernel"}.  counts=<a previous result's raw> accumulates into those arrays.  dyn_bin None counts the initial network alone.
+    A bin outside 1..r skips the observations that read it and raises EmgpuError(ERR_ARG) carrying .counts (the same dict)."""
+    if raw:
+        ib = np.ascontiguousarray(init_bin, dtype=np.uint8)
+        db = None if dyn_bin is None else np.ascontiguousarray(dyn_bin, dtype=np.uint32)
+    else:
+        ib = np.ascontiguousarray(np.asarray(init_bin, dtype=np.uint8).T)
+        db = None if dyn_bin is None else pack_dyn_bin(dyn_bin)
+    if ib.ndim != 2 or ib.shape[0] != model.n_initial:
+        raise ValueError("init_bin must hold n_initial entries per trajectory")
+    ld = ib.shape[1]
+    n = ld - int(col_offset) if n is None else int(n)
+    if db is not None and (db.ndim != 3 or db.shape != ((int(T) + 3) // 4, model.n_dyn, ld)):
+        raise ValueError("dyn_bin must hold T columns of n_dyn variables for the trajectories of init_bin")
+    ci, ct = _counts_arrays(model, counts)
+    p = score_params(n, T, transition_mode, ld, col_offset)
+    transitions = db is not None and int(T) > 1 and model.n_dyn > 0
+    rc = L.lib().emgpu_count_dbn_host(ctx._h, model._h, C.byref(p), _p(ib), _p(db), _p(ci), _p(ct) if transitions else None)
+    Ni, Nt = split_counts(model, (ci, ct))
+    out = {"N_initial": Ni, "N_transition": Nt, "raw": (ci, ct), "kernel": ctx.last_kernel()}
+    if rc < 0:
+        e = L.EmgpuError(int(rc), L.lib().emgpu_last_error().decode("utf-8", "replace"))
+        e.counts = out
+        raise e
+    return out
+
+
+def sample_count_host(ctx, model, n, T, seed, transition_mode=L.TRANSITION_REFERENCE_AUTO, first_index=0, counts=None):
+    """Sample n trajectories of T seconds into a device block (emgpu_sample_dbn_device), count them where they lie (emgpu_count_dbn_device)
+    and bring back the tables alone: the trace never crosses PCIe.  The trace is the one sample_dbn_host(ctx, model, n, T, seed,
+    transition_mode=..., first_index=...) returns, so the result equals count_dbn_host of that.  Returns count_dbn_host's dict, with
+    `kernel` the sampler's and `count_kernel` the counting kernel's."""
+    ni, nd, T, n = model.n_initial, model.n_dyn, int(T), int(n)
+    G4 = (T + 3) // 4
+    ci, ct = _counts_arrays(model, counts)
+    sizes = [("init_bin", ni * n), ("init_val", 4 * ni * n), ("dyn_bin", 4 * G4 * nd * n), ("dyn_val", 16 * G4 * nd * n), ("attempts", 4 * n),
+             ("ci", 8 * ci.size), ("ct", 8 * ct.size)]
+    off, o = {}, 0
+    for name, b in sizes:
+        off[name] = o
+        o += (b + 255) // 256 * 256
+    base = ctx.device_alloc(max(o, 256))
+    try:
+        at = {k: base + v for k, v in off.items()}
+        for name, a in (("ci", ci), ("ct", ct)):
+            if a.size:
+                device_upload(ctx, at[name], np.zeros_like(a))
+        p, keep = make_params(n, T, seed, first_index=first_index, transition_mode=transition_mode)
+        dense = nd > 0
+        sample_dbn_device(ctx, model, p, init_bin=at["init_bin"], init_val=at["init_val"], dyn_bin=at["dyn_bin"] if dense else 0,
+                          dyn_val=at["dyn_val"] if dense else 0, attempts=at["attempts"])
+        kernel = ctx.last_kernel()
+        transitions = dense and T > 1
+        count_dbn_device(ctx, model, score_params(n, T, p.transition_mode), at["init_bin"], at["dyn_bin"] if transitions else 0,
+                         at["ci"], at["ct"] if transitions else 0)
+        count_kernel = ctx.last_kernel()
+        ctx.sync()                                  # both launches' deferred errors
+        for name, a in (("ci", ci), ("ct", ct)):
+            if a.size:
+                a += device_download(ctx, at[name], np.zeros_like(a))
+    finally:
+        ctx.device_free(base)
+    del keep
+    Ni, Nt = split_counts(model, (ci, ct))
+    return {"N_initial": Ni, "N_transition": Nt, "raw": (ci, ct), "kernel": kernel, "count_kernel": count_kernel}
 
 
 def device_upload(ctx, addr, src):

@@ -414,6 +414,39 @@ int emgpu_score_dbn_device(emgpu_ctx *ctx, const emgpu_model *m, const emgpu_sco
 int emgpu_score_dbn_host(emgpu_ctx *ctx, const emgpu_model *m, const emgpu_score_params *p, const uint8_t *init_bin, const uint32_t *dyn_bin,
                          double *log_lik, double *initial);
 
+/* ------------------------------------------------------------------------------------------------
+ * Counting a trace: the sufficient statistics of a trace in the layout above -- how often every cell of the model's count tables N_initial /
+ * N_transition was observed.  The inverse of sampling: what EncounterModel.setParameters(N_initial, N_transition, ...) and preallocNInitial
+ * (EncounterModel.m) take, which the reference only ever reads from a file.  Parameters: emgpu_score_params, with the rules of
+ * emgpu_score_dbn_* (sample_time 1..65535; dyn_bin may be NULL only when nothing transitions, or when the transition network is not counted).
+ * An OBSERVATION is one of
+ *   (a) an initial node v of a trajectory: the cell (bin of v, column selected by its parents' bins) of N_initial{v} (asub2ind.m:13-14,
+ *       parents in ascending index);
+ *   (b) for t = 1 .. sample_time-1 and every row k of the temporal map, the (t+1) node of row k at column t: a cell of that node's
+ *       N_transition, parent bins read exactly as emgpu_score_dbn_* reads them under the same transition_mode: per step
+ *       (EMGPU_TRANSITION_PER_STEP, or REFERENCE_AUTO on a dependent-branch model), frozen at column 0 otherwise.
+ *       PER_STEP gives the sufficient statistics of a DBN seen as data.  The frozen mode is the inverse of the reference's frozen-parent
+ *       sampler (dbn_sample.m:97-135): a trace drawn that way counts back into the tables it was drawn from.
+ * Each observation adds exactly 1 to its cell: nothing is clamped or saturated and no add is lost.  An observation whose own bin, or any
+ * parent bin it reads, lies outside 1..r is SKIPPED: it adds nothing, no load or store leaves the buffers, and every other observation of
+ * that trajectory still counts (skipping is per observation, not per trajectory: that is what one pass can do).  A call that skipped anything
+ * reports EMGPU_ERR_ARG through the channel and by the rules of scoring: _host by its return value, with the counts written; _device at the
+ * next emgpu_ctx_sync, through the same pending word.
+ * The counts are uint64_t, one array per network: the nodes by variable id 1 .. n_initial (1 .. n_transition), each r x q column-major with
+ * exactly the element order and count of emgpu_model_get_f64(EMGPU_F_N_INITIAL / EMGPU_F_N_TRANSITION, node), concatenated; a transition
+ * node without a table has 0 elements.  emgpu_count_layout writes the nodes' element offsets and the total: offsets[n nodes + 1]; network 0 =
+ * initial, 1 = transition; host only, no ctx.
+ * Calls ACCUMULATE: the caller zeroes the arrays, and may count many traces (or ranks: add the per-rank tables) into one.  One call of
+ * 10 M x 240 s can put 2.4e9 into one cell, hence 64 bits; the conversion to the model's f64 N is exact below 2^53.
+ * Either counts pointer may be NULL: that network is not counted (and its observations report nothing).
+ * _host works in chunks of EMGPU_HOST_CHUNK_MB device bytes into device tables of its own and adds them to the caller's host arrays once, at
+ * the end; it needs no device memory proportional to n. */
+int emgpu_count_layout(const emgpu_model *m, int32_t network, int64_t *offsets);
+int emgpu_count_dbn_device(emgpu_ctx *ctx, const emgpu_model *m, const emgpu_score_params *p, const uint8_t *init_bin, const uint32_t *dyn_bin,
+                           uint64_t *counts_initial, uint64_t *counts_transition);
+int emgpu_count_dbn_host(emgpu_ctx *ctx, const emgpu_model *m, const emgpu_score_params *p, const uint8_t *init_bin, const uint32_t *dyn_bin,
+                         uint64_t *counts_initial, uint64_t *counts_transition);
+
 /* Pinned host memory for the outputs of the *_host entry points (hipHostMalloc, kept in a per-ctx pool: pinning gigabytes costs about as
  * much as copying them).  emgpu_sample_dbn_host recognises pinned output arrays and lets the copy engine write straight into them;
  * pageable arrays go through the library's own pinned staging buffers and a few host threads (below). */
