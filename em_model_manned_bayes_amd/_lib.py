@@ -23,6 +23,7 @@ F_N_INITIAL, F_N_TRANSITION, F_ALPHA_INITIAL, F_ALPHA_TRANSITION, F_BOUNDARIES, 
 F_LABELS_INITIAL, F_LABELS_TRANSITION = 64, 65
 
 TRANSITION_REFERENCE_AUTO, TRANSITION_PER_STEP = 0, 1
+VALUE_F32, VALUE_F64 = 0, 1       # emgpu_discretize_params.value_type
 FLAG_QUANTIZE500, FLAG_NO_RESAMPLE, FLAG_NO_DEDISC, FLAG_NO_TERMINATOR, FLAG_LOCAL_SMOOTH = 1, 2, 4, 8, 16
 
 # MATLAB error identifiers the reference raises for the same condition
@@ -147,6 +148,11 @@ class ScoreParams(C.Structure):     # emgpu_score_params
     _fields_ = [("n", C.c_int64), ("sample_time", C.c_int32), ("transition_mode", C.c_int32), ("ld", C.c_int64), ("col_offset", C.c_int64)]
 
 
+class DiscretizeParams(C.Structure):     # emgpu_discretize_params
+    _fields_ = [("n", C.c_int64), ("sample_time", C.c_int32), ("n_fine", C.c_int32), ("ld", C.c_int64), ("col_offset", C.c_int64),
+                ("value_type", C.c_int32), ("wrap_mask", C.c_uint32)]
+
+
 class BnParams(C.Structure):
     _fields_ = [("seed", C.c_uint64), ("first_index", C.c_uint64), ("n", C.c_int64), ("flags", C.c_uint32),
                 ("max_attempts", C.c_int32), ("bounds_sample", C.c_void_p),
@@ -177,6 +183,7 @@ SYMBOLS = [
     "emgpu_start_grid_log_weight", "emgpu_track_uncor_grid_host", "emgpu_track_uncor_grid_device",
     "emgpu_model_log_prob", "emgpu_score_dbn_device", "emgpu_score_dbn_host", "emgpu_device_upload", "emgpu_device_download",
     "emgpu_count_layout", "emgpu_count_dbn_device", "emgpu_count_dbn_host",
+    "emgpu_discretize_dbn_device", "emgpu_discretize_dbn_host",
 ]
 
 _lib = None
@@ -362,6 +369,8 @@ def lib():
     L.emgpu_count_layout.argtypes = [C.c_void_p, C.c_int32, C.c_void_p]
     for f in (L.emgpu_count_dbn_device, L.emgpu_count_dbn_host):
         f.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(ScoreParams)] + [C.c_void_p] * 4
+    for f in (L.emgpu_discretize_dbn_device, L.emgpu_discretize_dbn_host):
+        f.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(DiscretizeParams)] + [C.c_void_p] * 6
     _lib = L
     return L
 

@@ -75,7 +75,7 @@ struct emgpu_ctx {
     int device = 0;
     hipStream_t stream = nullptr;
     hipStream_t own_stream = nullptr;
-    uint32_t *d_status = nullptr;   // two words: the sampler's status bits, the bad-bin word of k_score_dbn and k_count_dbn (emgpu_ctx_sync reads and clears both)
+    uint32_t *d_status = nullptr;   // two words: the sampler's status bits, the bad-bin word of k_score_dbn, k_count_dbn and k_discretize_dbn (emgpu_ctx_sync reads and clears both)
     uint32_t *d_queue = nullptr;  // k_terminal_propagate: the launch's track queue (one word, zeroed by the launcher)
     EmgpuPresets *d_presets = nullptr;   // the start grid / log-weight block of the last DBN call that had one
     uint32_t *h_status = nullptr; // pinned, two words
@@ -123,7 +123,7 @@ struct emgpu_ctx {
 Uploaded &get_uploaded(emgpu_ctx *ctx, const emgpu_model *h, const std::set<uint64_t> *pinned = nullptr);
 void ensure_logp(emgpu_ctx *ctx, Uploaded &u, const Model &m);   // u.d_logp / u.lp_off, uploaded on first use
 namespace emgpu_detail {
-constexpr const char *kScoreBadBin = "a bin outside 1..r in the trace (score: the log-likelihood of those trajectories is NaN; count: the observations that read it were skipped)";
+constexpr const char *kScoreBadBin = "a bin outside 1..r in the trace (score: the log-likelihood of those trajectories is NaN; count: the observations that read it were skipped), or a bad value in a trace of values (discretize: its bin is 0)";
 }
 // slot-th scratch buffer of the ctx, at least `bytes` long.  Two users share the slots: the host-path sampling entry points of emgpu_host.cpp
 // take slot 0 (the start grid) and slot 1 (the index list) by number, and the round drivers of emgpu_capi.cpp (RoundScratch) take 0 ... k in

@@ -332,6 +332,18 @@ class EncounterModel:
         got = native.count_dbn_host(ctx, self.native, init_bin, dyn_bin, T, transition_mode)
         return got["N_initial"], got["N_transition"], None, None
 
+    def count_values(self, init_val, dyn_val=None, n_fine=4, wrap=None, transition_mode=L.TRANSITION_REFERENCE_AUTO, ctx=None):
+        """The sufficient statistics of VALUES in the shapes native.sample_dbn_host returns (init_val [n, n_initial], dyn_val [n, T, n_dyn] or
+        None; float32 or float64): the values are discretized with this model's boundaries and counted on the GPU
+        (native.discretize_count_host), in n_fine fine bins per bin for the pairs of hierarchical_discretize.m:43-49; wrap: the 1-based ids
+        of the variables whose last bin is the first (hierarchical_discretize.m:29).  Returns (N_initial, N_transition, all_repeat,
+        all_change), the two vectors [n_initial, 1] float64: m.setParameters(*m.count_values(iv, dv)) sets the tables and, through
+        updateResampleRates, the resample rates (a variable without pairs divides 0 by 0, as in the reference).  A NaN, or a categorical
+        value that is no integer in 1..r, raises EmgpuError(ERR_ARG)."""
+        ctx = ctx or native.default_context()
+        got = native.discretize_count_host(ctx, self.native, init_val, dyn_val, n_fine, wrap, transition_mode)
+        return got["N_initial"], got["N_transition"], got["repeat"].reshape(-1, 1), got["change"].reshape(-1, 1)
+
     def _start_grid(self, start_grid, n):
         """A start grid as the library takes it: [n, n_initial] int32 by variable id, None / NaN / 0 = unset."""
         grid = np.array([[0 if (v is None or (isinstance(v, float) and np.isnan(v))) else int(v) for v in row] for row in start_grid], dtype=np.int32)

@@ -777,6 +777,151 @@ def sample_count_host(ctx, model, n, T, seed, transition_mode=L.TRANSITION_REFER
     return {"N_initial": Ni, "N_transition": Nt, "raw": (ci, ct), "kernel": kernel, "count_kernel": count_kernel}
 
 
+def pack_dyn_val(dv):
+    """[n, T, nd] f32 or f64 -> [G4][nd][n][4] of the same dtype (the inverse of unpack_dyn_val; padding columns are 0)."""
+    dv = np.asarray(dv)
+    n, T, nd = dv.shape
+    G4 = (T + 3) // 4
+    b = np.zeros((n, G4 * 4, nd), dtype=dv.dtype)
+    b[:, :T, :] = dv
+    return np.ascontiguousarray(b.reshape(n, G4, 4, nd).transpose(1, 3, 0, 2))
+
+
+def wrap_mask(wrap):
+    """emgpu_discretize_params.wrap_mask of `wrap`: None, an int mask (bit v - 1 = variable v), or the 1-based ids of the variables that wrap"""
+    if wrap is None:
+        return 0
+    if isinstance(wrap, (int, np.integer)):
+        return int(wrap)
+    mask = 0
+    for v in wrap:
+        if not 1 <= int(v) <= 32:
+            raise ValueError("wrap holds 1-based variable ids")
+        mask |= 1 << (int(v) - 1)
+    return mask
+
+
+def discretize_params(n, sample_time, n_fine=0, value_type=L.VALUE_F32, wrap=None, ld=0, col_offset=0):
+    p = L.DiscretizeParams()
+    p.n, p.sample_time, p.n_fine, p.ld, p.col_offset = int(n), int(sample_time), int(n_fine), int(ld), int(col_offset)
+    p.value_type, p.wrap_mask = int(value_type), wrap_mask(wrap)
+    return p
+
+
+def discretize_dbn_device(ctx, model, params, init_val=0, dyn_val=0, init_bin=0, dyn_bin=0, repeat=0, change=0):
+    """emgpu_discretize_dbn_device: asynchronous, raw device pointers (ints; params: discretize_params).  init_val / dyn_val in the sampler's
+    layout (f32, or f64 under VALUE_F64) become init_bin u8 / dyn_bin u32 in the layout score_dbn_device and count_dbn_device read; either
+    pair may be 0.  repeat / change are uint64 [n_initial] by variable id, which the call ADDS to (0 with n_fine 0).  A bad value (NaN, a
+    categorical value that is no integer in 1..r) gets bin 0 and makes the next ctx.sync() raise EmgpuError(ERR_ARG)."""
+    L.check(L.lib().emgpu_discretize_dbn_device(ctx._h, model._h, C.byref(params), C.c_void_p(init_val or None), C.c_void_p(dyn_val or None),
+                                                C.c_void_p(init_bin or None), C.c_void_p(dyn_bin or None), C.c_void_p(repeat or None),
+                                                C.c_void_p(change or None)))
+
+
+def _value_arrays(model, init_val, dyn_val, T, raw):
+    """(init_val [n_i, ld] or None, dyn_val [G4, n_d, ld, 4] or None, ld, value_type) of a call's values: one dtype, f32 or f64"""
+    given = [np.asarray(a) for a in (init_val, dyn_val) if a is not None]
+    if not given:
+        raise ValueError("init_val and dyn_val are both None: nothing to discretize")
+    dt = np.float64 if any(a.dtype == np.float64 for a in given) else np.float32
+    iv = dv = None
+    if init_val is not None:
+        iv = np.ascontiguousarray(init_val, dtype=dt) if raw else np.ascontiguousarray(np.asarray(init_val, dtype=dt).T)
+        if iv.ndim != 2 or iv.shape[0] != model.n_initial:
+            raise ValueError("init_val must hold n_initial entries per trajectory")
+    if dyn_val is not None:
+        dv = np.ascontiguousarray(dyn_val, dtype=dt) if raw else pack_dyn_val(np.asarray(dyn_val, dtype=dt))
+        if dv.ndim != 4 or dv.shape[:2] != ((int(T) + 3) // 4, model.n_dyn) or dv.shape[3] != 4 or (iv is not None and dv.shape[2] != iv.shape[1]):
+            raise ValueError("dyn_val must hold T columns of n_dyn variables for the trajectories of init_val")
+    ld = iv.shape[1] if iv is not None else dv.shape[2]
+    return iv, dv, ld, (L.VALUE_F64 if dt == np.float64 else L.VALUE_F32)
+
+
+def _pair_vectors(model, counts):
+    """the repeat / change vectors of a call: fresh zeros, or a previous result's `raw` (accumulated into, in place)"""
+    if counts is None:
+        return np.zeros(model.n_initial, dtype=np.uint64), np.zeros(model.n_initial, dtype=np.uint64)
+    rep, chg = counts
+    for a in (rep, chg):
+        if not isinstance(a, np.ndarray) or a.dtype != np.uint64 or a.shape != (model.n_initial,) or not a.flags["C_CONTIGUOUS"]:
+            raise ValueError("counts must be the `raw` pair of a discretize of this model: contiguous uint64 arrays of n_initial entries")
+    return rep, chg
+
+
+def discretize_dbn_host(ctx, model, init_val, dyn_val, T, n_fine=0, wrap=None, raw=False, n=None, col_offset=0, counts=None):
+    """Values to bins, and the repeat / change counts of their fine bins (emgpu_discretize_dbn_host; the definition is in include/emgpu.h).
+    raw=False: the user-facing shapes sample_dbn_host returns (init_val [n, n_i], dyn_val [n, T, n_d]; either may be None); raw=True: the
+    library layout (init_val [n_i, ld], dyn_val [G4, n_d, ld, 4]), of which columns col_offset .. col_offset + n are discretized (n:
+    default ld - col_offset; the other columns of the outputs are 0).  float64 arrays are compared as doubles, anything else as float32.
+    Returns {"init_bin", "dyn_bin"} in the same layout as the values (u8; raw dyn_bin: u32 [G4, n_d, ld]; None where the values were),
+    "repeat" / "change" [n_initial] float64 by variable id, "raw": (u64 repeat, u64 change), "kernel".  counts=<a previous result's raw>
+    accumulates.  A bad value gets bin 0 and raises EmgpuError(ERR_ARG) carrying .bins (the same dict)."""
+    T = int(T)
+    iv, dv, ld, vt = _value_arrays(model, init_val, dyn_val, T, raw)
+    n = ld - int(col_offset) if n is None else int(n)
+    rep, chg = _pair_vectors(model, counts)
+    ib = None if iv is None else np.zeros(iv.shape, dtype=np.uint8)
+    db = None if dv is None else np.zeros(dv.shape[:3], dtype=np.uint32)
+    p = discretize_params(n, T, n_fine, vt, wrap, ld, col_offset)
+    rc = L.lib().emgpu_discretize_dbn_host(ctx._h if ctx is not None else None, model._h, C.byref(p), _p(iv), _p(dv), _p(ib), _p(db),
+                                           _p(rep) if n_fine else None, _p(chg) if n_fine else None)
+    out = {"init_bin": ib if raw or ib is None else ib.T.copy(), "dyn_bin": db if raw or db is None else unpack_dyn_bin(db, T),
+           "repeat": rep.astype(np.float64), "change": chg.astype(np.float64), "raw": (rep, chg),
+           "kernel": ctx.last_kernel() if ctx is not None else ""}
+    if rc < 0:
+        e = L.EmgpuError(int(rc), L.lib().emgpu_last_error().decode("utf-8", "replace"))
+        e.bins = out
+        raise e
+    return out
+
+
+def discretize_count_host(ctx, model, init_val, dyn_val, n_fine=0, wrap=None, transition_mode=L.TRANSITION_REFERENCE_AUTO):
+    """Values in the user-facing shapes (init_val [n, n_i], dyn_val [n, T, n_d] or None; f32 or f64) to the model's count tables and the two
+    vectors, all on the device: the values are uploaded, discretized (emgpu_discretize_dbn_device) and counted where the bins lie
+    (emgpu_count_dbn_device), and only the tables and the vectors come back.  Equals discretize_dbn_host followed by count_dbn_host.
+    Returns count_dbn_host's dict plus "repeat" / "change" [n_initial] float64 ("raw_pairs": the same as uint64), `kernel` the discretizer's,
+    `count_kernel` the counter's.
+    A bad value raises EmgpuError(ERR_ARG): its bin is 0, which counting skips."""
+    if init_val is None:
+        raise ValueError("counting needs init_val")
+    T = 1 if dyn_val is None else int(np.asarray(dyn_val).shape[1])
+    iv, dv, n, vt = _value_arrays(model, init_val, dyn_val, T, False)
+    ni, nd, G4 = model.n_initial, model.n_dyn, (T + 3) // 4
+    ci, ct = _counts_arrays(model, None)
+    rc = np.zeros(2 * ni, dtype=np.uint64)
+    dense = dv is not None and nd > 0
+    sizes = [("init_val", iv.nbytes), ("dyn_val", dv.nbytes if dense else 0), ("init_bin", ni * n), ("dyn_bin", 4 * G4 * nd * n if dense else 0),
+             ("ci", 8 * ci.size), ("ct", 8 * ct.size), ("rc", rc.nbytes)]
+    off, o = {}, 0
+    for name, b in sizes:
+        off[name] = o
+        o += (b + 255) // 256 * 256
+    base = ctx.device_alloc(max(o, 256))
+    try:
+        at = {k: base + v for k, v in off.items()}
+        for name, a in (("init_val", iv), ("dyn_val", dv if dense else None), ("ci", ci), ("ct", ct), ("rc", rc)):
+            if a is not None and a.size:
+                device_upload(ctx, at[name], a)
+        p = discretize_params(n, T, n_fine, vt, wrap)
+        discretize_dbn_device(ctx, model, p, at["init_val"], at["dyn_val"] if dense else 0, at["init_bin"], at["dyn_bin"] if dense else 0,
+                              at["rc"] if n_fine else 0, at["rc"] + 8 * ni if n_fine else 0)
+        kernel = ctx.last_kernel()
+        transitions = dense and T > 1
+        count_dbn_device(ctx, model, score_params(n, T, transition_mode), at["init_bin"], at["dyn_bin"] if transitions else 0,
+                         at["ci"], at["ct"] if transitions else 0)
+        count_kernel = ctx.last_kernel()
+        ctx.sync()                                  # both launches' deferred errors
+        for name, a in (("ci", ci), ("ct", ct), ("rc", rc)):
+            if a.size:
+                device_download(ctx, at[name], a)
+    finally:
+        ctx.device_free(base)
+    Ni, Nt = split_counts(model, (ci, ct))
+    rep, chg = rc[:ni].copy(), rc[ni:].copy()
+    return {"N_initial": Ni, "N_transition": Nt, "raw": (ci, ct), "repeat": rep.astype(np.float64), "change": chg.astype(np.float64),
+            "raw_pairs": (rep, chg), "kernel": kernel, "count_kernel": count_kernel}
+
+
 def device_upload(ctx, addr, src):
     """emgpu_device_upload: the numpy array `src` into device memory at addr, on the context's stream; complete on return."""
     src = np.ascontiguousarray(src)

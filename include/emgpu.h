@@ -447,6 +447,47 @@ int emgpu_count_dbn_device(emgpu_ctx *ctx, const emgpu_model *m, const emgpu_sco
 int emgpu_count_dbn_host(emgpu_ctx *ctx, const emgpu_model *m, const emgpu_score_params *p, const uint8_t *init_bin, const uint32_t *dyn_bin,
                          uint64_t *counts_initial, uint64_t *counts_transition);
 
+/* ------------------------------------------------------------------------------------------------
+ * Discretizing a trace: VALUES in the layout of emgpu_sample_out (init_val [n_initial][ld], dyn_val [G4][n_dyn][ld][4]) into the BINS
+ * emgpu_score_dbn_* and emgpu_count_dbn_* take (init_bin u8 [n_initial][ld]; dyn_bin u32 [G4][n_dyn][ld], byte c % 4 of word c / 4 = column
+ * c), and the repeat / change counts behind a model's resample rates: the training side's discretize_bayes.m, hierarchical_cutpoints.m and
+ * hierarchical_discretize.m in one pass.  ld (0 = n) and col_offset apply to the inputs and the outputs alike; columns outside the window,
+ * and columns >= sample_time of a larger trace, are neither read nor written (the padding bytes of the last word are written 0).
+ * For one value x, promoted exactly to double, of variable v with r bins and boundaries b[0..r] (EMGPU_F_BOUNDARIES):
+ *   coarse bin   d = 1 + #{q in 1..r-1 : x >= b[q]} (discretize_bayes.m:14-22): below b[0] gives 1, at or above b[r] gives r, +-inf follow
+ *                the compares, a value that equals a cut point belongs to the upper bin;
+ *   wrap         where bit v (variable id - 1) of wrap_mask is set: d = 1 + mod(d - 1, r - 1) (hierarchical_discretize.m:29);
+ *   categorical  a variable without boundaries ('*', em_read.m:97-99): x must be an integer in 1..r and d = x; never wrapped, no fine bin;
+ *   bad value    NaN, or a categorical value that is no integer in 1..r: the bin written is 0 (which scoring and counting treat as outside
+ *                1..r), no pair that holds the value is counted, no other value is affected, and the call reports EMGPU_ERR_ARG through the
+ *                channel and by the rules of scoring: _host by its return value, with the outputs written; _device at the next
+ *                emgpu_ctx_sync, through the same pending word;
+ *   fine bin     n_fine in 2..255, for every variable with boundaries: a = b[d-1], h = (b[d] - a) / n_fine,
+ *                f = 1 + #{k in 1..n_fine-1 : x >= a + k * h}: one double multiply and one double add per cut, not contracted, the
+ *                expression of hierarchical_cutpoints.m:14; equal to hierarchical_discretize.m:37-41 because a + k * h does not decrease in k;
+ *   pairs        (hierarchical_discretize.m:43-49) for row k of the temporal map, of variable v, and columns c = 1 .. sample_time-1: when
+ *                both values are good, d[c] == d[c-1] and d[c] is not v's zero bin (EMGPU_F_ZERO_BINS), repeat[v] += 1 if
+ *                f[c] == f[c-1], else change[v] += 1.  Categorical and static variables receive nothing.
+ * repeat and change are uint64_t[n_initial] by variable id, which calls ACCUMULATE into (emgpu_count_dbn_*): EncounterModel.m:243 derives
+ * resample_rates = all_change ./ (all_repeat + all_change) from them.  n_fine = 0: bins only, and both may be NULL.
+ * Either half (init_val with init_bin, dyn_val with dyn_bin) may be NULL, as a pair.  value_type: EMGPU_VALUE_F32, the sampler's arrays, or
+ * EMGPU_VALUE_F64, the same layout with 8-byte elements (tracks given as doubles are not rounded before the compare).  _device: dyn_val
+ * 16-byte aligned.  _host works in chunks of EMGPU_HOST_CHUNK_MB device bytes and needs no device memory proportional to n. */
+#define EMGPU_VALUE_F32 0
+#define EMGPU_VALUE_F64 1
+typedef struct {
+    int64_t n;
+    int32_t sample_time;
+    int32_t n_fine;        /* 0, or 2..255 */
+    int64_t ld, col_offset;
+    int32_t value_type;    /* EMGPU_VALUE_* */
+    uint32_t wrap_mask;    /* bit v - 1: variable v wraps */
+} emgpu_discretize_params;
+int emgpu_discretize_dbn_device(emgpu_ctx *ctx, const emgpu_model *m, const emgpu_discretize_params *p, const void *init_val,
+                                const void *dyn_val, uint8_t *init_bin, uint32_t *dyn_bin, uint64_t *repeat, uint64_t *change);
+int emgpu_discretize_dbn_host(emgpu_ctx *ctx, const emgpu_model *m, const emgpu_discretize_params *p, const void *init_val,
+                              const void *dyn_val, uint8_t *init_bin, uint32_t *dyn_bin, uint64_t *repeat, uint64_t *change);
+
 /* Pinned host memory for the outputs of the *_host entry points (hipHostMalloc, kept in a per-ctx pool: pinning gigabytes costs about as
  * much as copying them).  emgpu_sample_dbn_host recognises pinned output arrays and lets the copy engine write straight into them;
  * pageable arrays go through the library's own pinned staging buffers and a few host threads (below). */
