@@ -24,6 +24,7 @@ F_LABELS_INITIAL, F_LABELS_TRANSITION = 64, 65
 
 TRANSITION_REFERENCE_AUTO, TRANSITION_PER_STEP = 0, 1
 VALUE_F32, VALUE_F64 = 0, 1       # emgpu_discretize_params.value_type
+TRACKS_PLANAR, TRACKS_ROWS = 0, 1 # emgpu_track_values_params.layout
 FLAG_QUANTIZE500, FLAG_NO_RESAMPLE, FLAG_NO_DEDISC, FLAG_NO_TERMINATOR, FLAG_LOCAL_SMOOTH = 1, 2, 4, 8, 16
 
 # MATLAB error identifiers the reference raises for the same condition
@@ -153,6 +154,14 @@ class DiscretizeParams(C.Structure):     # emgpu_discretize_params
                 ("value_type", C.c_int32), ("wrap_mask", C.c_uint32)]
 
 
+class TrackValuesParams(C.Structure):     # emgpu_track_values_params
+    _fields_ = [("n", C.c_int64), ("points", C.c_int32), ("value_type", C.c_int32), ("ld", C.c_int64), ("col_offset", C.c_int64),
+                ("n_initial", C.c_int32), ("nd", C.c_int32), ("row_alt", C.c_int32), ("row_speed", C.c_int32), ("row_vertrate", C.c_int32),
+                ("row_acc", C.c_int32), ("row_turnrate", C.c_int32), ("slot_vertrate", C.c_int32), ("slot_acc", C.c_int32),
+                ("slot_turnrate", C.c_int32), ("layout", C.c_int32), ("reserved", C.c_int32), ("ur_speed", C.c_double),
+                ("ur_vertrate", C.c_double), ("ur_heading", C.c_double)]
+
+
 class BnParams(C.Structure):
     _fields_ = [("seed", C.c_uint64), ("first_index", C.c_uint64), ("n", C.c_int64), ("flags", C.c_uint32),
                 ("max_attempts", C.c_int32), ("bounds_sample", C.c_void_p),
@@ -184,6 +193,7 @@ SYMBOLS = [
     "emgpu_model_log_prob", "emgpu_score_dbn_device", "emgpu_score_dbn_host", "emgpu_device_upload", "emgpu_device_download",
     "emgpu_count_layout", "emgpu_count_dbn_device", "emgpu_count_dbn_host",
     "emgpu_discretize_dbn_device", "emgpu_discretize_dbn_host",
+    "emgpu_track_values_device", "emgpu_track_values_host",
 ]
 
 _lib = None
@@ -371,6 +381,8 @@ def lib():
         f.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(ScoreParams)] + [C.c_void_p] * 4
     for f in (L.emgpu_discretize_dbn_device, L.emgpu_discretize_dbn_host):
         f.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(DiscretizeParams)] + [C.c_void_p] * 6
+    for f in (L.emgpu_track_values_device, L.emgpu_track_values_host):
+        f.argtypes = [C.c_void_p, C.POINTER(TrackValuesParams)] + [C.c_void_p] * 3
     _lib = L
     return L
 

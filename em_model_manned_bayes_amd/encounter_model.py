@@ -640,6 +640,21 @@ class UncorEncounterModel(EncounterModel):
             out = out + (log_weight,)
         return out if len(out) > 1 else out[0]
 
+    def count_tracks(self, xyz, static=None, n_fine=4, wrap=None, transition_mode=L.TRANSITION_REFERENCE_AUTO,
+                     unit_ratios=((1852.0 / 0.3048) / 3600.0, 1.0 / 60.0, 1.0), ctx=None):
+        """The sufficient statistics of 1 Hz TRACKS xyz [n, P, 3] (feet, float64; what sample2track and a track file hold), counted on the
+        GPU (native.track_count_host): the tracks become P - 2 seconds of vertical rate, acceleration and turn rate and the initial L, v and
+        rates (the inverse of sample2track.m:183-237, in doubles), which are discretized with this model's boundaries and counted.  The
+        rows are found by label (_track_variables; without the three rates: dynvar:empty).  static = {1-based variable id: array [n] or
+        scalar}: the values of the variables a track does not carry (G, A); a variable left out is 0 and, where categorical, reported as
+        a bad value.  unit_ratios: sample2track.m:113-123.  Returns (N_initial, N_transition, all_repeat, all_change) like count_values:
+        m.setParameters(*m.count_tracks(xyz, static)) sets the tables and the resample rates."""
+        idxL, idxV, idxDV, idxDH, idxDPsi = self._track_variables()
+        ctx = ctx or native.default_context()
+        got = native.track_count_host(ctx, self.native, xyz, (idxL, idxV, idxDH, idxDV, idxDPsi), static, n_fine, wrap, transition_mode,
+                                      unit_ratios)
+        return got["N_initial"], got["N_transition"], got["repeat"].reshape(-1, 1), got["change"].reshape(-1, 1)
+
     def getDynamicLimits(self, initial, results, idx_G=None, idx_A=None, idx_L=None, idx_V=None, idx_DH=None, is_discretized=None):
         """dynamiclimits = getDynamicLimits(self, initial, results, ...)  (@UncorEncounterModel/getDynamicLimits.m).  The index
         arguments are accepted for signature compatibility; they are looked up from the labels like .track does."""

@@ -922,6 +922,127 @@ def discretize_count_host(ctx, model, init_val, dyn_val, n_fine=0, wrap=None, tr
             "raw_pairs": (rep, chg), "kernel": kernel, "count_kernel": count_kernel}
 
 
+def track_values_params(n, points, ur_speed, ur_vertrate, ur_heading, n_initial=5, nd=3, rows=(0, 1, 2, 3, 4), slots=(0, 1, 2),
+                        value_type=L.VALUE_F32, layout=L.TRACKS_ROWS, ld=0, col_offset=0):
+    """emgpu_track_values_params.  rows: the 0-based rows of init_val that receive altitude, speed, vertical rate, acceleration and turn rate
+    (-1: not written); slots: the 0-based rows of a dyn_val group that receive vertical rate, acceleration and turn rate."""
+    p = L.TrackValuesParams()
+    p.n, p.points, p.value_type, p.ld, p.col_offset = int(n), int(points), int(value_type), int(ld), int(col_offset)
+    p.n_initial, p.nd, p.layout = int(n_initial), int(nd), int(layout)
+    p.row_alt, p.row_speed, p.row_vertrate, p.row_acc, p.row_turnrate = (int(r) for r in rows)
+    p.slot_vertrate, p.slot_acc, p.slot_turnrate = (int(s) for s in slots)
+    p.ur_speed, p.ur_vertrate, p.ur_heading = float(ur_speed), float(ur_vertrate), float(ur_heading)
+    return p
+
+
+def track_values_device(ctx, params, xyz, init_val=0, dyn_val=0):
+    """emgpu_track_values_device: asynchronous, raw device pointers (ints; params: track_values_params).  xyz f64 in params.layout
+    (TRACKS_PLANAR [P, 3, n], what sample2track_device writes, or TRACKS_ROWS [n, P, 3]) becomes the named rows of init_val [n_initial, ld]
+    and dyn_val [G4, nd, ld, 4] (f32, or f64 under VALUE_F64), the layout discretize_dbn_device reads; either may be 0.  Every other row is
+    left as it is."""
+    L.check(L.lib().emgpu_track_values_device(ctx._h if ctx is not None else None, C.byref(params), C.c_void_p(xyz or None),
+                                              C.c_void_p(init_val or None), C.c_void_p(dyn_val or None)))
+
+
+def _fill_static(iv, static, written):
+    """static = {1-based variable id: array [n] or scalar} into the rows of init_val [n_initial, n] the kernel leaves"""
+    for v, a in (static or {}).items():
+        v = int(v)
+        if not 1 <= v <= iv.shape[0]:
+            raise ValueError("static names variable %d of %d" % (v, iv.shape[0]))
+        if v - 1 in written:
+            raise ValueError("static names variable %d, which the tracks give" % v)
+        iv[v - 1, :] = np.asarray(a, dtype=iv.dtype)
+
+
+def track_values_host(ctx, xyz, ur_speed, ur_vertrate, ur_heading, n_initial=5, nd=3, rows=(0, 1, 2, 3, 4), slots=(0, 1, 2),
+                      value_type=L.VALUE_F32, raw=False, static=None, want_init=True, want_dyn=True):
+    """The values of a trace from 1 Hz tracks (emgpu_track_values_host; the definition is in include/emgpu.h).  xyz [n, P, 3] f64 in feet,
+    P >= 3, gives T = P - 2 seconds.  rows / slots as in track_values_params.  Returns {"init_val", "dyn_val", "T", "kernel"}: init_val
+    [n, n_initial] and dyn_val [n, T, nd] (raw=True: the library layout, [n_initial, n] and [G4, nd, n, 4]), float32 or float64 by
+    value_type.  Rows the tracks do not give are 0, but for static = {1-based variable id: array [n] or scalar}, which fills rows of
+    init_val (G, A, ... of a model).  want_init / want_dyn False: that half is None."""
+    xyz = np.ascontiguousarray(xyz, dtype=np.float64)
+    if xyz.ndim != 3 or xyz.shape[2] != 3:
+        raise ValueError("xyz must be [n, points, 3]")
+    n, P = int(xyz.shape[0]), int(xyz.shape[1])
+    T, dt = P - 2, (np.float64 if value_type == L.VALUE_F64 else np.float32)
+    iv = np.zeros((int(n_initial), n), dtype=dt) if want_init else None
+    dv = np.zeros(((max(T, 0) + 3) // 4, int(nd), n, 4), dtype=dt) if want_dyn else None
+    if iv is not None:
+        _fill_static(iv, static, [int(r) for r in rows if int(r) >= 0])
+    p = track_values_params(n, P, ur_speed, ur_vertrate, ur_heading, n_initial, nd, rows, slots, value_type, L.TRACKS_ROWS)
+    L.check(L.lib().emgpu_track_values_host(ctx._h if ctx is not None else None, C.byref(p), _p(xyz), _p(iv), _p(dv)))
+    return {"init_val": iv if raw or iv is None else np.ascontiguousarray(iv.T),
+            "dyn_val": dv if raw or dv is None else unpack_dyn_val(dv, T), "T": T, "kernel": ctx.last_kernel()}
+
+
+def track_rows(model, variables):
+    """(rows, slots) of track_values_params for a model: variables = the 1-based ids of L, v, \\dot h (vertical rate), \\dot v (acceleration),
+    \\dot \\psi (turn rate), 0 = the model has none (L and v only); the slots are the rates' rows of the temporal map."""
+    idL, idV, idDH, idDV, idDPsi = (int(v) for v in variables)
+    tm = model.get_i32(L.F_TEMPORAL_MAP).reshape(-1, 2)[:, 0].tolist()
+    if not all(v in tm for v in (idDH, idDV, idDPsi)):
+        raise ValueError("the temporal map does not hold the three rates")
+    return (idL - 1, idV - 1, idDH - 1, idDV - 1, idDPsi - 1), (tm.index(idDH), tm.index(idDV), tm.index(idDPsi))
+
+
+def track_count_host(ctx, model, xyz, rows, static=None, n_fine=4, wrap=None, transition_mode=L.TRANSITION_REFERENCE_AUTO,
+                     unit_ratios=((1852.0 / 0.3048) / 3600.0, 1.0 / 60.0, 1.0), value_type=L.VALUE_F64):
+    """Tracks xyz [n, P, 3] f64 to the model's count tables and the repeat / change vectors, all on the device: the tracks are uploaded as
+    they lie, turned into values (emgpu_track_values_device, ROWS), discretized (emgpu_discretize_dbn_device) and counted
+    (emgpu_count_dbn_device) in one device block, and only the tables and the vectors come back.  rows: the 1-based variable ids of L, v,
+    \\dot h, \\dot v, \\dot \\psi (track_rows); static = {1-based variable id: array [n] or scalar}: the values of the variables the tracks
+    do not give (G, A), without which their bins are bad.  unit_ratios: (ur_speed, ur_vertrate, ur_heading) of sample2track.m:113-123.
+    Equals track_values_host followed by discretize_count_host.  Returns discretize_count_host's dict, `values_kernel` the first kernel's."""
+    xyz = np.ascontiguousarray(xyz, dtype=np.float64)
+    if xyz.ndim != 3 or xyz.shape[2] != 3:
+        raise ValueError("xyz must be [n, points, 3]")
+    n, P = int(xyz.shape[0]), int(xyz.shape[1])
+    T, ni, nd = P - 2, model.n_initial, model.n_dyn
+    G4 = (max(T, 0) + 3) // 4
+    r0, slots = track_rows(model, rows)
+    es, dt = (8, np.float64) if value_type == L.VALUE_F64 else (4, np.float32)
+    iv = np.zeros((ni, n), dtype=dt)
+    _fill_static(iv, static, [r for r in r0 if r >= 0])
+    ci, ct = _counts_arrays(model, None)
+    rc = np.zeros(2 * ni, dtype=np.uint64)
+    sizes = [("xyz", xyz.nbytes), ("init_val", iv.nbytes), ("dyn_val", 4 * es * G4 * nd * n), ("init_bin", ni * n), ("dyn_bin", 4 * G4 * nd * n),
+             ("ci", 8 * ci.size), ("ct", 8 * ct.size), ("rc", rc.nbytes)]
+    off, o = {}, 0
+    for name, b in sizes:
+        off[name] = o
+        o += (b + 255) // 256 * 256
+    p = track_values_params(n, P, *unit_ratios, n_initial=ni, nd=nd, rows=r0, slots=slots, value_type=value_type, layout=L.TRACKS_ROWS)
+    base = ctx.device_alloc(max(o, 256))
+    try:
+        at = {k: base + v for k, v in off.items()}
+        for name, a in (("xyz", xyz), ("init_val", iv), ("ci", ci), ("ct", ct), ("rc", rc)):
+            if a.size:
+                device_upload(ctx, at[name], a)
+        if nd > 3 and n:   # dynamic variables the tracks do not give: zeros, as track_values_host leaves them
+            device_upload(ctx, at["dyn_val"], np.zeros(4 * G4 * nd * n, dtype=dt))
+        track_values_device(ctx, p, at["xyz"], at["init_val"], at["dyn_val"])
+        values_kernel = ctx.last_kernel()
+        discretize_dbn_device(ctx, model, discretize_params(n, T, n_fine, value_type, wrap), at["init_val"], at["dyn_val"], at["init_bin"],
+                              at["dyn_bin"], at["rc"] if n_fine else 0, at["rc"] + 8 * ni if n_fine else 0)
+        kernel = ctx.last_kernel()
+        transitions = T > 1
+        count_dbn_device(ctx, model, score_params(n, T, transition_mode), at["init_bin"], at["dyn_bin"] if transitions else 0,
+                         at["ci"], at["ct"] if transitions else 0)
+        count_kernel = ctx.last_kernel()
+        ctx.sync()                                  # the launches' deferred errors
+        for name, a in (("ci", ci), ("ct", ct), ("rc", rc)):
+            if a.size:
+                device_download(ctx, at[name], a)
+    finally:
+        ctx.device_free(base)
+    Ni, Nt = split_counts(model, (ci, ct))
+    rep, chg = rc[:ni].copy(), rc[ni:].copy()
+    return {"N_initial": Ni, "N_transition": Nt, "raw": (ci, ct), "repeat": rep.astype(np.float64), "change": chg.astype(np.float64),
+            "raw_pairs": (rep, chg), "kernel": kernel, "count_kernel": count_kernel, "values_kernel": values_kernel}
+
+
 def device_upload(ctx, addr, src):
     """emgpu_device_upload: the numpy array `src` into device memory at addr, on the context's stream; complete on return."""
     src = np.ascontiguousarray(src)

@@ -488,6 +488,54 @@ int emgpu_discretize_dbn_device(emgpu_ctx *ctx, const emgpu_model *m, const emgp
 int emgpu_discretize_dbn_host(emgpu_ctx *ctx, const emgpu_model *m, const emgpu_discretize_params *p, const void *init_val,
                               const void *dyn_val, uint8_t *init_bin, uint32_t *dyn_bin, uint64_t *repeat, uint64_t *change);
 
+/* ------------------------------------------------------------------------------------------------
+ * Values from tracks: 1 Hz TRACKS (what emgpu_sample2track_*, emgpu_tracks_text_host and a track file hold) into the VALUES of a trace, in
+ * the layout emgpu_discretize_dbn_* reads.  The inverse of sample2track.m:183-237, line by line.
+ * One track is `points` = P >= 3 positions (x, y, z) in feet, one second apart, as doubles; it yields T = P - 2 seconds of values (row T - 1
+ * of the forward update never moved the track, so it cannot be recovered).  All arithmetic is double and not contracted:
+ *   displacement  t = 0 .. P-2: dx = x[t+1] - x[t], dy = y[t+1] - y[t], dz = z[t+1] - z[t]             (sample2track.m:211-212, :201)
+ *   speed         s[t] = sqrt(dx * dx + dy * dy): two multiplies, one add, an IEEE square root           (:211-212: |speed * (cosd, sind)|)
+ *   heading       h[t] = atan2(dy, dx) * 57.29577951308232, one multiply; where s[t] == 0, h[t] = h[t-1], with h[-1] = 0: a standing
+ *                 aircraft keeps its heading                                                             (:211-212: the angle; :189)
+ *   values        t = 0 .. T-1, true divisions:
+ *                 vertical rate  dz[t] / ur_vertrate                                                     (:201 with :131)
+ *                 acceleration   (s[t+1] - s[t]) / ur_speed                                              (:204 with :132)
+ *                 turn rate      w / ur_heading, d = h[t+1] - h[t], w = d - 360 * floor((d + 180) / 360): w lies in [-180, 180), a
+ *                                reversal is -180                                                        (:207 with :133)
+ *   initial rows  altitude z[0] (:186), speed s[0] / ur_speed (:188 with :126), the three rates their value at t = 0.
+ * Non-finite coordinates are not special-cased and nothing is reported (emgpu_discretize_dbn_* gives a NaN bin 0 and reports it).  A bad
+ * point k (0-based) touches, and nothing else: with a bad z, the vertical rates of seconds k-1 and k (and the altitude row for k = 0);
+ * with a bad x or y, the accelerations and turn rates of seconds k-2, k-1 and k (and the speed row for k <= 1), and the turn rates of a
+ * standing run (s == 0) that directly follows second k, which holds the heading of displacement k.  A NaN coordinate makes all of these
+ * NaN.  An infinite z gives infinite vertical rates; an infinite x or y gives accelerations +-inf, NaN, -+inf, but FINITE turn rates that
+ * differ from the clean track's: atan2 of an infinite displacement is a multiple of 90 degrees.  The initial rows follow their second 0.
+ * Outputs: init_val V [n_initial][ld] and dyn_val V [ceil(T/4)][nd][ld][4] (element t % 4 of group t / 4 = second t), V = float (one
+ * rounding of the double) or double by value_type.  Only the rows named are written: row_* in init_val (-1: not written), slot_* in
+ * dyn_val; every other row (G, A, any other variable) stays untouched and is the caller's to fill.  The elements of the last group behind T
+ * are written 0.  ld (0 = n) and col_offset as for emgpu_discretize_dbn_*.  Either half may be NULL (its rows or slots are then not looked
+ * at), not both.  layout: EMGPU_TRACKS_PLANAR xyz [P][3][n], what emgpu_sample2track_device writes; EMGPU_TRACKS_ROWS xyz [n][P][3], what
+ * emgpu_sample2track_host returns and a file holds.  Both give bit-equal values.
+ * _device: one launch on the ctx's stream; dyn_val 16-byte aligned.  _host: ROWS only, host arrays; works in chunks of EMGPU_HOST_CHUNK_MB
+ * device bytes (a chunk of tracks is uploaded as it lies: nothing is transposed on the host).
+ * Out of scope: tracks of unequal length in one call (cut them into windows of equal length), smoothing, the terminal model's traj layout,
+ * geodetic coordinates, and fitting a model. */
+#define EMGPU_TRACKS_PLANAR 0
+#define EMGPU_TRACKS_ROWS 1
+typedef struct {
+    int64_t n;
+    int32_t points;        /* P: 3 .. 65537 */
+    int32_t value_type;    /* EMGPU_VALUE_* */
+    int64_t ld, col_offset;
+    int32_t n_initial, nd; /* rows of init_val; rows per group of four seconds of dyn_val */
+    int32_t row_alt, row_speed, row_vertrate, row_acc, row_turnrate;   /* 0-based rows of init_val; -1: not written */
+    int32_t slot_vertrate, slot_acc, slot_turnrate;                    /* 0-based rows of a dyn_val group */
+    int32_t layout;        /* EMGPU_TRACKS_* */
+    int32_t reserved;
+    double ur_speed, ur_vertrate, ur_heading;                          /* as in emgpu_track_params */
+} emgpu_track_values_params;
+int emgpu_track_values_device(emgpu_ctx *ctx, const emgpu_track_values_params *p, const double *xyz, void *init_val, void *dyn_val);
+int emgpu_track_values_host(emgpu_ctx *ctx, const emgpu_track_values_params *p, const double *xyz, void *init_val, void *dyn_val);
+
 /* Pinned host memory for the outputs of the *_host entry points (hipHostMalloc, kept in a per-ctx pool: pinning gigabytes costs about as
  * much as copying them).  emgpu_sample_dbn_host recognises pinned output arrays and lets the copy engine write straight into them;
  * pageable arrays go through the library's own pinned staging buffers and a few host threads (below). */
