@@ -348,7 +348,7 @@ int emgpu_ctx_create(int32_t device, emgpu_ctx **out) {
     HIP_OK(hipMemset(c->d_status, 0, 2 * sizeof(uint32_t)));
     HIP_OK(hipMalloc((void **)&c->d_queue, sizeof(uint32_t)));
     HIP_OK(hipHostMalloc((void **)&c->h_status, 2 * sizeof(uint32_t), hipHostMallocDefault));
-    c->h_status[0] = c->h_status[1] = 0;
+    c->h_status[0] = *c->h_bad() = 0;
     *out = c.release();
     return EMGPU_OK;
     EMGPU_CATCH
@@ -373,8 +373,8 @@ int emgpu_ctx_sync(emgpu_ctx *ctx) {
     if (st & 1u) return fail(EMGPU_ERR_REJECT_CAP, "rejection loop reached max_attempts for at least one trajectory");
     if (st & 4u) return fail(EMGPU_ERR_PRESET, "Attempt to preset a dependent variable (a row of the start grid presets a node without its parents, or a bin outside 1..r)");
     if (st & 2u) return fail(EMGPU_ERR_EVENT_CAP, "an event list did not fit event_cap rows");
-    if (ctx->h_status[1]) {   // one error per call: a bad-bin report behind a sampler's error above is kept for the next sync
-        HIP_OK(hipMemsetAsync(ctx->d_status + 1, 0, sizeof(uint32_t), ctx->stream));
+    if (*ctx->h_bad()) {   // one error per call: a bad-bin report behind a sampler's error above is kept for the next sync
+        HIP_OK(hipMemsetAsync(ctx->d_bad(), 0, sizeof(uint32_t), ctx->stream));
         HIP_OK(hipStreamSynchronize(ctx->stream));
         return fail(EMGPU_ERR_ARG, emgpu_detail::kScoreBadBin);
     }

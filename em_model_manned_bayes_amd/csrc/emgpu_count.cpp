@@ -1,13 +1,12 @@
 // emgpu_count.cpp -- emgpu_count_layout / emgpu_count_dbn_device / emgpu_count_dbn_host: the sufficient statistics of a trace (k_count_dbn,
-// emgpu_kernels_count.hip; the definition is in emgpu_count.h and DESIGN.md).  The host entry point uploads and counts in chunks of
-// EMGPU_HOST_CHUNK_MB device bytes into device tables it keeps across the chunks, and adds them to the caller's once, at the end: it never
-// holds device memory proportional to n.
+// emgpu_kernels_count.hip; the definition is in emgpu_count.h and DESIGN.md).  The host entry point uploads and counts chunk by chunk
+// (emgpu_tracechunk.hpp) into device tables it keeps across the chunks, and adds them to the caller's once, at the end.
 #include <algorithm>
 #include <cstring>
 #include <utility>
 
 #include "emgpu_count.h"
-#include "emgpu_hostmem.hpp"
+#include "emgpu_tracechunk.hpp"
 
 using namespace emgpu_detail;
 
@@ -72,12 +71,6 @@ bool fill_count(const Model &m, const EmgpuPlan &P, const emgpu_score_params *p,
     return per_step;
 }
 
-void launch(emgpu_ctx *ctx, const EmgpuCountRun &A, bool per_step) {
-    const char *name = "";
-    launch_ok(emgpu::launch_count_dbn(A, per_step, ctx->stream, &name));
-    ctx->last_kernel = name;
-    ctx->last_launches++;
-}
 } // namespace
 
 extern "C" {
@@ -96,9 +89,7 @@ int emgpu_count_dbn_device(emgpu_ctx *ctx, const emgpu_model *h, const emgpu_sco
                            uint64_t *counts_initial, uint64_t *counts_transition) {
     EMGPU_TRY
     if (const int rc = check_args(h, p, init_bin, dyn_bin, counts_initial, counts_transition)) return rc;
-    if (!ctx) return fail(EMGPU_ERR_ARG, "null ctx");
-    CTX_LOCK(ctx);
-    HIP_OK(hipSetDevice(ctx->device));
+    CTX_ENTER(ctx);
     Uploaded &u = get_uploaded(ctx, h);
     EmgpuCountRun A;
     const bool per_step = fill_count(h->m, u.cp.plan, p, counts_initial != nullptr, counts_transition != nullptr, A);
@@ -106,10 +97,10 @@ int emgpu_count_dbn_device(emgpu_ctx *ctx, const emgpu_model *h, const emgpu_sco
     A.G.n = p->n; A.G.ld = p->ld ? p->ld : p->n;
     A.G.init_bin = init_bin ? init_bin + off : nullptr;
     A.G.dyn_bin = dyn_bin && p->sample_time > 1 ? dyn_bin + off : nullptr;
-    A.G.bad = ctx->d_status + 1;
+    A.G.bad = ctx->d_bad();
     A.counts_i = (unsigned long long *)counts_initial; A.counts_t = (unsigned long long *)counts_transition;
     ctx->last_launches = 0;
-    launch(ctx, A, per_step);
+    launch_recorded(ctx, emgpu::launch_count_dbn, A, per_step);
     return EMGPU_OK;
     EMGPU_CATCH
 }
@@ -118,9 +109,7 @@ int emgpu_count_dbn_host(emgpu_ctx *ctx, const emgpu_model *h, const emgpu_score
                          uint64_t *counts_initial, uint64_t *counts_transition) {
     EMGPU_TRY
     if (const int rc = check_args(h, p, init_bin, dyn_bin, counts_initial, counts_transition)) return rc;
-    if (!ctx) return fail(EMGPU_ERR_ARG, "null ctx");
-    CTX_LOCK(ctx);
-    HIP_OK(hipSetDevice(ctx->device));
+    CTX_ENTER(ctx);
     Uploaded &u = get_uploaded(ctx, h);
     EmgpuCountRun A;
     const bool per_step = fill_count(h->m, u.cp.plan, p, counts_initial != nullptr, counts_transition != nullptr, A);
@@ -137,40 +126,27 @@ int emgpu_count_dbn_host(emgpu_ctx *ctx, const emgpu_model *h, const emgpu_score
     HIP_OK(hipMemsetAsync(d_counts, 0, (cells_i + cells_t + 1) * sizeof(uint64_t), ctx->stream));
     A.counts_i = counts_initial ? (unsigned long long *)d_counts : nullptr;
     A.counts_t = counts_transition ? (unsigned long long *)(d_counts + cells_i) : nullptr;
-    // a chunk: c trajectories, c a multiple of 256 (the device arrays' trajectory dimension), of about host_chunk_target device bytes
-    const size_t per_lane = ni + 4 * rows_d;
-    const size_t target = host_chunk_target((size_t)256 << 20);
-    const int64_t c = (int64_t)std::min<size_t>(round_up((size_t)p->n, 256), std::max<size_t>(target / per_lane / 256 * 256, 256));
-    const size_t o_dyn = round_up(ni * (size_t)c, 256);
-    char *dev = (char *)device_block_or_trim(ctx, o_dyn + round_up(4 * rows_d * (size_t)c, 256) + 256, true);
-    if (!dev) return fail(EMGPU_ERR_HIP, "emgpu_count_dbn_host: out of device memory for one chunk");
-    struct Release { emgpu_ctx *ctx; void *p; ~Release() { (void)hipStreamSynchronize(ctx->stream); device_release(p); } } release{ctx, dev};
-    A.G.ld = c;
-    A.G.init_bin = (const uint8_t *)dev;
-    A.G.dyn_bin = rows_d ? (const uint32_t *)(dev + o_dyn) : nullptr;
-    A.G.bad = ctx->d_status + 1;
-    // the word may hold the report of an earlier _device call nobody has synchronized on yet: that one is not this call's (emgpu_score_dbn_host)
-    HIP_OK(hipMemcpyAsync(ctx->h_status + 1, ctx->d_status + 1, sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
-    HIP_OK(hipMemsetAsync(ctx->d_status + 1, 0, sizeof(uint32_t), ctx->stream));
-    HIP_OK(hipStreamSynchronize(ctx->stream));
-    const bool pending = ctx->h_status[1] != 0;
-    for (int64_t c0 = 0; c0 < p->n; c0 += c) {
-        const int64_t cn = std::min<int64_t>(c, p->n - c0);
+    enum { INIT, DYN };   // the chunk's arrays: the bins as the kernel reads them
+    ChunkBlock blk(ctx, "emgpu_count_dbn_host", p->n, {{1, ni}, {4, rows_d}});
+    const size_t c = (size_t)blk.c();
+    A.G.ld = blk.c();
+    A.G.init_bin = (const uint8_t *)blk.at(INIT);
+    A.G.dyn_bin = rows_d ? (const uint32_t *)blk.at(DYN) : nullptr;
+    A.G.bad = ctx->d_bad();
+    BadWordScope bad(ctx);
+    blk.each([&](int64_t c0, int64_t cn) {
         const size_t src = (size_t)(p->col_offset + c0);
-        HIP_OK(hipMemcpy2DAsync(dev, (size_t)c, init_bin + src, (size_t)ld, (size_t)cn, ni, hipMemcpyHostToDevice, ctx->stream));
-        if (rows_d) HIP_OK(hipMemcpy2DAsync(dev + o_dyn, 4 * (size_t)c, dyn_bin + src, 4 * (size_t)ld, 4 * (size_t)cn, rows_d, hipMemcpyHostToDevice, ctx->stream));
+        HIP_OK(hipMemcpy2DAsync(blk.at(INIT), c, init_bin + src, (size_t)ld, (size_t)cn, ni, hipMemcpyHostToDevice, ctx->stream));
+        if (rows_d) HIP_OK(hipMemcpy2DAsync(blk.at(DYN), 4 * c, dyn_bin + src, 4 * (size_t)ld, 4 * (size_t)cn, rows_d, hipMemcpyHostToDevice, ctx->stream));
         A.G.n = cn;
-        launch(ctx, A, per_step);
-        HIP_OK(hipStreamSynchronize(ctx->stream));   // the next chunk overwrites the buffer; the caller's arrays are pageable
-    }
+        launch_recorded(ctx, emgpu::launch_count_dbn, A, per_step);
+    });
     std::vector<uint64_t> got(cells_i + cells_t);
     B.down(got.data(), d_counts, got.size() * sizeof(uint64_t));
-    HIP_OK(hipMemcpyAsync(ctx->h_status + 1, ctx->d_status + 1, sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
-    HIP_OK(hipMemsetAsync(ctx->d_status + 1, pending ? 1 : 0, sizeof(uint32_t), ctx->stream));   // (any non-zero word is a report)
-    HIP_OK(hipStreamSynchronize(ctx->stream));
+    const bool reported = bad.finish();
     for (size_t j = 0; j < cells_i; j++) counts_initial[j] += got[j];
     for (size_t j = 0; j < cells_t; j++) counts_transition[j] += got[cells_i + j];
-    if (ctx->h_status[1]) return fail(EMGPU_ERR_ARG, kCountBadBin);
+    if (reported) return fail(EMGPU_ERR_ARG, kCountBadBin);
     return EMGPU_OK;
     EMGPU_CATCH
 }

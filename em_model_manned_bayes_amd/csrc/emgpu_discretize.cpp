@@ -1,13 +1,12 @@
 // emgpu_discretize.cpp -- emgpu_discretize_dbn_device / emgpu_discretize_dbn_host: a trace of values into a trace of bins, and the repeat /
 // change counts of its fine bins (k_discretize_dbn, emgpu_kernels_discretize.hip; the definition is in emgpu_discretize.h and DESIGN.md).
-// The host entry point uploads, discretizes and downloads in chunks of EMGPU_HOST_CHUNK_MB device bytes, into two device vectors it keeps
-// across the chunks and adds to the caller's once, at the end: it never holds device memory proportional to n.
-#include <algorithm>
+// The host entry point uploads, discretizes and downloads chunk by chunk (emgpu_tracechunk.hpp), into two device vectors it keeps across
+// the chunks and adds to the caller's once, at the end.
 #include <cstring>
 
 #include "emgpu_discretize.h"
-#include "emgpu_hostmem.hpp"
 #include "emgpu_score.h"
+#include "emgpu_tracechunk.hpp"
 
 using namespace emgpu_detail;
 
@@ -51,12 +50,6 @@ void fill(const Model &m, const Uploaded &u, const emgpu_discretize_params *p, E
     }
 }
 
-void launch(emgpu_ctx *ctx, const EmgpuDiscretizeRun &A, bool f64) {
-    const char *name = "";
-    launch_ok(emgpu::launch_discretize_dbn(A, f64, ctx->stream, &name));
-    ctx->last_kernel = name;
-    ctx->last_launches++;
-}
 } // namespace
 
 extern "C" {
@@ -66,9 +59,7 @@ int emgpu_discretize_dbn_device(emgpu_ctx *ctx, const emgpu_model *h, const emgp
     EMGPU_TRY
     if (const int rc = check_args(h, p, init_val, dyn_val, init_bin, dyn_bin, repeat, change)) return rc;
     if (((uintptr_t)dyn_val & 15u) || ((uintptr_t)dyn_bin & 3u)) return fail(EMGPU_ERR_ARG, "dyn_val must be 16-byte aligned and dyn_bin 4-byte aligned");
-    if (!ctx) return fail(EMGPU_ERR_ARG, "null ctx");
-    CTX_LOCK(ctx);
-    HIP_OK(hipSetDevice(ctx->device));
+    CTX_ENTER(ctx);
     Uploaded &u = get_uploaded(ctx, h);
     EmgpuDiscretizeRun A;
     fill(h->m, u, p, A);
@@ -82,9 +73,9 @@ int emgpu_discretize_dbn_device(emgpu_ctx *ctx, const emgpu_model *h, const emgp
     A.dyn_bin = dyn ? dyn_bin + off : nullptr;
     A.repeat = p->n_fine > 0 ? (unsigned long long *)repeat : nullptr;
     A.change = p->n_fine > 0 ? (unsigned long long *)change : nullptr;
-    A.bad = ctx->d_status + 1;
+    A.bad = ctx->d_bad();
     ctx->last_launches = 0;
-    launch(ctx, A, f64);
+    launch_recorded(ctx, emgpu::launch_discretize_dbn, A, f64);
     return EMGPU_OK;
     EMGPU_CATCH
 }
@@ -93,9 +84,7 @@ int emgpu_discretize_dbn_host(emgpu_ctx *ctx, const emgpu_model *h, const emgpu_
                               uint8_t *init_bin, uint32_t *dyn_bin, uint64_t *repeat, uint64_t *change) {
     EMGPU_TRY
     if (const int rc = check_args(h, p, init_val, dyn_val, init_bin, dyn_bin, repeat, change)) return rc;
-    if (!ctx) return fail(EMGPU_ERR_ARG, "null ctx");
-    CTX_LOCK(ctx);
-    HIP_OK(hipSetDevice(ctx->device));
+    CTX_ENTER(ctx);
     Uploaded &u = get_uploaded(ctx, h);
     EmgpuDiscretizeRun A;
     fill(h->m, u, p, A);
@@ -114,44 +103,30 @@ int emgpu_discretize_dbn_host(emgpu_ctx *ctx, const emgpu_model *h, const emgpu_
     HIP_OK(hipMemsetAsync(d_rc, 0, 2 * EMGPU_MAX_NI * sizeof(uint64_t), ctx->stream));
     A.repeat = pairs ? (unsigned long long *)d_rc : nullptr;
     A.change = pairs ? (unsigned long long *)(d_rc + EMGPU_MAX_NI) : nullptr;
-    // a chunk: c trajectories, c a multiple of 256 (the device arrays' trajectory dimension), of about host_chunk_target device bytes
-    const size_t per_lane = ni * (es + 1) + rows_d * (4 * es + 4);
-    const size_t target = host_chunk_target((size_t)256 << 20);
-    const int64_t c = (int64_t)std::min<size_t>(round_up((size_t)p->n, 256), std::max<size_t>(target / per_lane / 256 * 256, 256));
-    const size_t o_dv = round_up(ni * es * (size_t)c, 256), o_ib = o_dv + round_up(4 * es * rows_d * (size_t)c, 256);
-    const size_t o_db = o_ib + round_up(ni * (size_t)c, 256), total = o_db + round_up(4 * rows_d * (size_t)c, 256) + 256;
-    char *dev = (char *)device_block_or_trim(ctx, total, true);
-    if (!dev) return fail(EMGPU_ERR_HIP, "emgpu_discretize_dbn_host: out of device memory for one chunk");
-    struct Release { emgpu_ctx *ctx; void *p; ~Release() { (void)hipStreamSynchronize(ctx->stream); device_release(p); } } release{ctx, dev};
-    A.ld = c;
-    A.init_val = ni ? dev : nullptr;
-    A.dyn_val = rows_d ? dev + o_dv : nullptr;
-    A.init_bin = ni ? (uint8_t *)(dev + o_ib) : nullptr;
-    A.dyn_bin = rows_d ? (uint32_t *)(dev + o_db) : nullptr;
-    A.bad = ctx->d_status + 1;
-    // the word may hold the report of an earlier _device call nobody has synchronized on yet: that one is not this call's (emgpu_score_dbn_host)
-    HIP_OK(hipMemcpyAsync(ctx->h_status + 1, ctx->d_status + 1, sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
-    HIP_OK(hipMemsetAsync(ctx->d_status + 1, 0, sizeof(uint32_t), ctx->stream));
-    HIP_OK(hipStreamSynchronize(ctx->stream));
-    const bool pending = ctx->h_status[1] != 0;
-    for (int64_t c0 = 0; c0 < p->n; c0 += c) {
-        const int64_t cn = std::min<int64_t>(c, p->n - c0);
+    enum { INIT_VAL, DYN_VAL, INIT_BIN, DYN_BIN };   // the chunk's arrays: the values as the kernel reads them, the bins as it writes them
+    ChunkBlock blk(ctx, "emgpu_discretize_dbn_host", p->n, {{es, ni}, {4 * es, rows_d}, {1, ni}, {4, rows_d}});
+    const size_t c = (size_t)blk.c();
+    A.ld = blk.c();
+    A.init_val = ni ? blk.at(INIT_VAL) : nullptr;
+    A.dyn_val = rows_d ? blk.at(DYN_VAL) : nullptr;
+    A.init_bin = ni ? (uint8_t *)blk.at(INIT_BIN) : nullptr;
+    A.dyn_bin = rows_d ? (uint32_t *)blk.at(DYN_BIN) : nullptr;
+    A.bad = ctx->d_bad();
+    BadWordScope bad(ctx);
+    blk.each([&](int64_t c0, int64_t cn) {
         const size_t src = (size_t)(p->col_offset + c0);
-        if (ni) HIP_OK(hipMemcpy2DAsync(dev, es * (size_t)c, (const char *)init_val + es * src, es * (size_t)ld, es * (size_t)cn, ni, hipMemcpyHostToDevice, ctx->stream));
-        if (rows_d) HIP_OK(hipMemcpy2DAsync(dev + o_dv, 4 * es * (size_t)c, (const char *)dyn_val + 4 * es * src, 4 * es * (size_t)ld, 4 * es * (size_t)cn, rows_d, hipMemcpyHostToDevice, ctx->stream));
+        if (ni) HIP_OK(hipMemcpy2DAsync(blk.at(INIT_VAL), es * c, (const char *)init_val + es * src, es * (size_t)ld, es * (size_t)cn, ni, hipMemcpyHostToDevice, ctx->stream));
+        if (rows_d) HIP_OK(hipMemcpy2DAsync(blk.at(DYN_VAL), 4 * es * c, (const char *)dyn_val + 4 * es * src, 4 * es * (size_t)ld, 4 * es * (size_t)cn, rows_d, hipMemcpyHostToDevice, ctx->stream));
         A.n = cn;
-        launch(ctx, A, f64);
-        if (ni) HIP_OK(hipMemcpy2DAsync(init_bin + src, (size_t)ld, dev + o_ib, (size_t)c, (size_t)cn, ni, hipMemcpyDeviceToHost, ctx->stream));
-        if (rows_d) HIP_OK(hipMemcpy2DAsync(dyn_bin + src, 4 * (size_t)ld, dev + o_db, 4 * (size_t)c, 4 * (size_t)cn, rows_d, hipMemcpyDeviceToHost, ctx->stream));
-        HIP_OK(hipStreamSynchronize(ctx->stream));   // the next chunk overwrites the buffer; the caller's arrays are pageable
-    }
+        launch_recorded(ctx, emgpu::launch_discretize_dbn, A, f64);
+        if (ni) HIP_OK(hipMemcpy2DAsync(init_bin + src, (size_t)ld, blk.at(INIT_BIN), c, (size_t)cn, ni, hipMemcpyDeviceToHost, ctx->stream));
+        if (rows_d) HIP_OK(hipMemcpy2DAsync(dyn_bin + src, 4 * (size_t)ld, blk.at(DYN_BIN), 4 * c, 4 * (size_t)cn, rows_d, hipMemcpyDeviceToHost, ctx->stream));
+    });
     uint64_t got[2 * EMGPU_MAX_NI] = {0};
     if (pairs) B.down(got, d_rc, sizeof got);
-    HIP_OK(hipMemcpyAsync(ctx->h_status + 1, ctx->d_status + 1, sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
-    HIP_OK(hipMemsetAsync(ctx->d_status + 1, pending ? 1 : 0, sizeof(uint32_t), ctx->stream));   // (any non-zero word is a report)
-    HIP_OK(hipStreamSynchronize(ctx->stream));
+    const bool reported = bad.finish();
     for (int v = 0; pairs && v < A.ni; v++) { repeat[v] += got[v]; change[v] += got[EMGPU_MAX_NI + v]; }
-    if (ctx->h_status[1]) return fail(EMGPU_ERR_ARG, kBadValue);
+    if (reported) return fail(EMGPU_ERR_ARG, kBadValue);
     return EMGPU_OK;
     EMGPU_CATCH
 }

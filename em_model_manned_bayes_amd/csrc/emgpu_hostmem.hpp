@@ -1,6 +1,6 @@
 // emgpu_hostmem.hpp -- what the host-pointer units share: emgpu_memory.cpp (which defines all of it), emgpu_host.cpp (the chunked
-// sampling path), emgpu_files.cpp (the text tables and files) emgpu_score.cpp (the chunked scoring path), emgpu_count.cpp (the chunked counting path),
-// emgpu_discretize.cpp (the chunked discretizing path) and emgpu_trackval.cpp (the chunked values-from-tracks path).  Nothing else includes it.
+// sampling path), emgpu_files.cpp (the text tables and files) and emgpu_tracechunk.hpp (the chunk block and loop of the four chunked
+// trace paths: emgpu_score.cpp, emgpu_count.cpp, emgpu_discretize.cpp and emgpu_trackval.cpp include that).  Nothing else includes it.
 #pragma once
 #include <chrono>
 

@@ -79,6 +79,9 @@ struct emgpu_ctx {
     uint32_t *d_queue = nullptr;  // k_terminal_propagate: the launch's track queue (one word, zeroed by the launcher)
     EmgpuPresets *d_presets = nullptr;   // the start grid / log-weight block of the last DBN call that had one
     uint32_t *h_status = nullptr; // pinned, two words
+    static constexpr int kBadWord = 1;   // the bad-bin word's place in both (a plain store by the kernels, no atomic)
+    uint32_t *d_bad() const { return d_status + kBadWord; }
+    uint32_t *h_bad() const { return h_status + kBadWord; }
     std::map<uint64_t, Uploaded> cache; // by Model::uid
     uint64_t use_clock = 0;
     std::string last_kernel;

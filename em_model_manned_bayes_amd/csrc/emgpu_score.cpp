@@ -1,12 +1,11 @@
 // emgpu_score.cpp -- emgpu_score_dbn_device / emgpu_score_dbn_host: the log-likelihood of a trace under a model (k_score_dbn,
-// emgpu_kernels_score.hip; the definition is in emgpu_score.h and DESIGN.md).  The host entry point uploads, scores and downloads in chunks of
-// EMGPU_HOST_CHUNK_MB device bytes: it never holds device memory proportional to n.
-#include <algorithm>
+// emgpu_kernels_score.hip; the definition is in emgpu_score.h and DESIGN.md).  The host entry point uploads, scores and downloads chunk by chunk
+// (emgpu_tracechunk.hpp).
 #include <cstring>
 #include <string>
 
-#include "emgpu_hostmem.hpp"
 #include "emgpu_score.h"
+#include "emgpu_tracechunk.hpp"
 
 using namespace emgpu_detail;
 
@@ -24,8 +23,10 @@ void ensure_score_tables(emgpu_ctx *ctx, Uploaded &u, const Model &m) {
     HIP_OK(hipStreamSynchronize(ctx->stream));   // lp is a local
 }
 
-// the kernel's argument block but its buffers
-bool fill_score(const Uploaded &u, const emgpu_score_params *p, EmgpuScoreRun &A) {
+// the kernel's argument block but its buffers, the model's tables on the device
+bool fill_score(emgpu_ctx *ctx, const emgpu_model *h, const emgpu_score_params *p, EmgpuScoreRun &A) {
+    Uploaded &u = get_uploaded(ctx, h);
+    ensure_score_tables(ctx, u, h->m);
     const bool per_step = emgpu::fill_trace_graph(u.cp.plan, p, u.lp_off, u.lpt_off, A);
     A.logp_i = u.d_logp; A.logp_t = u.d_logpt;
     return per_step;
@@ -35,12 +36,6 @@ int check_args(const emgpu_model *h, const emgpu_score_params *p, const void *in
     return emgpu::check_trace_args(h, p, init_bin, dyn_bin, log_lik != nullptr, "log_lik", true);
 }
 
-void launch(emgpu_ctx *ctx, const EmgpuScoreRun &A, bool per_step) {
-    const char *name = "";
-    launch_ok(emgpu::launch_score_dbn(A, per_step, ctx->stream, &name));
-    ctx->last_kernel = name;
-    ctx->last_launches++;
-}
 } // namespace
 
 namespace emgpu {
@@ -92,21 +87,17 @@ int emgpu_score_dbn_device(emgpu_ctx *ctx, const emgpu_model *h, const emgpu_sco
                            double *log_lik, double *initial) {
     EMGPU_TRY
     if (const int rc = check_args(h, p, init_bin, dyn_bin, log_lik)) return rc;
-    if (!ctx) return fail(EMGPU_ERR_ARG, "null ctx");
-    CTX_LOCK(ctx);
-    HIP_OK(hipSetDevice(ctx->device));
-    Uploaded &u = get_uploaded(ctx, h);
-    ensure_score_tables(ctx, u, h->m);
+    CTX_ENTER(ctx);
     EmgpuScoreRun A;
-    const bool per_step = fill_score(u, p, A);
+    const bool per_step = fill_score(ctx, h, p, A);
     const size_t off = (size_t)p->col_offset;
     A.n = p->n; A.ld = p->ld ? p->ld : p->n;
     A.init_bin = init_bin ? init_bin + off : nullptr;
     A.dyn_bin = dyn_bin && p->sample_time > 1 ? dyn_bin + off : nullptr;
     A.log_lik = log_lik; A.initial = initial;
-    A.bad = ctx->d_status + 1;
+    A.bad = ctx->d_bad();
     ctx->last_launches = 0;
-    launch(ctx, A, per_step);
+    launch_recorded(ctx, emgpu::launch_score_dbn, A, per_step);
     return EMGPU_OK;
     EMGPU_CATCH
 }
@@ -115,54 +106,35 @@ int emgpu_score_dbn_host(emgpu_ctx *ctx, const emgpu_model *h, const emgpu_score
                          double *log_lik, double *initial) {
     EMGPU_TRY
     if (const int rc = check_args(h, p, init_bin, dyn_bin, log_lik)) return rc;
-    if (!ctx) return fail(EMGPU_ERR_ARG, "null ctx");
-    CTX_LOCK(ctx);
-    HIP_OK(hipSetDevice(ctx->device));
-    Uploaded &u = get_uploaded(ctx, h);
-    ensure_score_tables(ctx, u, h->m);
+    CTX_ENTER(ctx);
     EmgpuScoreRun A;
-    const bool per_step = fill_score(u, p, A);
+    const bool per_step = fill_score(ctx, h, p, A);
     ctx->last_launches = 0;
     ctx->last_kernel = per_step ? "k_score_dbn[per-step]" : "k_score_dbn[frozen]";
     if (p->n == 0) return EMGPU_OK;
     const int64_t ld = p->ld ? p->ld : p->n;
     const size_t ni = (size_t)A.ni, rows_d = dyn_bin && p->sample_time > 1 ? (size_t)((p->sample_time + 3) / 4) * (size_t)A.nd : 0;
-    // a chunk: c trajectories, c a multiple of 256 (the device arrays' trajectory dimension), of about host_chunk_target device bytes
-    const size_t per_lane = ni + 4 * rows_d + 16;
-    const size_t target = host_chunk_target((size_t)256 << 20);
-    const int64_t c = (int64_t)std::min<size_t>(round_up((size_t)p->n, 256), std::max<size_t>(target / per_lane / 256 * 256, 256));
-    const size_t o_dyn = round_up(ni * (size_t)c, 256), o_ll = o_dyn + round_up(4 * rows_d * (size_t)c, 256), o_in = o_ll + 8 * (size_t)c;
     CallBuffers B(ctx);
-    char *dev = (char *)device_block_or_trim(ctx, o_in + 8 * (size_t)c, true);
-    if (!dev) return fail(EMGPU_ERR_HIP, "emgpu_score_dbn_host: out of device memory for one chunk");
-    struct Release { emgpu_ctx *ctx; void *p; ~Release() { (void)hipStreamSynchronize(ctx->stream); device_release(p); } } release{ctx, dev};
-    A.ld = c;
-    A.init_bin = (const uint8_t *)dev;
-    A.dyn_bin = rows_d ? (const uint32_t *)(dev + o_dyn) : nullptr;
-    A.log_lik = (double *)(dev + o_ll);
-    A.initial = initial ? (double *)(dev + o_in) : nullptr;
-    A.bad = ctx->d_status + 1;
-    // the word may hold the report of an earlier _device call nobody has synchronized on yet: that one is not this call's.  Take it out
-    // before the first chunk and put it back behind the last, for the emgpu_ctx_sync it belongs to.
-    HIP_OK(hipMemcpyAsync(ctx->h_status + 1, ctx->d_status + 1, sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
-    HIP_OK(hipMemsetAsync(ctx->d_status + 1, 0, sizeof(uint32_t), ctx->stream));
-    HIP_OK(hipStreamSynchronize(ctx->stream));
-    const bool pending = ctx->h_status[1] != 0;
-    for (int64_t c0 = 0; c0 < p->n; c0 += c) {
-        const int64_t cn = std::min<int64_t>(c, p->n - c0);
+    enum { INIT, DYN, LL, INITIAL };   // the chunk's arrays: the bins as the kernel reads them, a double per lane for each output
+    ChunkBlock blk(ctx, "emgpu_score_dbn_host", p->n, {{1, ni}, {4, rows_d}, {8, 1}, {8, 1}});
+    const size_t c = (size_t)blk.c();
+    A.ld = blk.c();
+    A.init_bin = (const uint8_t *)blk.at(INIT);
+    A.dyn_bin = rows_d ? (const uint32_t *)blk.at(DYN) : nullptr;
+    A.log_lik = (double *)blk.at(LL);
+    A.initial = initial ? (double *)blk.at(INITIAL) : nullptr;
+    A.bad = ctx->d_bad();
+    BadWordScope bad(ctx);
+    blk.each([&](int64_t c0, int64_t cn) {
         const size_t src = (size_t)(p->col_offset + c0);
-        HIP_OK(hipMemcpy2DAsync(dev, (size_t)c, init_bin + src, (size_t)ld, (size_t)cn, ni, hipMemcpyHostToDevice, ctx->stream));
-        if (rows_d) HIP_OK(hipMemcpy2DAsync(dev + o_dyn, 4 * (size_t)c, dyn_bin + src, 4 * (size_t)ld, 4 * (size_t)cn, rows_d, hipMemcpyHostToDevice, ctx->stream));
+        HIP_OK(hipMemcpy2DAsync(blk.at(INIT), c, init_bin + src, (size_t)ld, (size_t)cn, ni, hipMemcpyHostToDevice, ctx->stream));
+        if (rows_d) HIP_OK(hipMemcpy2DAsync(blk.at(DYN), 4 * c, dyn_bin + src, 4 * (size_t)ld, 4 * (size_t)cn, rows_d, hipMemcpyHostToDevice, ctx->stream));
         A.n = cn;
-        launch(ctx, A, per_step);
+        launch_recorded(ctx, emgpu::launch_score_dbn, A, per_step);
         B.down(log_lik + c0, A.log_lik, 8 * (size_t)cn);
         if (initial) B.down(initial + c0, A.initial, 8 * (size_t)cn);
-        HIP_OK(hipStreamSynchronize(ctx->stream));   // the next chunk overwrites the buffer; the caller's arrays are pageable
-    }
-    HIP_OK(hipMemcpyAsync(ctx->h_status + 1, ctx->d_status + 1, sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
-    HIP_OK(hipMemsetAsync(ctx->d_status + 1, pending ? 1 : 0, sizeof(uint32_t), ctx->stream));   // (any non-zero word is a report)
-    HIP_OK(hipStreamSynchronize(ctx->stream));
-    if (ctx->h_status[1]) return fail(EMGPU_ERR_ARG, kScoreBadBin);
+    });
+    if (bad.finish()) return fail(EMGPU_ERR_ARG, kScoreBadBin);
     return EMGPU_OK;
     EMGPU_CATCH
 }

@@ -1,14 +1,12 @@
 // emgpu_trackval.cpp -- emgpu_track_values_device / emgpu_track_values_host: 1 Hz tracks into the values of a trace (k_track_values,
 // emgpu_kernels_trackval.hip; the definition is in emgpu_trackval.h and DESIGN.md).  The host entry point takes tracks as a file holds them
 // ([n][points][3]): a chunk of tracks is one contiguous piece of the caller's array, so it is uploaded as it lies and the ROWS kernel reads
-// it; nothing is transposed on the host.  It works in chunks of EMGPU_HOST_CHUNK_MB device bytes and never holds device memory
-// proportional to n.
-#include <algorithm>
+// it; nothing is transposed on the host.  It works chunk by chunk (emgpu_tracechunk.hpp).
 #include <cmath>
 #include <cstring>
 
-#include "emgpu_hostmem.hpp"
 #include "emgpu_plan.h"
+#include "emgpu_tracechunk.hpp"
 #include "emgpu_trackval.h"
 
 using namespace emgpu_detail;
@@ -47,12 +45,6 @@ int check_args(const emgpu_track_values_params *p, const double *xyz, const void
     return EMGPU_OK;
 }
 
-void launch(emgpu_ctx *ctx, const EmgpuTrackValuesRun &A, bool rows, bool f64) {
-    const char *name = "";
-    launch_ok(emgpu::launch_track_values(A, rows, f64, ctx->stream, &name));
-    ctx->last_kernel = name;
-    ctx->last_launches++;
-}
 } // namespace
 
 extern "C" {
@@ -64,9 +56,7 @@ int emgpu_track_values_device(emgpu_ctx *ctx, const emgpu_track_values_params *p
     const size_t es = f64 ? 8 : 4, off = (size_t)p->col_offset;
     if (((uintptr_t)xyz & 7u) || ((uintptr_t)init_val & (es - 1)) || ((uintptr_t)dyn_val & 15u))
         return fail(EMGPU_ERR_ARG, "xyz must be 8-byte aligned, init_val aligned to its element and dyn_val 16-byte aligned");
-    if (!ctx) return fail(EMGPU_ERR_ARG, "null ctx");
-    CTX_LOCK(ctx);
-    HIP_OK(hipSetDevice(ctx->device));
+    CTX_ENTER(ctx);
     EmgpuTrackValuesRun A{};
     A.n = p->n; A.ld = p->ld ? p->ld : p->n; A.P = p->points; A.nd = p->nd;
     const int32_t row[5] = {p->row_alt, p->row_speed, p->row_vertrate, p->row_acc, p->row_turnrate};
@@ -77,7 +67,7 @@ int emgpu_track_values_device(emgpu_ctx *ctx, const emgpu_track_values_params *p
     A.init_val = init_val ? (char *)init_val + es * off : nullptr;
     A.dyn_val = dyn_val ? (char *)dyn_val + 4 * es * off : nullptr;
     ctx->last_launches = 0;
-    launch(ctx, A, p->layout == EMGPU_TRACKS_ROWS, f64);
+    launch_recorded(ctx, emgpu::launch_track_values, A, p->layout == EMGPU_TRACKS_ROWS, f64);
     return EMGPU_OK;
     EMGPU_CATCH
 }
@@ -86,9 +76,7 @@ int emgpu_track_values_host(emgpu_ctx *ctx, const emgpu_track_values_params *p, 
     EMGPU_TRY
     if (const int rc = check_args(p, xyz, init_val, dyn_val)) return rc;
     if (p->layout != EMGPU_TRACKS_ROWS) return fail(EMGPU_ERR_ARG, "emgpu_track_values_host takes tracks as rows (EMGPU_TRACKS_ROWS)");
-    if (!ctx) return fail(EMGPU_ERR_ARG, "null ctx");
-    CTX_LOCK(ctx);
-    HIP_OK(hipSetDevice(ctx->device));
+    CTX_ENTER(ctx);
     const bool f64 = p->value_type == EMGPU_VALUE_F64;
     ctx->last_launches = 0;
     ctx->last_kernel = f64 ? "k_track_values[ROWS,f64]" : "k_track_values[ROWS,f32]";
@@ -100,39 +88,31 @@ int emgpu_track_values_host(emgpu_ctx *ctx, const emgpu_track_values_params *p, 
     const int32_t row[5] = {p->row_alt, p->row_speed, p->row_vertrate, p->row_acc, p->row_turnrate};
     const int32_t slot[3] = {p->slot_vertrate, p->slot_acc, p->slot_turnrate};
     const size_t ni = init_val ? 5 : 0, rows_d = dyn_val ? 3 * G4 : 0;
-    // a chunk: c tracks, c a multiple of 256, of about host_chunk_target device bytes
-    const size_t per_lane = 24 * P + ni * es + rows_d * 4 * es;
-    const size_t target = host_chunk_target((size_t)256 << 20);
-    const int64_t c = (int64_t)std::min<size_t>(round_up((size_t)p->n, 256), std::max<size_t>(target / per_lane / 256 * 256, 256));
-    const size_t o_iv = round_up(24 * P * (size_t)c, 256), o_dv = o_iv + round_up(ni * es * (size_t)c, 256);
-    const size_t total = o_dv + round_up(4 * es * rows_d * (size_t)c, 256) + 256;
-    char *dev = (char *)device_block_or_trim(ctx, total, true);
-    if (!dev) return fail(EMGPU_ERR_HIP, "emgpu_track_values_host: out of device memory for one chunk");
-    struct Release { emgpu_ctx *ctx; void *p; ~Release() { (void)hipStreamSynchronize(ctx->stream); device_release(p); } } release{ctx, dev};
+    enum { XYZ, INIT_VAL, DYN_VAL };   // the chunk's arrays: the tracks as they lie (one row of 24 P bytes per lane), the values as the kernel writes them
+    ChunkBlock blk(ctx, "emgpu_track_values_host", p->n, {{24 * P, 1}, {es, ni}, {4 * es, rows_d}});
+    const size_t c = (size_t)blk.c();
     EmgpuTrackValuesRun A{};
-    A.ld = c; A.P = p->points; A.nd = 3;
+    A.ld = blk.c(); A.P = p->points; A.nd = 3;
     for (int a = 0; a < 5; a++) A.row[a] = row[a] >= 0 ? a : -1;
     for (int k = 0; k < 3; k++) A.slot[k] = k;
     A.ur_speed = p->ur_speed; A.ur_vertrate = p->ur_vertrate; A.ur_heading = p->ur_heading;
-    A.xyz = (const double *)dev;
-    A.init_val = ni ? dev + o_iv : nullptr;
-    A.dyn_val = rows_d ? dev + o_dv : nullptr;
-    for (int64_t c0 = 0; c0 < p->n; c0 += c) {
-        const int64_t cn = std::min<int64_t>(c, p->n - c0);
+    A.xyz = (const double *)blk.at(XYZ);
+    A.init_val = ni ? blk.at(INIT_VAL) : nullptr;
+    A.dyn_val = rows_d ? blk.at(DYN_VAL) : nullptr;
+    blk.each([&](int64_t c0, int64_t cn) {
         const size_t dst = (size_t)(p->col_offset + c0);
-        HIP_OK(hipMemcpyAsync(dev, xyz + 3 * P * (size_t)c0, 24 * P * (size_t)cn, hipMemcpyHostToDevice, ctx->stream));
+        HIP_OK(hipMemcpyAsync(blk.at(XYZ), xyz + 3 * P * (size_t)c0, 24 * P * (size_t)cn, hipMemcpyHostToDevice, ctx->stream));
         A.n = cn;
-        launch(ctx, A, true, f64);
+        launch_recorded(ctx, emgpu::launch_track_values, A, true, f64);
         for (int a = 0; ni && a < 5; a++)
             if (row[a] >= 0)
-                HIP_OK(hipMemcpyAsync((char *)init_val + es * ((size_t)row[a] * (size_t)ld + dst), dev + o_iv + es * (size_t)a * (size_t)c, es * (size_t)cn,
+                HIP_OK(hipMemcpyAsync((char *)init_val + es * ((size_t)row[a] * (size_t)ld + dst), blk.at(INIT_VAL) + es * (size_t)a * c, es * (size_t)cn,
                                       hipMemcpyDeviceToHost, ctx->stream));
         for (int k = 0; rows_d && k < 3; k++)
             HIP_OK(hipMemcpy2DAsync((char *)dyn_val + 4 * es * ((size_t)slot[k] * (size_t)ld + dst), 4 * es * (size_t)p->nd * (size_t)ld,
-                                    dev + o_dv + 4 * es * (size_t)k * (size_t)c, 4 * es * 3 * (size_t)c, 4 * es * (size_t)cn, G4, hipMemcpyDeviceToHost,
+                                    blk.at(DYN_VAL) + 4 * es * (size_t)k * c, 4 * es * 3 * c, 4 * es * (size_t)cn, G4, hipMemcpyDeviceToHost,
                                     ctx->stream));
-        HIP_OK(hipStreamSynchronize(ctx->stream));   // the next chunk overwrites the buffer; the caller's arrays are pageable
-    }
+    });
     return EMGPU_OK;
     EMGPU_CATCH
 }

@@ -1,6 +1,7 @@
 """Thin object layer over the C ABI: NativeModel (emgpu_model*), Context (emgpu_ctx*) and the
 sampling calls with numpy (host) or raw device pointers (torch tensors' data_ptr()).
 """
+import contextlib
 import ctypes as C
 import re
 
@@ -610,9 +611,7 @@ def split_rows(a, ends):
 
 def unpack_dyn_bin(db, T):
     """[G4][nd][n] uint32 (4 seconds per word) -> [n, T, nd] uint8."""
-    G4, nd, n = db.shape
-    b = db.view(np.uint8).reshape(G4, nd, n, 4)          # little endian: byte w = column 4g+w
-    return np.ascontiguousarray(b.transpose(2, 0, 3, 1).reshape(n, G4 * 4, nd)[:, :T, :])
+    return unpack_dyn_val(db.view(np.uint8).reshape(db.shape + (4,)), T)     # little endian: byte w = column 4g+w
 
 
 def unpack_dyn_val(dv, T):
@@ -623,12 +622,8 @@ def unpack_dyn_val(dv, T):
 
 def pack_dyn_bin(db):
     """[n, T, nd] uint8 -> [G4][nd][n] uint32 (the inverse of unpack_dyn_bin; padding columns are 0)."""
-    db = np.asarray(db, dtype=np.uint8)
-    n, T, nd = db.shape
-    G4 = (T + 3) // 4
-    b = np.zeros((n, G4 * 4, nd), dtype=np.uint8)
-    b[:, :T, :] = db
-    return np.ascontiguousarray(b.reshape(n, G4, 4, nd).transpose(1, 3, 0, 2)).view(np.uint32).reshape(G4, nd, n)
+    b = pack_dyn_val(np.asarray(db, dtype=np.uint8))
+    return b.view(np.uint32).reshape(b.shape[:3])
 
 
 def score_params(n, sample_time, transition_mode=L.TRANSITION_REFERENCE_AUTO, ld=0, col_offset=0):
@@ -645,12 +640,9 @@ def score_dbn_device(ctx, model, params, init_bin, dyn_bin=0, log_lik=0, initial
                                            C.c_void_p(log_lik or None), C.c_void_p(initial or None)))
 
 
-def score_dbn_host(ctx, model, init_bin, dyn_bin, T, transition_mode=L.TRANSITION_REFERENCE_AUTO, raw=False, n=None, col_offset=0):
-    """log P(trajectory | model) of a host trace (emgpu_score_dbn_host; the definition is in include/emgpu.h).  raw=False: the user-facing
-    shapes sample_dbn_host returns (init_bin [n, n_i] u8, dyn_bin [n, T, n_d] u8 or None); raw=True: the library layout (init_bin [n_i, ld]
-    u8, dyn_bin [G4, n_d, ld] u32), of which columns col_offset .. col_offset + n are scored (n: default ld - col_offset).
-    Returns {"log_lik" [n], "initial" [n], "kernel"}.  The rejection loop's normalisation (altitude / speed / layers) is not part of the
-    number.  A bin outside 1..r raises EmgpuError(ERR_ARG) carrying .log_lik / .initial (NaN for exactly those trajectories)."""
+def _bin_arrays(model, init_bin, dyn_bin, T, raw, n, col_offset):
+    """(init_bin [n_i, ld] u8, dyn_bin [G4, n_d, ld] u32 or None, ld, n) of a call's trace of bins, in the library layout (n: default
+    ld - col_offset)"""
     if raw:
         ib = np.ascontiguousarray(init_bin, dtype=np.uint8)
         db = None if dyn_bin is None else np.ascontiguousarray(dyn_bin, dtype=np.uint32)
@@ -663,13 +655,29 @@ def score_dbn_host(ctx, model, init_bin, dyn_bin, T, transition_mode=L.TRANSITIO
     n = ld - int(col_offset) if n is None else int(n)
     if db is not None and (db.ndim != 3 or db.shape != ((int(T) + 3) // 4, model.n_dyn, ld)):
         raise ValueError("dyn_bin must hold T columns of n_dyn variables for the trajectories of init_bin")
+    return ib, db, ld, n
+
+
+def _raise(rc, **carried):
+    """EmgpuError of a call's negative status and the library's message, carrying what the call has to show all the same"""
+    e = L.EmgpuError(int(rc), L.lib().emgpu_last_error().decode("utf-8", "replace"))
+    for k, v in carried.items():
+        setattr(e, k, v)
+    raise e
+
+
+def score_dbn_host(ctx, model, init_bin, dyn_bin, T, transition_mode=L.TRANSITION_REFERENCE_AUTO, raw=False, n=None, col_offset=0):
+    """log P(trajectory | model) of a host trace (emgpu_score_dbn_host; the definition is in include/emgpu.h).  raw=False: the user-facing
+    shapes sample_dbn_host returns (init_bin [n, n_i] u8, dyn_bin [n, T, n_d] u8 or None); raw=True: the library layout (init_bin [n_i, ld]
+    u8, dyn_bin [G4, n_d, ld] u32), of which columns col_offset .. col_offset + n are scored (n: default ld - col_offset).
+    Returns {"log_lik" [n], "initial" [n], "kernel"}.  The rejection loop's normalisation (altitude / speed / layers) is not part of the
+    number.  A bin outside 1..r raises EmgpuError(ERR_ARG) carrying .log_lik / .initial (NaN for exactly those trajectories)."""
+    ib, db, ld, n = _bin_arrays(model, init_bin, dyn_bin, T, raw, n, col_offset)
     p = score_params(n, T, transition_mode, ld, col_offset)
     ll, ini = np.zeros(max(n, 0), dtype=np.float64), np.zeros(max(n, 0), dtype=np.float64)
     rc = L.lib().emgpu_score_dbn_host(ctx._h, model._h, C.byref(p), _p(ib), _p(db), _p(ll), _p(ini))
     if rc < 0:
-        e = L.EmgpuError(int(rc), L.lib().emgpu_last_error().decode("utf-8", "replace"))
-        e.log_lik, e.initial = ll, ini
-        raise e
+        _raise(rc, log_lik=ll, initial=ini)
     return {"log_lik": ll, "initial": ini, "kernel": ctx.last_kernel()}
 
 
@@ -705,6 +713,32 @@ def _counts_arrays(model, counts):
     return [ci, ct]
 
 
+def _counts_result(model, ci, ct, pairs=None, **kernels):
+    """the dict the counting calls return: the tables of the u64 arrays ci / ct, the two vectors of pairs = (u64 repeat, u64 change) where
+    the call has them, and the kernels' names"""
+    Ni, Nt = split_counts(model, (ci, ct))
+    out = {"N_initial": Ni, "N_transition": Nt, "raw": (ci, ct)}
+    if pairs is not None:
+        out.update({"repeat": pairs[0].astype(np.float64), "change": pairs[1].astype(np.float64), "raw_pairs": pairs})
+    out.update(kernels)
+    return out
+
+
+@contextlib.contextmanager
+def _device_arrays(ctx, **nbytes):
+    """One device block (emgpu_device_alloc) holding arrays of these sizes at 256-byte offsets, in the order given: {name: address}.  The
+    block is freed when the scope ends, however it ends."""
+    off, o = {}, 0
+    for name, b in nbytes.items():
+        off[name] = o
+        o += (int(b) + 255) // 256 * 256
+    base = ctx.device_alloc(max(o, 256))
+    try:
+        yield {k: base + v for k, v in off.items()}
+    finally:
+        ctx.device_free(base)
+
+
 def count_dbn_host(ctx, model, init_bin, dyn_bin, T, transition_mode=L.TRANSITION_REFERENCE_AUTO, raw=False, n=None, col_offset=0, counts=None):
     """The sufficient statistics of a host trace (emgpu_count_dbn_host; the definition is in include/emgpu.h): how often every cell of the
     model's N_initial / N_transition was observed.  The trace is given as to score_dbn_host (raw=False: init_bin [n, n_i] u8, dyn_bin
@@ -712,28 +746,14 @@ def count_dbn_host(ctx, model, init_bin, dyn_bin, T, transition_mode=L.TRANSITIO
     Returns {"N_initial": [r x q float64 per variable], "N_transition": [per node, (0, 0) where no table], "raw": (u64 initial, u64
     transition), "kernel"}.  counts=<a previous result's raw> accumulates into those arrays.  dyn_bin None counts the initial network alone.
     A bin outside 1..r skips the observations that read it and raises EmgpuError(ERR_ARG) carrying .counts (the same dict)."""
-    if raw:
-        ib = np.ascontiguousarray(init_bin, dtype=np.uint8)
-        db = None if dyn_bin is None else np.ascontiguousarray(dyn_bin, dtype=np.uint32)
-    else:
-        ib = np.ascontiguousarray(np.asarray(init_bin, dtype=np.uint8).T)
-        db = None if dyn_bin is None else pack_dyn_bin(dyn_bin)
-    if ib.ndim != 2 or ib.shape[0] != model.n_initial:
-        raise ValueError("init_bin must hold n_initial entries per trajectory")
-    ld = ib.shape[1]
-    n = ld - int(col_offset) if n is None else int(n)
-    if db is not None and (db.ndim != 3 or db.shape != ((int(T) + 3) // 4, model.n_dyn, ld)):
-        raise ValueError("dyn_bin must hold T columns of n_dyn variables for the trajectories of init_bin")
+    ib, db, ld, n = _bin_arrays(model, init_bin, dyn_bin, T, raw, n, col_offset)
     ci, ct = _counts_arrays(model, counts)
     p = score_params(n, T, transition_mode, ld, col_offset)
     transitions = db is not None and int(T) > 1 and model.n_dyn > 0
     rc = L.lib().emgpu_count_dbn_host(ctx._h, model._h, C.byref(p), _p(ib), _p(db), _p(ci), _p(ct) if transitions else None)
-    Ni, Nt = split_counts(model, (ci, ct))
-    out = {"N_initial": Ni, "N_transition": Nt, "raw": (ci, ct), "kernel": ctx.last_kernel()}
+    out = _counts_result(model, ci, ct, kernel=ctx.last_kernel())
     if rc < 0:
-        e = L.EmgpuError(int(rc), L.lib().emgpu_last_error().decode("utf-8", "replace"))
-        e.counts = out
-        raise e
+        _raise(rc, counts=out)
     return out
 
 
@@ -745,15 +765,8 @@ def sample_count_host(ctx, model, n, T, seed, transition_mode=L.TRANSITION_REFER
     ni, nd, T, n = model.n_initial, model.n_dyn, int(T), int(n)
     G4 = (T + 3) // 4
     ci, ct = _counts_arrays(model, counts)
-    sizes = [("init_bin", ni * n), ("init_val", 4 * ni * n), ("dyn_bin", 4 * G4 * nd * n), ("dyn_val", 16 * G4 * nd * n), ("attempts", 4 * n),
-             ("ci", 8 * ci.size), ("ct", 8 * ct.size)]
-    off, o = {}, 0
-    for name, b in sizes:
-        off[name] = o
-        o += (b + 255) // 256 * 256
-    base = ctx.device_alloc(max(o, 256))
-    try:
-        at = {k: base + v for k, v in off.items()}
+    with _device_arrays(ctx, init_bin=ni * n, init_val=4 * ni * n, dyn_bin=4 * G4 * nd * n, dyn_val=16 * G4 * nd * n, attempts=4 * n,
+                        ci=8 * ci.size, ct=8 * ct.size) as at:
         for name, a in (("ci", ci), ("ct", ct)):
             if a.size:
                 device_upload(ctx, at[name], np.zeros_like(a))
@@ -770,11 +783,8 @@ def sample_count_host(ctx, model, n, T, seed, transition_mode=L.TRANSITION_REFER
         for name, a in (("ci", ci), ("ct", ct)):
             if a.size:
                 a += device_download(ctx, at[name], np.zeros_like(a))
-    finally:
-        ctx.device_free(base)
     del keep
-    Ni, Nt = split_counts(model, (ci, ct))
-    return {"N_initial": Ni, "N_transition": Nt, "raw": (ci, ct), "kernel": kernel, "count_kernel": count_kernel}
+    return _counts_result(model, ci, ct, kernel=kernel, count_kernel=count_kernel)
 
 
 def pack_dyn_val(dv):
@@ -869,10 +879,38 @@ def discretize_dbn_host(ctx, model, init_val, dyn_val, T, n_fine=0, wrap=None, r
            "repeat": rep.astype(np.float64), "change": chg.astype(np.float64), "raw": (rep, chg),
            "kernel": ctx.last_kernel() if ctx is not None else ""}
     if rc < 0:
-        e = L.EmgpuError(int(rc), L.lib().emgpu_last_error().decode("utf-8", "replace"))
-        e.bins = out
-        raise e
+        _raise(rc, bins=out)
     return out
+
+
+def _discretize_count_in_block(ctx, model, at, n, T, n_fine, value_type, wrap, transition_mode, dense, **kernels):
+    """The values that lie at at["init_val"] / at["dyn_val"] of a _device_arrays block (dense: it has the dynamic half) discretized into
+    at["init_bin"] / at["dyn_bin"] and counted there, into fresh tables at at["ci"] / at["ct"] and vectors at at["rc"] (2 n_initial u64),
+    which alone come back: discretize_count_host's dict."""
+    ni = model.n_initial
+    ci, ct = _counts_arrays(model, None)
+    rc = np.zeros(2 * ni, dtype=np.uint64)
+    for name, a in (("ci", ci), ("ct", ct), ("rc", rc)):
+        if a.size:
+            device_upload(ctx, at[name], a)
+    discretize_dbn_device(ctx, model, discretize_params(n, T, n_fine, value_type, wrap), at["init_val"], at["dyn_val"] if dense else 0,
+                          at["init_bin"], at["dyn_bin"] if dense else 0, at["rc"] if n_fine else 0, at["rc"] + 8 * ni if n_fine else 0)
+    kernel = ctx.last_kernel()
+    transitions = dense and T > 1
+    count_dbn_device(ctx, model, score_params(n, T, transition_mode), at["init_bin"], at["dyn_bin"] if transitions else 0,
+                     at["ci"], at["ct"] if transitions else 0)
+    count_kernel = ctx.last_kernel()
+    ctx.sync()                                  # the launches' deferred errors
+    for name, a in (("ci", ci), ("ct", ct), ("rc", rc)):
+        if a.size:
+            device_download(ctx, at[name], a)
+    return _counts_result(model, ci, ct, (rc[:ni].copy(), rc[ni:].copy()), kernel=kernel, count_kernel=count_kernel, **kernels)
+
+
+def _discretize_count_bytes(model, n, T, dense):
+    """the arrays of _discretize_count_in_block besides the values, for _device_arrays"""
+    return dict(init_bin=model.n_initial * n, dyn_bin=4 * ((T + 3) // 4) * model.n_dyn * n if dense else 0,
+                ci=8 * int(model.count_layout(0)[-1]), ct=8 * int(model.count_layout(1)[-1]), rc=16 * model.n_initial)
 
 
 def discretize_count_host(ctx, model, init_val, dyn_val, n_fine=0, wrap=None, transition_mode=L.TRANSITION_REFERENCE_AUTO):
@@ -886,40 +924,12 @@ def discretize_count_host(ctx, model, init_val, dyn_val, n_fine=0, wrap=None, tr
         raise ValueError("counting needs init_val")
     T = 1 if dyn_val is None else int(np.asarray(dyn_val).shape[1])
     iv, dv, n, vt = _value_arrays(model, init_val, dyn_val, T, False)
-    ni, nd, G4 = model.n_initial, model.n_dyn, (T + 3) // 4
-    ci, ct = _counts_arrays(model, None)
-    rc = np.zeros(2 * ni, dtype=np.uint64)
-    dense = dv is not None and nd > 0
-    sizes = [("init_val", iv.nbytes), ("dyn_val", dv.nbytes if dense else 0), ("init_bin", ni * n), ("dyn_bin", 4 * G4 * nd * n if dense else 0),
-             ("ci", 8 * ci.size), ("ct", 8 * ct.size), ("rc", rc.nbytes)]
-    off, o = {}, 0
-    for name, b in sizes:
-        off[name] = o
-        o += (b + 255) // 256 * 256
-    base = ctx.device_alloc(max(o, 256))
-    try:
-        at = {k: base + v for k, v in off.items()}
-        for name, a in (("init_val", iv), ("dyn_val", dv if dense else None), ("ci", ci), ("ct", ct), ("rc", rc)):
+    dense = dv is not None and model.n_dyn > 0
+    with _device_arrays(ctx, init_val=iv.nbytes, dyn_val=dv.nbytes if dense else 0, **_discretize_count_bytes(model, n, T, dense)) as at:
+        for name, a in (("init_val", iv), ("dyn_val", dv if dense else None)):
             if a is not None and a.size:
                 device_upload(ctx, at[name], a)
-        p = discretize_params(n, T, n_fine, vt, wrap)
-        discretize_dbn_device(ctx, model, p, at["init_val"], at["dyn_val"] if dense else 0, at["init_bin"], at["dyn_bin"] if dense else 0,
-                              at["rc"] if n_fine else 0, at["rc"] + 8 * ni if n_fine else 0)
-        kernel = ctx.last_kernel()
-        transitions = dense and T > 1
-        count_dbn_device(ctx, model, score_params(n, T, transition_mode), at["init_bin"], at["dyn_bin"] if transitions else 0,
-                         at["ci"], at["ct"] if transitions else 0)
-        count_kernel = ctx.last_kernel()
-        ctx.sync()                                  # both launches' deferred errors
-        for name, a in (("ci", ci), ("ct", ct), ("rc", rc)):
-            if a.size:
-                device_download(ctx, at[name], a)
-    finally:
-        ctx.device_free(base)
-    Ni, Nt = split_counts(model, (ci, ct))
-    rep, chg = rc[:ni].copy(), rc[ni:].copy()
-    return {"N_initial": Ni, "N_transition": Nt, "raw": (ci, ct), "repeat": rep.astype(np.float64), "change": chg.astype(np.float64),
-            "raw_pairs": (rep, chg), "kernel": kernel, "count_kernel": count_kernel}
+        return _discretize_count_in_block(ctx, model, at, n, T, n_fine, vt, wrap, transition_mode, dense)
 
 
 def track_values_params(n, points, ur_speed, ur_vertrate, ur_heading, n_initial=5, nd=3, rows=(0, 1, 2, 3, 4), slots=(0, 1, 2),
@@ -944,6 +954,15 @@ def track_values_device(ctx, params, xyz, init_val=0, dyn_val=0):
                                               C.c_void_p(init_val or None), C.c_void_p(dyn_val or None)))
 
 
+def _track_array(xyz):
+    """(xyz [n, P, 3] as contiguous f64, n, P)"""
+    xyz = np.ascontiguousarray(xyz, dtype=np.float64)
+    if xyz.ndim != 3 or xyz.shape[2] != 3:
+        raise ValueError("xyz must be [n, points, 3]")
+    n, P = int(xyz.shape[0]), int(xyz.shape[1])
+    return xyz, n, P
+
+
 def _fill_static(iv, static, written):
     """static = {1-based variable id: array [n] or scalar} into the rows of init_val [n_initial, n] the kernel leaves"""
     for v, a in (static or {}).items():
@@ -962,10 +981,7 @@ def track_values_host(ctx, xyz, ur_speed, ur_vertrate, ur_heading, n_initial=5, 
     [n, n_initial] and dyn_val [n, T, nd] (raw=True: the library layout, [n_initial, n] and [G4, nd, n, 4]), float32 or float64 by
     value_type.  Rows the tracks do not give are 0, but for static = {1-based variable id: array [n] or scalar}, which fills rows of
     init_val (G, A, ... of a model).  want_init / want_dyn False: that half is None."""
-    xyz = np.ascontiguousarray(xyz, dtype=np.float64)
-    if xyz.ndim != 3 or xyz.shape[2] != 3:
-        raise ValueError("xyz must be [n, points, 3]")
-    n, P = int(xyz.shape[0]), int(xyz.shape[1])
+    xyz, n, P = _track_array(xyz)
     T, dt = P - 2, (np.float64 if value_type == L.VALUE_F64 else np.float32)
     iv = np.zeros((int(n_initial), n), dtype=dt) if want_init else None
     dv = np.zeros(((max(T, 0) + 3) // 4, int(nd), n, 4), dtype=dt) if want_dyn else None
@@ -995,52 +1011,22 @@ def track_count_host(ctx, model, xyz, rows, static=None, n_fine=4, wrap=None, tr
     \\dot h, \\dot v, \\dot \\psi (track_rows); static = {1-based variable id: array [n] or scalar}: the values of the variables the tracks
     do not give (G, A), without which their bins are bad.  unit_ratios: (ur_speed, ur_vertrate, ur_heading) of sample2track.m:113-123.
     Equals track_values_host followed by discretize_count_host.  Returns discretize_count_host's dict, `values_kernel` the first kernel's."""
-    xyz = np.ascontiguousarray(xyz, dtype=np.float64)
-    if xyz.ndim != 3 or xyz.shape[2] != 3:
-        raise ValueError("xyz must be [n, points, 3]")
-    n, P = int(xyz.shape[0]), int(xyz.shape[1])
+    xyz, n, P = _track_array(xyz)
     T, ni, nd = P - 2, model.n_initial, model.n_dyn
     G4 = (max(T, 0) + 3) // 4
     r0, slots = track_rows(model, rows)
     es, dt = (8, np.float64) if value_type == L.VALUE_F64 else (4, np.float32)
     iv = np.zeros((ni, n), dtype=dt)
     _fill_static(iv, static, [r for r in r0 if r >= 0])
-    ci, ct = _counts_arrays(model, None)
-    rc = np.zeros(2 * ni, dtype=np.uint64)
-    sizes = [("xyz", xyz.nbytes), ("init_val", iv.nbytes), ("dyn_val", 4 * es * G4 * nd * n), ("init_bin", ni * n), ("dyn_bin", 4 * G4 * nd * n),
-             ("ci", 8 * ci.size), ("ct", 8 * ct.size), ("rc", rc.nbytes)]
-    off, o = {}, 0
-    for name, b in sizes:
-        off[name] = o
-        o += (b + 255) // 256 * 256
     p = track_values_params(n, P, *unit_ratios, n_initial=ni, nd=nd, rows=r0, slots=slots, value_type=value_type, layout=L.TRACKS_ROWS)
-    base = ctx.device_alloc(max(o, 256))
-    try:
-        at = {k: base + v for k, v in off.items()}
-        for name, a in (("xyz", xyz), ("init_val", iv), ("ci", ci), ("ct", ct), ("rc", rc)):
+    with _device_arrays(ctx, xyz=xyz.nbytes, init_val=iv.nbytes, dyn_val=4 * es * G4 * nd * n, **_discretize_count_bytes(model, n, T, True)) as at:
+        for name, a in (("xyz", xyz), ("init_val", iv)):
             if a.size:
                 device_upload(ctx, at[name], a)
         if nd > 3 and n:   # dynamic variables the tracks do not give: zeros, as track_values_host leaves them
             device_upload(ctx, at["dyn_val"], np.zeros(4 * G4 * nd * n, dtype=dt))
         track_values_device(ctx, p, at["xyz"], at["init_val"], at["dyn_val"])
-        values_kernel = ctx.last_kernel()
-        discretize_dbn_device(ctx, model, discretize_params(n, T, n_fine, value_type, wrap), at["init_val"], at["dyn_val"], at["init_bin"],
-                              at["dyn_bin"], at["rc"] if n_fine else 0, at["rc"] + 8 * ni if n_fine else 0)
-        kernel = ctx.last_kernel()
-        transitions = T > 1
-        count_dbn_device(ctx, model, score_params(n, T, transition_mode), at["init_bin"], at["dyn_bin"] if transitions else 0,
-                         at["ci"], at["ct"] if transitions else 0)
-        count_kernel = ctx.last_kernel()
-        ctx.sync()                                  # the launches' deferred errors
-        for name, a in (("ci", ci), ("ct", ct), ("rc", rc)):
-            if a.size:
-                device_download(ctx, at[name], a)
-    finally:
-        ctx.device_free(base)
-    Ni, Nt = split_counts(model, (ci, ct))
-    rep, chg = rc[:ni].copy(), rc[ni:].copy()
-    return {"N_initial": Ni, "N_transition": Nt, "raw": (ci, ct), "repeat": rep.astype(np.float64), "change": chg.astype(np.float64),
-            "raw_pairs": (rep, chg), "kernel": kernel, "count_kernel": count_kernel, "values_kernel": values_kernel}
+        return _discretize_count_in_block(ctx, model, at, n, T, n_fine, value_type, wrap, transition_mode, True, values_kernel=ctx.last_kernel())
 
 
 def device_upload(ctx, addr, src):

@@ -193,6 +193,7 @@ def _mixed_launch(gpu_ctx, pairs, blocks, lo, n_total, T):
     dv = torch.zeros((G4, nd, ld, 4), dtype=torch.float32, device=dev)
     at = torch.zeros((ld,), dtype=torch.int32, device=dev)
     p, _keep = native.make_params(n_total, T, SEED, first_index=FIRST + lo, **uncor_indices(pairs[0][1]))
+    torch.cuda.synchronize()      # the zero fills run on torch's stream, the launch on the ctx's own non-blocking one
     native.sample_dbn_blocks_device(gpu_ctx, [pr[0] for pr in pairs], p, blocks, init_bin=ib.data_ptr(), init_val=iv.data_ptr(),
                                     dyn_bin=db.data_ptr(), dyn_val=dv.data_ptr(), attempts=at.data_ptr(), ld=ld, col_offset=lo)
     gpu_ctx.sync()
