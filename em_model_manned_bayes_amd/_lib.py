@@ -194,6 +194,7 @@ SYMBOLS = [
     "emgpu_count_layout", "emgpu_count_dbn_device", "emgpu_count_dbn_host",
     "emgpu_discretize_dbn_device", "emgpu_discretize_dbn_host",
     "emgpu_track_values_device", "emgpu_track_values_host",
+    "emgpu_count_dbn_weighted_device", "emgpu_count_dbn_weighted_host",
 ]
 
 _lib = None
@@ -379,6 +380,8 @@ def lib():
     L.emgpu_count_layout.argtypes = [C.c_void_p, C.c_int32, C.c_void_p]
     for f in (L.emgpu_count_dbn_device, L.emgpu_count_dbn_host):
         f.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(ScoreParams)] + [C.c_void_p] * 4
+    for f in (L.emgpu_count_dbn_weighted_device, L.emgpu_count_dbn_weighted_host):
+        f.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(ScoreParams)] + [C.c_void_p] * 5
     for f in (L.emgpu_discretize_dbn_device, L.emgpu_discretize_dbn_host):
         f.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(DiscretizeParams)] + [C.c_void_p] * 6
     for f in (L.emgpu_track_values_device, L.emgpu_track_values_host):

@@ -35,6 +35,20 @@ struct EmgpuCountRun {
     uint32_t d_nmask[EMGPU_MAX_ND];  // rows whose (t+1) node is a parent of row k, and k itself
 };
 
+// The weighted count (emgpu_kernels_wcount.hip): every observation of trajectory i adds weights[i], an exact u64 addition; a
+// trajectory of weight 0 adds nothing and reports nothing, whatever its bins hold.  The partials are u64 (ds_add_u64), so the same LDS bytes
+// hold half the cells; C.i_lds / C.d_lds / C.lds_used are assigned under that cap (fill_count).  EMGPU_COUNT_WG_TRAJ keeps a u64 partial from
+// wrapping as well: 65536 trajectories * 65534 seconds * (2^32 - 1) < 2^64.  One call takes n * max(1, T-1) <= 2^32 (the entry points
+// refuse more), so no cell of the caller's tables can wrap within a call: 2^32 * (2^32 - 1) < 2^64.
+#ifndef EMGPU_WCOUNT_LDS_CELLS
+#define EMGPU_WCOUNT_LDS_CELLS 4096   // u64 partial counts (32 KB); tools/wcount_time.py times the -DEMGPU_WCOUNT_LDS_CELLS=8192 variant against it
+#endif
+struct EmgpuWCountRun {
+    EmgpuCountRun C;
+    const uint32_t *weights;         // [n], one per trajectory of the window: not offset by col_offset
+};
+
 namespace emgpu {
 hipError_t launch_count_dbn(const EmgpuCountRun &A, bool per_step, hipStream_t s, const char **name);
+hipError_t launch_count_dbn_weighted(const EmgpuWCountRun &A, bool per_step, hipStream_t s, const char **name);
 }

@@ -321,15 +321,22 @@ class EncounterModel:
         T = 1 if dyn_bin is None else int(np.asarray(dyn_bin).shape[1])
         return native.score_dbn_host(ctx, self.native, init_bin, dyn_bin, T, transition_mode)["log_lik"]
 
-    def count(self, init_bin, dyn_bin=None, transition_mode=L.TRANSITION_REFERENCE_AUTO, ctx=None):
+    def count(self, init_bin, dyn_bin=None, transition_mode=L.TRANSITION_REFERENCE_AUTO, ctx=None, weights=None):
         """The sufficient statistics of bins in the shapes native.sample_dbn_host returns (init_bin [n, n_initial], dyn_bin [n, T, n_dyn];
         None: the initial network alone, N_transition all zero): how often every cell of this model's graph was observed, counted on the
         GPU.  Returns (N_initial, N_transition, None, None), the argument order of setParameters, so m.setParameters(*m.count(ib, db))
         makes the trace the model.  all_repeat and all_change are None: they describe continuous values inside a bin, which a bin trace
-        does not carry (updateResampleRates tolerates None).  An observation that reads a bin outside 1..r raises EmgpuError(ERR_ARG)."""
+        does not carry (updateResampleRates tolerates None).  An observation that reads a bin outside 1..r raises EmgpuError(ERR_ARG).
+        weights: an integer array [n] in 0 .. 2**32 - 1 (native.quantize_weights makes one from log-weights); every observation of
+        trajectory i then adds weights[i] (native.count_dbn_weighted_host), and a trajectory of weight 0 is left out whatever its bins hold.
+        m.setParameters(*m.count(ib, db, weights=w)) makes the reweighted trace the model, up to the common factor exp(log_scale), which no
+        column's normalisation sees.  None: the unweighted count."""
         ctx = ctx or native.default_context()
         T = 1 if dyn_bin is None else int(np.asarray(dyn_bin).shape[1])
-        got = native.count_dbn_host(ctx, self.native, init_bin, dyn_bin, T, transition_mode)
+        if weights is not None:
+            got = native.count_dbn_weighted_host(ctx, self.native, init_bin, dyn_bin, T, weights, transition_mode)
+        else:
+            got = native.count_dbn_host(ctx, self.native, init_bin, dyn_bin, T, transition_mode)
         return got["N_initial"], got["N_transition"], None, None
 
     def count_values(self, init_val, dyn_val=None, n_fine=4, wrap=None, transition_mode=L.TRANSITION_REFERENCE_AUTO, ctx=None):

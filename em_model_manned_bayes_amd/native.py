@@ -787,6 +787,120 @@ def sample_count_host(ctx, model, n, T, seed, transition_mode=L.TRANSITION_REFER
     return _counts_result(model, ci, ct, kernel=kernel, count_kernel=count_kernel)
 
 
+def count_dbn_weighted_device(ctx, model, params, init_bin, dyn_bin, weights, counts_initial=0, counts_transition=0):
+    """emgpu_count_dbn_weighted_device: count_dbn_device in which every observation of trajectory i adds weights[i] -- a device array of
+    params.n uint32, not offset by col_offset -- instead of 1.  A trajectory of weight 0 adds nothing and reports nothing, whatever its bins
+    hold.  One call takes n * max(1, sample_time - 1) <= 2**32."""
+    L.check(L.lib().emgpu_count_dbn_weighted_device(ctx._h, model._h, C.byref(params), C.c_void_p(init_bin or None), C.c_void_p(dyn_bin or None),
+                                                    C.c_void_p(weights or None), C.c_void_p(counts_initial or None),
+                                                    C.c_void_p(counts_transition or None)))
+
+
+def _weights_array(weights, n):
+    """a call's weights as contiguous uint32 [n]: an integer array of that shape with values in 0 .. 2**32 - 1, or ValueError"""
+    w = np.asarray(weights)
+    if w.dtype.kind not in "iu" or w.shape != (int(n),):
+        raise ValueError("weights must be an integer array [n], one entry per trajectory (quantize_weights makes one from log-weights)")
+    if w.size and (int(w.min()) < 0 or int(w.max()) > 2**32 - 1):
+        raise ValueError("weights must lie in 0 .. 2**32 - 1")
+    return np.ascontiguousarray(w, dtype=np.uint32)
+
+
+def count_dbn_weighted_host(ctx, model, init_bin, dyn_bin, T, weights, transition_mode=L.TRANSITION_REFERENCE_AUTO, raw=False, n=None,
+                            col_offset=0, counts=None):
+    """count_dbn_host in which every observation of trajectory i adds weights[i] instead of 1 (emgpu_count_dbn_weighted_host; include/emgpu.h):
+    the importance-weighted sufficient statistics of a trace, and, with weights in {0, 1}, the count of a subset.  weights: an integer array
+    [n] with values in 0 .. 2**32 - 1, entry i for trajectory col_offset + i of a raw trace (ValueError otherwise, before the library is
+    called).  A trajectory of weight 0 adds nothing and reports nothing, whatever its bins hold.  Returns count_dbn_host's dict; the tables are
+    exact integers (float64 N_initial / N_transition: exact below 2**53, `raw` always)."""
+    ib, db, ld, n = _bin_arrays(model, init_bin, dyn_bin, T, raw, n, col_offset)
+    w = _weights_array(weights, n)
+    ci, ct = _counts_arrays(model, counts)
+    p = score_params(n, T, transition_mode, ld, col_offset)
+    transitions = db is not None and int(T) > 1 and model.n_dyn > 0
+    rc = L.lib().emgpu_count_dbn_weighted_host(ctx._h, model._h, C.byref(p), _p(ib), _p(db), _p(w), _p(ci), _p(ct) if transitions else None)
+    out = _counts_result(model, ci, ct, kernel=ctx.last_kernel())
+    if rc < 0:
+        _raise(rc, counts=out)
+    return out
+
+
+def quantize_weights(log_w, bits=24, keep=None):
+    """Log-weights -> (w uint32 [n], log_scale): the integer weights count_dbn_weighted_* take, so that the real weight of trajectory i is
+    w[i] * exp(log_scale).  The live entries are the finite log_w[i] (with keep[i] true where keep is given); m is their maximum,
+    w = rint(exp(log_w - m) * (2**bits - 1)) for them (ties to even; the largest weight becomes 2**bits - 1) and 0 for every other entry:
+    NaN (a trajectory whose scoring reported a bad bin), -inf, and entries not kept.  log_scale = m - log(2**bits - 1); with no live entry w
+    is all zeros and log_scale is -inf.  +inf anywhere is a ValueError, and so is bits outside 1 .. 32.  Pure numpy."""
+    bits = int(bits)
+    if not 1 <= bits <= 32:
+        raise ValueError("quantize_weights: bits must lie in 1 .. 32")
+    lw = np.asarray(log_w, dtype=np.float64).reshape(-1)
+    if np.isposinf(lw).any():
+        raise ValueError("quantize_weights: a log-weight of +inf has no finite scale")
+    live = np.isfinite(lw)
+    if keep is not None:
+        keep = np.asarray(keep, dtype=bool).reshape(-1)
+        if keep.shape != lw.shape:
+            raise ValueError("quantize_weights: keep must have one entry per log-weight")
+        live &= keep
+    w = np.zeros(lw.shape, dtype=np.uint32)
+    if not live.any():
+        return w, float("-inf")
+    m = float(lw[live].max())
+    top = float(2**bits - 1)
+    w[live] = np.rint(np.exp(lw[live] - m) * top).astype(np.uint64).astype(np.uint32)
+    return w, m - float(np.log(top))
+
+
+def reweight_count_host(ctx, proposal, target, n, T, seed, bits=24, transition_mode=L.TRANSITION_REFERENCE_AUTO, first_index=0, counts=None):
+    """The importance-weighted sufficient statistics of a sample without the trace crossing PCIe: draw n trajectories of T
+    seconds under `proposal` into a device block, score the trace under both models where it lies, download the two log_lik arrays (16
+    bytes per trajectory), quantize log_lik_target - log_lik_proposal on the host (quantize_weights, `bits`), upload the weights (4 bytes
+    per trajectory), count the trace with them where it lies (emgpu_count_dbn_weighted_device, in `proposal`'s tables: both models have one
+    shape) and download the tables.  Equals sample_weighted_host, quantize_weights and count_dbn_weighted_host in a row.
+    Returns count_dbn_host's dict plus weights [n] uint32, log_scale (the real weight of trajectory i is weights[i] * exp(log_scale)),
+    ess = (sum w)**2 / sum w**2 (0.0 when every weight is 0), log_lik_proposal, log_lik_target, kernel (the sampler's), score_kernel and
+    count_kernel.  ValueError when the models differ in shape (sample_weighted_host's check)."""
+    if not _same_shape(proposal, target):
+        raise ValueError("reweight_count_host: proposal and target differ in n_initial, r_initial, the temporal map or the dynamic variables' r")
+    ni, nd, T, n = proposal.n_initial, proposal.n_dyn, int(T), int(n)
+    G4 = (T + 3) // 4
+    ci, ct = _counts_arrays(proposal, counts)
+    with _device_arrays(ctx, init_bin=ni * n, init_val=4 * ni * n, dyn_bin=4 * G4 * nd * n, dyn_val=16 * G4 * nd * n, attempts=4 * n,
+                        ll_p=8 * n, ll_t=8 * n, w=4 * n, ci=8 * ci.size, ct=8 * ct.size) as at:
+        for name, a in (("ci", ci), ("ct", ct)):
+            if a.size:
+                device_upload(ctx, at[name], np.zeros_like(a))
+        p, keep = make_params(n, T, seed, first_index=first_index, transition_mode=transition_mode)
+        dense = nd > 0
+        sample_dbn_device(ctx, proposal, p, init_bin=at["init_bin"], init_val=at["init_val"], dyn_bin=at["dyn_bin"] if dense else 0,
+                          dyn_val=at["dyn_val"] if dense else 0, attempts=at["attempts"])
+        kernel = ctx.last_kernel()
+        sp = score_params(n, T, p.transition_mode)
+        score_dbn_device(ctx, proposal, sp, at["init_bin"], at["dyn_bin"] if dense else 0, at["ll_p"])
+        score_dbn_device(ctx, target, sp, at["init_bin"], at["dyn_bin"] if dense else 0, at["ll_t"])
+        score_kernel = ctx.last_kernel()
+        ctx.sync()                                  # the three launches' deferred errors
+        ll_p = device_download(ctx, at["ll_p"], np.zeros(n, np.float64))
+        ll_t = device_download(ctx, at["ll_t"], np.zeros(n, np.float64))
+        w, log_scale = quantize_weights(ll_t - ll_p, bits)
+        transitions = dense and T > 1
+        count_kernel = ""
+        if n > 0:
+            device_upload(ctx, at["w"], w)
+            count_dbn_weighted_device(ctx, proposal, sp, at["init_bin"], at["dyn_bin"] if transitions else 0, at["w"],
+                                      at["ci"], at["ct"] if transitions else 0)
+            count_kernel = ctx.last_kernel()
+            ctx.sync()
+            for name, a in (("ci", ci), ("ct", ct)):
+                if a.size:
+                    a += device_download(ctx, at[name], np.zeros_like(a))
+    del keep
+    s1, s2 = float(w.astype(np.float64).sum()), float((w.astype(np.float64) ** 2).sum())
+    return _counts_result(proposal, ci, ct, weights=w, log_scale=log_scale, ess=s1 * s1 / s2 if s2 > 0 else 0.0, log_lik_proposal=ll_p,
+                          log_lik_target=ll_t, kernel=kernel, score_kernel=score_kernel, count_kernel=count_kernel)
+
+
 def pack_dyn_val(dv):
     """[n, T, nd] f32 or f64 -> [G4][nd][n][4] of the same dtype (the inverse of unpack_dyn_val; padding columns are 0)."""
     dv = np.asarray(dv)

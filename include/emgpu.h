@@ -448,6 +448,26 @@ int emgpu_count_dbn_host(emgpu_ctx *ctx, const emgpu_model *m, const emgpu_score
                          uint64_t *counts_initial, uint64_t *counts_transition);
 
 /* ------------------------------------------------------------------------------------------------
+ * Counting a trace with integer weights (importance-weighted N).  Everything not restated here is the unweighted count's:
+ * the observations, the parent bins per transition mode, the layout of emgpu_count_layout, accumulation, NULL counts pointers.
+ *   weights   const uint32_t[n], one entry per trajectory of the window; NOT offset by col_offset (like log_lik).  _device: a device
+ *             pointer, _host: a host pointer.  NULL is EMGPU_ERR_ARG: the unweighted call exists for that.
+ *   adds      every observation of trajectory i adds weights[i] to its cell, an exact uint64 addition: the result does not depend on the
+ *             order of the adds (no float atomics anywhere).
+ *   weight 0  the trajectory adds nothing and reports nothing.  Its bins may hold anything, bins outside 1..r included: it never raises
+ *             the bad-bin report.  A weight of 0 is the mask that leaves a trajectory of a device-resident trace out.
+ *   weight >0 the unweighted rules: an observation that reads a bin outside 1..r is skipped, the others count, and the call reports
+ *             EMGPU_ERR_ARG through the same word and protocol (_host by its return value, _device at the next emgpu_ctx_sync).
+ *   bounds    no load or store leaves the buffers, whatever the bins and weights are.
+ *   one call  n * max(1, sample_time - 1) > 2^32 is refused with EMGPU_ERR_ARG (split the call): below that bound no cell can wrap within a
+ *             call, because 2^32 * (2^32 - 1) < 2^64.  Accumulating over several calls stays the caller's business.
+ * All argument checks come before any device work.  Weights come from log-weights by a host-side quantization (native.quantize_weights). */
+int emgpu_count_dbn_weighted_device(emgpu_ctx *ctx, const emgpu_model *m, const emgpu_score_params *p, const uint8_t *init_bin,
+                                    const uint32_t *dyn_bin, const uint32_t *weights, uint64_t *counts_initial, uint64_t *counts_transition);
+int emgpu_count_dbn_weighted_host(emgpu_ctx *ctx, const emgpu_model *m, const emgpu_score_params *p, const uint8_t *init_bin,
+                                  const uint32_t *dyn_bin, const uint32_t *weights, uint64_t *counts_initial, uint64_t *counts_transition);
+
+/* ------------------------------------------------------------------------------------------------
  * Discretizing a trace: VALUES in the layout of emgpu_sample_out (init_val [n_initial][ld], dyn_val [G4][n_dyn][ld][4]) into the BINS
  * emgpu_score_dbn_* and emgpu_count_dbn_* take (init_bin u8 [n_initial][ld]; dyn_bin u32 [G4][n_dyn][ld], byte c % 4 of word c / 4 = column
  * c), and the repeat / change counts behind a model's resample rates: the training side's discretize_bayes.m, hierarchical_cutpoints.m and
