@@ -85,6 +85,37 @@ __device__ __forceinline__ uint32_t wave_inclusive_add(uint32_t x) {
     return x;
 }
 
+// LDS addresses as 32-bit integers: the worker reaches four places of its request's owner (the kind word, the bin byte, the result slot of
+// the owner's row, attempt[owner]) from ONE computed row address.  Left as array indexing the row address was put together again for each.
+template <class T>
+__device__ __forceinline__ uint32_t lds_addr(const T *p) { return (uint32_t)(uintptr_t)(const __attribute__((address_space(3))) T *)p; }
+template <class T>
+__device__ __forceinline__ __attribute__((address_space(3))) T *lds_at(uint32_t a) { return (__attribute__((address_space(3))) T *)(uintptr_t)a; }
+
+// The boundaries of the dynamic variables as the workers read them: entry 16 k + b (b = bin - 1) holds {a_b, (a_{b+1} - a_b) * 2^-32}, one
+// 16-byte LDS read per draw.  dediscretize.m:39 is a + (b - a) * u with u = (x' + 0.5) * 2^-32 (exact in f64); (b - a) * 2^-32 is exact
+// too unless it is subnormal (a model with such a pair is refused when its plan is built: dedisc_scalable in emgpu_model.cpp), so
+// d32 * (x' + 0.5) rounds the same real number as (b - a) * u, and the sum after it is the oracle's.
+struct BndScaled { double a, d32; };
+__device__ __forceinline__ BndScaled bnd_scaled(double a, double b) {
+    const double dd = b - a;
+    return BndScaled{a, dd * (1.0 / 4294967296.0)};
+}
+// k8 = 8 * variable, b1 = the 1-based bin
+__device__ __forceinline__ double dedisc_draw(const BndScaled *tab, uint32_t k8, uint32_t b1, uint32_t x) {
+#pragma clang fp contract(off)
+    const BndScaled e = tab[2u * k8 + b1 - 1u];
+    const double xh = (double)clamp32(x) + 0.5;
+    const double mm = e.d32 * xh;
+    return e.a + mm;
+}
+// The table a kernel hands to coop_dedisc chooses the form of the whole cooperative pass: a BndScaled table the trimmed one (the dense
+// forms of the fast kernel: k_uncor_fast, _idx, _mixed and their +start twins), the plain double[ND][16] the form as it was -- the
+// event-list forms of the fast kernel, k_dbn_step2 and k_dbn_step keep it: with the trimmed pass k_uncor_fast_evw<9,6,6,6> lost its
+// fourth wave and three instances (k_uncor_fast_ev<7,4,6,4>, k_dbn_step2<16,4> with the per-lane row loop) gained scratch.
+template <class BT>
+struct CoopTrim { static constexpr bool value = std::is_convertible<BT, const BndScaled *>::value; };
+
 // One worker pass: lanes 0..cnt-1 each serve the request queue[q0 + lane].  A request is owner | sb << 6 (sb = the
 // bit of the owner's need mask); with LB the worker reads the owner's bin and kind word from the owner's LDS row,
 // without it the owner encoded them (kind << 11, bin << 12).
@@ -119,6 +150,40 @@ __device__ __forceinline__ void coop_worker_pass(CoopLds<ND, LB> &W, int lane, u
         W.res[owner * L::kStride + s] = (float)v;
     }
 }
+// ... and its trimmed form: one owner-row address for the kind word, the bin byte and the result slot, fields taken with v_bfe_u32, the
+// section as RES + kind, one 16-byte read of the scaled table
+template <int ND, bool MSBFIRST, bool LB, bool IDX = false>
+__device__ __forceinline__ void coop_worker_pass(CoopLds<ND, LB> &W, int lane, uint32_t q0, uint32_t cnt, uint64_t gidx, const Rng &rng, int g8,
+                                                 uint32_t ivpack, const BndScaled *s_bnd) {
+    using L = CoopLds<ND, LB>;
+    static_assert(EMGPU_SEC_DEDISC_TRANS == EMGPU_SEC_DEDISC_RES + 1u, "the kind bit is added to the section");
+    const uint32_t q = q0 + (uint32_t)lane;
+    if (q < cnt) {
+        const uint32_t d = W.queue[q];
+        const uint32_t owner = d & 63u, sb = (d >> 6) & 31u;
+        const uint32_t s = MSBFIRST ? (sb ^ 7u) : sb;
+        // the owner's row, computed once (two instructions with inline constants: a multiply-add would take the stride from a scalar register,
+        // and so would the masks of shift-and-mask field extractions below: this loop has no scalar register to spare, HISTORY.md section 14)
+        uint32_t orow = owner * (uint32_t)L::kStride;
+        asm("" : "+v"(orow));
+        orow = lds_addr(W.res) + 4u * orow;
+        asm("" : "+v"(orow));
+        const uint32_t kind = LB ? __builtin_amdgcn_ubfe(*lds_at<const uint32_t>(orow + L::kKind * 4u), sb, 1u) : ((d >> 11) & 1u);
+        uint32_t b1 = LB ? *lds_at<const uint8_t>(orow + L::kBins * 4u + s) : ((d >> 12) & 63u);
+        asm("" : "+v"(b1));   // (a byte as loaded: no mask where it is used, a basic block later)
+        const uint32_t k8 = (d >> 6) & 24u;   // 8 * variable: the byte order within a variable's stream leaves bits 3-4 alone
+        uint64_t go = gidx - (uint64_t)lane + (uint64_t)owner;
+        if constexpr (LB && IDX) go = *lds_at<const uint64_t>(orow + L::kGidx * 4u);   // an index list may be in use (coop_publish_gidx)
+        const uint32_t iv = __builtin_amdgcn_ubfe(ivpack, k8, 8u);
+        const uint32_t att = *lds_at<const uint32_t>(lds_addr(W.attempt) + 4u * owner);
+        const uint32_t j = s & 7u, jhi = __builtin_amdgcn_ubfe(s, 2u, 1u);   // second of the block; which of its two Philox calls
+        const uint4 r4 = philox4x32((uint32_t)go, (uint32_t)(go >> 32), att,
+                                       (((EMGPU_SEC_DEDISC_RES << 28) | (uint32_t)(2 * g8)) + (kind << 28)) | ((iv << 20) | jhi), rng.k0, rng.k1);
+        const uint32_t w = j & 3u;
+        const uint32_t x = w == 0 ? r4.x : (w == 1 ? r4.y : (w == 2 ? r4.z : r4.w));
+        *lds_at<float>(orow + 4u * s) = (float)dedisc_draw(s_bnd, k8, b1, x);
+    }
+}
 
 // needmask / kindmask: bit (8k + j) for dynamic variable k, second j of the block; with MSBFIRST
 // the byte of a variable is an MSB-first stream instead: bit (8k + 7 - j).
@@ -128,10 +193,10 @@ __device__ __forceinline__ void coop_worker_pass(CoopLds<ND, LB> &W, int lane, u
 // lane then writes its own requests to consecutive slots (find-first-set, one LDS store, clear the bit: no ballot
 // or rank per request), kCap positions per round, and the workers serve exactly ceil(requests / 64) passes.
 // Without LB (k_dbn_step, the fallback kernel) the round-1 scheme stays: one ballot + rank per compaction step.
-template <int ND, bool MSBFIRST = false, bool LB = false, bool IDX = false>
+template <int ND, bool MSBFIRST = false, bool LB = false, bool IDX = false, class BT>
 __device__ __forceinline__ void coop_dedisc(CoopLds<ND, LB> &W, int lane, uint64_t gidx, const Rng &rng, int g8,
                                             uint32_t needmask, uint32_t kindmask, const uint32_t (&pbA)[ND], const uint32_t (&pbB)[ND],
-                                            const uint32_t (&ivar)[ND], const double (*s_bnd)[16]) {
+                                            const uint32_t (&ivar)[ND], BT s_bnd) {
     using L = CoopLds<ND, LB>;
     uint32_t ivpack = 0u; // wave-uniform byte table of the variables' RNG ids
 #pragma unroll
@@ -139,7 +204,9 @@ __device__ __forceinline__ void coop_dedisc(CoopLds<ND, LB> &W, int lane, uint64
     uint32_t m = needmask;
     if constexpr (LB) {
         if (__ballot(m != 0u) == 0ull) return;
-        const uint32_t c = (uint32_t)__popc(m);
+        uint32_t c = (uint32_t)__popc(m);
+        // the count on its own: folded into v_bcnt's addend, the first prefix step became two copies and the v_bcnt again
+        if constexpr (CoopTrim<BT>::value) asm("" : "+v"(c));
         const uint32_t inc = wave_inclusive_add(c);
         const uint32_t total = (uint32_t)__builtin_amdgcn_readlane((int)inc, 63);
         // byte positions of this lane's requests in the (virtual, unbounded) queue: [a, aend)
@@ -151,12 +218,24 @@ __device__ __forceinline__ void coop_dedisc(CoopLds<ND, LB> &W, int lane, uint64
         if (total <= (uint32_t)L::kCap) {
             // the usual case, one round: find-first-set, one LDS store, clear the bit
             EMGPU_COUNT(1, lane, 1);
-            typename L::Request *qp = reinterpret_cast<typename L::Request *>(reinterpret_cast<char *>(W.queue) + a);
-            while (__ballot(m != 0u) != 0ull) {
-                EMGPU_COUNT(2, lane, 1);
-                if (m != 0u) {
-                    *qp++ = (typename L::Request)((uint32_t)lane | (((uint32_t)__ffs((int)m) - 1u) << 6));
+            if constexpr (CoopTrim<BT>::value) {
+                // mask and pointer move in every lane (m &= m - 1 leaves 0 at 0, a lane that is done writes no more): only the store is
+                // predicated, and no value is carried round the loop through a copy
+                uint32_t qa = lds_addr(W.queue) + a;
+                while (__ballot(m != 0u) != 0ull) {
+                    EMGPU_COUNT(2, lane, 1);
+                    if (m != 0u) *lds_at<typename L::Request>(qa) = (typename L::Request)((uint32_t)lane | ((uint32_t)__builtin_ctz(m) << 6));
+                    qa += kReq;
                     m &= m - 1u;
+                }
+            } else {
+                typename L::Request *qp = reinterpret_cast<typename L::Request *>(reinterpret_cast<char *>(W.queue) + a);
+                while (__ballot(m != 0u) != 0ull) {
+                    EMGPU_COUNT(2, lane, 1);
+                    if (m != 0u) {
+                        *qp++ = (typename L::Request)((uint32_t)lane | (((uint32_t)__ffs((int)m) - 1u) << 6));
+                        m &= m - 1u;
+                    }
                 }
             }
             wave_sync();
@@ -382,11 +461,23 @@ __device__ __forceinline__ void coop_publish_gidx(CoopLds<ND, true> &W, int lane
 }
 
 // publish the packed bins of this lane's block for the workers (CoopLds<ND, true>)
-template <int ND>
+// W2: one two-word store per variable, the two words from wherever they are -- as 8- and 16-byte stores their operands were first
+// assembled with one register copy per word.  (LDS operations of a wave complete in order: a wait the compiler sets for an operation of
+// its own covers these too, and the workers read only after wave_sync.)  Part of the trimmed pass (CoopTrim): the other kernels keep the
+// vector stores -- k_uncor_fast_evw<9,6,6,6> has no register left for the difference (129 against 125, and 128 are its fourth wave).
+template <int ND, bool W2 = false>
 __device__ __forceinline__ void coop_publish_bins(CoopLds<ND, true> &W, int lane, const uint32_t (&pbA)[ND], const uint32_t (&pbB)[ND]) {
-    uint2 *bp = reinterpret_cast<uint2 *>(&W.res[lane * CoopLds<ND, true>::kStride + CoopLds<ND, true>::kBins]);
+    if constexpr (W2) {
+        const uint32_t bp = lds_addr(&W.res[lane * CoopLds<ND, true>::kStride]);
 #pragma unroll
-    for (int k = 0; k < ND; k++) bp[k] = make_uint2(pbA[k], pbB[k]);
+        for (int k = 0; k < ND; k++)
+            asm volatile("ds_write2_b32 %0, %1, %2 offset0:%3 offset1:%4"
+                         : : "v"(bp), "v"(pbA[k]), "v"(pbB[k]), "n"(CoopLds<ND, true>::kBins + 2 * k), "n"(CoopLds<ND, true>::kBins + 2 * k + 1) : "memory");
+    } else {
+        uint2 *bp = reinterpret_cast<uint2 *>(&W.res[lane * CoopLds<ND, true>::kStride + CoopLds<ND, true>::kBins]);
+#pragma unroll
+        for (int k = 0; k < ND; k++) bp[k] = make_uint2(pbA[k], pbB[k]);
+    }
 }
 
 // BOTH: dyn_bin and dyn_val are both there (the launch code checked): no null tests -- eight wave-uniform branches less per variable

@@ -518,6 +518,33 @@ __device__ __forceinline__ EvStream *evw_lds() {
     if constexpr (EVW != 0) { __shared__ EvStream s[16]; return s; }
     else return nullptr;
 }
+// The workers' boundary table, filled by the first 48 threads of the workgroup (visible after the caller's barrier).  TRIM: the scaled table
+// of the trimmed cooperative pass (emgpu_coop.h: BndScaled, CoopTrim), entry 16 k + q = boundary q of variable k and the scaled width of
+// the bin above it; else the plain one, for the event-list forms, which keep the pass as it was.
+template <bool TRIM>
+__device__ __forceinline__ auto fast_bnd_table(const EmgpuPlan &P, int tid) {
+    if constexpr (TRIM) {
+        __shared__ BndScaled s[3 * 16];
+#pragma unroll
+        for (int k = 0; k < 3; k++) // k stays a compile-time index into the plan (a per-lane index would force it into scratch)
+            if ((tid >> 4) == k) {
+                const int q = tid & 15;
+                const double a = (q < (int)P.d_nb[k]) ? P.bnd[P.d_boff[k] + q] : 0.0;
+                const double b = (q + 1 < (int)P.d_nb[k]) ? P.bnd[P.d_boff[k] + q + 1] : 0.0;   // (a bin is at most d_nb - 1 <= 15: entry 15 is never a bin's)
+                s[16 * k + q] = bnd_scaled(a, b);
+            }
+        return (const BndScaled *)s;
+    } else {
+        __shared__ double s[3][16];
+#pragma unroll
+        for (int k = 0; k < 3; k++)
+            if ((tid >> 4) == k) {
+                const int q = tid & 15;
+                s[k][q] = (q < (int)P.d_nb[k]) ? P.bnd[P.d_boff[k] + q] : 0.0;
+            }
+        return (const double (*)[16])s;
+    }
+}
 // The request queue of the rows-by-the-wave form: EVW 2 -- the cooperative dediscretize's own queue, idle in that form: 254 requests per
 // round, the workgroup stays within 40 KB of LDS (four per CU) and 128 registers (four waves per SIMD); EVW 3 -- 1 024 requests per round in
 // LDS of its own (three workgroups per CU), for lists of several hundred rows per wave and block (haa_v1: ~900), where 254 mean four rounds
@@ -538,7 +565,8 @@ __device__ __forceinline__ void uncor_fast_body(const EmgpuPlan &P, const EmgpuR
     // <7,4,6,6> instance too since the packed compare pass freed its registers
     constexpr bool LB = true;
     __shared__ CoopLds<3, LB> s_wave[4];
-    __shared__ double s_bnd[3][16];
+    // the dense forms run the trimmed cooperative pass; the event-list forms keep the pass as it was (emgpu_coop.h: CoopTrim says why)
+    constexpr bool TRIM = !EV;
     const int tid = threadIdx.x, lane = tid & 63;
     CoopLds<3, LB> &W = s_wave[tid >> 6];
     const int64_t i = i0 + tid;
@@ -550,12 +578,7 @@ __device__ __forceinline__ void uncor_fast_body(const EmgpuPlan &P, const EmgpuR
     }
     Rng rng{(uint32_t)gidx, (uint32_t)(gidx >> 32), 0u, (uint32_t)A.seed, (uint32_t)(A.seed >> 32)};
     const int T = A.T;
-#pragma unroll
-    for (int k = 0; k < 3; k++) // k stays a compile-time index into the plan (a per-lane index would force it into scratch)
-        if ((tid >> 4) == k) {
-            const int q = tid & 15;
-            s_bnd[k][q] = (q < (int)P.d_nb[k]) ? P.bnd[P.d_boff[k] + q] : 0.0;
-        }
+    const auto s_bnd = fast_bnd_table<TRIM>(P, tid);
 
     int bin[NI];
     double val[NI];
@@ -641,7 +664,13 @@ __device__ __forceinline__ void uncor_fast_body(const EmgpuPlan &P, const EmgpuR
         h_Rk[k] = U(F.Rk[k]); h_RR1[k] = U(F.RR1[k]); h_slot[k] = U(F.slot[k]);
         // each word in a scalar register of its own: as parts of the argument load's eight-register tuple they are spilled and reloaded together,
         // the hot words (RR1, slot) with the cold one (Rk), as soon as the loop runs short of scalar registers
-        asm("" : "+s"(h_Rk[k]), "+s"(h_RR1[k]), "+s"(h_slot[k]));
+        // (the dense forms: a copy and not an empty asm on the word in place -- tied to its input, the output was assigned the tuple's own
+        // register again, and the tuple was reloaded in the passes and at the stores; the event-list forms lose a register to the copies)
+        if constexpr (!EV) {
+            asm("s_mov_b32 %0, %1" : "=s"(h_Rk[k]) : "s"(h_Rk[k]));
+            asm("s_mov_b32 %0, %1" : "=s"(h_RR1[k]) : "s"(h_RR1[k]));
+            asm("s_mov_b32 %0, %1" : "=s"(h_slot[k]) : "s"(h_slot[k]));
+        } else asm("" : "+s"(h_Rk[k]), "+s"(h_RR1[k]), "+s"(h_slot[k]));
         const uint64_t a = (uint64_t)(P.cthr + P.d_coff[k]);
         h_ctab[k] = reinterpret_cast<const uint32_t *>(((uint64_t)U((uint32_t)(a >> 32)) << 32) | U((uint32_t)a));
     }
@@ -684,11 +713,11 @@ __device__ __forceinline__ void uncor_fast_body(const EmgpuPlan &P, const EmgpuR
         const uint32_t need24 = valid ? (need8[0] | (need8[1] << 8) | (need8[2] << 16)) : 0u;
         const uint32_t kind24 = kind8[0] | (kind8[1] << 8) | (kind8[2] << 16);
         if constexpr (EVW >= 2) {   // events only: no result slots, no fill -- every row is one request of the wave's queue
-            coop_publish_bins<3>(W, lane, pbA, pbB);
+            coop_publish_bins<3, TRIM>(W, lane, pbA, pbB);
             ev_rows_block_wide<3, EVW == 3 ? kEvRowsQueue<3> : kFastRowsQueue>(W, s_evq, lane, s_evw, P.nact, SW, rng, P.bnd, g8, T, valid, hit24, kind24, prevw, A, i);
         } else {
         coop_zero_results<3, LB>(W, lane);
-        if constexpr (LB) coop_publish_bins<3>(W, lane, pbA, pbB);
+        if constexpr (LB) coop_publish_bins<3, TRIM>(W, lane, pbA, pbB);
         coop_dedisc<3, true, LB, IDX>(W, lane, gidx, rng, g8, need24, kind24, pbA, pbB, ivs, s_bnd);   // dediscretize.m:39
         if (!EV || A.dyn_bin != nullptr || A.dyn_val != nullptr)   // (an event-list call without the dense trace: no forward fill at all)
 #pragma unroll

@@ -677,6 +677,14 @@ uint32_t bernoulli_threshold(double rate) {
     return lo;
 }
 
+// The fast kernels' workers dediscretize from {a, (b - a) * 2^-32} (BndScaled, emgpu_coop.h): a + d32 * (x' + 0.5) is dediscretize.m:39
+// to the bit as long as the scaling by 2^-32 is exact, i.e. the width is 0, or not below 2^-990 (the scaled width stays normal), or not
+// finite.  Decided here, once per model, for every variable: no kernel tests it.
+static bool dedisc_scalable(double a, double b) {
+    const double dd = b - a;
+    return dd == 0.0 || !(std::fabs(dd) < 0x1p-990);
+}
+
 CompiledPlan compile_plan(const Model &m) {
     CompiledPlan cp;
     EmgpuPlan &P = cp.plan;
@@ -697,6 +705,9 @@ CompiledPlan compile_plan(const Model &m) {
         if (m.boundaries[v].size() > 255) throw Error(EMGPU_ERR_UNSUPPORTED, "too many boundaries");
         if (!m.boundaries[v].empty() && (int)m.boundaries[v].size() < m.r_initial[v] + 1)
             throw Error(EMGPU_ERR_ARG, "boundaries shorter than r+1 (dediscretize.m:33-38 would fail)");
+        for (size_t q = 0; q + 1 < m.boundaries[v].size(); q++)
+            if (!dedisc_scalable(m.boundaries[v][q], m.boundaries[v][q + 1]))
+                throw Error(EMGPU_ERR_UNSUPPORTED, "two boundaries closer than 2^-990: the scaled bin width (b - a) * 2^-32 would be subnormal");
         cp.bnd.insert(cp.bnd.end(), m.boundaries[v].begin(), m.boundaries[v].end());
     }
     cp.bnd.push_back(0.0);
