@@ -1,6 +1,6 @@
 // emgpu_count.cpp -- emgpu_count_layout / emgpu_count_dbn_device / emgpu_count_dbn_host: the sufficient statistics of a trace (k_count_dbn,
 // emgpu_kernels_count.hip; the definition is in emgpu_count.h and DESIGN.md), and emgpu_count_dbn_weighted_device / _host: the same with a
-// u32 weight per trajectory (emgpu_kernels_wcount.hip).  The host entry points upload and count chunk by chunk
+// u32 weight per trajectory (the kernel's weighted instances).  The host entry points upload and count chunk by chunk
 // (emgpu_tracechunk.hpp) into device tables they keep across the chunks, and add them to the caller's once, at the end.
 #include <algorithm>
 #include <cstring>
@@ -79,61 +79,49 @@ bool fill_count(const Model &m, const EmgpuPlan &P, const emgpu_score_params *p,
     return per_step;
 }
 
-// the two launchers behind one signature: the weighted kernel when the call has weights (`weights` at the first trajectory of A.G)
-void launch_count(emgpu_ctx *ctx, const EmgpuCountRun &A, const uint32_t *weights, bool per_step) {
-    if (!weights) return launch_recorded(ctx, emgpu::launch_count_dbn, A, per_step);
-    EmgpuWCountRun W;
-    W.C = A; W.weights = weights;
-    launch_recorded(ctx, emgpu::launch_count_dbn_weighted, W, per_step);
-}
-const char *kernel_name(bool weighted, bool per_step) {
-    if (weighted) return per_step ? "k_count_dbn[per-step,weighted]" : "k_count_dbn[frozen,weighted]";
-    return per_step ? "k_count_dbn[per-step]" : "k_count_dbn[frozen]";
-}
+// a call's arrays as the caller passed them; weights: null in an unweighted call, else one per trajectory (the weighted instances)
+struct CountCall {
+    const emgpu_score_params *p;
+    const uint8_t *init_bin;
+    const uint32_t *dyn_bin, *weights;
+    uint64_t *counts_initial, *counts_transition;
+};
 
-int count_device(emgpu_ctx *ctx, const emgpu_model *h, const emgpu_score_params *p, const uint8_t *init_bin, const uint32_t *dyn_bin,
-                 bool weighted, const uint32_t *weights, uint64_t *counts_initial, uint64_t *counts_transition) {
-    if (const int rc = check_args(h, p, init_bin, dyn_bin, counts_initial, counts_transition, weighted, weights)) return rc;
-    CTX_ENTER(ctx);
-    Uploaded &u = get_uploaded(ctx, h);
-    EmgpuCountRun A;
-    const bool per_step = fill_count(h->m, u.cp.plan, p, counts_initial != nullptr, counts_transition != nullptr,
-                                     weighted ? EMGPU_WCOUNT_LDS_CELLS : EMGPU_COUNT_LDS_CELLS, A);
+// the caller's device arrays, counted where they are: one launch
+int count_device(emgpu_ctx *ctx, const emgpu_model *, const CountCall &c, EmgpuCountRun &A, bool per_step) {
+    const emgpu_score_params *p = c.p;
     const size_t off = (size_t)p->col_offset;
     A.G.n = p->n; A.G.ld = p->ld ? p->ld : p->n;
-    A.G.init_bin = init_bin ? init_bin + off : nullptr;
-    A.G.dyn_bin = dyn_bin && p->sample_time > 1 ? dyn_bin + off : nullptr;
+    A.G.init_bin = c.init_bin ? c.init_bin + off : nullptr;
+    A.G.dyn_bin = c.dyn_bin && p->sample_time > 1 ? c.dyn_bin + off : nullptr;
     A.G.bad = ctx->d_bad();
-    A.counts_i = (unsigned long long *)counts_initial; A.counts_t = (unsigned long long *)counts_transition;
-    ctx->last_launches = 0;
-    launch_count(ctx, A, weights, per_step);
+    A.counts_i = (unsigned long long *)c.counts_initial; A.counts_t = (unsigned long long *)c.counts_transition;
+    launch_recorded(ctx, emgpu::launch_count_dbn, A, c.weights, per_step);
     return EMGPU_OK;
 }
 
-int count_host(emgpu_ctx *ctx, const emgpu_model *h, const emgpu_score_params *p, const uint8_t *init_bin, const uint32_t *dyn_bin,
-               bool weighted, const uint32_t *weights, uint64_t *counts_initial, uint64_t *counts_transition) {
-    if (const int rc = check_args(h, p, init_bin, dyn_bin, counts_initial, counts_transition, weighted, weights)) return rc;
-    CTX_ENTER(ctx);
-    Uploaded &u = get_uploaded(ctx, h);
-    EmgpuCountRun A;
-    const bool per_step = fill_count(h->m, u.cp.plan, p, counts_initial != nullptr, counts_transition != nullptr,
-                                     weighted ? EMGPU_WCOUNT_LDS_CELLS : EMGPU_COUNT_LDS_CELLS, A);
-    ctx->last_launches = 0;
-    ctx->last_kernel = kernel_name(weighted, per_step);
+// the caller's host arrays: uploaded and counted chunk by chunk, one launch per chunk
+int count_host(emgpu_ctx *ctx, const emgpu_model *h, const CountCall &c, EmgpuCountRun &A, bool per_step) {
+    const emgpu_score_params *p = c.p;
+    const bool weighted = c.weights != nullptr;
+    // an empty call reports its kernel too: with no table to count into yet (fill_count) the launcher names the instance and launches nothing
+    const char *name = "";
+    (void)emgpu::launch_count_dbn(A, c.weights, per_step, ctx->stream, &name);
+    ctx->last_kernel = name;
     if (p->n == 0) return EMGPU_OK;
     const int64_t ld = p->ld ? p->ld : p->n;
-    const bool dyn = counts_transition && dyn_bin && p->sample_time > 1;
+    const bool dyn = c.counts_transition && c.dyn_bin && p->sample_time > 1;
     const size_t ni = (size_t)A.G.ni, rows_d = dyn ? (size_t)((p->sample_time + 3) / 4) * (size_t)A.G.nd : 0;
     // the device tables of this call: the model's size, whatever n is
-    const size_t cells_i = counts_initial ? (size_t)layout(h->m, 0).back() : 0, cells_t = counts_transition ? (size_t)layout(h->m, 1).back() : 0;
+    const size_t cells_i = c.counts_initial ? (size_t)layout(h->m, 0).back() : 0, cells_t = c.counts_transition ? (size_t)layout(h->m, 1).back() : 0;
     CallBuffers B(ctx);
     uint64_t *d_counts = B.alloc<uint64_t>((cells_i + cells_t + 1) * sizeof(uint64_t));
     HIP_OK(hipMemsetAsync(d_counts, 0, (cells_i + cells_t + 1) * sizeof(uint64_t), ctx->stream));
-    A.counts_i = counts_initial ? (unsigned long long *)d_counts : nullptr;
-    A.counts_t = counts_transition ? (unsigned long long *)(d_counts + cells_i) : nullptr;
+    A.counts_i = c.counts_initial ? (unsigned long long *)d_counts : nullptr;
+    A.counts_t = c.counts_transition ? (unsigned long long *)(d_counts + cells_i) : nullptr;
     enum { INIT, DYN, WEIGHT };   // the chunk's arrays: the bins as the kernel reads them, and a weighted call's 4 bytes per lane
     ChunkBlock blk(ctx, weighted ? "emgpu_count_dbn_weighted_host" : "emgpu_count_dbn_host", p->n, {{1, ni}, {4, rows_d}, {4, weighted ? 1u : 0u}});
-    const size_t c = (size_t)blk.c();
+    const size_t cl = (size_t)blk.c();
     A.G.ld = blk.c();
     A.G.init_bin = (const uint8_t *)blk.at(INIT);
     A.G.dyn_bin = rows_d ? (const uint32_t *)blk.at(DYN) : nullptr;
@@ -141,19 +129,31 @@ int count_host(emgpu_ctx *ctx, const emgpu_model *h, const emgpu_score_params *p
     BadWordScope bad(ctx);
     blk.each([&](int64_t c0, int64_t cn) {
         const size_t src = (size_t)(p->col_offset + c0);
-        HIP_OK(hipMemcpy2DAsync(blk.at(INIT), c, init_bin + src, (size_t)ld, (size_t)cn, ni, hipMemcpyHostToDevice, ctx->stream));
-        if (rows_d) HIP_OK(hipMemcpy2DAsync(blk.at(DYN), 4 * c, dyn_bin + src, 4 * (size_t)ld, 4 * (size_t)cn, rows_d, hipMemcpyHostToDevice, ctx->stream));
-        if (weighted) HIP_OK(hipMemcpyAsync(blk.at(WEIGHT), weights + c0, 4 * (size_t)cn, hipMemcpyHostToDevice, ctx->stream));   // not offset by col_offset
+        HIP_OK(hipMemcpy2DAsync(blk.at(INIT), cl, c.init_bin + src, (size_t)ld, (size_t)cn, ni, hipMemcpyHostToDevice, ctx->stream));
+        if (rows_d) HIP_OK(hipMemcpy2DAsync(blk.at(DYN), 4 * cl, c.dyn_bin + src, 4 * (size_t)ld, 4 * (size_t)cn, rows_d, hipMemcpyHostToDevice, ctx->stream));
+        if (weighted) HIP_OK(hipMemcpyAsync(blk.at(WEIGHT), c.weights + c0, 4 * (size_t)cn, hipMemcpyHostToDevice, ctx->stream));   // not offset by col_offset
         A.G.n = cn;
-        launch_count(ctx, A, weighted ? (const uint32_t *)blk.at(WEIGHT) : nullptr, per_step);
+        launch_recorded(ctx, emgpu::launch_count_dbn, A, weighted ? (const uint32_t *)blk.at(WEIGHT) : nullptr, per_step);
     });
     std::vector<uint64_t> got(cells_i + cells_t);
     B.down(got.data(), d_counts, got.size() * sizeof(uint64_t));
     const bool reported = bad.finish();
-    for (size_t j = 0; j < cells_i; j++) counts_initial[j] += got[j];
-    for (size_t j = 0; j < cells_t; j++) counts_transition[j] += got[cells_i + j];
+    for (size_t j = 0; j < cells_i; j++) c.counts_initial[j] += got[j];
+    for (size_t j = 0; j < cells_t; j++) c.counts_transition[j] += got[cells_i + j];
     if (reported) return fail(EMGPU_ERR_ARG, kCountBadBin);
     return EMGPU_OK;
+}
+
+// What every entry point opens with, then its path: the argument check, the context, the uploaded model, the argument block under the form's
+// cell cap (u64 partials hold half the cells) and a launch count of zero.  `weighted`: the entry point takes weights, which must be there.
+int count(decltype(count_device) *path, emgpu_ctx *ctx, const emgpu_model *h, bool weighted, const CountCall &c) {
+    if (const int rc = check_args(h, c.p, c.init_bin, c.dyn_bin, c.counts_initial, c.counts_transition, weighted, c.weights)) return rc;
+    CTX_ENTER(ctx);
+    EmgpuCountRun A;
+    const bool per_step = fill_count(h->m, get_uploaded(ctx, h).cp.plan, c.p, c.counts_initial != nullptr, c.counts_transition != nullptr,
+                                     weighted ? EMGPU_WCOUNT_LDS_CELLS : EMGPU_COUNT_LDS_CELLS, A);
+    ctx->last_launches = 0;
+    return path(ctx, h, c, A, per_step);
 }
 
 } // namespace
@@ -173,28 +173,28 @@ int emgpu_count_layout(const emgpu_model *h, int32_t network, int64_t *offsets) 
 int emgpu_count_dbn_device(emgpu_ctx *ctx, const emgpu_model *h, const emgpu_score_params *p, const uint8_t *init_bin, const uint32_t *dyn_bin,
                            uint64_t *counts_initial, uint64_t *counts_transition) {
     EMGPU_TRY
-    return count_device(ctx, h, p, init_bin, dyn_bin, false, nullptr, counts_initial, counts_transition);
+    return count(count_device, ctx, h, false, {p, init_bin, dyn_bin, nullptr, counts_initial, counts_transition});
     EMGPU_CATCH
 }
 
 int emgpu_count_dbn_host(emgpu_ctx *ctx, const emgpu_model *h, const emgpu_score_params *p, const uint8_t *init_bin, const uint32_t *dyn_bin,
                          uint64_t *counts_initial, uint64_t *counts_transition) {
     EMGPU_TRY
-    return count_host(ctx, h, p, init_bin, dyn_bin, false, nullptr, counts_initial, counts_transition);
+    return count(count_host, ctx, h, false, {p, init_bin, dyn_bin, nullptr, counts_initial, counts_transition});
     EMGPU_CATCH
 }
 
 int emgpu_count_dbn_weighted_device(emgpu_ctx *ctx, const emgpu_model *h, const emgpu_score_params *p, const uint8_t *init_bin,
                                     const uint32_t *dyn_bin, const uint32_t *weights, uint64_t *counts_initial, uint64_t *counts_transition) {
     EMGPU_TRY
-    return count_device(ctx, h, p, init_bin, dyn_bin, true, weights, counts_initial, counts_transition);
+    return count(count_device, ctx, h, true, {p, init_bin, dyn_bin, weights, counts_initial, counts_transition});
     EMGPU_CATCH
 }
 
 int emgpu_count_dbn_weighted_host(emgpu_ctx *ctx, const emgpu_model *h, const emgpu_score_params *p, const uint8_t *init_bin,
                                   const uint32_t *dyn_bin, const uint32_t *weights, uint64_t *counts_initial, uint64_t *counts_transition) {
     EMGPU_TRY
-    return count_host(ctx, h, p, init_bin, dyn_bin, true, weights, counts_initial, counts_transition);
+    return count(count_host, ctx, h, true, {p, init_bin, dyn_bin, weights, counts_initial, counts_transition});
     EMGPU_CATCH
 }
 

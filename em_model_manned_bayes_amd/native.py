@@ -746,11 +746,18 @@ def count_dbn_host(ctx, model, init_bin, dyn_bin, T, transition_mode=L.TRANSITIO
     Returns {"N_initial": [r x q float64 per variable], "N_transition": [per node, (0, 0) where no table], "raw": (u64 initial, u64
     transition), "kernel"}.  counts=<a previous result's raw> accumulates into those arrays.  dyn_bin None counts the initial network alone.
     A bin outside 1..r skips the observations that read it and raises EmgpuError(ERR_ARG) carrying .counts (the same dict)."""
+    return _count_host(ctx, model, init_bin, dyn_bin, T, None, transition_mode, raw, n, col_offset, counts)
+
+
+def _count_host(ctx, model, init_bin, dyn_bin, T, weights, transition_mode, raw, n, col_offset, counts):
+    """count_dbn_host (weights None) and count_dbn_weighted_host: the weights choose the entry point, which takes them before the counts"""
     ib, db, ld, n = _bin_arrays(model, init_bin, dyn_bin, T, raw, n, col_offset)
+    w = None if weights is None else _weights_array(weights, n)
     ci, ct = _counts_arrays(model, counts)
     p = score_params(n, T, transition_mode, ld, col_offset)
     transitions = db is not None and int(T) > 1 and model.n_dyn > 0
-    rc = L.lib().emgpu_count_dbn_host(ctx._h, model._h, C.byref(p), _p(ib), _p(db), _p(ci), _p(ct) if transitions else None)
+    entry, w_arg = (L.lib().emgpu_count_dbn_host, ()) if w is None else (L.lib().emgpu_count_dbn_weighted_host, (_p(w),))
+    rc = entry(ctx._h, model._h, C.byref(p), _p(ib), _p(db), *w_arg, _p(ci), _p(ct) if transitions else None)
     out = _counts_result(model, ci, ct, kernel=ctx.last_kernel())
     if rc < 0:
         _raise(rc, counts=out)
@@ -813,16 +820,8 @@ def count_dbn_weighted_host(ctx, model, init_bin, dyn_bin, T, weights, transitio
     [n] with values in 0 .. 2**32 - 1, entry i for trajectory col_offset + i of a raw trace (ValueError otherwise, before the library is
     called).  A trajectory of weight 0 adds nothing and reports nothing, whatever its bins hold.  Returns count_dbn_host's dict; the tables are
     exact integers (float64 N_initial / N_transition: exact below 2**53, `raw` always)."""
-    ib, db, ld, n = _bin_arrays(model, init_bin, dyn_bin, T, raw, n, col_offset)
-    w = _weights_array(weights, n)
-    ci, ct = _counts_arrays(model, counts)
-    p = score_params(n, T, transition_mode, ld, col_offset)
-    transitions = db is not None and int(T) > 1 and model.n_dyn > 0
-    rc = L.lib().emgpu_count_dbn_weighted_host(ctx._h, model._h, C.byref(p), _p(ib), _p(db), _p(w), _p(ci), _p(ct) if transitions else None)
-    out = _counts_result(model, ci, ct, kernel=ctx.last_kernel())
-    if rc < 0:
-        _raise(rc, counts=out)
-    return out
+    # np.asarray: never None, so a missing weights argument fails _weights_array's check like any other non-integer array
+    return _count_host(ctx, model, init_bin, dyn_bin, T, np.asarray(weights), transition_mode, raw, n, col_offset, counts)
 
 
 def quantize_weights(log_w, bits=24, keep=None):

@@ -3,7 +3,13 @@ from the definition in include/emgpu.h, asub2ind.m:13-14 (column of the parents'
 step) and :97-135 (frozen), over the graph score_ref.graph() reads from the model's own arrays.  It never calls the library.
 
 count() takes the user-facing shapes and returns the two lists of [r, q] integer tables plus the number of skipped observations: an
-observation whose own bin, or any parent bin it reads, is outside 1..r adds nothing; every other observation adds 1 (np.add.at)."""
+observation whose own bin, or any parent bin it reads, is outside 1..r adds nothing; every other observation adds 1 (np.add.at).
+
+With weights (include/emgpu.h "Counting a trace with integer weights") the observations, their cells and the parent bins are
+the same; what changes is the weighting:
+  - a trajectory of weight 0 is REMOVED first: it adds nothing and is not part of the bad-bin accounting, whatever its bins hold;
+  - every observation of a remaining trajectory i adds weights[i] to its cell (np.add.at in uint64: exact, order-free);
+  - an observation of a remaining trajectory whose own bin, or any parent bin it reads, is outside 1..r adds nothing and is counted in `skipped`."""
 import numpy as np
 
 from score_ref import AUTO, PER_STEP, graph  # noqa: F401  (re-exported for the tests)
@@ -26,10 +32,20 @@ def shapes(g):
     return ini, tr
 
 
-def count(g, init_bin, dyn_bin=None, mode=AUTO, n_transition=None):
-    """init_bin [n, ni], dyn_bin [n, T, nd] or None (1-based bins) -> (N_initial: list of [r, q] int64 by variable id, N_transition: list
-    by transition node id, (0, 0) where the node has no table, skipped observations)"""
+def count(g, init_bin, dyn_bin=None, mode=AUTO, n_transition=None, weights=None):
+    """init_bin [n, ni], dyn_bin [n, T, nd] or None (1-based bins), weights None or [n] integers in 0 .. 2**32 - 1 -> (N_initial: list of
+    [r, q] tables by variable id (int64; uint64 with weights), N_transition: list by transition node id, (0, 0) where the node has no table,
+    skipped observations)"""
     ib = np.asarray(init_bin).astype(np.int64)
+    w, dtype = (lambda ok: 1), np.int64                          # what the observations `ok` add, and the tables' type
+    if weights is not None:
+        wt = np.asarray(weights)
+        assert wt.ndim == 1 and wt.dtype.kind in "iu" and (wt.size == 0 or (int(wt.min()) >= 0 and int(wt.max()) <= 2**32 - 1))
+        assert len(wt) == ib.shape[0]
+        live = wt > 0                                            # weight 0: removed before anything is looked at
+        wt, ib = wt[live].astype(np.uint64), ib[live]
+        dyn_bin = None if dyn_bin is None else np.asarray(dyn_bin)[live]
+        w, dtype = (lambda ok: wt[ok]), np.uint64
     n, ni = ib.shape
     shp_i, shp_t = shapes(g)
     ok_i = (ib >= 1) & (ib <= g["r_i"][None, :])
@@ -42,13 +58,13 @@ def count(g, init_bin, dyn_bin=None, mode=AUTO, n_transition=None):
             col += stride * (ibc[:, u] - 1)
             stride *= int(g["r_i"][u])
             ok &= ok_i[:, u]
-        N = np.zeros(shp_i[v], dtype=np.int64)
-        np.add.at(N, (ibc[ok, v] - 1, col[ok]), 1)
+        N = np.zeros(shp_i[v], dtype=dtype)
+        np.add.at(N, (ibc[ok, v] - 1, col[ok]), w(ok))
         skipped += int((~ok).sum())
         N_i.append(N)
     tm = g["tm"]
     nt = (len(g["r_t"]) if "r_t" in g else 0) if n_transition is None else int(n_transition)
-    N_t = [np.zeros(shp_t.get(v, (0, 0)), dtype=np.int64) for v in range(nt)]
+    N_t = [np.zeros(shp_t.get(v, (0, 0)), dtype=dtype) for v in range(nt)]
     if dyn_bin is not None and len(tm) and np.asarray(dyn_bin).shape[1] > 1:
         db = np.asarray(dyn_bin).astype(np.int64)
         T = db.shape[1]
@@ -73,7 +89,7 @@ def count(g, init_bin, dyn_bin=None, mode=AUTO, n_transition=None):
                     col += stride * (b - 1)
                     stride *= int(g["r_t"][u])
                     ok &= o
-                np.add.at(N_t[tv], (dbc[ok, t, k] - 1, col[ok]), 1)
+                np.add.at(N_t[tv], (dbc[ok, t, k] - 1, col[ok]), w(ok))
                 skipped += int((~ok).sum())
     return N_i, N_t, skipped
 

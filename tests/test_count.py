@@ -86,6 +86,24 @@ def test_count_ref_equals_a_triple_loop_on_a_hand_written_model(depend, mode):
     assert R.flat(Ni).tolist() == [int(x) for N in Ni for x in N.T.reshape(-1)] and R.flat(Ni).dtype == np.uint64
 
 
+def test_count_ref_with_unit_weights_is_the_unweighted_count():
+    """the one restatement's two forms agree where they must: weights of 1 change no table and no skip, corrupt bins included"""
+    ib = np.array([[1, 1, 1], [2, 3, 2], [1, 2, 2], [2, 2, 1], [0, 1, 2]])          # trajectory 4: A has bin 0
+    T = 6
+    db = np.array([[[1 + (i + t) % 3, 1 + (i * t) % 2] for t in range(T)] for i in range(5)])
+    db[3, 2, 0] = 4                                                                # B has bin r + 1 at t = 2
+    for depend, mode in ((False, R.AUTO), (False, R.PER_STEP), (True, R.AUTO)):
+        g = R.graph(_hand_model(depend))
+        want_i, want_t, want_skipped = R.count(g, ib, db, mode)
+        got_i, got_t, got_skipped = R.count(g, ib, db, mode, weights=np.ones(5, dtype=np.uint32))
+        assert got_skipped == want_skipped and want_skipped > 3
+        assert all(a.dtype == np.int64 for a in want_i + want_t) and all(a.dtype == np.uint64 for a in got_i + got_t)
+        assert len(got_i) == len(want_i) == 3 and len(got_t) == len(want_t) == 5
+        for a, b in zip(got_i + got_t, want_i + want_t):
+            assert a.shape == b.shape and np.array_equal(a, b)
+        assert sum(int(x.sum()) for x in got_i + got_t) == 5 * 3 + 5 * (T - 1) * 2 - want_skipped
+
+
 @pytest.mark.parametrize("name", SHIPPED)
 def test_count_layout_matches_the_models_own_tables(name, model_dir):
     assert len(SHIPPED) >= 20

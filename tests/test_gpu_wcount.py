@@ -1,11 +1,11 @@
-"""-m gpu: the weighted k_count_dbn against the numpy restatement of its definition (wcount_ref.wcount).  Counts are integers,
+"""-m gpu: the weighted k_count_dbn against the numpy restatement of its definition (count_ref.count(..., weights=w)).  Counts are integers,
 so every comparison is exact equality whatever the kernel's accumulation scheme does (run lengths per lane, u64 LDS partials per workgroup,
 64-bit global adds).  Traces come from native.sample_dbn_host or are built by hand; each is counted by emgpu_count_dbn_weighted_host and by
 emgpu_count_dbn_weighted_device, the latter into buffers with guard words behind both tables."""
 import numpy as np
 import pytest
 
-import wcount_ref as W
+import count_ref as W
 from em_model_manned_bayes_amd import _lib as L
 from em_model_manned_bayes_amd import em_io, native, synthetic
 from em_model_manned_bayes_amd import encounter_model as E
@@ -53,8 +53,8 @@ def _weights(kind, n, seed=1):
 
 
 def _ref(g, ib, db, T, w, mode, nt):
-    """wcount_ref of a raw trace as the library's two flat arrays and the skipped observations"""
-    Ni, Nt, skipped = W.wcount(g, ib.T, None if db is None else native.unpack_dyn_bin(db, T), w, mode, n_transition=nt)
+    """count_ref with weights of a raw trace as the library's two flat arrays and the skipped observations"""
+    Ni, Nt, skipped = W.count(g, ib.T, None if db is None else native.unpack_dyn_bin(db, T), mode, n_transition=nt, weights=w)
     return W.flat(Ni), W.flat(Nt), skipped
 
 

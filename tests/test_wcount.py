@@ -1,5 +1,5 @@
 """Counting a trace with integer weights, the parts that need no GPU: native.quantize_weights against hand-computed answers,
-the numpy restatement wcount_ref.wcount against a triple Python loop and against count_ref through three identities, the argument checks of
+the numpy restatement count_ref.count(..., weights=w) against a triple Python loop and against count_ref through three identities, the argument checks of
 emgpu_count_dbn_weighted_* (made before any device work: there is no context on this box to do any), and the Python surface."""
 import ctypes as C
 import math
@@ -8,7 +8,6 @@ import numpy as np
 import pytest
 
 import count_ref as R
-import wcount_ref as W
 from em_model_manned_bayes_amd import _lib as L
 from em_model_manned_bayes_amd import em_io, native
 from em_model_manned_bayes_amd import encounter_model as E
@@ -88,7 +87,7 @@ def _hand_trace():
 
 @pytest.mark.parametrize("depend,mode", [(False, AUTO), (False, PER_STEP), (True, AUTO)])
 def test_wcount_ref_equals_a_triple_loop_on_a_hand_written_model(depend, mode):
-    g = W.graph(_hand_model(depend))
+    g = R.graph(_hand_model(depend))
     assert g["depend"] == depend
     per_step = depend or mode == PER_STEP
     ib, db, weights = _hand_trace()
@@ -128,7 +127,7 @@ def test_wcount_ref_equals_a_triple_loop_on_a_hand_written_model(depend, mode):
                     col += stride * (x - 1)
                     stride *= rr
                 Nt[3 + k][own - 1, col] += wt
-    got_i, got_t, got_skipped = W.wcount(g, ib, db, weights, mode)
+    got_i, got_t, got_skipped = R.count(g, ib, db, mode, weights=weights)
     assert got_skipped == skipped and 2 <= skipped <= 6      # trajectory 3's plants only: trajectory 4's are not looked at
     for x, y in zip(got_i + got_t, Ni + Nt):
         assert x.dtype == np.uint64 and x.shape == y.shape and [int(v) for v in x.reshape(-1)] == [int(v) for v in y.reshape(-1)]
@@ -137,17 +136,17 @@ def test_wcount_ref_equals_a_triple_loop_on_a_hand_written_model(depend, mode):
     # without trajectory 3 nothing is skipped, although trajectory 4 is full of bad bins
     w2 = weights.copy()
     w2[3] = 0
-    assert W.wcount(g, ib, db, w2, mode)[2] == 0
+    assert R.count(g, ib, db, mode, weights=w2)[2] == 0
     # the initial network alone, and T = 1
     for d in (None, db[:, :1]):
-        only_i, only_t, _ = W.wcount(g, ib, d, weights, mode)
+        only_i, only_t, _ = R.count(g, ib, d, mode, weights=weights)
         assert all(np.array_equal(x, y) for x, y in zip(only_i, got_i)) and not any(x.any() for x in only_t)
 
 
 # ---- 3. three identities on the reference alone
 @pytest.mark.parametrize("depend,mode", [(False, AUTO), (False, PER_STEP), (True, AUTO)])
 def test_wcount_ref_identities(depend, mode):
-    g = W.graph(_hand_model(depend))
+    g = R.graph(_hand_model(depend))
     rs = np.random.RandomState(25)
     n, T = 40, 7
     ib = np.stack([rs.randint(1, r + 1, size=n) for r in (2, 3, 2)], axis=1)
@@ -155,16 +154,16 @@ def test_wcount_ref_identities(depend, mode):
     ib[3, 1], db[7, 2, 0], db[9, T - 1, 1] = 0, 4, 0              # bad bins take part in all three
     same = lambda x, y: all(np.array_equal(a.astype(np.int64), b) for a, b in zip(x[0] + x[1], y[0] + y[1])) and x[2] == y[2]   # noqa: E731
     # all weights 1: count_ref
-    assert same(W.wcount(g, ib, db, np.ones(n, np.uint32), mode), R.count(g, ib, db, mode))
+    assert same(R.count(g, ib, db, mode, weights=np.ones(n, np.uint32)), R.count(g, ib, db, mode))
     # weights in {0, 1}: count_ref of the subset
     m = rs.randint(0, 2, size=n).astype(np.uint32)
     m[[3, 7]] = (0, 1)
-    assert same(W.wcount(g, ib, db, m, mode), R.count(g, ib[m > 0], db[m > 0], mode))
+    assert same(R.count(g, ib, db, mode, weights=m), R.count(g, ib[m > 0], db[m > 0], mode))
     # weight k: the trajectory repeated k times
     k = rs.randint(0, 5, size=n).astype(np.uint32)
     k[[3, 7, 9]] = (2, 0, 4)
     rep = np.repeat(np.arange(n), k)
-    got, want = W.wcount(g, ib, db, k, mode), R.count(g, ib[rep], db[rep], mode)
+    got, want = R.count(g, ib, db, mode, weights=k), R.count(g, ib[rep], db[rep], mode)
     assert same(got[:2] + (0,), want[:2] + (0,))                  # (a skipped observation is one, whatever its trajectory's weight:
     assert 0 < got[2] < want[2]                                   # the repeated trace skips it k times)
 
