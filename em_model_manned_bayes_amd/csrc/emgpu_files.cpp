@@ -297,10 +297,7 @@ void run_tracks(TracksCall &S, CallBuffers &B, const Events &ev) {
     A.alt0 = S.d_in + n; A.speed0 = S.d_in + 2 * n;
     A.table = S.T->d; A.ncol = S.in->ncol; A.c_vr = S.in->col_vertrate; A.c_acc = S.in->col_acc; A.c_tr = S.in->col_turnrate;
     A.first = S.d_first; A.len = S.d_len; A.rowidx = S.d_rowidx; A.xoff = S.d_xoff; A.xyz = S.d_xyz; A.flags = S.d_flags; A.vmm = S.d_vmm;
-    const char *name = "";
-    const hipError_t e = emgpu::launch_sample2track_table(A, ctx->stream, &name);
-    ctx->last_kernel = name;
-    launch_ok(e);
+    launch_named(ctx, [&](const char **name) { return emgpu::launch_sample2track_table(A, ctx->stream, name); });
     HIP_OK(hipEventRecord(ev[1], ctx->stream));
     B.down(S.out->flags, S.d_flags, n);
     B.down(S.out->speed_minmax, S.d_vmm, 2 * n * 8);
@@ -353,8 +350,7 @@ int emgpu_format_g_host(emgpu_ctx *ctx, const float *x, int64_t n, char *out, in
     EMGPU_TRY
     if (!ctx || !offsets || (n > 0 && !x) || (cap > 0 && !out)) return fail(EMGPU_ERR_ARG, "null argument");
     if (n < 0 || cap < 0) return fail(EMGPU_ERR_ARG, "n < 0 or cap < 0");
-    CTX_LOCK(ctx);
-    HIP_OK(hipSetDevice(ctx->device));
+    CTX_DEVICE(ctx);
     offsets[0] = 0;
     if (n == 0) return EMGPU_OK;
     uint64_t paths[2] = {0, 0};
@@ -383,8 +379,7 @@ int emgpu_format_f0_host(emgpu_ctx *ctx, const double *x, int64_t n, char *out, 
     EMGPU_TRY
     if (!ctx || !offsets || (n > 0 && !x) || (cap > 0 && !out)) return fail(EMGPU_ERR_ARG, "null argument");
     if (n < 0 || cap < 0) return fail(EMGPU_ERR_ARG, "n < 0 or cap < 0");
-    CTX_LOCK(ctx);
-    HIP_OK(hipSetDevice(ctx->device));
+    CTX_DEVICE(ctx);
     offsets[0] = 0;
     if (n == 0) return EMGPU_OK;
     return format_values(ctx, "emgpu_format_f0_host", x, n, out, cap, offsets, 20, [&](auto... pass) { return emgpu::launch_format_f0(pass..., ctx->stream); });
@@ -398,8 +393,7 @@ int emgpu_parse_table_host(emgpu_ctx *ctx, const char *text, int64_t nbytes, int
     EMGPU_TRY
     if (!ctx || !rows || (nbytes > 0 && !text) || (rows_cap > 0 && !out)) return fail(EMGPU_ERR_ARG, "null argument");
     if (nbytes < 0 || rows_cap < 0 || ncol < 1 || ncol > 4096) return fail(EMGPU_ERR_ARG, "nbytes < 0, rows_cap < 0 or ncol outside 1..4096");
-    CTX_LOCK(ctx);
-    HIP_OK(hipSetDevice(ctx->device));
+    CTX_DEVICE(ctx);
     *rows = 0;
     if (hard_tokens) *hard_tokens = 0;
     DeviceTable T;
@@ -423,8 +417,7 @@ int emgpu_tracks_text_host(emgpu_ctx *ctx, const emgpu_track_params *p, const em
     for (int32_t c : {in->col_vertrate, in->col_acc, in->col_turnrate})
         if (c < 0 || c >= in->ncol) return fail(EMGPU_ERR_ARG, "an update column outside 0..ncol-1");
     if (out->csv_cap < 0 || out->xyz_cap < 0 || (out->csv && !out->offsets)) return fail(EMGPU_ERR_ARG, "csv_cap / xyz_cap < 0, or csv without offsets");
-    CTX_LOCK(ctx);
-    HIP_OK(hipSetDevice(ctx->device));
+    CTX_DEVICE(ctx);
     const auto t_call = Clock::now();
     const size_t n = (size_t)p->n;
     for (int k = 0; k < 5; k++) out->totals[k] = 0;

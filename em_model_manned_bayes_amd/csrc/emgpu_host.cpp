@@ -128,8 +128,7 @@ static const int32_t *upload_start_grid(emgpu_ctx *ctx, const int32_t *start, si
 int emgpu_sample_dbn_host(emgpu_ctx *ctx, const emgpu_model *h, const emgpu_sample_params *p, const emgpu_sample_out *out) {
     EMGPU_TRY
     if (!ctx || !h || !p || !out) return fail(EMGPU_ERR_ARG, "null argument");
-    CTX_LOCK(ctx);
-    HIP_OK(hipSetDevice(ctx->device));
+    CTX_DEVICE(ctx);
     const auto t_call = Clock::now();
     const Model &m = h->m;
     const size_t n = (size_t)(p->n > 0 ? p->n : 0), ni = (size_t)m.n_initial, nd = (size_t)m.n_dyn();
@@ -279,8 +278,7 @@ int emgpu_sample_uncor_host(emgpu_ctx *ctx, const emgpu_model *h, const emgpu_sa
     const Model &m = h->m;
     for (int k = 0; k < 3; k++)
         if (out->ctrl_var[k] < 1 || out->ctrl_var[k] > m.n_initial) return fail(EMGPU_ERR_ARG, "ctrl_var: a variable id outside 1..n_initial");
-    CTX_LOCK(ctx);
-    HIP_OK(hipSetDevice(ctx->device));
+    CTX_DEVICE(ctx);
     const auto t_call = Clock::now();
     const size_t n = (size_t)p->n, ni = (size_t)m.n_initial, T = (size_t)p->sample_time, cap = (size_t)p->event_cap;
     out->totals[0] = out->totals[1] = 0;
@@ -415,8 +413,7 @@ int emgpu_sample_text_host(emgpu_ctx *ctx, const emgpu_model *h, const emgpu_sam
     if (p->indices) return fail(EMGPU_ERR_ARG, "emgpu_sample_text_host: index lists are not supported");
     if (p->n < 0 || p->sample_time < 1) return fail(EMGPU_ERR_ARG, "n < 0 or sample_time < 1");
     if (out->id_first < 0 || out->id_first > ((int64_t)1 << 53) - p->n) return fail(EMGPU_ERR_ARG, "id_first < 0 or id_first + n > 2^53");
-    CTX_LOCK(ctx);
-    HIP_OK(hipSetDevice(ctx->device));
+    CTX_DEVICE(ctx);
     const auto t_call = Clock::now();
     const Model &m = h->m;
     const size_t n = (size_t)p->n, ni = (size_t)m.n_initial, nd = (size_t)m.n_dyn(), T = (size_t)p->sample_time, G4 = (T + 3) / 4;

@@ -43,11 +43,6 @@ using emgpu_detail::fail;
         if (_e != hipSuccess) throw Error(EMGPU_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(_e)); \
     } while (0)
 
-// the status a launcher returned (EMGPU_CATCH turns the throw into fail(EMGPU_ERR_HIP, "kernel launch: ..."))
-inline void launch_ok(hipError_t e) {
-    if (e != hipSuccess) throw Error(EMGPU_ERR_HIP, std::string("kernel launch: ") + hipGetErrorString(e));
-}
-
 struct Uploaded {
     uint64_t version = 0;
     uint64_t last_use = 0;
@@ -89,7 +84,7 @@ struct emgpu_ctx {
     double *d_layers = nullptr;
     size_t d_layers_cap = 0;
     const uint32_t **d_thr_base = nullptr; // terminal propagation: per-model table pointers
-    size_t d_thr_base_cap = 0;
+    size_t d_thr_base_cap = 0;             // bytes, like d_layers_cap
     // Side streams for the blocks of a mixed batch (created on first use): independent launches that share the ctx stream's
     // ordering at both ends, so that one block's tail runs under the next block's head instead of in front of it.
     static constexpr int kSide = 3;
@@ -120,7 +115,31 @@ struct emgpu_ctx {
     uint64_t format_paths[2] = {0, 0}; // emgpu_format_g_host: values formatted on the 64-bit / the multiword path (emgpu_debug_format_paths)
 };
 
-// emgpu_capi.cpp
+// ---- how an entry point takes its ctx.  CTX_DEVICE: lock the ctx and make its device current -- behind an argument check that has
+// already refused a null ctx in the entry point's own words ("null argument" with its other pointers, mostly).  CTX_ENTER: the same for an
+// entry point whose check leaves the ctx to the macro, which says "null ctx": everything that can be said without a device has been said
+// before ctx is looked at.  CTX_LOCK alone is for the entry points that touch no device (emgpu_ctx_set_stream, emgpu_debug_format_paths,
+// emgpu_host_free) or have something to say between the lock and the device (emgpu_device_free).
+#define CTX_LOCK(ctx) std::lock_guard<std::recursive_mutex> _ctx_lock((ctx)->mu)
+#define CTX_DEVICE(ctx) CTX_LOCK(ctx); HIP_OK(hipSetDevice((ctx)->device))
+#define CTX_ENTER(ctx) if (!(ctx)) return fail(EMGPU_ERR_ARG, "null ctx"); CTX_DEVICE(ctx)
+
+// ---- a launcher's status.  launch_ok checks it (EMGPU_CATCH turns the throw into fail(EMGPU_ERR_HIP, "kernel launch: ...")).
+inline void launch_ok(hipError_t e) {
+    if (e != hipSuccess) throw Error(EMGPU_ERR_HIP, std::string("kernel launch: ") + hipGetErrorString(e));
+}
+// launch(&name) launches and says which kernel it chose: the name goes into ctx->last_kernel BEFORE the status is checked, so that after a
+// failed launch emgpu_last_kernel_name says which kernel failed; last_launches is not touched (these entry points never counted).  The trace
+// units' emgpu_detail::launch_recorded (emgpu_tracechunk.hpp) is the other order on purpose: it counts, and names and counts only a launch
+// that succeeded: emgpu_last_launch_count is the number of launches that were made, and there the name goes with the count.
+template <typename Launch> void launch_named(emgpu_ctx *ctx, Launch launch) {
+    const char *name = "";
+    const hipError_t e = launch(&name);
+    ctx->last_kernel = name;
+    launch_ok(e);
+}
+
+// emgpu_ctx.cpp
 // The model's tables on this ctx's device, uploaded (again) when the model's version is not the uploaded one.  `pinned`: uids that must survive
 // the eviction of old entries (the other models of the current call).
 Uploaded &get_uploaded(emgpu_ctx *ctx, const emgpu_model *h, const std::set<uint64_t> *pinned = nullptr);
@@ -128,11 +147,22 @@ void ensure_logp(emgpu_ctx *ctx, Uploaded &u, const Model &m);   // u.d_logp / u
 namespace emgpu_detail {
 constexpr const char *kScoreBadBin = "a bin outside 1..r in the trace (score: the log-likelihood of those trajectories is NaN; count: the observations that read it were skipped), or a bad value in a trace of values (discretize: its bin is 0)";
 }
+// A device buffer the ctx owns, *p with room for *cap bytes, must hold `need` bytes.  Large enough (and there): nothing happens, and the
+// contents stay.  Otherwise the ctx stream is synchronized (nothing in flight may still read the old block), the block freed, *p and *cap
+// set to null / 0 -- a hipMalloc that throws leaves an empty buffer behind, never a pointer to freed memory for the next call to use and
+// emgpu_ctx_free to free again -- and `size` bytes (>= need: the caller's head-room, if it wants any) allocated and recorded.
+void ctx_grow(emgpu_ctx *ctx, void **p, size_t *cap, size_t need, size_t size);
 // slot-th scratch buffer of the ctx, at least `bytes` long.  Two users share the slots: the host-path sampling entry points of emgpu_host.cpp
-// take slot 0 (the start grid) and slot 1 (the index list) by number, and the round drivers of emgpu_capi.cpp (RoundScratch) take 0 ... k in
+// take slot 0 (the start grid) and slot 1 (the index list) by number, and the round drivers of emgpu_terminal.cpp and emgpu_track.cpp (RoundScratch, emgpu_rounds.hpp) take 0 ... k in
 // request order.  They never meet in one call: a host-path entry point samples through the *_device entry points and never enters a round
 // driver, a round driver draws through launch_dbn / launch_bn and never enters the host path, and CTX_LOCK lets one call at a time use a ctx.
 void *ctx_scratch(emgpu_ctx *ctx, size_t slot, size_t bytes);
+// emgpu_sample.cpp: what the round drivers draw through
+void fill_run(emgpu_ctx *ctx, const Uploaded &u, const Model &m, const emgpu_sample_params *p, EmgpuRun &A);   // the run of a DBN call, outputs unbound
+// The block of device memory a launch reads its start grid / log-weight pointers through (one per ctx, rewritten per launch).
+const EmgpuPresets *upload_presets(emgpu_ctx *ctx, Uploaded &u, const Model &m, const int32_t *start, double *log_weight, const int64_t *row);
+void launch_dbn(emgpu_ctx *ctx, const Uploaded &u, const EmgpuRun &A, hipStream_t stream = nullptr, const EmgpuPresets *presets = nullptr);
+void fill_bn(emgpu_ctx *ctx, const Uploaded &u, const Model &m, const emgpu_bn_params *p, EmgpuBnRun &A);      // the run of a BN call, outputs unbound
 // emgpu_memory.cpp
 void ctx_release_host_side(emgpu_ctx *ctx, bool everything);    // trim (false: pools and staging) / free (true: streams and events too)
 
@@ -142,8 +172,6 @@ template <typename Run> void set_track_units(Run &A, const emgpu_track_params *p
     A.ur_speed = p->ur_speed; A.ur_vertrate = p->ur_vertrate; A.ur_heading = p->ur_heading;
     A.min_speed = p->min_speed; A.max_speed = p->max_speed;
 }
-
-#define CTX_LOCK(ctx) std::lock_guard<std::recursive_mutex> _ctx_lock((ctx)->mu)
 
 // The device buffers of one host-pointer call: fresh per call, freed when the call returns or throws, after the ctx stream has drained.
 // up / down copy on the ctx stream and do nothing for zero bytes or a null host pointer.
@@ -172,6 +200,13 @@ class CallBuffers {
     void up(void *dst, const void *src, size_t bytes) {
         if (bytes && src) HIP_OK(hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, ctx_->stream));
     }
+    // a device copy of a caller's array, complete when this returns (the array is the caller's memory: it may be gone behind the call)
+    template <typename T> T *copy_of(const T *src, size_t bytes) {
+        T *d = alloc<T>(bytes);
+        up(d, src, bytes);
+        HIP_OK(hipStreamSynchronize(ctx_->stream));
+        return d;
+    }
     void down(void *dst, const void *src, size_t bytes) {
         if (bytes && dst) HIP_OK(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, ctx_->stream));
     }
@@ -180,29 +215,3 @@ class CallBuffers {
     emgpu_ctx *ctx_;
     std::vector<void *> ptrs_;
 };
-
-// The device scratch of one round-driver call: the ctx's scratch blocks 0, 1, ... in request order (kept by the ctx between calls).  The
-// stream is synchronized when the scope ends, however it ends: the rounds' launches read this scratch and the caller's buffers.
-class RoundScratch {
-  public:
-    explicit RoundScratch(emgpu_ctx *ctx) : ctx_(ctx) {}
-    RoundScratch(const RoundScratch &) = delete;
-    RoundScratch &operator=(const RoundScratch &) = delete;
-    ~RoundScratch() { (void)hipStreamSynchronize(ctx_->stream); }
-    template <typename T> T *alloc(size_t bytes) { return static_cast<T *>(ctx_scratch(ctx_, slot_++, bytes ? bytes : 1)); }
-
-  private:
-    emgpu_ctx *ctx_;
-    size_t slot_ = 0;
-};
-
-// What a round driver's host wrapper does with the rounds' status: under EMGPU_OK or EMGPU_ERR_REJECT_CAP (the accepted lanes are valid, the
-// others carry attempts -1) copy() brings the outputs back, and the rounds' message survives whatever the copies do to the thread's.
-template <typename Copy> int copy_back_accepted(emgpu_ctx *ctx, int rc, Copy copy) {
-    if (rc != EMGPU_OK && rc != EMGPU_ERR_REJECT_CAP) return rc;
-    const std::string msg = g_err;
-    copy();
-    HIP_OK(hipStreamSynchronize(ctx->stream));
-    if (rc != EMGPU_OK) g_err = msg;
-    return rc;
-}

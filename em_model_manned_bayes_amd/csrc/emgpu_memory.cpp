@@ -272,8 +272,7 @@ int emgpu_trace_alloc(emgpu_ctx *ctx, const emgpu_model *h, const emgpu_sample_p
     if (!(want & (EMGPU_TRACE_INIT | EMGPU_TRACE_DENSE | EMGPU_TRACE_EVENTS | EMGPU_TRACE_ATTEMPTS)) || (want & ~15u)) return fail(EMGPU_ERR_ARG, "want: a combination of EMGPU_TRACE_*");
     if ((want & EMGPU_TRACE_EVENTS) && p->event_cap < 1) return fail(EMGPU_ERR_ARG, "EMGPU_TRACE_EVENTS needs event_cap >= 1");
     if (candidates < 0 || candidates > 8) return fail(EMGPU_ERR_ARG, "candidates outside 0..8");
-    CTX_LOCK(ctx);
-    HIP_OK(hipSetDevice(ctx->device));
+    CTX_DEVICE(ctx);
     const TraceLayout L = trace_layout(h->m, p, want);
     std::unique_ptr<emgpu_trace> t(new emgpu_trace());
     t->rep.bytes = (int64_t)L.bytes;
@@ -366,9 +365,7 @@ int emgpu_trace_report(const emgpu_trace *t, emgpu_trace_report_t *out) {
 int emgpu_trace_free(emgpu_ctx *ctx, emgpu_trace *t) {
     EMGPU_TRY
     if (!t) return EMGPU_OK;
-    if (!ctx) return fail(EMGPU_ERR_ARG, "null ctx");
-    CTX_LOCK(ctx);
-    HIP_OK(hipSetDevice(ctx->device));
+    CTX_ENTER(ctx);
     HIP_OK(hipStreamSynchronize(ctx->stream));   // nothing in flight may still write the block when somebody else takes it
     ctx->trace_pool.push_back(t->blk);
     delete t;
@@ -381,8 +378,7 @@ int emgpu_trace_free(emgpu_ctx *ctx, emgpu_trace *t) {
 int emgpu_device_alloc(emgpu_ctx *ctx, uint64_t bytes, void **out) {
     EMGPU_TRY
     if (!ctx || !out) return fail(EMGPU_ERR_ARG, "null argument");
-    CTX_LOCK(ctx);
-    HIP_OK(hipSetDevice(ctx->device));
+    CTX_DEVICE(ctx);
     const size_t need = std::max<size_t>((size_t)bytes, 256);
     void *p = device_block_or_trim(ctx, need);
     if (!p) return fail(EMGPU_ERR_HIP, "emgpu_device_alloc: out of device memory (" + std::to_string(need) + " bytes)");
@@ -411,8 +407,7 @@ static int device_copy(emgpu_ctx *ctx, void *dst, const void *src, uint64_t byte
     if (!ctx) return fail(EMGPU_ERR_ARG, "null ctx");
     if (bytes == 0) return EMGPU_OK;
     if (!dst || !src) return fail(EMGPU_ERR_ARG, "null argument");
-    CTX_LOCK(ctx);
-    HIP_OK(hipSetDevice(ctx->device));
+    CTX_DEVICE(ctx);
     HIP_OK(hipMemcpyAsync(dst, src, (size_t)bytes, kind, ctx->stream));
     HIP_OK(hipStreamSynchronize(ctx->stream));
     return EMGPU_OK;
@@ -429,8 +424,7 @@ int emgpu_device_download(emgpu_ctx *ctx, void *dst_host, const void *src_device
 int emgpu_host_alloc(emgpu_ctx *ctx, uint64_t bytes, void **out) {
     EMGPU_TRY
     if (!ctx || !out) return fail(EMGPU_ERR_ARG, "null argument");
-    CTX_LOCK(ctx);
-    HIP_OK(hipSetDevice(ctx->device));
+    CTX_DEVICE(ctx);
     const size_t need = std::max<size_t>((size_t)bytes, 64);   // (portable: emgpu_sample_dbn_multi_host hands one caller array to the contexts of several devices)
     emgpu_ctx::HostBlock *best = nullptr;
     for (auto &b : ctx->host_pool)

@@ -688,6 +688,9 @@ static bool dedisc_scalable(double a, double b) {
 CompiledPlan compile_plan(const Model &m) {
     CompiledPlan cp;
     EmgpuPlan &P = cp.plan;
+    // the padding too (`plan{}` zeroes the members, and the four bytes in front of `cthr` kept what the stack held): save_bin writes the
+    // struct raw, and two caches of one model must be the same bytes
+    memset(&P, 0, sizeof P);
     const int ni = m.n_initial, nt = m.n_transition, nd = m.n_dyn();
     if (ni > EMGPU_MAX_NI) throw Error(EMGPU_ERR_UNSUPPORTED, "n_initial exceeds EMGPU_MAX_NI");
     if (nd > EMGPU_MAX_ND) throw Error(EMGPU_ERR_UNSUPPORTED, "more dynamic variables than EMGPU_MAX_ND");

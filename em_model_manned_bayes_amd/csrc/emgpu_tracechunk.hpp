@@ -8,11 +8,9 @@
 
 #include "emgpu_hostmem.hpp"
 
-// behind an entry point's own argument check: everything that can be said without a device has been said before ctx is looked at
-#define CTX_ENTER(ctx) if (!(ctx)) return fail(EMGPU_ERR_ARG, "null ctx"); CTX_LOCK(ctx); HIP_OK(hipSetDevice((ctx)->device))
-
 namespace emgpu_detail {
-// launcher(args..., the ctx stream, &name): its status checked, its kernel recorded
+// launcher(args..., the ctx stream, &name): its status checked, its kernel recorded and counted -- after success only, unlike launch_named
+// (emgpu_internal.hpp), which names the kernel before it checks and never counts: see there
 template <typename Launcher, typename... Args> void launch_recorded(emgpu_ctx *ctx, Launcher launcher, const Args &...args) {
     const char *name = "";
     launch_ok(launcher(args..., ctx->stream, &name));

@@ -312,7 +312,7 @@ REFUSAL_SPEC = S.by_id("tiny")["spec"]
 
 @pytest.mark.parametrize("variant", terminal_refusal_variants(REFUSAL_SPEC), ids=lambda v: v[0])
 def test_refused_model_sets_give_err_unsupported(variant, tmp_path, shapes, geometry, gpu_ctx):
-    """Each refusal of terminal_tables (emgpu_capi.cpp), provoked by a set of ten loadable files: EMGPU_ERR_UNSUPPORTED with its message,
+    """Each refusal of terminal_tables (emgpu_terminal.cpp), provoked by a set of ten loadable files: EMGPU_ERR_UNSUPPORTED with its message,
     from the host-pointer entry point; afterwards the same context completes a good call that equals the oracle."""
     id_, message, edit = variant
     d = write_terminal_shape_directory(str(tmp_path / id_), edit=edit, **REFUSAL_SPEC)

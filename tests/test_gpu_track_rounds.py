@@ -1,5 +1,5 @@
 """-m gpu: the host code around the track kernels -- the rejection-round loop both .track drivers iterate over (RejectionRounds in
-emgpu_capi.cpp), the copy-back that keeps the rounds' message, and the terminal encounter chain's kernel names and smoothing-cap refusal.
+emgpu_rounds.hpp), the copy-back that keeps the rounds' message, and the terminal encounter chain's kernel names and smoothing-cap refusal.
 
 The uncor case is small enough for the CPU oracle to name every lane: n = 257, T = 30, record_stride = 10, seed 0xC0DE, first_index 0 on
 uncor_1200code_v2p1.  O.uncor_track accepts 243 lanes at attempt 1, 12 at attempt 2 and 2 (lanes 126 and 154) at attempt 3, so rounds 0, 1

@@ -535,7 +535,7 @@ def terminal_shape_models(directory, native_too=True):
 
 
 def terminal_refusal_variants(spec):
-    """The sets of ten trajectory models the library refuses (terminal_tables in emgpu_capi.cpp), as (id, words of the message, edit) with
+    """The sets of ten trajectory models the library refuses (terminal_tables in emgpu_terminal.cpp), as (id, words of the message, edit) with
     edit an argument of write_terminal_shape_directory(**spec): each is loadable -- the refusal is the terminal entry points' own."""
     def seven_initial(k, m):
         m = dict(m)
