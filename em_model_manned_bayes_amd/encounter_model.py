@@ -662,6 +662,22 @@ class UncorEncounterModel(EncounterModel):
                                       unit_ratios)
         return got["N_initial"], got["N_transition"], got["repeat"].reshape(-1, 1), got["change"].reshape(-1, 1)
 
+    @staticmethod
+    def track_xyz(results, stride=10):
+        """The 1 Hz positions [n, P, 3] (x east, y north, z up, in feet) of .track results, whose rows are `stride` to the second."""
+        return np.ascontiguousarray(np.stack([np.stack([r["east_ft"], r["north_ft"], r["up_ft"]], axis=1)[::int(stride)] for r in results]))
+
+    def pair(self, own_xyz, intruder_xyz, pose=None, weights=None, idx_own=None, idx_intruder=None, nmac_h_ft=500.0, nmac_v_ft=100.0,
+             layout="rows", ctx=None):
+        """Pairs intruder tracks with ownship tracks and returns their miss distances, CPA times and NMAC flags, evaluated on the GPU: a
+        thin wrapper over native.miss_distance (set A is the ownship, set B the intruder).  own_xyz / intruder_xyz: 1 Hz positions in
+        feet, [n, P, 3] (track_xyz of .track results, sample2track's tracks) or layout="planar" [P, 3, n]; one ownship track serves every
+        intruder.  pose: native.make_pose(heading_deg, ox, oy, oz), which turns and places each intruder -- uncor tracks all start at the
+        origin heading east, so without one every pair starts as a collision.  weights: integer importance weights
+        (native.quantize_weights) for totals[5:8].  Returns native.miss_distance's dict."""
+        return native.miss_distance(own_xyz, intruder_xyz, idx_a=idx_own, idx_b=idx_intruder, pose_b=pose, weights=weights, nmac_h_ft=nmac_h_ft,
+                                    nmac_v_ft=nmac_v_ft, layout=layout, ctx=ctx)
+
     def getDynamicLimits(self, initial, results, idx_G=None, idx_A=None, idx_L=None, idx_V=None, idx_DH=None, is_discretized=None):
         """dynamiclimits = getDynamicLimits(self, initial, results, ...)  (@UncorEncounterModel/getDynamicLimits.m).  The index
         arguments are accepted for signature compatibility; they are looked up from the labels like .track does."""

@@ -266,3 +266,30 @@ def dbn_hierarchical_sample(parms, dirichlet_initial, dirichlet_transition, samp
     if num_samples == 1:
         return inits[0], evs[0]
     return inits, evs
+
+
+NM_TO_FT = 6076.1154855643      # CorTerminalModel.m:124
+
+
+def getGeneratedMissDistance(traj, nmac_h_ft=500.0, nmac_v_ft=100.0):
+    """[hmd_ft, vmd_ft, tcpa_s, tcpa_index_own, tcpa_index_int] = getGeneratedMissDistance(traj)  (CorTerminalModel.m:117-133) on the
+    GPU (native.miss_distance).  traj: two dicts with t_s, x_nm, y_nm, z_ft, ownship and intruder.  The times are intersected on the host
+    (:120); the coordinates are converted to feet with the factor of :124 BEFORE the differences are taken (the reference converts the
+    root: the two agree to rounding).  The indices are 0-based positions in the two trajectories' own arrays.  Returns
+    (hmd_ft, vmd_ft, tcpa_s, tcpa_index_own, tcpa_index_int); without a common time, or with no second whose distance is a number,
+    (nan, nan, nan, -1, -1)."""
+    own, intr = traj
+    _, ia, ib = np.intersect1d(np.asarray(own["t_s"], dtype=np.float64).reshape(-1), np.asarray(intr["t_s"], dtype=np.float64).reshape(-1),
+                               return_indices=True)
+    if ia.size == 0:
+        return float("nan"), float("nan"), float("nan"), -1, -1
+
+    def feet(t, k):
+        col = lambda f: np.asarray(t[f], dtype=np.float64).reshape(-1)[k]          # noqa: E731
+        return np.stack([col("x_nm") * NM_TO_FT, col("y_nm") * NM_TO_FT, col("z_ft")], axis=1)[None]
+    got = native.miss_distance(feet(own, ia), feet(intr, ib), nmac_h_ft=nmac_h_ft, nmac_v_ft=nmac_v_ft)
+    k = int(got["t_cpa"][0])
+    if k < 0:
+        return float("nan"), float("nan"), float("nan"), -1, -1
+    return (float(got["hmd_ft"][0]), float(got["vmd_ft"][0]), float(np.asarray(own["t_s"], dtype=np.float64).reshape(-1)[ia[k]]), int(ia[k]),
+            int(ib[k]))

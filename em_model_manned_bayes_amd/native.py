@@ -206,17 +206,21 @@ class NativeModel:
 
 
 class Context:
-    """One device + one stream (emgpu_ctx).  Raises EmgpuError(ERR_NO_DEVICE) without a GPU."""
+    """One device + one stream (emgpu_ctx).  Raises EmgpuError(ERR_NO_DEVICE) without a GPU.  `stream` is the raw hipStream_t the context
+    was last given (0: the HIP default stream), or None while it runs on the stream it created for itself: what a context-free call
+    (miss_distance_device) takes to stay ordered behind this context's launches."""
 
     def __init__(self, device=0, stream=None):
         h = C.c_void_p()
         L.check(L.lib().emgpu_ctx_create(int(device), C.byref(h)))
         self._h = h
+        self.stream = None
         if stream is not None:
             self.set_stream(stream)
 
     def set_stream(self, stream_ptr):
         L.check(L.lib().emgpu_ctx_set_stream(self._h, C.c_void_p(int(stream_ptr) if stream_ptr else 0)))
+        self.stream = int(stream_ptr) if stream_ptr else 0
 
     def sync(self):
         L.check(L.lib().emgpu_ctx_sync(self._h))
@@ -1140,6 +1144,110 @@ def track_count_host(ctx, model, xyz, rows, static=None, n_fine=4, wrap=None, tr
             device_upload(ctx, at["dyn_val"], np.zeros(4 * G4 * nd * n, dtype=dt))
         track_values_device(ctx, p, at["xyz"], at["init_val"], at["dyn_val"])
         return _discretize_count_in_block(ctx, model, at, n, T, n_fine, value_type, wrap, transition_mode, True, values_kernel=ctx.last_kernel())
+
+
+def miss_params(n_pairs, n_a, n_b, points, nmac_h_ft=500.0, nmac_v_ft=100.0, ld_a=0, ld_b=0):
+    """emgpu_miss_params: n_pairs pairs of a column of set A (n_a columns, pitch ld_a, 0 = n_a) and a column of set B, `points` seconds each;
+    the NMAC thresholds of track.m:175 in feet."""
+    p = L.MissParams()
+    p.n_pairs, p.n_a, p.n_b, p.ld_a, p.ld_b, p.points = int(n_pairs), int(n_a), int(n_b), int(ld_a), int(ld_b), int(points)
+    p.nmac_h_ft, p.nmac_v_ft = float(nmac_h_ft), float(nmac_v_ft)
+    return p
+
+
+def miss_distance_device(params, xyz_a, xyz_b, idx_a=0, idx_b=0, pose_b=0, weights=0, hmd=0, vmd=0, t_cpa=0, flags=0, totals=0, stream=None):
+    """emgpu_miss_distance_device: asynchronous, raw device pointers (ints, 0 = none; params: miss_params).  xyz_a / xyz_b f64 PLANAR
+    [P, 3, ld], idx_a / idx_b int64 [n_pairs], pose_b f64 [5, n_pairs] (make_pose), weights uint32 [n_pairs]; hmd / vmd f64, t_cpa int32,
+    flags uint8 [n_pairs] each, totals uint64 [8], ADDED to.  The call takes no context: it runs on the current device and on `stream`, a
+    raw hipStream_t (0: the HIP default stream; None: torch's current stream).  To stay ordered behind a sampler, pass the stream its
+    Context was given (Context.stream)."""
+    if stream is None:
+        import torch
+        stream = torch.cuda.current_stream().cuda_stream
+    L.check(L.lib().emgpu_miss_distance_device(C.c_void_p(int(stream) or None), C.byref(params), *(C.c_void_p(int(a) or None) for a in (
+        xyz_a, xyz_b, idx_a, idx_b, pose_b, weights, hmd, vmd, t_cpa, flags, totals))))
+
+
+def make_pose(heading_deg, ox=0.0, oy=0.0, oz=0.0):
+    """The pose_b of miss_distance: [5, n] float64 on the host, rows cos, sin of heading_deg (counter-clockwise, MATLAB's cosd / sind: the
+    reduction in degrees of CorTerminalModel._sincosd, so that multiples of 90 give exact 0 and +-1), then the offsets ox, oy, oz in feet.
+    Track B is turned about its own origin by the heading, then moved by the offset.  The arguments broadcast against each other."""
+    from .encounter_model import CorTerminalModel
+    h, ox, oy, oz = np.broadcast_arrays(*(np.atleast_1d(np.asarray(a, dtype=np.float64)) for a in (heading_deg, ox, oy, oz)))
+    s, c = CorTerminalModel._sincosd(h)
+    return np.ascontiguousarray(np.stack([c, s, ox, oy, oz]) + 0.0)   # (+ 0.0: -0.0 becomes 0.0)
+
+
+def _planar_tracks(xyz, layout, dev):
+    """xyz as a contiguous float64 PLANAR [P, 3, n] tensor on dev: numpy [n, P, 3] (layout "rows") or [P, 3, n] ("planar"), or a torch
+    tensor in either layout, uploaded and transposed by torch"""
+    import torch
+    if layout not in ("rows", "planar"):
+        raise ValueError("layout must be 'rows' or 'planar'")
+    if not isinstance(xyz, torch.Tensor):
+        xyz = np.ascontiguousarray(xyz, dtype=np.float64)
+        xyz = xyz if xyz.flags.writeable else xyz.copy()      # (torch takes no read-only array; the tensor is only read)
+    t = xyz if isinstance(xyz, torch.Tensor) else torch.from_numpy(xyz)
+    if t.dim() != 3 or t.shape[2 if layout == "rows" else 1] != 3:
+        raise ValueError("xyz must be [n, points, 3] (layout 'rows') or [points, 3, n] ('planar')")
+    t = t.to(device=dev, dtype=torch.float64)
+    return (t.permute(1, 2, 0) if layout == "rows" else t).contiguous()
+
+
+def miss_distance(xyz_a, xyz_b, idx_a=None, idx_b=None, pose_b=None, weights=None, nmac_h_ft=500.0, nmac_v_ft=100.0, layout="rows", ctx=None,
+                  stream=None):
+    """Horizontal / vertical miss distance, time of closest approach and NMAC flags of paired 1 Hz tracks on the GPU
+    (emgpu_miss_distance_device; the definition is in include/emgpu.h: CorTerminalModel.m:117-133, track.m:175).  xyz_a / xyz_b: numpy
+    arrays [n, P, 3] in feet (layout "rows", what sample2track_host and a track file hold) or [P, 3, n] ("planar"), or torch tensors in
+    that layout, on the device or not; both sets hold the same P points.  Torch does the plumbing: the upload, the transposition to
+    PLANAR on the device, the outputs.  idx_a / idx_b: integer arrays, one column per pair; without idx_x pair i takes column i of set X,
+    or column 0 of a set of one (one ownship against every intruder); the number of pairs is the longest of what is given.  pose_b:
+    [5, n_pairs] float64 from make_pose.  weights: integers [n_pairs] in 0 .. 2**32 - 1 (quantize_weights), ValueError otherwise; they
+    enter totals[5:8] only.
+    Returns {"hmd_ft", "vmd_ft" float64, "t_cpa" int32, "flags" uint8 (L.MISS_*), "nmac" bool: NMAC at the CPA, "totals" uint64 [8]} as
+    numpy arrays; totals[6] / totals[5] is the weighted NMAC rate.
+    The kernel runs on `stream` (a raw hipStream_t) or, without one, on torch's current stream.  ctx: a Context whose earlier device
+    calls produced the inputs -- its stream is used when it was given one (Context.stream), and when it runs on a stream of its own
+    (Context.stream is None) ctx.sync() is called first, so that the inputs are complete."""
+    import torch
+    n_of = lambda t: int(t.shape[0 if layout == "rows" else 2])          # noqa: E731
+    for t in (xyz_a, xyz_b):
+        if getattr(t, "ndim", 0) != 3:
+            raise ValueError("xyz must be [n, points, 3] (layout 'rows') or [points, 3, n] ('planar')")
+    n_a, n_b = n_of(xyz_a), n_of(xyz_b)
+    idx = [None if i is None else np.ascontiguousarray(i, dtype=np.int64).reshape(-1) if not isinstance(i, torch.Tensor) else i
+           for i in (idx_a, idx_b)]
+    n_pairs = max([len(i) for i in idx if i is not None] + [n for n, i in zip((n_a, n_b), idx) if i is None])
+    w = None if weights is None else _weights_array(weights, n_pairs)
+    if pose_b is not None:
+        pose_b = np.ascontiguousarray(pose_b, dtype=np.float64) if not isinstance(pose_b, torch.Tensor) else pose_b
+        if tuple(pose_b.shape) != (5, n_pairs):
+            raise ValueError("pose_b must be [5, n_pairs] (make_pose)")
+    dev = xyz_a.device if isinstance(xyz_a, torch.Tensor) and xyz_a.is_cuda else torch.device("cuda", torch.cuda.current_device())
+    if ctx is not None and stream is None:
+        stream = ctx.stream
+        if stream is None:
+            ctx.sync()
+    with torch.cuda.device(dev):
+        a, b = _planar_tracks(xyz_a, layout, dev), _planar_tracks(xyz_b, layout, dev)
+        if a.shape[0] != b.shape[0]:
+            raise ValueError("both sets of tracks must hold the same number of points")
+        up = lambda x, dt: None if x is None else (x if isinstance(x, torch.Tensor) else torch.from_numpy(x)).to(device=dev, dtype=dt).contiguous()  # noqa: E731
+        d_ia, d_ib, d_pose = up(idx[0], torch.int64), up(idx[1], torch.int64), up(pose_b, torch.float64)
+        d_w = None if w is None else torch.from_numpy(w.view(np.int32)).to(dev)
+        hmd, vmd = torch.empty(n_pairs, dtype=torch.float64, device=dev), torch.empty(n_pairs, dtype=torch.float64, device=dev)
+        t_cpa, flags = torch.empty(n_pairs, dtype=torch.int32, device=dev), torch.empty(n_pairs, dtype=torch.uint8, device=dev)
+        totals = torch.zeros(8, dtype=torch.int64, device=dev)
+        ptr = lambda t: 0 if t is None else t.data_ptr()                 # noqa: E731
+        if stream is not None:
+            torch.cuda.synchronize(dev)      # the uploads ran on torch's stream, the kernel will not
+        miss_distance_device(miss_params(n_pairs, n_a, n_b, a.shape[0], nmac_h_ft, nmac_v_ft), ptr(a), ptr(b), ptr(d_ia), ptr(d_ib), ptr(d_pose),
+                             ptr(d_w), ptr(hmd), ptr(vmd), ptr(t_cpa), ptr(flags), ptr(totals), stream=stream)
+        if stream is not None:
+            torch.cuda.synchronize(dev)
+        fl = flags.cpu().numpy()
+        return {"hmd_ft": hmd.cpu().numpy(), "vmd_ft": vmd.cpu().numpy(), "t_cpa": t_cpa.cpu().numpy(), "flags": fl,
+                "nmac": (fl & L.MISS_NMAC_CPA) != 0, "totals": totals.cpu().numpy().view(np.uint64)}
 
 
 def device_upload(ctx, addr, src):

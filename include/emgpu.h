@@ -556,6 +556,59 @@ typedef struct {
 int emgpu_track_values_device(emgpu_ctx *ctx, const emgpu_track_values_params *p, const double *xyz, void *init_val, void *dyn_val);
 int emgpu_track_values_host(emgpu_ctx *ctx, const emgpu_track_values_params *p, const double *xyz, void *init_val, void *dyn_val);
 
+/* ------------------------------------------------------------------------------------------------
+ * Miss distance of paired tracks: horizontal miss distance (HMD), vertical miss distance (VMD) at that moment, the time of closest
+ * approach (CPA) and whether the encounter is a near mid-air collision (NMAC): CorTerminalModel.m:117-133 (getGeneratedMissDistance) and
+ * track.m:175 (nmac = abs(hmd_ft) < 500 & abs(vmd_ft) < 100), for any two sets of 1 Hz tracks.
+ * Inputs     two sets of tracks in the PLANAR layout xyz f64 [P][3][ld] that emgpu_sample2track_device writes: set A has n_a columns with
+ *            pitch ld_a, set B n_b columns with pitch ld_b (0 = n).  Both hold the same P = `points` >= 1 points, one second apart,
+ *            starting at the same second, in feet.
+ * Pairs      n_pairs of them.  idx_a / idx_b: optional const int64_t [n_pairs] device arrays.  With idx_x == NULL pair i uses column i of
+ *            set X when n_x > 1 (which requires n_pairs <= n_x) and column 0 when n_x == 1: one ownship against every intruder.
+ * Pose of B  pose_b: optional const double [5][n_pairs], {c, s, ox, oy, oz} per pair.  Per point x' = (c * x - s * y) + ox,
+ *            y' = (s * x + c * y) + oy, z' = z + oz: each product and sum one IEEE double operation in the order written, nothing
+ *            contracted.  The caller supplies cosine and sine, so no device sin / cos enters the result.  NULL: B's points are used as
+ *            they lie, with no arithmetic (uncor tracks all start at the origin heading east: without a pose no pairing of them is useful).
+ * Per second p = 0 .. P-1: dx = xa - xb', dy = ya - yb', d[p] = sqrt(dx * dx + dy * dy) (two multiplies, one add, an IEEE square root;
+ *            :122-124, in feet), dz[p] = zb' - za (:125).
+ * CPA        t_cpa = the first p at which d[p] is smallest, seconds whose d is NaN skipped (MATLAB's min, :127); hmd = d[t_cpa],
+ *            vmd = dz[t_cpa] (:128).  The minimum is over the square roots, not the squares: two different squares can round to one root,
+ *            and then the earlier second wins.  No second with a non-NaN d: hmd = vmd = NaN, t_cpa = -1, EMGPU_MISS_NO_CPA.
+ * Flags      uint8 per pair.  EMGPU_MISS_NMAC_CPA: hmd < nmac_h_ft && fabs(vmd) < nmac_v_ft (track.m:175).  EMGPU_MISS_NMAC_ANY: some
+ *            second has d[p] < nmac_h_ft && fabs(dz[p]) < nmac_v_ft.  NaN compares false.  EMGPU_MISS_NO_CPA.  EMGPU_MISS_BAD_INDEX: an
+ *            index outside 0 .. n_x-1; no load is made for that pair, its outputs are NaN, NaN, -1 and it has no other flag.  No load or
+ *            store leaves the buffers, whatever the indices and coordinates hold.
+ * Outputs    hmd f64 [n_pairs], vmd f64 [n_pairs], t_cpa int32 [n_pairs], flags uint8 [n_pairs], each may be NULL; totals uint64 [8], which
+ *            the call ADDS to (the caller zeroes it, as for the count tables): [0] pairs evaluated (indices in range), [1] NMAC at CPA,
+ *            [2] NMAC at any second, [3] no CPA, [4] bad index, [5] sum of w over the evaluated pairs, [6] sum of w * NMAC_CPA,
+ *            [7] sum of w * NMAC_ANY.  weights: optional const uint32_t [n_pairs] (NULL: 1), the integer weights of the weighted count.
+ *            They enter the totals only: every pair is evaluated whatever its weight.  The totals are integers, so the result does not
+ *            depend on the order of the adds; with n_pairs <= 2^32 no entry can wrap within a call.  totals[6] / totals[5] is the
+ *            importance-weighted NMAC rate.
+ * The call takes no context: hip_stream is a hipStream_t as emgpu_ctx_set_stream takes it (NULL: the HIP default stream), the device is
+ * the calling thread's current one, every pointer but p is a device pointer, and the call is asynchronous on that stream.
+ * EMGPU_ERR_ARG, with a message that names the argument, before any device work: NULL p, xyz_a or xyz_b; every output NULL; points < 1 or
+ * > 65537; n_pairs < 0 or > 2^32; n_a or n_b < 1; ld_x < n_x; idx_x == NULL with n_x > 1 and n_pairs > n_x; a threshold that is negative
+ * or NaN.  n_pairs == 0 succeeds and launches nothing.
+ * Out of scope: tracks of different length or start time (a lag per pair), interpolation between the 1 Hz samples, the ROWS layout, a
+ * _host entry point (the chunk driver belongs to the context; the Python binding uploads with torch), the terminal model's traj layout,
+ * slant range, and a cross-entropy driver loop. */
+#define EMGPU_MISS_NMAC_CPA 1u
+#define EMGPU_MISS_NMAC_ANY 2u
+#define EMGPU_MISS_NO_CPA 4u
+#define EMGPU_MISS_BAD_INDEX 8u
+typedef struct {
+    int64_t n_pairs;
+    int64_t n_a, n_b;
+    int64_t ld_a, ld_b;    /* 0 = n_a / n_b */
+    int32_t points;        /* P: 1 .. 65537 */
+    int32_t reserved;
+    double nmac_h_ft, nmac_v_ft;
+} emgpu_miss_params;
+int emgpu_miss_distance_device(void *hip_stream, const emgpu_miss_params *p, const double *xyz_a, const double *xyz_b, const int64_t *idx_a,
+                               const int64_t *idx_b, const double *pose_b, const uint32_t *weights, double *hmd, double *vmd,
+                               int32_t *t_cpa, uint8_t *flags, uint64_t *totals);
+
 /* Pinned host memory for the outputs of the *_host entry points (hipHostMalloc, kept in a per-ctx pool: pinning gigabytes costs about as
  * much as copying them).  emgpu_sample_dbn_host recognises pinned output arrays and lets the copy engine write straight into them;
  * pageable arrays go through the library's own pinned staging buffers and a few host threads (below). */

@@ -1,0 +1,95 @@
+"""tools/miss_time.py [--n N] [--points P] [--warmup W] [--launches K] -- k_miss_distance on device-resident tracks, on one GPU: 4 M pairs x
+241 points by default (two PLANAR sets of 24 P n bytes each, seeded straight tracks made by torch).  Three pairings are timed between
+two events on torch's current stream, every launch with a random pose per pair and all five outputs:
+  identity    pair i = column i of both sets: a streaming read of both arrays;
+  ownship     n_a = 1: one ownship track against every column of set B, which is read once;
+  permuted    a random permutation as idx_b: every load of set B is alone in its 64-byte sector.
+In the same process and on the same buffers, torch.sum over the two arrays (and over set B alone, for `ownship`) reads the same bytes.
+Each figure is the median of the launches behind the warm-up; the JSON line holds every launch.  identity_nopose_ms is the identity pairing
+without a pose.  The numbers are a record (HISTORY.md section 30), not a gate."""
+import argparse
+import json
+import os
+import statistics
+import sys
+
+HERE = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--n", type=int, default=4_000_000)
+    ap.add_argument("--points", type=int, default=241)
+    ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--launches", type=int, default=7)
+    args = ap.parse_args()
+    sys.path.insert(0, HERE)
+    import numpy as np
+    import torch
+    from em_model_manned_bayes_amd import _lib as L
+    from em_model_manned_bayes_amd import native
+    dev = torch.device("cuda", 0)
+    stream = torch.cuda.current_stream(dev)
+    n, P = args.n, args.points
+    gen = torch.Generator(device=dev)
+    gen.manual_seed(30)
+
+    def tracks():
+        xyz = torch.empty((P, 3, n), dtype=torch.float64, device=dev)
+        start = (torch.rand((3, n), dtype=torch.float64, device=dev, generator=gen) - 0.5) * 6000.0
+        vel = (torch.rand((3, n), dtype=torch.float64, device=dev, generator=gen) - 0.5) * 400.0
+        vel[2] *= 0.1
+        for p in range(P):
+            xyz[p] = start + vel * float(p)
+        return xyz
+    a, b = tracks(), tracks()
+    own = a[:, :, :1].contiguous()
+    rs = np.random.RandomState(30)
+    pose = torch.from_numpy(native.make_pose(rs.uniform(-180.0, 180.0, n), rs.uniform(-3000.0, 3000.0, n), rs.uniform(-3000.0, 3000.0, n),
+                                             rs.uniform(-300.0, 300.0, n))).to(dev)
+    perm = torch.randperm(n, device=dev, generator=gen)
+    hmd, vmd = torch.empty(n, dtype=torch.float64, device=dev), torch.empty(n, dtype=torch.float64, device=dev)
+    t_cpa, flags = torch.empty(n, dtype=torch.int32, device=dev), torch.empty(n, dtype=torch.uint8, device=dev)
+    totals = torch.zeros(8, dtype=torch.int64, device=dev)
+    torch.cuda.synchronize()
+
+    def timed(fn):
+        ms = []
+        for _ in range(args.warmup + args.launches):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record(stream)
+            fn()
+            e1.record(stream)
+            torch.cuda.synchronize()
+            ms.append(round(e0.elapsed_time(e1), 4))
+        return ms[args.warmup:]
+
+    def launch(xa, n_a, idx_b=0, with_pose=True):
+        totals.zero_()
+        native.miss_distance_device(native.miss_params(n, n_a, n, P), xa.data_ptr(), b.data_ptr(), 0, idx_b, pose.data_ptr() if with_pose else 0, 0,
+                                    hmd.data_ptr(), vmd.data_ptr(), t_cpa.data_ptr(), flags.data_ptr(), totals.data_ptr(), stream=stream.cuda_stream)
+
+    ms, tot = {}, {}
+    for name, fn in (("identity", lambda: launch(a, n)), ("ownship", lambda: launch(own, 1)), ("permuted", lambda: launch(a, n, perm.data_ptr())),
+                     ("identity_nopose", lambda: launch(a, n, with_pose=False))):
+        ms[name] = timed(fn)
+        tot[name] = [int(x) for x in totals.cpu().numpy().view(np.uint64)]
+    sum_ab = timed(lambda: (torch.sum(a), torch.sum(b)))
+    sum_b = timed(lambda: torch.sum(b))
+    med = statistics.median
+    both, one = 2 * 24 * P * n, 24 * P * n + 24 * P
+    out = {"lib": L.lib().emgpu_version().decode(), "device": torch.cuda.get_device_name(0), "n_pairs": n, "points": P,
+           "bytes_read_identity": both, "bytes_read_ownship": one,
+           "identity_ms": ms["identity"], "ownship_ms": ms["ownship"], "permuted_ms": ms["permuted"], "identity_nopose_ms": ms["identity_nopose"],
+           "sum_both_ms": sum_ab, "sum_b_ms": sum_b,
+           "median_ms": {k: round(med(v), 4) for k, v in list(ms.items()) + [("sum_both", sum_ab), ("sum_b", sum_b)]},
+           "identity_GBps": round(both / med(ms["identity"]) / 1e6, 1), "ownship_GBps": round(one / med(ms["ownship"]) / 1e6, 1),
+           "permuted_GBps": round(both / med(ms["permuted"]) / 1e6, 1), "sum_both_GBps": round(both / med(sum_ab) / 1e6, 1),
+           "ratio_identity_to_sum": round(med(ms["identity"]) / med(sum_ab), 3), "ratio_ownship_to_sum_b": round(med(ms["ownship"]) / med(sum_b), 3),
+           "ratio_permuted_to_sum": round(med(ms["permuted"]) / med(sum_ab), 3),
+           "ratio_identity_nopose_to_sum": round(med(ms["identity_nopose"]) / med(sum_ab), 3), "totals": tot}
+    print(json.dumps(out))
+
+
+if __name__ == "__main__":
+    main()
