@@ -158,14 +158,18 @@ __device__ __forceinline__ void pack_bins_pk(const uint32_t (&nb2)[4], uint32_t 
 
 // Eight seconds of one dynamic variable, interior block (every second is a draw), decided from the high halfwords:
 // same outputs as eight_seconds_pass<M, false, false>.  Returns a word that is non-zero when some compare of this lane needs the low
-// halfword (the caller then redoes the block exactly): tie_t | tie_r, the transition compares' and the resample compares' share of it,
-// which only the redo looks at apart.  No carries, no VCC: nothing here needs wait states.
+// halfword (the caller then redoes the block exactly).  No carries, no VCC: nothing here needs wait states.
+// ZL (the dense forms): ONE tie word, kTieT | kTieR of it the transition compares' and the resample compares' share, which only the redo
+// looks at apart; tie_r is not used.  The odd bits of the four counts are ORed as they are and moved, once, into the free bits 8-11 of
+// both halves of the word that collects the resample fields; one mask leaves the tie bits of both kinds.  !ZL (the event-list forms, kept
+// as they were): two words, tie_t and tie_r, and their OR is returned.
 // zwave (ZL only, wave-uniform): some lane of the wave has a column with a real threshold below 2^16; the x_h = 0 test is for those waves.
+constexpr uint32_t kTieT = 0x01000100u, kTieR = 0x00550055u;
 template <int M, bool ZL = true>
 __device__ __forceinline__ uint32_t eight_seconds_pk(const uint4 &th, const uint4 &rh, const uint32_t (&tp)[(M + 1) / 2], uint32_t bnl, uint32_t bnh, uint32_t zc, bool zwave,
                                                  uint32_t RR1, uint32_t cur_in, uint32_t &cur_out, uint32_t &pbA, uint32_t &pbB, uint32_t &hit8, uint32_t &chg8,
                                                  uint32_t &tie_t, uint32_t &tie_r) {
-    uint32_t nb2[4], par = 0u, hitA = 0u;
+    uint32_t nb2[4], acc4[4], par = 0u, hitA = 0u;
 #pragma unroll
     for (int p = 0; p < 4; p++) {
         const uint32_t w = word_of(th, p), wr = word_of(rh, p);
@@ -178,14 +182,20 @@ __device__ __forceinline__ uint32_t eight_seconds_pk(const uint4 &th, const uint
             asm("v_pk_min_u16 %0, %0, 2 op_sel_hi:[1,0]" : "+v"(d));
             if (t == 0) acc = d; else asm("v_pk_add_u16 %0, %0, %1" : "+v"(acc) : "v"(d));
         }
-        par |= acc;                                                                          // an odd count in either half: a tie
+        if constexpr (ZL) acc4[p] = acc; else par |= acc;                                    // an odd count in either half: a tie
         uint32_t cnt = acc;
         if (M > 3) asm("v_pk_lshrrev_b16 %0, 1, %1 op_sel_hi:[0,1]" : "=v"(cnt) : "v"(acc));
         nb2[p] = __builtin_amdgcn_perm(bnh, bnl, cnt);                                       // dbn_sample.m:144: bins of 2p (byte 0) and 2p+1 (byte 2); bytes 1 and 3 (selector 0) are never read
         uint32_t u;                                                                          // resample_events.m:24: 0 no hit, 1 tie, 2 hit
         asm("v_pk_sub_u16 %0, %1, %2 clamp" : "=v"(u) : "s"(RR1), "v"(wr));
         asm("v_pk_min_u16 %0, %0, 2 op_sel_hi:[1,0]" : "+v"(u));
-        hitA = p ? ((hitA << 2) | u) : u;
+        if constexpr (ZL) {   // (as written: left to the compiler the three steps became two shifts, an OR of three, a shift and an OR)
+            if (p) asm("v_lshl_or_b32 %0, %0, 2, %1" : "+v"(hitA) : "v"(u)); else hitA = u;
+        } else hitA = p ? ((hitA << 2) | u) : u;
+    }
+    if constexpr (ZL) {
+        asm("v_or3_b32 %0, %1, %2, %3" : "=v"(par) : "v"(acc4[0]), "v"(acc4[1]), "v"(acc4[2]));
+        asm("v_or_b32 %0, %0, %1" : "+v"(par) : "v"(acc4[3]));
     }
     // x_h = 0 ties with a threshold whose high half is 0 (it has no T'): a lane whose column has one (zc = 1 | 1 << 16) treats every
     // such draw as a tie; on the others (zc = 0) x_h = 0 fires nothing and the difference below saturates to 0.  ZL = false: every lane
@@ -195,14 +205,27 @@ __device__ __forceinline__ uint32_t eight_seconds_pk(const uint4 &th, const uint
         asm("v_pk_min_u16 %0, %1, %2" : "=v"(mz) : "v"(th.x), "v"(th.y));
         asm("v_pk_min_u16 %0, %0, %1" : "+v"(mz) : "v"(th.z));
         asm("v_pk_min_u16 %0, %0, %1" : "+v"(mz) : "v"(th.w));
-        if constexpr (ZL) asm("v_pk_sub_u16 %0, %1, %2 clamp" : "=v"(zt) : "v"(zc), "v"(mz));  // 1 in a half <=> zc and that half of mz is 0
-        else asm("v_pk_sub_u16 %0, 1, %1 op_sel_hi:[0,1] clamp" : "=v"(zt) : "v"(mz));          // 1 in a half <=> that half of mz is 0
+        if constexpr (ZL) {
+            asm("v_pk_sub_u16 %0, %1, %2 clamp" : "=v"(zt) : "v"(zc), "v"(mz));              // 1 in a half <=> zc and that half of mz is 0
+            asm("v_or_b32 %0, %0, %1" : "+v"(par) : "v"(zt));                                // bit 0, where the odd bit of a count is: no zero of zt's on the other path
+        } else asm("v_pk_sub_u16 %0, 1, %1 op_sel_hi:[0,1] clamp" : "=v"(zt) : "v"(mz));    // 1 in a half <=> that half of mz is 0
     }
-    hit8 = (hitA & 0xAAu) | ((hitA >> 17) & 0x55u);                                          // bit 1 of every 2-bit field, MSB-first
+    if constexpr (!ZL) hit8 = (hitA & 0xAAu) | ((hitA >> 17) & 0x55u);                       // bit 1 of every 2-bit field, MSB-first
     pack_bins_pk(nb2, cur_in, cur_out, pbA, pbB, chg8);
-    tie_t = (par & 0x00010001u) | zt;
-    tie_r = hitA & 0x00550055u;
-    return tie_t | tie_r;
+    if constexpr (ZL) {
+        // bit 1 of every 2-bit field, MSB-first: the low half's in place, the high half's between them (hitA holds nothing above bit 23)
+        // ((hitA & 0xAA) | ((hitA >> 17) & ~0xAA) as one bit select; written as an AND and an AND-OR when left to the compiler)
+        asm("v_bitop3_b32 %0, %1, %2, %3 bitop3:0xe4" : "=v"(hit8) : "v"(hitA), "v"(hitA >> 17), "s"(0xAAu));
+        uint32_t z;
+        asm("v_lshl_or_b32 %0, %1, 8, %2" : "=v"(z) : "v"(par), "v"(hitA));                  // a count is at most 2 M <= 14: bits 8-11
+        tie_t = z & (kTieT | kTieR);
+        tie_r = 0u;
+        return tie_t;
+    } else {
+        tie_t = (par & 0x00010001u) | zt;
+        tie_r = hitA & 0x00550055u;
+        return tie_t | tie_r;
+    }
 }
 
 // Eight seconds of one dynamic variable.  Outputs: bins packed 1-based 4 per word (pbA: seconds
@@ -477,7 +500,8 @@ __device__ __forceinline__ void eight_seconds(const Rng &rng, uint32_t tvar, uin
         EMGPU_COUNT(0, (int)(threadIdx.x & 63), 1);
         // wave-uniform: 1 transition, 2 resample low halfwords needed.  (The empty asm pins the two compares to this block: derived from
         // the pass's words alone they were hoisted into the hot path, beside the one ballot they are there to replace.)
-        asm volatile("" : "+v"(tie_t), "+v"(tie_r));
+        if constexpr (ZL) { asm volatile("" : "+v"(tie_t)); tie_r = tie_t & kTieR; tie_t &= kTieT; }   // (one tie word: eight_seconds_pk)
+        else asm volatile("" : "+v"(tie_t), "+v"(tie_r));
         const uint32_t which = edge ? 3u : ((__ballot(tie_t != 0u) != 0ull ? 1u : 0u) | (__ballot(tie_r != 0u) != 0ull ? 2u : 0u));
         if constexpr (CHIP) {
             const uint32_t lw0 = col_slot[LW0], lw1 = M > 2 ? col_slot[LW1] : 0u, codes = col_slot[DW] >> DS;   // (LDS reads)
