@@ -181,155 +181,109 @@ __device__ __forceinline__ double lane_presets(const EmgpuPlan &P, const int32_t
     return lw;
 }
 
-// Initial network + dediscretize + rejection loop, shared by every DBN kernel.
-// bn_sample.m:39-57, dbn_hierarchical_sample.m:25-31, UncorEncounterModel.m:248-281.
-// bin[]: 0-based bins by topological position; val[]: dediscretised f64.  Returns the number of
-// attempts used (>= 1) or -1 when max_attempts was reached; leaves rng.attempt at the accepted attempt.
+// The presets a lane draws its initial network under, for the two init_network_ps forms: from its row of a start grid (Qp->start, row
+// Qp->row[lane], or lane itself without a row list) with its log-weight stored where wanted (Qp->log_weight), or the model's own start
+// (Qp null, or live = false: a lane outside the run reads no row and writes no weight).  PlanPtr: const EmgpuPlan *, or a KargPlan (below)
+// whose entries stay loads from the kernel-argument segment.
+template <int NI, typename PlanPtr>
+__device__ __forceinline__ void lane_start(PlanPtr P, const EmgpuRun &A, const EmgpuPresets *Qp, int64_t lane, bool live, int (&sp)[NI]) {
+    if (Qp && live) {
+        const EmgpuPresets &Q = *Qp;
+        const int64_t row = Q.row ? Q.row[lane] : lane;
+        const double lw = lane_presets<NI>(*(const EmgpuPlan *)P, Q.start ? Q.start + (size_t)row * (size_t)P->ni : nullptr, Q.log_weight ? Q.logp : nullptr, Q.lp_off, A.status, sp);
+        if (Q.log_weight) Q.log_weight[row] = lw;
+    } else {
+#pragma unroll
+        for (int p = 0; p < NI; p++) sp[p] = p < P->ni ? (int)P->i_start[p] : 0;
+    }
+}
+
+// What every DBN kernel stores of lane i after the draw: bit 1 of *status when no attempt was accepted, the attempts used, and the initial
+// state by variable id.  A macro over the kernel's own P, A, NI, bin[] and val[], not a function: k_dbn_step and k_dbn_step2 take the plan
+// and the run by value, and handing them on by reference changed the code of their instances (HISTORY.md section 32).
+#define EMGPU_STORE_INIT(i, attempts_used)                                                                             \
+    {                                                                                                                  \
+        if (attempts_used < 0) atomicOr(A.status, 1u);                                                                 \
+        if (A.attempts) A.attempts[i] = attempts_used;                                                                 \
+        _Pragma("unroll") for (int p = 0; p < NI; p++) {                                                               \
+            if (p < P.ni) {                                                                                            \
+                if (A.init_bin) A.init_bin[(size_t)P.i_var[p] * A.ld + i] = (uint8_t)(bin[p] + 1);                     \
+                if (A.init_val) A.init_val[(size_t)P.i_var[p] * A.ld + i] = (float)val[p];                             \
+            }                                                                                                          \
+        }                                                                                                              \
+    }
+
+// Initial network + dediscretize + rejection loop, shared by every DBN kernel: four forms of one body (emgpu_init_body.h), by how the plan
+// is read and where a node's preset comes from.  bin[]: 0-based bins by topological position; val[]: dediscretised f64.  Each returns the
+// number of attempts used (>= 1) or -1 when max_attempts was reached, and leaves rng.attempt at the accepted attempt.
+#define EMGPU_INIT_P(f) P.f
+#define EMGPU_INIT_FRESH_PLAN
+// The plan by reference, the model's own presets.
 template <int NI>
 __device__ __forceinline__ int32_t init_network(const EmgpuPlan &P, const EmgpuRun &A, Rng &rng, int (&bin)[NI], double (&val)[NI]) {
     int32_t attempts_used = -1;
     const bool no_dedisc = (A.flags & EMGPU_FLAG_NO_DEDISC) != 0;
-    for (uint32_t attempt = 0; attempt < (uint32_t)A.max_attempts; attempt++) {
-        rng.attempt = attempt;
-        uint4 wc = make_uint4(0, 0, 0, 0);
-        int wblk = -1;
-#pragma unroll
-        for (int p = 0; p < NI; p++) {
-            if (p < P.ni && P.i_start[p] != 0) { // bn_sample.m:44-50
-                bin[p] = (int)P.i_start[p] - 1;
-            } else if (p < P.ni) {
-                uint32_t col = 0; // asub2ind.m:13-14 as strides
-#pragma unroll
-                for (int q = 0; q < p; q++) col += P.i_stride[p][q] * (uint32_t)bin[q];
-                const int r = P.i_r[p];
-                const int var = P.i_var[p];
-                if ((var >> 2) != wblk) { wblk = var >> 2; wc = rng.block(EMGPU_SEC_INIT, 0u, (uint32_t)wblk); }
-                bin[p] = draw_bin(P.thr + P.i_off[p] + (size_t)col * (uint32_t)(r - 1), r, word_of(wc, var & 3)); // bn_sample.m:55
-            }
-        }
-        // dbn_hierarchical_sample.m:25-31
-        wblk = -1;
-#pragma unroll
-        for (int p = 0; p < NI; p++) {
-            double v = (double)(bin[p] + 1);
-            if (p < P.ni && !no_dedisc && P.i_nb[p] != 0 && !P.i_skip[p]) {
-                const int var = P.i_var[p];
-                if ((var >> 2) != wblk) { wblk = var >> 2; wc = rng.block(EMGPU_SEC_DEDISC_INIT, 0u, (uint32_t)wblk); }
-                v = (P.i_zero[p] == bin[p] + 1) ? 0.0 : dedisc_f64(P.bnd, P.i_boff[p], bin[p], word_of(wc, var & 3));
-            }
-            val[p] = v;
-        }
-        // UncorEncounterModel.m:259-272
-        if (A.pos_L >= 0 && (A.layers != nullptr || (A.flags & EMGPU_FLAG_QUANTIZE500))) {
-            double h_ft = pick<NI>(val, A.pos_L);
-            if (A.layers != nullptr) {
-                int b = (int)h_ft;
-                b = b < 1 ? 1 : (b > A.n_layers ? A.n_layers : b);
-                const double lo = A.layers[2 * (b - 1)], hi = A.layers[2 * (b - 1) + 1];
-                const uint4 wl = rng.block(EMGPU_SEC_LAYER, 0u, 0u);
-                {
-#pragma clang fp contract(off)
-                    const double d = hi - lo;
-                    const double m = uniform32(wl.x) * d;
-                    h_ft = lo + m;
-                }
-            }
-            if ((A.flags & EMGPU_FLAG_QUANTIZE500) && A.pos_dh >= 0 && pick<NI>(val, A.pos_dh) == 0.0) h_ft = round500(h_ft);
-            put<NI>(val, A.pos_L, h_ft);
-        }
-        bool good = true;
-        if (A.pos_v >= 0 && A.pos_dh >= 0) { // :275
-#pragma clang fp contract(off)
-            const double lhs = pick<NI>(val, A.pos_v) * 1.68781;
-            const double rhs = fabs(pick<NI>(val, A.pos_dh)) / 60.0;
-            good = lhs > rhs;
-        }
-        if (good) { attempts_used = (int32_t)attempt + 1; break; }
-    }
+#define EMGPU_INIT_PRESET(p) const auto &preset = P.i_start[p];
+#include "emgpu_init_body.h"
+#undef EMGPU_INIT_PRESET
     return attempts_used;
 }
 
-// The same with the lane's presets possibly coming from a start grid (Q->start, row `lane`) and its log-weight wanted (Q->log_weight):
-// k_dbn_generic and the +start instances of the fast kernel (Q null: the model's own start, like init_network).  The lane's row of the grid
-// is Q->row[lane] (lane itself without a row list).  live = false: a lane outside the run (the fast kernel keeps those alive as workers of
-// their wave) -- it reads no row and writes no weight, and draws under the model's own start.
+// The same with the lane's presets possibly coming from a start grid and its log-weight wanted (lane_start): k_dbn_generic and the +start
+// instances of the fast kernel.  live = false: a lane outside the run (the fast kernel keeps those alive as workers of their wave).
 template <int NI>
 __device__ __forceinline__ int32_t init_network_ps(const EmgpuPlan &P, const EmgpuRun &A, const EmgpuPresets *Qp, Rng &rng, int (&bin)[NI], double (&val)[NI], int64_t lane,
                                                    bool live = true) {
-    constexpr bool PS = true;
     int32_t attempts_used = -1;
     const bool no_dedisc = (A.flags & EMGPU_FLAG_NO_DEDISC) != 0;
     int sp[NI];
-    if constexpr (PS) {
-        if (Qp && live) {
-            const EmgpuPresets &Q = *Qp;
-            const int64_t row = Q.row ? Q.row[lane] : lane;
-            const double lw = lane_presets<NI>(P, Q.start ? Q.start + (size_t)row * (size_t)P.ni : nullptr, Q.log_weight ? Q.logp : nullptr, Q.lp_off, A.status, sp);
-            if (Q.log_weight) Q.log_weight[row] = lw;
-        } else {
-#pragma unroll
-            for (int p = 0; p < NI; p++) sp[p] = p < P.ni ? (int)P.i_start[p] : 0;
-        }
-    }
-    for (uint32_t attempt = 0; attempt < (uint32_t)A.max_attempts; attempt++) {
-        rng.attempt = attempt;
-        uint4 wc = make_uint4(0, 0, 0, 0);
-        int wblk = -1;
-#pragma unroll
-        for (int p = 0; p < NI; p++) {
-            const int preset = PS ? sp[p] : (p < P.ni ? (int)P.i_start[p] : 0);
-            if (p < P.ni && preset != 0) { // bn_sample.m:44-50
-                bin[p] = preset - 1;
-            } else if (p < P.ni) {
-                uint32_t col = 0; // asub2ind.m:13-14 as strides
-#pragma unroll
-                for (int q = 0; q < p; q++) col += P.i_stride[p][q] * (uint32_t)bin[q];
-                const int r = P.i_r[p];
-                const int var = P.i_var[p];
-                if ((var >> 2) != wblk) { wblk = var >> 2; wc = rng.block(EMGPU_SEC_INIT, 0u, (uint32_t)wblk); }
-                bin[p] = draw_bin(P.thr + P.i_off[p] + (size_t)col * (uint32_t)(r - 1), r, word_of(wc, var & 3)); // bn_sample.m:55
-            }
-        }
-        // dbn_hierarchical_sample.m:25-31
-        wblk = -1;
-#pragma unroll
-        for (int p = 0; p < NI; p++) {
-            double v = (double)(bin[p] + 1);
-            if (p < P.ni && !no_dedisc && P.i_nb[p] != 0 && !P.i_skip[p]) {
-                const int var = P.i_var[p];
-                if ((var >> 2) != wblk) { wblk = var >> 2; wc = rng.block(EMGPU_SEC_DEDISC_INIT, 0u, (uint32_t)wblk); }
-                v = (P.i_zero[p] == bin[p] + 1) ? 0.0 : dedisc_f64(P.bnd, P.i_boff[p], bin[p], word_of(wc, var & 3));
-            }
-            val[p] = v;
-        }
-        // UncorEncounterModel.m:259-272
-        if (A.pos_L >= 0 && (A.layers != nullptr || (A.flags & EMGPU_FLAG_QUANTIZE500))) {
-            double h_ft = pick<NI>(val, A.pos_L);
-            if (A.layers != nullptr) {
-                int b = (int)h_ft;
-                b = b < 1 ? 1 : (b > A.n_layers ? A.n_layers : b);
-                const double lo = A.layers[2 * (b - 1)], hi = A.layers[2 * (b - 1) + 1];
-                const uint4 wl = rng.block(EMGPU_SEC_LAYER, 0u, 0u);
-                {
-#pragma clang fp contract(off)
-                    const double d = hi - lo;
-                    const double m = uniform32(wl.x) * d;
-                    h_ft = lo + m;
-                }
-            }
-            if ((A.flags & EMGPU_FLAG_QUANTIZE500) && A.pos_dh >= 0 && pick<NI>(val, A.pos_dh) == 0.0) h_ft = round500(h_ft);
-            put<NI>(val, A.pos_L, h_ft);
-        }
-        bool good = true;
-        if (A.pos_v >= 0 && A.pos_dh >= 0) { // :275
-#pragma clang fp contract(off)
-            const double lhs = pick<NI>(val, A.pos_v) * 1.68781;
-            const double rhs = fabs(pick<NI>(val, A.pos_dh)) / 60.0;
-            good = lhs > rhs;
-        }
-        if (good) { attempts_used = (int32_t)attempt + 1; break; }
-    }
+    lane_start<NI>(&P, A, Qp, lane, live, sp);
+#define EMGPU_INIT_PRESET(p) const int preset = sp[p];
+#include "emgpu_init_body.h"
+#undef EMGPU_INIT_PRESET
     return attempts_used;
 }
+#undef EMGPU_INIT_P
+#undef EMGPU_INIT_FRESH_PLAN
+
+// init_network for the dense 16-variable instances of k_dbn_step2 (and the -DEMGPU_FAST_INIT_KARG measuring variant of k_uncor_fast),
+// reading the plan through the kernel-argument segment with the pointer laundered once per attempt.  The initial network of 16 variables
+// uses 120 parent strides + five small tables: as loop invariants of the attempt loop they are loaded ahead of it, outlive the scalar
+// register file (657 v_writelane ahead of the loop, 708 v_readlane inside it) and keep 30 vector registers as spill space for the whole
+// kernel: 155 registers, three waves per SIMD.  Loaded where they are used they are scalar loads and nothing else: <= 128 registers, which
+// (with the 36-word LDS rows of coop_dedisc_sc) is a fourth wave.
+typedef const __attribute__((address_space(4))) EmgpuPlan *KargPlan;
+#define EMGPU_INIT_P(f) P->f
+#define EMGPU_INIT_FRESH_PLAN KargPlan P = Pk; asm volatile("" : "+s"(P));   // (the plan's entries are loaded where this attempt uses them)
+template <int NI>
+__device__ __forceinline__ int32_t init_network_karg(KargPlan Pk, const EmgpuRun &A, Rng &rng, int (&bin)[NI], double (&val)[NI]) {
+    int32_t attempts_used = -1;
+    const bool no_dedisc = (A.flags & EMGPU_FLAG_NO_DEDISC) != 0;
+#define EMGPU_INIT_PRESET(p) const auto &preset = P->i_start[p];
+#include "emgpu_init_body.h"
+#undef EMGPU_INIT_PRESET
+    return attempts_used;
+}
+
+// init_network_ps the same way, for the +start twin of the dense 16-variable instances (emgpu_kernels_step2_ps.hip): the lane's presets
+// are worked out once, through a pointer laundered of its own (lane_presets' 120 strides are not kept for the attempt loop), and live in
+// vector registers across the attempts; everything else of the plan is loaded where an attempt uses it.
+template <int NI>
+__device__ __forceinline__ int32_t init_network_ps_karg(KargPlan Pk, const EmgpuRun &A, const EmgpuPresets *Qp, Rng &rng, int (&bin)[NI], double (&val)[NI], int64_t lane,
+                                                        bool live) {
+    int32_t attempts_used = -1;
+    const bool no_dedisc = (A.flags & EMGPU_FLAG_NO_DEDISC) != 0;
+    int sp[NI];
+    {
+        EMGPU_INIT_FRESH_PLAN
+        lane_start<NI>(P, A, Qp, lane, live, sp);
+    }
+#define EMGPU_INIT_PRESET(p) const int &preset = sp[p];
+#include "emgpu_init_body.h"
+#undef EMGPU_INIT_PRESET
+    return attempts_used;
+}
+#undef EMGPU_INIT_P
+#undef EMGPU_INIT_FRESH_PLAN
 
 } // namespace emgpu

@@ -34,14 +34,7 @@ __global__ void __launch_bounds__(256) k_dbn_generic(const EmgpuPlan P, const Em
     for (int p = 0; p < NI; p++) { bin[p] = 0; val[p] = 0.0; }
 
     const int32_t attempts_used = init_network_ps<NI>(P, A, Q, rng, bin, val, i);   // (the one DBN kernel that takes a start grid)
-    if (attempts_used < 0) atomicOr(A.status, 1u);
-    if (A.attempts) A.attempts[i] = attempts_used;
-#pragma unroll
-    for (int p = 0; p < NI; p++) {
-        if (p >= P.ni) continue;
-        if (A.init_bin) A.init_bin[(size_t)P.i_var[p] * A.ld + i] = (uint8_t)(bin[p] + 1);
-        if (A.init_val) A.init_val[(size_t)P.i_var[p] * A.ld + i] = (float)val[p];
-    }
+    EMGPU_STORE_INIT(i, attempts_used);
     if (P.nd == 0 && !want_events) return;
 
     // ---------------- transition network ---------------------------------------------------------
@@ -228,6 +221,7 @@ __global__ void __launch_bounds__(256) k_bn(const EmgpuPlan P, const EmgpuBnRun 
     }
     for (uint32_t attempt = 0; attempt < (uint32_t)A.max_attempts; attempt++) {
         rng.attempt = attempt;
+        // "preset or draw a bin" as in emgpu_init_body.h, written out: taken from there it moved k_bn<NI,false>'s registers (HISTORY.md section 32)
         uint4 wc = make_uint4(0, 0, 0, 0);
         int wblk = -1;
 #pragma unroll
@@ -246,6 +240,7 @@ __global__ void __launch_bounds__(256) k_bn(const EmgpuPlan P, const EmgpuBnRun 
                 bin[p] = draw_bin(P.thr + P.i_off[p] + (size_t)col * (uint32_t)(r - 1), r, word_of(wc, var & 3));
             }
         }
+        // the dediscretize stage really is k_bn's own: EMGPU_SEC_GEOM_DEDISC, no i_skip, and the bounds test in the same loop
         wblk = -1;
         bool good = true;
 #pragma unroll

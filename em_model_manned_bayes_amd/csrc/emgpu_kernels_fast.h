@@ -29,7 +29,6 @@
 #include "emgpu_coop.h"
 #include "emgpu_device.h"
 #include "emgpu_events.h"
-#include "emgpu_init_karg.h"
 #include "emgpu_launch.h"
 
 namespace emgpu {
@@ -618,17 +617,7 @@ __device__ __forceinline__ void uncor_fast_body(const EmgpuPlan &P, const EmgpuR
         attempts_used = init_network<NI>(P, A, rng, bin, val);
 #endif
     }
-    if (valid) {
-        if (attempts_used < 0) atomicOr(A.status, 1u);
-        if (A.attempts) A.attempts[i] = attempts_used;
-#pragma unroll
-        for (int p = 0; p < NI; p++) {
-            if (p < P.ni) {
-                if (A.init_bin) A.init_bin[(size_t)P.i_var[p] * A.ld + i] = (uint8_t)(bin[p] + 1);
-                if (A.init_val) A.init_val[(size_t)P.i_var[p] * A.ld + i] = (float)val[p];
-            }
-        }
-    }
+    if (valid) EMGPU_STORE_INIT(i, attempts_used);
     W.attempt[lane] = rng.attempt;
     __syncthreads(); // s_bnd visible to every wave (the only block-wide barrier)
 

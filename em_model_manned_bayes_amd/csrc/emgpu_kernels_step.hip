@@ -48,17 +48,7 @@ __global__ void __launch_bounds__(256, 2) k_dbn_step(const EmgpuPlan P, const Em
 #pragma unroll
     for (int p = 0; p < NI; p++) { bin[p] = 0; val[p] = 0.0; }
     const int32_t attempts_used = init_network<NI>(P, A, rng, bin, val);
-    if (valid) {
-        if (attempts_used < 0) atomicOr(A.status, 1u);
-        if (A.attempts) A.attempts[i] = attempts_used;
-#pragma unroll
-        for (int p = 0; p < NI; p++) {
-            if (p < P.ni) {
-                if (A.init_bin) A.init_bin[(size_t)P.i_var[p] * A.ld + i] = (uint8_t)(bin[p] + 1);
-                if (A.init_val) A.init_val[(size_t)P.i_var[p] * A.ld + i] = (float)val[p];
-            }
-        }
-    }
+    if (valid) EMGPU_STORE_INIT(i, attempts_used);
     W.attempt[lane] = rng.attempt;
     const uint32_t *__restrict__ gtab = CT ? P.cthr : P.thr + P.d_off[0];
     const uint32_t ntab = CT ? P.cthr_total : P.thr_total - P.d_off[0];

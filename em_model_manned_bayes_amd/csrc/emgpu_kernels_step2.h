@@ -22,7 +22,6 @@
 #include "emgpu_coop.h"
 #include "emgpu_device.h"
 #include "emgpu_events.h"
-#include "emgpu_init_karg.h"
 #include "emgpu_launch.h"
 
 namespace emgpu {

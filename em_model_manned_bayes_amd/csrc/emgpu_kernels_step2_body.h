@@ -52,17 +52,7 @@
             else attempts_used = init_network_ps<NI>(P, A, Q, rng, bin, val, i, valid);
         } else if constexpr (!LBK) attempts_used = init_network_karg<NI>((KargPlan)__builtin_amdgcn_kernarg_segment_ptr(), A, rng, bin, val);
         else attempts_used = init_network<NI>(P, A, rng, bin, val);
-        if (valid) {
-            if (attempts_used < 0) atomicOr(A.status, 1u);
-            if (A.attempts) A.attempts[i] = attempts_used;
-#pragma unroll
-            for (int p = 0; p < NI; p++) {
-                if (p < P.ni) {
-                    if (A.init_bin) A.init_bin[(size_t)P.i_var[p] * A.ld + i] = (uint8_t)(bin[p] + 1);
-                    if (A.init_val) A.init_val[(size_t)P.i_var[p] * A.ld + i] = (float)val[p];
-                }
-            }
-        }
+        if (valid) EMGPU_STORE_INIT(i, attempts_used);
         // The event-list set-up looks plan arrays up by run-time positions (P.i_zero[P.a_pos[b]], P.d_ivar[P.d_emit[e]]).  Done on the by-value
         // kernel argument itself that made the 16-variable instances keep a private copy of the whole plan (2.6 KB of scratch per lane,
         // every later P.x a scratch load, the table's buffer resource no longer provably uniform: a waterfall loop round every gather --
