@@ -26,6 +26,7 @@ TRANSITION_REFERENCE_AUTO, TRANSITION_PER_STEP = 0, 1
 VALUE_F32, VALUE_F64 = 0, 1       # emgpu_discretize_params.value_type
 TRACKS_PLANAR, TRACKS_ROWS = 0, 1 # emgpu_track_values_params.layout
 MISS_NMAC_CPA, MISS_NMAC_ANY, MISS_NO_CPA, MISS_BAD_INDEX = 1, 2, 4, 8   # emgpu_miss_distance_device's flags
+ENC_END, ENC_FALLBACK, ENC_NO_ENTRY, ENC_SATURATED, ENC_BAD_INDEX = 1, 2, 4, 8, 16   # emgpu_encounter_pose_device's flags
 FLAG_QUANTIZE500, FLAG_NO_RESAMPLE, FLAG_NO_DEDISC, FLAG_NO_TERMINATOR, FLAG_LOCAL_SMOOTH = 1, 2, 4, 8, 16
 
 # MATLAB error identifiers the reference raises for the same condition
@@ -168,6 +169,12 @@ class MissParams(C.Structure):     # emgpu_miss_params
                 ("points", C.c_int32), ("reserved", C.c_int32), ("nmac_h_ft", C.c_double), ("nmac_v_ft", C.c_double)]
 
 
+class EncounterParams(C.Structure):     # emgpu_encounter_params
+    _fields_ = [("n_pairs", C.c_int64), ("n_a", C.c_int64), ("n_b", C.c_int64), ("ld_a", C.c_int64), ("ld_b", C.c_int64),
+                ("points", C.c_int32), ("max_attempts", C.c_int32), ("seed", C.c_uint64), ("first_index", C.c_uint64),
+                ("radius_ft", C.c_double), ("half_height_ft", C.c_double), ("rate_scale", C.c_double)]
+
+
 class BnParams(C.Structure):
     _fields_ = [("seed", C.c_uint64), ("first_index", C.c_uint64), ("n", C.c_int64), ("flags", C.c_uint32),
                 ("max_attempts", C.c_int32), ("bounds_sample", C.c_void_p),
@@ -202,6 +209,7 @@ SYMBOLS = [
     "emgpu_track_values_device", "emgpu_track_values_host",
     "emgpu_count_dbn_weighted_device", "emgpu_count_dbn_weighted_host",
     "emgpu_miss_distance_device",
+    "emgpu_encounter_pose_device",
 ]
 
 _lib = None
@@ -394,6 +402,7 @@ def lib():
     for f in (L.emgpu_track_values_device, L.emgpu_track_values_host):
         f.argtypes = [C.c_void_p, C.POINTER(TrackValuesParams)] + [C.c_void_p] * 3
     L.emgpu_miss_distance_device.argtypes = [C.c_void_p, C.POINTER(MissParams)] + [C.c_void_p] * 11
+    L.emgpu_encounter_pose_device.argtypes = [C.c_void_p, C.POINTER(EncounterParams)] + [C.c_void_p] * 9
     _lib = L
     return L
 

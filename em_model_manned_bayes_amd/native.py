@@ -1210,14 +1210,7 @@ def miss_distance(xyz_a, xyz_b, idx_a=None, idx_b=None, pose_b=None, weights=Non
     calls produced the inputs -- its stream is used when it was given one (Context.stream), and when it runs on a stream of its own
     (Context.stream is None) ctx.sync() is called first, so that the inputs are complete."""
     import torch
-    n_of = lambda t: int(t.shape[0 if layout == "rows" else 2])          # noqa: E731
-    for t in (xyz_a, xyz_b):
-        if getattr(t, "ndim", 0) != 3:
-            raise ValueError("xyz must be [n, points, 3] (layout 'rows') or [points, 3, n] ('planar')")
-    n_a, n_b = n_of(xyz_a), n_of(xyz_b)
-    idx = [None if i is None else np.ascontiguousarray(i, dtype=np.int64).reshape(-1) if not isinstance(i, torch.Tensor) else i
-           for i in (idx_a, idx_b)]
-    n_pairs = max([len(i) for i in idx if i is not None] + [n for n, i in zip((n_a, n_b), idx) if i is None])
+    n_a, n_b, idx, n_pairs = _pair_columns(xyz_a, xyz_b, idx_a, idx_b, layout)
     w = None if weights is None else _weights_array(weights, n_pairs)
     if pose_b is not None:
         pose_b = np.ascontiguousarray(pose_b, dtype=np.float64) if not isinstance(pose_b, torch.Tensor) else pose_b
@@ -1248,6 +1241,141 @@ def miss_distance(xyz_a, xyz_b, idx_a=None, idx_b=None, pose_b=None, weights=Non
         fl = flags.cpu().numpy()
         return {"hmd_ft": hmd.cpu().numpy(), "vmd_ft": vmd.cpu().numpy(), "t_cpa": t_cpa.cpu().numpy(), "flags": fl,
                 "nmac": (fl & L.MISS_NMAC_CPA) != 0, "totals": totals.cpu().numpy().view(np.uint64)}
+
+
+def encounter_params(n_pairs, n_a, n_b, points, radius_ft, half_height_ft, seed, first_index=0, max_attempts=16, rate_scale=1.0, ld_a=0, ld_b=0):
+    """emgpu_encounter_params: n_pairs pairs of a column of set A (the ownship; n_a columns, pitch ld_a, 0 = n_a) and a column of set B (the
+    intruder), an encounter cylinder of radius_ft and half_height_ft around the ownship, the seed and the global index of pair 0;
+    rate_scale divides the rate where it is folded into weights_out."""
+    p = L.EncounterParams()
+    p.n_pairs, p.n_a, p.n_b, p.ld_a, p.ld_b, p.points = int(n_pairs), int(n_a), int(n_b), int(ld_a), int(ld_b), int(points)
+    p.max_attempts, p.seed, p.first_index = int(max_attempts), int(seed) & (2**64 - 1), int(first_index) & (2**64 - 1)
+    p.radius_ft, p.half_height_ft, p.rate_scale = float(radius_ft), float(half_height_ft), float(rate_scale)
+    return p
+
+
+def encounter_pose_device(params, xyz_a, xyz_b, idx_a=0, idx_b=0, weights_in=0, pose=0, rate=0, flags=0, weights_out=0, stream=None):
+    """emgpu_encounter_pose_device: asynchronous, raw device pointers (ints, 0 = none; params: encounter_params).  xyz_a / xyz_b f64 PLANAR
+    [P, 3, ld] (points 0 and 1 are read), idx_a / idx_b int64 [n_pairs], weights_in uint32 [n_pairs]; pose f64 [5, n_pairs] (what
+    miss_distance_device takes as pose_b), rate f64, flags uint8 (L.ENC_*), weights_out uint32 [n_pairs] each.  No context: the current
+    device and `stream`, a raw hipStream_t (0: the HIP default stream; None: torch's current stream)."""
+    if stream is None:
+        import torch
+        stream = torch.cuda.current_stream().cuda_stream
+    L.check(L.lib().emgpu_encounter_pose_device(C.c_void_p(int(stream) or None), C.byref(params), *(C.c_void_p(int(a) or None) for a in (
+        xyz_a, xyz_b, idx_a, idx_b, weights_in, pose, rate, flags, weights_out))))
+
+
+def _pair_columns(xyz_a, xyz_b, idx_a, idx_b, layout):
+    """(n_a, n_b, [idx_a, idx_b] as int64 vectors or None, n_pairs) of a pairing of two sets of tracks, as miss_distance reads its arguments"""
+    import torch
+    n_of = lambda t: int(t.shape[0 if layout == "rows" else 2])          # noqa: E731
+    for t in (xyz_a, xyz_b):
+        if getattr(t, "ndim", 0) != 3:
+            raise ValueError("xyz must be [n, points, 3] (layout 'rows') or [points, 3, n] ('planar')")
+    n_a, n_b = n_of(xyz_a), n_of(xyz_b)
+    idx = [None if i is None else np.ascontiguousarray(i, dtype=np.int64).reshape(-1) if not isinstance(i, torch.Tensor) else i
+           for i in (idx_a, idx_b)]
+    return n_a, n_b, idx, max([len(i) for i in idx if i is not None] + [n for n, i in zip((n_a, n_b), idx) if i is None])
+
+
+def _encounter_pose_tensors(a, b, n_a, n_b, n_pairs, d_ia, d_ib, d_w, want_weights, radius_ft, half_height_ft, seed, rate_scale, first_index,
+                            max_attempts, stream):
+    """k_encounter_pose on PLANAR device tensors a, b: the device tensors (pose [5, n_pairs], rate, flags, weights or None), launched on
+    `stream` (None: torch's current stream) and not waited for"""
+    import torch
+    dev = a.device
+    pose = torch.empty((5, n_pairs), dtype=torch.float64, device=dev)
+    rate = torch.empty(n_pairs, dtype=torch.float64, device=dev)
+    flags = torch.empty(n_pairs, dtype=torch.uint8, device=dev)
+    w_out = torch.empty(n_pairs, dtype=torch.int32, device=dev) if want_weights else None
+    ptr = lambda t: 0 if t is None else t.data_ptr()                 # noqa: E731
+    p = encounter_params(n_pairs, n_a, n_b, a.shape[0], radius_ft, half_height_ft, seed, first_index, max_attempts,
+                         1.0 if rate_scale is None else rate_scale)
+    encounter_pose_device(p, ptr(a), ptr(b), ptr(d_ia), ptr(d_ib), ptr(d_w), ptr(pose), ptr(rate), ptr(flags), ptr(w_out), stream=stream)
+    return pose, rate, flags, w_out
+
+
+def encounter_pose(xyz_a, xyz_b, radius_ft, half_height_ft, seed, idx_a=None, idx_b=None, weights=None, rate_scale=None, first_index=0,
+                   max_attempts=16, layout="rows", ctx=None, stream=None):
+    """Places each intruder (set B) on the encounter cylinder of radius_ft and half_height_ft around its ownship (set A) on the GPU
+    (emgpu_encounter_pose_device; the definition is in include/emgpu.h): a seeded random heading, an entry point where the intruder flies
+    into the cylinder, drawn in proportion to the flux through the side and the ends, and the volume the cylinder sweeps per second
+    relative to the intruder, in cubic feet per second.  xyz_a / xyz_b, idx_a / idx_b, layout, ctx and stream are miss_distance's; only the
+    first two points of each track are read.  Pair i draws from the global index first_index + i, so a call on rows k .. of a set with
+    first_index=k gives rows k .. of the call on the whole set.
+    weights: integers [n_pairs] in 0 .. 2**32 - 1 (quantize_weights) to fold the rate into; True: fold it into weights of 1.  Either needs
+    rate_scale (ValueError without): the weight is floor(w * rate / rate_scale + 0.5), clamped to 2**32 - 1 (L.ENC_SATURATED), so
+    rate_scale is the rate that keeps a weight as it is -- ks times a bound on the relative speed is the caller's to give.
+    Returns {"pose" float64 [5, n_pairs] (miss_distance's pose_b), "rate" float64, "flags" uint8 (L.ENC_*), "weights" uint32 or None}."""
+    import torch
+    n_a, n_b, idx, n_pairs = _pair_columns(xyz_a, xyz_b, idx_a, idx_b, layout)
+    want_weights = weights is not None and weights is not False
+    if want_weights and rate_scale is None:
+        raise ValueError("weights need a rate_scale: the rate that leaves a weight as it is")
+    w = _weights_array(weights, n_pairs) if want_weights and weights is not True else None
+    dev = xyz_a.device if isinstance(xyz_a, torch.Tensor) and xyz_a.is_cuda else torch.device("cuda", torch.cuda.current_device())
+    if ctx is not None and stream is None:
+        stream = ctx.stream
+        if stream is None:
+            ctx.sync()
+    with torch.cuda.device(dev):
+        a, b = _planar_tracks(xyz_a, layout, dev), _planar_tracks(xyz_b, layout, dev)
+        if a.shape[0] != b.shape[0]:
+            raise ValueError("both sets of tracks must hold the same number of points")
+        up = lambda x: None if x is None else (x if isinstance(x, torch.Tensor) else torch.from_numpy(x)).to(device=dev, dtype=torch.int64).contiguous()  # noqa: E731
+        d_w = None if w is None else torch.from_numpy(w.view(np.int32)).to(dev)
+        if stream is not None:
+            torch.cuda.synchronize(dev)      # the uploads ran on torch's stream, the kernel will not
+        pose, rate, flags, w_out = _encounter_pose_tensors(a, b, n_a, n_b, n_pairs, up(idx[0]), up(idx[1]), d_w, want_weights, radius_ft,
+                                                           half_height_ft, seed, rate_scale, first_index, max_attempts, stream)
+        if stream is not None:
+            torch.cuda.synchronize(dev)
+        return {"pose": pose.cpu().numpy(), "rate": rate.cpu().numpy(), "flags": flags.cpu().numpy(),
+                "weights": None if w_out is None else w_out.cpu().numpy().view(np.uint32)}
+
+
+def encounter_miss(xyz_a, xyz_b, radius_ft, half_height_ft, seed, idx_a=None, idx_b=None, weights=None, rate_scale=None, first_index=0,
+                   max_attempts=16, nmac_h_ft=500.0, nmac_v_ft=100.0, layout="rows", ctx=None, stream=None):
+    """encounter_pose and then miss_distance on one stream, the pose and the rate-folded weights never leaving the device: the intruders
+    placed on the encounter cylinder, then HMD, VMD, CPA time and NMAC flags of the pairs.  The arguments are encounter_pose's and the
+    NMAC thresholds.  With weights (and rate_scale) totals[5:8] are sums of w * rate / rate_scale, so totals[6] / totals[5] is
+    P(NMAC | encounter); without, every pair counts 1 there.
+    Returns miss_distance's dict plus "rate" float64, "encounter_flags" uint8 (L.ENC_*) and "weights" uint32 or None."""
+    import torch
+    n_a, n_b, idx, n_pairs = _pair_columns(xyz_a, xyz_b, idx_a, idx_b, layout)
+    want_weights = weights is not None and weights is not False
+    if want_weights and rate_scale is None:
+        raise ValueError("weights need a rate_scale: the rate that leaves a weight as it is")
+    w = _weights_array(weights, n_pairs) if want_weights and weights is not True else None
+    dev = xyz_a.device if isinstance(xyz_a, torch.Tensor) and xyz_a.is_cuda else torch.device("cuda", torch.cuda.current_device())
+    if ctx is not None and stream is None:
+        stream = ctx.stream
+        if stream is None:
+            ctx.sync()
+    with torch.cuda.device(dev):
+        a, b = _planar_tracks(xyz_a, layout, dev), _planar_tracks(xyz_b, layout, dev)
+        if a.shape[0] != b.shape[0]:
+            raise ValueError("both sets of tracks must hold the same number of points")
+        up = lambda x: None if x is None else (x if isinstance(x, torch.Tensor) else torch.from_numpy(x)).to(device=dev, dtype=torch.int64).contiguous()  # noqa: E731
+        d_ia, d_ib = up(idx[0]), up(idx[1])
+        d_w = None if w is None else torch.from_numpy(w.view(np.int32)).to(dev)
+        hmd, vmd = torch.empty(n_pairs, dtype=torch.float64, device=dev), torch.empty(n_pairs, dtype=torch.float64, device=dev)
+        t_cpa, flags = torch.empty(n_pairs, dtype=torch.int32, device=dev), torch.empty(n_pairs, dtype=torch.uint8, device=dev)
+        totals = torch.zeros(8, dtype=torch.int64, device=dev)
+        ptr = lambda t: 0 if t is None else t.data_ptr()                 # noqa: E731
+        if stream is not None:
+            torch.cuda.synchronize(dev)      # the uploads ran on torch's stream, the kernels will not
+        pose, rate, eflags, w_out = _encounter_pose_tensors(a, b, n_a, n_b, n_pairs, d_ia, d_ib, d_w, want_weights, radius_ft, half_height_ft,
+                                                            seed, rate_scale, first_index, max_attempts, stream)
+        miss_distance_device(miss_params(n_pairs, n_a, n_b, a.shape[0], nmac_h_ft, nmac_v_ft), ptr(a), ptr(b), ptr(d_ia), ptr(d_ib), ptr(pose),
+                             ptr(w_out), ptr(hmd), ptr(vmd), ptr(t_cpa), ptr(flags), ptr(totals), stream=stream)
+        if stream is not None:
+            torch.cuda.synchronize(dev)
+        fl = flags.cpu().numpy()
+        return {"hmd_ft": hmd.cpu().numpy(), "vmd_ft": vmd.cpu().numpy(), "t_cpa": t_cpa.cpu().numpy(), "flags": fl,
+                "nmac": (fl & L.MISS_NMAC_CPA) != 0, "totals": totals.cpu().numpy().view(np.uint64), "rate": rate.cpu().numpy(),
+                "encounter_flags": eflags.cpu().numpy(), "weights": None if w_out is None else w_out.cpu().numpy().view(np.uint32)}
 
 
 def device_upload(ctx, addr, src):

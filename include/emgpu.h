@@ -609,6 +609,65 @@ int emgpu_miss_distance_device(void *hip_stream, const emgpu_miss_params *p, con
                                const int64_t *idx_b, const double *pose_b, const uint32_t *weights, double *hmd, double *vmd,
                                int32_t *t_cpa, uint8_t *flags, uint64_t *totals);
 
+/* ------------------------------------------------------------------------------------------------
+ * Placing the intruder on the encounter cylinder: per pair a random heading of the intruder, its entry point on the surface of a cylinder
+ * of radius R and half height H around the ownship, at a point where it flies INTO the cylinder, and the volume the cylinder sweeps per
+ * second relative to it (Kochenderfer et al., "Airspace Encounter Models for Estimating Collision Risk": airspace density x E[rate] is the
+ * encounter rate, sum(w rate NMAC) / sum(w rate) is P(NMAC | encounter)).  The call writes the pose {c, s, ox, oy, oz} that
+ * emgpu_miss_distance_device reads, the rate, and optionally integer weights with the rate folded in.
+ * Inputs     the two PLANAR sets of emgpu_miss_distance_device (A = ownship, B = intruder), n_a, n_b, ld_a, ld_b, n_pairs, idx_a / idx_b
+ *            with the same column selection, n_x = 1 broadcast and bad-index rule.  points >= 2; only points 0 and 1 are read.
+ * Draws      Philox as everywhere: key = seed, counter = {g_lo, g_hi, 0, 13 << 28 | a << 20 | block} with
+ *            g = first_index + i; section 13 is ENCOUNTER; u(x) = (min(x, 2^32 - 2) + 0.5) * 2^-32.
+ *            A unit-disc point (a = 0: the heading; a = 1: an end-cap position): attempt j = 0 .. max_attempts-1 takes words 2 (j & 1) and
+ *            2 (j & 1) + 1 of block j >> 1, p = 2 u - 1, q = 2 u' - 1; the first attempt with 0 < p * p + q * q <= 1 is taken; none:
+ *            (p, q) = (1, 0) and EMGPU_ENC_FALLBACK.  a = 2, block 0: word 0 = u1 (surface), word 1 = u2 (lateral offset), word 2 = u3
+ *            (height).
+ * Per pair   all in f64, every product, sum, quotient and root one IEEE operation in the order written, nothing contracted, no device
+ *            sin / cos / atan2:
+ *            1. (ax, ay, az) = A[1] - A[0], (bx, by, bz) = B[1] - B[0]: the displacements of the first second.
+ *            2. r = sqrt(p * p + q * q), c = p / r, s = q / r (a = 0); vx = c * bx - s * by, vy = s * bx + c * by.
+ *            3. rx = vx - ax, ry = vy - ay, wr = bz - az, g = sqrt(rx * rx + ry * ry).
+ *            4. Qs = ks * g, Qe = ke * fabs(wr), with ks = (4 * R) * H and ke = (pi * R) * R computed once on the host; Q = Qs + Qe.
+ *               !(Q > 0) or Q infinite: EMGPU_ENC_NO_ENTRY, ox = oy = oz = NaN, rate 0, weight 0; c and s are written as drawn, no a = 1
+ *               or a = 2 draw enters, and the pair has no EMGPU_ENC_END.
+ *            5. Side entry iff u1 * Q < Qs: ex = rx / g, ey = ry / g, m = 2 * u2 - 1, l = R * m, h = R * sqrt(1 - m * m),
+ *               relx = (-h) * ex - l * ey, rely = l * ex - h * ey, dz = H * (2 * u3 - 1): uniform in the lateral offset, on the half
+ *               that faces the relative velocity.  Otherwise EMGPU_ENC_END: (p', q') the a = 1 disc point, relx = R * p', rely = R * q',
+ *               dz = +H when wr < 0, else -H (an intruder that descends relative to the ownship enters through the top).  The a = 1
+ *               draw and its EMGPU_ENC_FALLBACK belong to end entries only.
+ *            6. ox = (A0x + relx) - (c * B0x - s * B0y), oy = (A0y + rely) - (s * B0x + c * B0y), oz = (A0z + dz) - B0z.
+ *            7. rate = Q.
+ *            8. weights_out = f <= 2^32 - 1 ? f : 2^32 - 1 with f = floor(w * (Q / rate_scale) + 0.5), w = weights_in[i] (NULL: 1);
+ *               EMGPU_ENC_SATURATED when the clamp acted (a NaN f, 0 * inf, clamps too).  Without weights_out no weight is formed and
+ *               the flag is never set.
+ * Outputs    pose f64 [5][n_pairs], rate f64 [n_pairs], flags uint8 [n_pairs], weights_out uint32 [n_pairs]; each may be NULL, not all.
+ *            A bad index: pose NaN, rate 0, weight 0, EMGPU_ENC_BAD_INDEX alone, no load.  No load or store leaves the buffers.
+ * The call takes no context and no model, like emgpu_miss_distance_device: hip_stream, the current device, device pointers, asynchronous.
+ * EMGPU_ERR_ARG, with a message that names the argument, before any device work: NULL p, xyz_a or xyz_b; every output NULL; points < 2 or
+ * > 65537; the n_pairs / n_x / ld_x / idx_x rules of emgpu_miss_distance_device; radius_ft, half_height_ft or rate_scale not finite or
+ * <= 0; max_attempts outside 1 .. 16; weights_in without weights_out.  n_pairs == 0 succeeds and launches nothing.
+ * Out of scope: a caller-supplied heading, a placement such that the CPA falls at a chosen second, the ROWS layout, a _host entry point,
+ * float weights, the terminal model's traj layout. */
+#define EMGPU_ENC_END 1u
+#define EMGPU_ENC_FALLBACK 2u
+#define EMGPU_ENC_NO_ENTRY 4u
+#define EMGPU_ENC_SATURATED 8u
+#define EMGPU_ENC_BAD_INDEX 16u
+typedef struct {
+    int64_t n_pairs;
+    int64_t n_a, n_b;
+    int64_t ld_a, ld_b;    /* 0 = n_a / n_b */
+    int32_t points;        /* P: 2 .. 65537 */
+    int32_t max_attempts;  /* 1 .. 16 */
+    uint64_t seed, first_index;
+    double radius_ft, half_height_ft;
+    double rate_scale;     /* > 0; enters weights_out only */
+} emgpu_encounter_params;
+int emgpu_encounter_pose_device(void *hip_stream, const emgpu_encounter_params *p, const double *xyz_a, const double *xyz_b, const int64_t *idx_a,
+                                const int64_t *idx_b, const uint32_t *weights_in, double *pose, double *rate, uint8_t *flags,
+                                uint32_t *weights_out);
+
 /* Pinned host memory for the outputs of the *_host entry points (hipHostMalloc, kept in a per-ctx pool: pinning gigabytes costs about as
  * much as copying them).  emgpu_sample_dbn_host recognises pinned output arrays and lets the copy engine write straight into them;
  * pageable arrays go through the library's own pinned staging buffers and a few host threads (below). */
