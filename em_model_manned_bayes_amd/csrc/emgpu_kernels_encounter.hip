@@ -14,8 +14,6 @@
 // The compiler's figures (registers, LDS, scratch) are in DESIGN.md section 33.
 #include <hip/hip_runtime.h>
 
-#include <algorithm>
-
 #include "emgpu_device.h"
 #include "emgpu_encounter.h"
 
@@ -46,19 +44,19 @@ __device__ __forceinline__ bool disc_point(uint32_t g_lo, uint32_t g_hi, uint32_
 __global__ __launch_bounds__(kBlock) void k_encounter_pose(const EmgpuEncounterRun A) {
     const double nan = __builtin_nan(""), inf = __builtin_inf();
     const uint32_t k0 = (uint32_t)A.seed, k1 = (uint32_t)(A.seed >> 32);
-    const size_t np = (size_t)A.n_pairs, la = (size_t)A.ld_a, lb = (size_t)A.ld_b;
+    const size_t np = (size_t)A.dim.n_pairs, la = (size_t)A.dim.ld_a, lb = (size_t)A.dim.ld_b;
     // tile j of this workgroup: pairs (blockIdx.x + j * gridDim.x) * 256 ...
-    for (int64_t tile = blockIdx.x; tile * kBlock < A.n_pairs; tile += gridDim.x) {
+    for (int64_t tile = blockIdx.x; tile * kBlock < A.dim.n_pairs; tile += gridDim.x) {
         const int64_t i = tile * kBlock + threadIdx.x;
-        if (i >= A.n_pairs) continue;
-        const int64_t ia = A.idx_a ? A.idx_a[i] : (A.n_a > 1 ? i : 0), ib = A.idx_b ? A.idx_b[i] : (A.n_b > 1 ? i : 0);
-        const bool bad = ia < 0 || ia >= A.n_a || ib < 0 || ib >= A.n_b;
+        if (i >= A.dim.n_pairs) continue;
+        const int64_t ia = pair_column(A.col.idx_a, A.dim.n_a, i), ib = pair_column(A.col.idx_b, A.dim.n_b, i);
+        const bool bad = ia < 0 || ia >= A.dim.n_a || ib < 0 || ib >= A.dim.n_b;   // (spelled here: in a shared helper it moves registers)
         double c = nan, s = nan, ox = nan, oy = nan, oz = nan, rate = 0.0;
         uint32_t fl = EMGPU_ENC_BAD_INDEX, wout = 0u;
         if (!bad) {
             const uint64_t g = A.first_index + (uint64_t)i;
             const uint32_t g_lo = (uint32_t)g, g_hi = (uint32_t)(g >> 32);
-            const double *a = A.xyz_a + (size_t)ia, *b = A.xyz_b + (size_t)ib;
+            const double *a = A.col.xyz_a + (size_t)ia, *b = A.col.xyz_b + (size_t)ib;
             const double a0x = a[0], a0y = a[la], a0z = a[2 * la], a1x = a[3 * la], a1y = a[4 * la], a1z = a[5 * la];
             const double b0x = b[0], b0y = b[lb], b0z = b[2 * lb], b1x = b[3 * lb], b1y = b[4 * lb], b1z = b[5 * lb];
             // 1. the displacements of the first second
@@ -122,9 +120,8 @@ __global__ __launch_bounds__(kBlock) void k_encounter_pose(const EmgpuEncounterR
 namespace emgpu {
 hipError_t launch_encounter_pose(const EmgpuEncounterRun &A, hipStream_t s, const char **name) {
     if (name) *name = "k_encounter_pose";
-    if (A.n_pairs <= 0) return hipSuccess;
-    const int64_t tiles = (A.n_pairs + kBlock - 1) / kBlock;
-    const dim3 grid((unsigned)std::min<int64_t>(tiles, 2048));
+    if (A.dim.n_pairs <= 0) return hipSuccess;
+    const dim3 grid = pair_grid(A.dim.n_pairs, kBlock);
     hipLaunchKernelGGL(k_encounter_pose, grid, dim3(kBlock), 0, s, A);
     return hipGetLastError();
 }

@@ -16,8 +16,6 @@
 // Compiler's figures (hipcc -O3, gfx950): <no pose> 64 VGPRs, <pose> 79 VGPRs, 256 bytes of LDS, no scratch.
 #include <hip/hip_runtime.h>
 
-#include <algorithm>
-
 #include "emgpu_miss.h"
 
 namespace {
@@ -29,13 +27,13 @@ __global__ __launch_bounds__(kBlock) void k_miss_distance(const EmgpuMissRun A) 
     const double nan = __builtin_nan("");
     uint32_t n_eval = 0u, n_cpa = 0u, n_any = 0u, n_none = 0u, n_bad = 0u;
     unsigned long long w_eval = 0ull, w_cpa = 0ull, w_any = 0ull;
-    const size_t step_a = 3 * (size_t)A.ld_a, step_b = 3 * (size_t)A.ld_b;
+    const size_t step_a = 3 * (size_t)A.dim.ld_a, step_b = 3 * (size_t)A.dim.ld_b;
     // tile j of this workgroup: pairs (blockIdx.x + j * gridDim.x) * 256 ...
-    for (int64_t tile = blockIdx.x; tile * kBlock < A.n_pairs; tile += gridDim.x) {
+    for (int64_t tile = blockIdx.x; tile * kBlock < A.dim.n_pairs; tile += gridDim.x) {
         const int64_t i = tile * kBlock + threadIdx.x;
-        if (i >= A.n_pairs) continue;
-        const int64_t ia = A.idx_a ? A.idx_a[i] : (A.n_a > 1 ? i : 0), ib = A.idx_b ? A.idx_b[i] : (A.n_b > 1 ? i : 0);
-        const bool bad = ia < 0 || ia >= A.n_a || ib < 0 || ib >= A.n_b;
+        if (i >= A.dim.n_pairs) continue;
+        const int64_t ia = pair_column(A.col.idx_a, A.dim.n_a, i), ib = pair_column(A.col.idx_b, A.dim.n_b, i);
+        const bool bad = ia < 0 || ia >= A.dim.n_a || ib < 0 || ib >= A.dim.n_b;   // (spelled here: in a shared helper it moves registers)
         double best = nan, vmd = nan;
         int32_t t = -1;
         uint32_t fl = EMGPU_MISS_BAD_INDEX;
@@ -43,15 +41,15 @@ __global__ __launch_bounds__(kBlock) void k_miss_distance(const EmgpuMissRun A) 
             double c = 1.0, s = 0.0, ox = 0.0, oy = 0.0, oz = 0.0;
             if (POSE) {
                 const double *q = A.pose + (size_t)i;
-                const size_t np = (size_t)A.n_pairs;
+                const size_t np = (size_t)A.dim.n_pairs;
                 c = q[0]; s = q[np]; ox = q[2 * np]; oy = q[3 * np]; oz = q[4 * np];
             }
-            const double *a = A.xyz_a + (size_t)ia, *b = A.xyz_b + (size_t)ib;
+            const double *a = A.col.xyz_a + (size_t)ia, *b = A.col.xyz_b + (size_t)ib;
             bool any = false;
 #pragma unroll 4
             for (int p = 0; p < A.P; p++, a += step_a, b += step_b) {
-                const double xa = a[0], ya = a[(size_t)A.ld_a], za = a[2 * (size_t)A.ld_a];
-                double xb = b[0], yb = b[(size_t)A.ld_b], zb = b[2 * (size_t)A.ld_b];
+                const double xa = a[0], ya = a[(size_t)A.dim.ld_a], za = a[2 * (size_t)A.dim.ld_a];
+                double xb = b[0], yb = b[(size_t)A.dim.ld_b], zb = b[2 * (size_t)A.dim.ld_b];
                 if (POSE) {
                     const double xr = (c * xb - s * yb) + ox, yr = (s * xb + c * yb) + oy;
                     xb = xr; yb = yr; zb = zb + oz;
@@ -100,10 +98,8 @@ __global__ __launch_bounds__(kBlock) void k_miss_distance(const EmgpuMissRun A) 
 namespace emgpu {
 hipError_t launch_miss_distance(const EmgpuMissRun &A, hipStream_t s, const char **name) {
     if (name) *name = A.pose ? "k_miss_distance[pose]" : "k_miss_distance";
-    if (A.n_pairs <= 0) return hipSuccess;
-    // enough workgroups to fill the chip, few enough that the atomics of stage 3 are paid 2048 times at most
-    const int64_t tiles = (A.n_pairs + kBlock - 1) / kBlock;
-    const dim3 grid((unsigned)std::min<int64_t>(tiles, 2048));
+    if (A.dim.n_pairs <= 0) return hipSuccess;
+    const dim3 grid = pair_grid(A.dim.n_pairs, kBlock);   // the atomics of stage 3 are paid 2048 times at most
     if (A.pose) hipLaunchKernelGGL(k_miss_distance<true>, grid, dim3(kBlock), 0, s, A);
     else hipLaunchKernelGGL(k_miss_distance<false>, grid, dim3(kBlock), 0, s, A);
     return hipGetLastError();

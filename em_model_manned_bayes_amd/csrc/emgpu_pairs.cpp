@@ -1,0 +1,93 @@
+// emgpu_pairs.cpp -- the two entry points on paired 1 Hz tracks (the pairing: emgpu_pairs.h), side by side: emgpu_miss_distance_device
+// (k_miss_distance, emgpu_miss.h) and emgpu_encounter_pose_device (k_encounter_pose, emgpu_encounter.h).  They take no context: they need
+// no model table, no scratch and no status word, so they run on the stream they are given and on the calling thread's current device.
+#include <cmath>
+
+#include "emgpu_internal.hpp"
+#include "emgpu_encounter.h"
+#include "emgpu_miss.h"
+
+namespace {
+// What can be said about a pairing without a device, for either params struct: EMGPU_OK, or the error (recorded).  have_out: the caller
+// passed an output; `nothing`: its message when it passed none.  min_points: 1 where one second is enough, 2 where a velocity is read.
+template <class Params>
+int check_pairing(const Params *p, const double *xyz_a, const double *xyz_b, const int64_t *idx_a, const int64_t *idx_b, bool have_out,
+                  const char *nothing, int min_points) {
+    if (!p) return fail(EMGPU_ERR_ARG, "null argument: p");
+    if (!xyz_a) return fail(EMGPU_ERR_ARG, "null argument: xyz_a");
+    if (!xyz_b) return fail(EMGPU_ERR_ARG, "null argument: xyz_b");
+    if (!have_out) return fail(EMGPU_ERR_ARG, nothing);
+    if (p->points < min_points || p->points > 65537) return fail(EMGPU_ERR_ARG, "points outside " + std::to_string(min_points) + "..65537");
+    if (p->n_pairs < 0 || p->n_pairs > ((int64_t)1 << 32)) return fail(EMGPU_ERR_ARG, "n_pairs outside 0..2^32");
+    if (p->n_a < 1) return fail(EMGPU_ERR_ARG, "n_a < 1");
+    if (p->n_b < 1) return fail(EMGPU_ERR_ARG, "n_b < 1");
+    if (p->ld_a != 0 && p->ld_a < p->n_a) return fail(EMGPU_ERR_ARG, "ld_a < n_a");
+    if (p->ld_b != 0 && p->ld_b < p->n_b) return fail(EMGPU_ERR_ARG, "ld_b < n_b");
+    if (!idx_a && p->n_a > 1 && p->n_pairs > p->n_a) return fail(EMGPU_ERR_ARG, "n_pairs > n_a without idx_a");
+    if (!idx_b && p->n_b > 1 && p->n_pairs > p->n_b) return fail(EMGPU_ERR_ARG, "n_pairs > n_b without idx_b");
+    return EMGPU_OK;
+}
+
+// the pairing's part of an argument block, the pitches' default (0 = n_x) filled in
+template <class Params>
+void fill_pairing(const Params *p, const double *xyz_a, const double *xyz_b, const int64_t *idx_a, const int64_t *idx_b, EmgpuPairDims &dim,
+                  EmgpuPairCols &col) {
+    dim = {p->n_pairs, p->n_a, p->n_b, p->ld_a ? p->ld_a : p->n_a, p->ld_b ? p->ld_b : p->n_b};
+    col = {xyz_a, xyz_b, idx_a, idx_b};
+}
+} // namespace
+
+extern "C" {
+
+int emgpu_miss_distance_device(void *hip_stream, const emgpu_miss_params *p, const double *xyz_a, const double *xyz_b, const int64_t *idx_a,
+                               const int64_t *idx_b, const double *pose_b, const uint32_t *weights, double *hmd, double *vmd,
+                               int32_t *t_cpa, uint8_t *flags, uint64_t *totals) {
+    EMGPU_TRY
+    if (const int rc = check_pairing(p, xyz_a, xyz_b, idx_a, idx_b, hmd || vmd || t_cpa || flags || totals,
+                                     "null hmd, vmd, t_cpa, flags and totals: nothing to write", 1))
+        return rc;
+    if (!(p->nmac_h_ft >= 0.0)) return fail(EMGPU_ERR_ARG, "nmac_h_ft is negative or NaN");
+    if (!(p->nmac_v_ft >= 0.0)) return fail(EMGPU_ERR_ARG, "nmac_v_ft is negative or NaN");
+    if (((uintptr_t)xyz_a | (uintptr_t)xyz_b | (uintptr_t)idx_a | (uintptr_t)idx_b | (uintptr_t)pose_b | (uintptr_t)hmd | (uintptr_t)vmd |
+         (uintptr_t)totals) & 7u)
+        return fail(EMGPU_ERR_ARG, "xyz_a, xyz_b, idx_a, idx_b, pose_b, hmd, vmd and totals must be 8-byte aligned");
+    if (((uintptr_t)weights | (uintptr_t)t_cpa) & 3u) return fail(EMGPU_ERR_ARG, "weights and t_cpa must be 4-byte aligned");
+    if (p->n_pairs == 0) return EMGPU_OK;
+    EmgpuMissRun A{};
+    fill_pairing(p, xyz_a, xyz_b, idx_a, idx_b, A.dim, A.col);
+    A.P = p->points; A.nmac_h = p->nmac_h_ft; A.nmac_v = p->nmac_v_ft; A.pose = pose_b; A.weights = weights;
+    A.hmd = hmd; A.vmd = vmd; A.t_cpa = t_cpa; A.flags = flags; A.totals = (unsigned long long *)totals;
+    launch_ok(emgpu::launch_miss_distance(A, (hipStream_t)hip_stream, nullptr));
+    return EMGPU_OK;
+    EMGPU_CATCH
+}
+
+int emgpu_encounter_pose_device(void *hip_stream, const emgpu_encounter_params *p, const double *xyz_a, const double *xyz_b, const int64_t *idx_a,
+                                const int64_t *idx_b, const uint32_t *weights_in, double *pose, double *rate, uint8_t *flags,
+                                uint32_t *weights_out) {
+    EMGPU_TRY
+    if (const int rc = check_pairing(p, xyz_a, xyz_b, idx_a, idx_b, pose || rate || flags || weights_out,
+                                     "null pose, rate, flags and weights_out: nothing to write", 2))
+        return rc;
+    if (!(std::isfinite(p->radius_ft) && p->radius_ft > 0.0)) return fail(EMGPU_ERR_ARG, "radius_ft is not a finite positive number");
+    if (!(std::isfinite(p->half_height_ft) && p->half_height_ft > 0.0)) return fail(EMGPU_ERR_ARG, "half_height_ft is not a finite positive number");
+    if (!(std::isfinite(p->rate_scale) && p->rate_scale > 0.0)) return fail(EMGPU_ERR_ARG, "rate_scale is not a finite positive number");
+    if (p->max_attempts < 1 || p->max_attempts > 16) return fail(EMGPU_ERR_ARG, "max_attempts outside 1..16");
+    if (weights_in && !weights_out) return fail(EMGPU_ERR_ARG, "weights_in without weights_out");
+    if (((uintptr_t)xyz_a | (uintptr_t)xyz_b | (uintptr_t)idx_a | (uintptr_t)idx_b | (uintptr_t)pose | (uintptr_t)rate) & 7u)
+        return fail(EMGPU_ERR_ARG, "xyz_a, xyz_b, idx_a, idx_b, pose and rate must be 8-byte aligned");
+    if (((uintptr_t)weights_in | (uintptr_t)weights_out) & 3u) return fail(EMGPU_ERR_ARG, "weights_in and weights_out must be 4-byte aligned");
+    if (p->n_pairs == 0) return EMGPU_OK;
+    EmgpuEncounterRun A{};
+    fill_pairing(p, xyz_a, xyz_b, idx_a, idx_b, A.dim, A.col);
+    A.seed = p->seed; A.first_index = p->first_index; A.max_attempts = p->max_attempts;
+    A.R = p->radius_ft; A.H = p->half_height_ft; A.rate_scale = p->rate_scale;
+    A.ks = (4.0 * A.R) * A.H;                       // the side's projected area per unit of horizontal speed: 2 R x 2 H
+    A.ke = (3.14159265358979323846 * A.R) * A.R;    // an end's area
+    A.weights_in = weights_in; A.pose = pose; A.rate = rate; A.flags = flags; A.weights_out = weights_out;
+    launch_ok(emgpu::launch_encounter_pose(A, (hipStream_t)hip_stream, nullptr));
+    return EMGPU_OK;
+    EMGPU_CATCH
+}
+
+} // extern "C"

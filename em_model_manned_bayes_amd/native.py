@@ -4,6 +4,7 @@ sampling calls with numpy (host) or raw device pointers (torch tensors' data_ptr
 import contextlib
 import ctypes as C
 import re
+import types
 
 import numpy as np
 
@@ -1194,6 +1195,101 @@ def _planar_tracks(xyz, layout, dev):
     return (t.permute(1, 2, 0) if layout == "rows" else t).contiguous()
 
 
+def _pair_columns(xyz_a, xyz_b, idx_a, idx_b, layout):
+    """(n_a, n_b, [idx_a, idx_b] as int64 vectors or None, n_pairs) of a pairing of two sets of tracks, as miss_distance reads its arguments"""
+    import torch
+    n_of = lambda t: int(t.shape[0 if layout == "rows" else 2])          # noqa: E731
+    for t in (xyz_a, xyz_b):
+        if getattr(t, "ndim", 0) != 3:
+            raise ValueError("xyz must be [n, points, 3] (layout 'rows') or [points, 3, n] ('planar')")
+    n_a, n_b = n_of(xyz_a), n_of(xyz_b)
+    idx = [None if i is None else np.ascontiguousarray(i, dtype=np.int64).reshape(-1) if not isinstance(i, torch.Tensor) else i
+           for i in (idx_a, idx_b)]
+    return n_a, n_b, idx, max([len(i) for i in idx if i is not None] + [n for n, i in zip((n_a, n_b), idx) if i is None])
+
+
+@contextlib.contextmanager
+def _paired(xyz_a, xyz_b, columns, w, pose_b, layout, ctx, stream):
+    """The pairing step of miss_distance, encounter_pose and encounter_miss: what a launch on paired tracks needs, as a namespace of
+    dev, stream (resolved; None: torch's current stream), the PLANAR device tensors a / b, n_a, n_b, n_pairs, and d_ia, d_ib (int64), d_w
+    (uint32 held as int32) and d_pose on the device or None.  columns = _pair_columns(...), w = _weights_array(...) or None: the caller has
+    them before torch.cuda is touched.  The body runs on dev with the uploads complete for its stream; leaving it waits for that stream."""
+    import torch
+    n_a, n_b, idx, n_pairs = columns
+    dev = xyz_a.device if isinstance(xyz_a, torch.Tensor) and xyz_a.is_cuda else torch.device("cuda", torch.cuda.current_device())
+    if ctx is not None and stream is None:
+        stream = ctx.stream
+        if stream is None:
+            ctx.sync()
+    with torch.cuda.device(dev):
+        a, b = _planar_tracks(xyz_a, layout, dev), _planar_tracks(xyz_b, layout, dev)
+        if a.shape[0] != b.shape[0]:
+            raise ValueError("both sets of tracks must hold the same number of points")
+        up = lambda x, dt: None if x is None else (x if isinstance(x, torch.Tensor) else torch.from_numpy(x)).to(device=dev, dtype=dt).contiguous()  # noqa: E731
+        pr = types.SimpleNamespace(dev=dev, stream=stream, a=a, b=b, n_a=n_a, n_b=n_b, n_pairs=n_pairs, d_ia=up(idx[0], torch.int64),
+                                   d_ib=up(idx[1], torch.int64), d_pose=up(pose_b, torch.float64),
+                                   d_w=None if w is None else torch.from_numpy(w.view(np.int32)).to(dev))
+        # torch.cuda.synchronize brackets the launches only when they do not run on torch's stream, where the uploads ran
+        pr.guard = (lambda: None) if stream is None else (lambda: torch.cuda.synchronize(dev))
+        pr.guard()
+        yield pr
+        pr.guard()
+
+
+def _ptr(t):
+    return 0 if t is None else t.data_ptr()
+
+
+def _miss_tensors(pr, d_pose, d_w, nmac_h_ft, nmac_v_ft):
+    """k_miss_distance on the pairing pr with the device tensors d_pose and d_w (or None): the device tensors (hmd, vmd, t_cpa, flags,
+    totals), launched on pr.stream and not waited for"""
+    import torch
+    n, dev = pr.n_pairs, pr.dev
+    hmd, vmd = torch.empty(n, dtype=torch.float64, device=dev), torch.empty(n, dtype=torch.float64, device=dev)
+    t_cpa, flags = torch.empty(n, dtype=torch.int32, device=dev), torch.empty(n, dtype=torch.uint8, device=dev)
+    totals = torch.zeros(8, dtype=torch.int64, device=dev)
+    pr.guard()      # totals was zeroed on torch's stream
+    miss_distance_device(miss_params(n, pr.n_a, pr.n_b, pr.a.shape[0], nmac_h_ft, nmac_v_ft), _ptr(pr.a), _ptr(pr.b), _ptr(pr.d_ia), _ptr(pr.d_ib),
+                         _ptr(d_pose), _ptr(d_w), _ptr(hmd), _ptr(vmd), _ptr(t_cpa), _ptr(flags), _ptr(totals), stream=pr.stream)
+    return hmd, vmd, t_cpa, flags, totals
+
+
+def _miss_dict(hmd, vmd, t_cpa, flags, totals):
+    """miss_distance's dict from _miss_tensors' device tensors"""
+    fl = flags.cpu().numpy()
+    return {"hmd_ft": hmd.cpu().numpy(), "vmd_ft": vmd.cpu().numpy(), "t_cpa": t_cpa.cpu().numpy(), "flags": fl,
+            "nmac": (fl & L.MISS_NMAC_CPA) != 0, "totals": totals.cpu().numpy().view(np.uint64)}
+
+
+def _encounter_pose_tensors(pr, want_weights, radius_ft, half_height_ft, seed, rate_scale, first_index, max_attempts):
+    """k_encounter_pose on the pairing pr: the device tensors (pose [5, n_pairs], rate, flags, weights or None), launched on pr.stream and
+    not waited for"""
+    import torch
+    n, dev = pr.n_pairs, pr.dev
+    pose = torch.empty((5, n), dtype=torch.float64, device=dev)
+    rate = torch.empty(n, dtype=torch.float64, device=dev)
+    flags = torch.empty(n, dtype=torch.uint8, device=dev)
+    w_out = torch.empty(n, dtype=torch.int32, device=dev) if want_weights else None
+    p = encounter_params(n, pr.n_a, pr.n_b, pr.a.shape[0], radius_ft, half_height_ft, seed, first_index, max_attempts,
+                         1.0 if rate_scale is None else rate_scale)
+    encounter_pose_device(p, _ptr(pr.a), _ptr(pr.b), _ptr(pr.d_ia), _ptr(pr.d_ib), _ptr(pr.d_w), _ptr(pose), _ptr(rate), _ptr(flags), _ptr(w_out),
+                          stream=pr.stream)
+    return pose, rate, flags, w_out
+
+
+def _encounter_dict(rate, flags, w_out, flags_key="flags"):
+    """the rate, flags and weights of encounter_pose's dict from _encounter_pose_tensors' device tensors"""
+    return {"rate": rate.cpu().numpy(), flags_key: flags.cpu().numpy(), "weights": None if w_out is None else w_out.cpu().numpy().view(np.uint32)}
+
+
+def _encounter_weights(weights, rate_scale, n_pairs):
+    """(whether weights_out is wanted, weights_in as _weights_array or None) of encounter_pose's `weights`"""
+    want = weights is not None and weights is not False
+    if want and rate_scale is None:
+        raise ValueError("weights need a rate_scale: the rate that leaves a weight as it is")
+    return want, _weights_array(weights, n_pairs) if want and weights is not True else None
+
+
 def miss_distance(xyz_a, xyz_b, idx_a=None, idx_b=None, pose_b=None, weights=None, nmac_h_ft=500.0, nmac_v_ft=100.0, layout="rows", ctx=None,
                   stream=None):
     """Horizontal / vertical miss distance, time of closest approach and NMAC flags of paired 1 Hz tracks on the GPU
@@ -1210,37 +1306,15 @@ def miss_distance(xyz_a, xyz_b, idx_a=None, idx_b=None, pose_b=None, weights=Non
     calls produced the inputs -- its stream is used when it was given one (Context.stream), and when it runs on a stream of its own
     (Context.stream is None) ctx.sync() is called first, so that the inputs are complete."""
     import torch
-    n_a, n_b, idx, n_pairs = _pair_columns(xyz_a, xyz_b, idx_a, idx_b, layout)
-    w = None if weights is None else _weights_array(weights, n_pairs)
+    columns = _pair_columns(xyz_a, xyz_b, idx_a, idx_b, layout)
+    w = None if weights is None else _weights_array(weights, columns[3])
     if pose_b is not None:
         pose_b = np.ascontiguousarray(pose_b, dtype=np.float64) if not isinstance(pose_b, torch.Tensor) else pose_b
-        if tuple(pose_b.shape) != (5, n_pairs):
+        if tuple(pose_b.shape) != (5, columns[3]):
             raise ValueError("pose_b must be [5, n_pairs] (make_pose)")
-    dev = xyz_a.device if isinstance(xyz_a, torch.Tensor) and xyz_a.is_cuda else torch.device("cuda", torch.cuda.current_device())
-    if ctx is not None and stream is None:
-        stream = ctx.stream
-        if stream is None:
-            ctx.sync()
-    with torch.cuda.device(dev):
-        a, b = _planar_tracks(xyz_a, layout, dev), _planar_tracks(xyz_b, layout, dev)
-        if a.shape[0] != b.shape[0]:
-            raise ValueError("both sets of tracks must hold the same number of points")
-        up = lambda x, dt: None if x is None else (x if isinstance(x, torch.Tensor) else torch.from_numpy(x)).to(device=dev, dtype=dt).contiguous()  # noqa: E731
-        d_ia, d_ib, d_pose = up(idx[0], torch.int64), up(idx[1], torch.int64), up(pose_b, torch.float64)
-        d_w = None if w is None else torch.from_numpy(w.view(np.int32)).to(dev)
-        hmd, vmd = torch.empty(n_pairs, dtype=torch.float64, device=dev), torch.empty(n_pairs, dtype=torch.float64, device=dev)
-        t_cpa, flags = torch.empty(n_pairs, dtype=torch.int32, device=dev), torch.empty(n_pairs, dtype=torch.uint8, device=dev)
-        totals = torch.zeros(8, dtype=torch.int64, device=dev)
-        ptr = lambda t: 0 if t is None else t.data_ptr()                 # noqa: E731
-        if stream is not None:
-            torch.cuda.synchronize(dev)      # the uploads ran on torch's stream, the kernel will not
-        miss_distance_device(miss_params(n_pairs, n_a, n_b, a.shape[0], nmac_h_ft, nmac_v_ft), ptr(a), ptr(b), ptr(d_ia), ptr(d_ib), ptr(d_pose),
-                             ptr(d_w), ptr(hmd), ptr(vmd), ptr(t_cpa), ptr(flags), ptr(totals), stream=stream)
-        if stream is not None:
-            torch.cuda.synchronize(dev)
-        fl = flags.cpu().numpy()
-        return {"hmd_ft": hmd.cpu().numpy(), "vmd_ft": vmd.cpu().numpy(), "t_cpa": t_cpa.cpu().numpy(), "flags": fl,
-                "nmac": (fl & L.MISS_NMAC_CPA) != 0, "totals": totals.cpu().numpy().view(np.uint64)}
+    with _paired(xyz_a, xyz_b, columns, w, pose_b, layout, ctx, stream) as pr:
+        out = _miss_tensors(pr, pr.d_pose, pr.d_w, nmac_h_ft, nmac_v_ft)
+    return _miss_dict(*out)
 
 
 def encounter_params(n_pairs, n_a, n_b, points, radius_ft, half_height_ft, seed, first_index=0, max_attempts=16, rate_scale=1.0, ld_a=0, ld_b=0):
@@ -1266,36 +1340,6 @@ def encounter_pose_device(params, xyz_a, xyz_b, idx_a=0, idx_b=0, weights_in=0, 
         xyz_a, xyz_b, idx_a, idx_b, weights_in, pose, rate, flags, weights_out))))
 
 
-def _pair_columns(xyz_a, xyz_b, idx_a, idx_b, layout):
-    """(n_a, n_b, [idx_a, idx_b] as int64 vectors or None, n_pairs) of a pairing of two sets of tracks, as miss_distance reads its arguments"""
-    import torch
-    n_of = lambda t: int(t.shape[0 if layout == "rows" else 2])          # noqa: E731
-    for t in (xyz_a, xyz_b):
-        if getattr(t, "ndim", 0) != 3:
-            raise ValueError("xyz must be [n, points, 3] (layout 'rows') or [points, 3, n] ('planar')")
-    n_a, n_b = n_of(xyz_a), n_of(xyz_b)
-    idx = [None if i is None else np.ascontiguousarray(i, dtype=np.int64).reshape(-1) if not isinstance(i, torch.Tensor) else i
-           for i in (idx_a, idx_b)]
-    return n_a, n_b, idx, max([len(i) for i in idx if i is not None] + [n for n, i in zip((n_a, n_b), idx) if i is None])
-
-
-def _encounter_pose_tensors(a, b, n_a, n_b, n_pairs, d_ia, d_ib, d_w, want_weights, radius_ft, half_height_ft, seed, rate_scale, first_index,
-                            max_attempts, stream):
-    """k_encounter_pose on PLANAR device tensors a, b: the device tensors (pose [5, n_pairs], rate, flags, weights or None), launched on
-    `stream` (None: torch's current stream) and not waited for"""
-    import torch
-    dev = a.device
-    pose = torch.empty((5, n_pairs), dtype=torch.float64, device=dev)
-    rate = torch.empty(n_pairs, dtype=torch.float64, device=dev)
-    flags = torch.empty(n_pairs, dtype=torch.uint8, device=dev)
-    w_out = torch.empty(n_pairs, dtype=torch.int32, device=dev) if want_weights else None
-    ptr = lambda t: 0 if t is None else t.data_ptr()                 # noqa: E731
-    p = encounter_params(n_pairs, n_a, n_b, a.shape[0], radius_ft, half_height_ft, seed, first_index, max_attempts,
-                         1.0 if rate_scale is None else rate_scale)
-    encounter_pose_device(p, ptr(a), ptr(b), ptr(d_ia), ptr(d_ib), ptr(d_w), ptr(pose), ptr(rate), ptr(flags), ptr(w_out), stream=stream)
-    return pose, rate, flags, w_out
-
-
 def encounter_pose(xyz_a, xyz_b, radius_ft, half_height_ft, seed, idx_a=None, idx_b=None, weights=None, rate_scale=None, first_index=0,
                    max_attempts=16, layout="rows", ctx=None, stream=None):
     """Places each intruder (set B) on the encounter cylinder of radius_ft and half_height_ft around its ownship (set A) on the GPU
@@ -1308,31 +1352,11 @@ def encounter_pose(xyz_a, xyz_b, radius_ft, half_height_ft, seed, idx_a=None, id
     rate_scale (ValueError without): the weight is floor(w * rate / rate_scale + 0.5), clamped to 2**32 - 1 (L.ENC_SATURATED), so
     rate_scale is the rate that keeps a weight as it is -- ks times a bound on the relative speed is the caller's to give.
     Returns {"pose" float64 [5, n_pairs] (miss_distance's pose_b), "rate" float64, "flags" uint8 (L.ENC_*), "weights" uint32 or None}."""
-    import torch
-    n_a, n_b, idx, n_pairs = _pair_columns(xyz_a, xyz_b, idx_a, idx_b, layout)
-    want_weights = weights is not None and weights is not False
-    if want_weights and rate_scale is None:
-        raise ValueError("weights need a rate_scale: the rate that leaves a weight as it is")
-    w = _weights_array(weights, n_pairs) if want_weights and weights is not True else None
-    dev = xyz_a.device if isinstance(xyz_a, torch.Tensor) and xyz_a.is_cuda else torch.device("cuda", torch.cuda.current_device())
-    if ctx is not None and stream is None:
-        stream = ctx.stream
-        if stream is None:
-            ctx.sync()
-    with torch.cuda.device(dev):
-        a, b = _planar_tracks(xyz_a, layout, dev), _planar_tracks(xyz_b, layout, dev)
-        if a.shape[0] != b.shape[0]:
-            raise ValueError("both sets of tracks must hold the same number of points")
-        up = lambda x: None if x is None else (x if isinstance(x, torch.Tensor) else torch.from_numpy(x)).to(device=dev, dtype=torch.int64).contiguous()  # noqa: E731
-        d_w = None if w is None else torch.from_numpy(w.view(np.int32)).to(dev)
-        if stream is not None:
-            torch.cuda.synchronize(dev)      # the uploads ran on torch's stream, the kernel will not
-        pose, rate, flags, w_out = _encounter_pose_tensors(a, b, n_a, n_b, n_pairs, up(idx[0]), up(idx[1]), d_w, want_weights, radius_ft,
-                                                           half_height_ft, seed, rate_scale, first_index, max_attempts, stream)
-        if stream is not None:
-            torch.cuda.synchronize(dev)
-        return {"pose": pose.cpu().numpy(), "rate": rate.cpu().numpy(), "flags": flags.cpu().numpy(),
-                "weights": None if w_out is None else w_out.cpu().numpy().view(np.uint32)}
+    columns = _pair_columns(xyz_a, xyz_b, idx_a, idx_b, layout)
+    want_weights, w = _encounter_weights(weights, rate_scale, columns[3])
+    with _paired(xyz_a, xyz_b, columns, w, None, layout, ctx, stream) as pr:
+        pose, *out = _encounter_pose_tensors(pr, want_weights, radius_ft, half_height_ft, seed, rate_scale, first_index, max_attempts)
+    return {"pose": pose.cpu().numpy(), **_encounter_dict(*out)}
 
 
 def encounter_miss(xyz_a, xyz_b, radius_ft, half_height_ft, seed, idx_a=None, idx_b=None, weights=None, rate_scale=None, first_index=0,
@@ -1342,40 +1366,12 @@ def encounter_miss(xyz_a, xyz_b, radius_ft, half_height_ft, seed, idx_a=None, id
     NMAC thresholds.  With weights (and rate_scale) totals[5:8] are sums of w * rate / rate_scale, so totals[6] / totals[5] is
     P(NMAC | encounter); without, every pair counts 1 there.
     Returns miss_distance's dict plus "rate" float64, "encounter_flags" uint8 (L.ENC_*) and "weights" uint32 or None."""
-    import torch
-    n_a, n_b, idx, n_pairs = _pair_columns(xyz_a, xyz_b, idx_a, idx_b, layout)
-    want_weights = weights is not None and weights is not False
-    if want_weights and rate_scale is None:
-        raise ValueError("weights need a rate_scale: the rate that leaves a weight as it is")
-    w = _weights_array(weights, n_pairs) if want_weights and weights is not True else None
-    dev = xyz_a.device if isinstance(xyz_a, torch.Tensor) and xyz_a.is_cuda else torch.device("cuda", torch.cuda.current_device())
-    if ctx is not None and stream is None:
-        stream = ctx.stream
-        if stream is None:
-            ctx.sync()
-    with torch.cuda.device(dev):
-        a, b = _planar_tracks(xyz_a, layout, dev), _planar_tracks(xyz_b, layout, dev)
-        if a.shape[0] != b.shape[0]:
-            raise ValueError("both sets of tracks must hold the same number of points")
-        up = lambda x: None if x is None else (x if isinstance(x, torch.Tensor) else torch.from_numpy(x)).to(device=dev, dtype=torch.int64).contiguous()  # noqa: E731
-        d_ia, d_ib = up(idx[0]), up(idx[1])
-        d_w = None if w is None else torch.from_numpy(w.view(np.int32)).to(dev)
-        hmd, vmd = torch.empty(n_pairs, dtype=torch.float64, device=dev), torch.empty(n_pairs, dtype=torch.float64, device=dev)
-        t_cpa, flags = torch.empty(n_pairs, dtype=torch.int32, device=dev), torch.empty(n_pairs, dtype=torch.uint8, device=dev)
-        totals = torch.zeros(8, dtype=torch.int64, device=dev)
-        ptr = lambda t: 0 if t is None else t.data_ptr()                 # noqa: E731
-        if stream is not None:
-            torch.cuda.synchronize(dev)      # the uploads ran on torch's stream, the kernels will not
-        pose, rate, eflags, w_out = _encounter_pose_tensors(a, b, n_a, n_b, n_pairs, d_ia, d_ib, d_w, want_weights, radius_ft, half_height_ft,
-                                                            seed, rate_scale, first_index, max_attempts, stream)
-        miss_distance_device(miss_params(n_pairs, n_a, n_b, a.shape[0], nmac_h_ft, nmac_v_ft), ptr(a), ptr(b), ptr(d_ia), ptr(d_ib), ptr(pose),
-                             ptr(w_out), ptr(hmd), ptr(vmd), ptr(t_cpa), ptr(flags), ptr(totals), stream=stream)
-        if stream is not None:
-            torch.cuda.synchronize(dev)
-        fl = flags.cpu().numpy()
-        return {"hmd_ft": hmd.cpu().numpy(), "vmd_ft": vmd.cpu().numpy(), "t_cpa": t_cpa.cpu().numpy(), "flags": fl,
-                "nmac": (fl & L.MISS_NMAC_CPA) != 0, "totals": totals.cpu().numpy().view(np.uint64), "rate": rate.cpu().numpy(),
-                "encounter_flags": eflags.cpu().numpy(), "weights": None if w_out is None else w_out.cpu().numpy().view(np.uint32)}
+    columns = _pair_columns(xyz_a, xyz_b, idx_a, idx_b, layout)
+    want_weights, w = _encounter_weights(weights, rate_scale, columns[3])
+    with _paired(xyz_a, xyz_b, columns, w, None, layout, ctx, stream) as pr:
+        pose, rate, eflags, w_out = _encounter_pose_tensors(pr, want_weights, radius_ft, half_height_ft, seed, rate_scale, first_index, max_attempts)
+        out = _miss_tensors(pr, pose, w_out, nmac_h_ft, nmac_v_ft)
+    return dict(_miss_dict(*out), **_encounter_dict(rate, eflags, w_out, "encounter_flags"))
 
 
 def device_upload(ctx, addr, src):

@@ -6,6 +6,7 @@ xyz_a / xyz_b are PLANAR [P, 3, ld] as the library takes them; only columns 0 ..
 import numpy as np
 
 import oracle as O
+from pair_cases import pairing
 
 END, FALLBACK, NO_ENTRY, SATURATED, BAD_INDEX = 1, 2, 4, 8, 16
 SECTION = 13
@@ -51,13 +52,7 @@ def encounter(xyz_a, xyz_b, n_a, n_b, n_pairs, radius_ft, half_height_ft, seed, 
     R, H = float(radius_ft), float(half_height_ft)
     ks, ke = (4.0 * R) * H, (np.pi * R) * R
 
-    def columns(idx, n):
-        if idx is not None:
-            return np.asarray(idx, dtype=np.int64).reshape(-1)[:n_pairs]
-        return np.arange(n_pairs, dtype=np.int64) if n > 1 else np.zeros(n_pairs, dtype=np.int64)
-    ia, ib = columns(idx_a, n_a), columns(idx_b, n_b)
-    bad = (ia < 0) | (ia >= n_a) | (ib < 0) | (ib >= n_b)
-    ja, jb = np.where(bad, 0, ia), np.where(bad, 0, ib)
+    bad, ja, jb = pairing(idx_a, idx_b, n_a, n_b, n_pairs)
     A0, A1, B0, B1 = xyz_a[0][:, ja], xyz_a[1][:, ja], xyz_b[0][:, jb], xyz_b[1][:, jb]           # [3, n_pairs] each
     gidx = (np.uint64(int(first_index) & (2**64 - 1)) + np.arange(n_pairs, dtype=np.uint64))
     with np.errstate(all="ignore"):

@@ -4,6 +4,8 @@ for the root, the minimum over the ROOTS with NaNs masked, integer totals in uin
 xyz_a / xyz_b are PLANAR [P, 3, ld] as the library takes them; only columns 0 .. n_x-1 are looked at."""
 import numpy as np
 
+from pair_cases import pairing, planar  # noqa: F401  (planar: the tests of other layers take it from here)
+
 NMAC_CPA, NMAC_ANY, NO_CPA, BAD_INDEX = 1, 2, 4, 8
 
 
@@ -13,13 +15,7 @@ def miss(xyz_a, xyz_b, n_a, n_b, n_pairs, idx_a=None, idx_b=None, pose_b=None, w
     P = xyz_a.shape[0]
     assert xyz_b.shape[0] == P and P >= 1 and xyz_a.shape[1] == xyz_b.shape[1] == 3
 
-    def columns(idx, n):
-        if idx is not None:
-            return np.asarray(idx, dtype=np.int64).reshape(-1)[:n_pairs]
-        return np.arange(n_pairs, dtype=np.int64) if n > 1 else np.zeros(n_pairs, dtype=np.int64)
-    ia, ib = columns(idx_a, n_a), columns(idx_b, n_b)
-    bad = (ia < 0) | (ia >= n_a) | (ib < 0) | (ib >= n_b)
-    ja, jb = np.where(bad, 0, ia), np.where(bad, 0, ib)
+    bad, ja, jb = pairing(idx_a, idx_b, n_a, n_b, n_pairs)
     xa, ya, za = (xyz_a[:, c, :][:, ja] for c in range(3))           # [P, n_pairs]
     xb, yb, zb = (xyz_b[:, c, :][:, jb] for c in range(3))
     with np.errstate(all="ignore"):
@@ -49,12 +45,3 @@ def miss(xyz_a, xyz_b, n_a, n_b, n_pairs, idx_a=None, idx_b=None, pose_b=None, w
            w[any_].sum(dtype=np.uint64)]
     tot += np.array([int(x) for x in add], dtype=np.uint64)
     return {"hmd": hmd, "vmd": vmd, "t_cpa": t, "flags": flags, "totals": tot}
-
-
-def planar(xyz_rows, ld=None):
-    """tracks [n, P, 3] as PLANAR [P, 3, ld] (ld >= n; the columns behind n hold a pattern no result may depend on)"""
-    xyz_rows = np.asarray(xyz_rows, dtype=np.float64)
-    n, P, _ = xyz_rows.shape
-    out = np.full((P, 3, n if ld is None else ld), 7.0e9)
-    out[:, :, :n] = np.transpose(xyz_rows, (1, 2, 0))
-    return out

@@ -9,30 +9,15 @@ import pytest
 
 import encounter_ref as R
 import miss_ref
+import pair_cases as PC
 from em_model_manned_bayes_amd import _lib as L
 from em_model_manned_bayes_amd import em_io, native
 from em_model_manned_bayes_amd import encounter_model as E
 
 pytestmark = pytest.mark.gpu
 
-GUARD, FILL = 64, 0xA5
 OUTS = (("pose", np.float64, 5), ("rate", np.float64, 1), ("flags", np.uint8, 1), ("weights", np.uint32, 1))
 RADIUS, HALF_HEIGHT, SCALE = 6000.0, 800.0, 1.0e9
-_cache = {}
-
-
-def _tracks(n, P, seed):
-    """n random tracks [n, P, 3] of a few thousand feet extent, drawn once per shape and shared (read-only)"""
-    key = (n, P, seed)
-    if key not in _cache:
-        rs = np.random.RandomState(seed * 7919 + n * 131 + P)
-        start = np.concatenate([rs.uniform(-2500.0, 2500.0, (n, 1, 2)), rs.uniform(1000.0, 1600.0, (n, 1, 1))], axis=2)
-        vel = np.concatenate([rs.uniform(-250.0, 250.0, (n, 1, 2)), rs.uniform(-30.0, 30.0, (n, 1, 1))], axis=2)
-        wob = np.cumsum(rs.uniform(-20.0, 20.0, (n, P, 3)), axis=1)
-        xyz = np.ascontiguousarray(start + vel * np.arange(P)[None, :, None] + wob)
-        xyz.setflags(write=False)
-        _cache[key] = xyz
-    return _cache[key]
 
 
 def _run(a, b, n_a, n_b, n_pairs, seed=7, idx_a=None, idx_b=None, weights_in=None, want=("pose", "rate", "flags", "weights"), first_index=0,
@@ -44,34 +29,21 @@ def _run(a, b, n_a, n_b, n_pairs, seed=7, idx_a=None, idx_b=None, weights_in=Non
     d_a, d_b = up(a, np.float64), up(b, np.float64)
     d_ia, d_ib = up(idx_a, np.int64), up(idx_b, np.int64)
     d_w = None if weights_in is None else torch.from_numpy(np.asarray(weights_in, dtype=np.uint32).view(np.int32).copy()).to(dev)
-    size = {name: k * n_pairs * np.dtype(dt).itemsize for name, dt, k in OUTS}
-    bufs = {name: torch.from_numpy(np.full(size[name] + 2 * GUARD, FILL, dtype=np.uint8)).to(dev) for name in want}
+    size = {name: k * n_pairs * np.dtype(dt).itemsize for name, dt, k in OUTS if name in want}
+    bufs = PC.guarded(size, dev)
     ptr = lambda t: 0 if t is None else t.data_ptr()          # noqa: E731
-    at = lambda name: bufs[name].data_ptr() + GUARD if name in want else 0          # noqa: E731
+    at = lambda name: bufs[name].data_ptr() + PC.GUARD if name in want else 0          # noqa: E731
     p = native.encounter_params(n_pairs, n_a, n_b, a.shape[0], RADIUS, HALF_HEIGHT, seed, first_index, max_attempts, rate_scale,
                                 ld_a=a.shape[2], ld_b=b.shape[2])
     torch.cuda.synchronize()
     native.encounter_pose_device(p, ptr(d_a), ptr(d_b), ptr(d_ia), ptr(d_ib), ptr(d_w), at("pose"), at("rate"), at("flags"), at("weights"),
                                  stream=stream)
     torch.cuda.synchronize()
-    out = {}
-    for name, dt, k in OUTS:
-        if name in want:
-            raw = bufs[name].cpu().numpy()
-            assert (raw[:GUARD] == FILL).all() and (raw[GUARD + size[name]:] == FILL).all(), "guard bytes of " + name
-            out[name] = raw[GUARD:GUARD + size[name]].copy().view(dt).reshape((5, n_pairs) if k == 5 else (n_pairs,))
-    return out
+    dts = {name: dt for name, dt, _k in OUTS}
+    return {name: raw.view(dts[name]).reshape((5, n_pairs) if name == "pose" else (n_pairs,)) for name, raw in PC.payloads(bufs, size).items()}
 
 
-def _same(got, want, names=("pose", "rate", "flags", "weights")):
-    for name in names:
-        g, w = got[name], want[name]
-        if g.dtype == np.float64:
-            nan = np.isnan(w)
-            ulps = np.abs(g.view(np.int64)[~nan] - w.view(np.int64)[~nan])
-            assert np.array_equal(np.isnan(g), nan) and not ulps.any(), "%s: largest difference %d ulps" % (name, ulps.max(initial=0))
-        else:
-            assert np.array_equal(g, w), (name, g, w)
+_same = lambda got, want, names=("pose", "rate", "flags", "weights"): PC.same(got, want, names)          # noqa: E731
 
 
 def _check(a, b, n_a, n_b, n_pairs, **kw):
@@ -87,10 +59,10 @@ def _check(a, b, n_a, n_b, n_pairs, **kw):
 @pytest.mark.parametrize("P", [2, 3, 9])
 @pytest.mark.parametrize("n", [1, 63, 64, 65, 255, 256, 257, 600])
 def test_tiles_and_tails(n, P):
-    a, b = miss_ref.planar(_tracks(n, P, 1), n + 3), miss_ref.planar(_tracks(n, P, 2), n + 9)       # ld > n
+    a, b = miss_ref.planar(PC.tracks(n, P, 1), n + 3), miss_ref.planar(PC.tracks(n, P, 2), n + 9)       # ld > n
     got, _ = _check(a, b, n, n, n, seed=n * 16 + P)                                                  # identity
     assert not (got["flags"] & (L.ENC_BAD_INDEX | L.ENC_NO_ENTRY | L.ENC_FALLBACK)).any() and (got["rate"] > 0.0).all()
-    own = miss_ref.planar(_tracks(1, P, 3), 5)
+    own = miss_ref.planar(PC.tracks(1, P, 3), 5)
     _check(own, b, 1, n, n)                                                                          # one ownship
     _check(a, own, n, 1, n)
     rs = np.random.RandomState(n * 64 + P)
@@ -100,7 +72,7 @@ def test_tiles_and_tails(n, P):
 
 def test_a_workgroup_walks_a_second_tile():
     n = 2048 * 256 + 300
-    a, b = miss_ref.planar(_tracks(n, 2, 4)), miss_ref.planar(_tracks(n, 2, 5))
+    a, b = miss_ref.planar(PC.tracks(n, 2, 4)), miss_ref.planar(PC.tracks(n, 2, 5))
     got, _ = _check(a, b, n, n, n, max_attempts=3)
     end = (got["flags"] & L.ENC_END) != 0
     assert 0.05 < end.mean() < 0.95 and 0 < ((got["flags"] & L.ENC_FALLBACK) != 0).sum() < 0.03 * n      # 0.215^3 = 0.0099, ends once more
@@ -109,7 +81,7 @@ def test_a_workgroup_walks_a_second_tile():
 # ---- 2. indices
 def test_a_bad_index_loads_nothing_and_leaves_its_neighbours_alone():
     n, P = 70, 5
-    a, b = miss_ref.planar(_tracks(n, P, 6), n + 2), miss_ref.planar(_tracks(n, P, 7), n)
+    a, b = miss_ref.planar(PC.tracks(n, P, 6), n + 2), miss_ref.planar(PC.tracks(n, P, 7), n)
     ia, ib = np.arange(n, dtype=np.int64), np.arange(n, dtype=np.int64)[::-1].copy()
     good, _ = _check(a, b, n, n, n, idx_a=ia, idx_b=ib, weights_in=np.full(n, 3))
     ia[[0, 64]], ia[33], ib[5], ib[69] = -1, n, 2**62, -2**63
@@ -125,7 +97,7 @@ def test_a_bad_index_loads_nothing_and_leaves_its_neighbours_alone():
 # ---- 3. the rejection loop
 def test_one_attempt_and_sixteen():
     n, P = 1000, 2
-    a, b = miss_ref.planar(_tracks(n, P, 8)), miss_ref.planar(_tracks(n, P, 9))
+    a, b = miss_ref.planar(PC.tracks(n, P, 8)), miss_ref.planar(PC.tracks(n, P, 9))
     one, want = _check(a, b, n, n, n, max_attempts=1)
     fell = (one["flags"] & L.ENC_FALLBACK) != 0
     assert fell.any() and np.array_equal(fell, (want["flags"] & R.FALLBACK) != 0)
@@ -140,7 +112,7 @@ def test_one_attempt_and_sixteen():
 
 def test_first_index_names_the_rows_of_a_longer_call():
     n, P, k = 600, 3, 277
-    a, b = _tracks(n, P, 10), _tracks(n, P, 11)
+    a, b = PC.tracks(n, P, 10), PC.tracks(n, P, 11)
     whole, _ = _check(miss_ref.planar(a), miss_ref.planar(b), n, n, n)
     part, _ = _check(miss_ref.planar(a[k:]), miss_ref.planar(b[k:]), n - k, n - k, n - k, first_index=k)
     for name in ("pose", "rate", "flags", "weights"):
@@ -152,7 +124,7 @@ def test_first_index_names_the_rows_of_a_longer_call():
 # ---- 4. no entry, ends only, NaN
 def test_two_aircraft_standing_still_have_no_entry():
     n, P = 130, 2
-    a, b = _tracks(n, P, 12).copy(), _tracks(n, P, 13).copy()
+    a, b = PC.tracks(n, P, 12).copy(), PC.tracks(n, P, 13).copy()
     still = np.zeros(n, dtype=bool)
     still[[0, 63, 64, 129]] = True
     a[still, 1], b[still, 1] = a[still, 0], b[still, 0]
@@ -164,7 +136,7 @@ def test_two_aircraft_standing_still_have_no_entry():
 
 def test_purely_vertical_relative_motion_enters_through_an_end():
     n, P = 300, 2
-    a, b = _tracks(n, P, 14).copy(), _tracks(n, P, 15).copy()
+    a, b = PC.tracks(n, P, 14).copy(), PC.tracks(n, P, 15).copy()
     a[:, 1, :2], b[:, 1, :2] = a[:, 0, :2], b[:, 0, :2]                      # no horizontal motion at all: g = 0 whatever the heading
     got, _ = _check(miss_ref.planar(a), miss_ref.planar(b), n, n, n)
     wr = (b[:, 1, 2] - b[:, 0, 2]) - (a[:, 1, 2] - a[:, 0, 2])
@@ -176,7 +148,7 @@ def test_purely_vertical_relative_motion_enters_through_an_end():
 
 def test_a_nan_coordinate_in_either_point_is_no_entry():
     n, P = 66, 3
-    a, b = _tracks(n, P, 16).copy(), _tracks(n, P, 17).copy()
+    a, b = PC.tracks(n, P, 16).copy(), PC.tracks(n, P, 17).copy()
     a[1, 0, 0], a[2, 1, 1], b[3, 0, 2], b[65, 1, 0], a[64, 1, 2], b[5, 0, 1] = (np.nan,) * 6
     b[6, 1, 0], a[7, 2, 0] = np.inf, np.nan                                  # an infinite speed; a NaN in point 2, which is not read
     got, _ = _check(miss_ref.planar(a), miss_ref.planar(b), n, n, n)
@@ -189,7 +161,7 @@ def test_a_nan_coordinate_in_either_point_is_no_entry():
 # ---- 5. weights
 def test_weights_that_saturate_and_weights_out_alone():
     n, P = 257, 2
-    a, b = miss_ref.planar(_tracks(n, P, 18)), miss_ref.planar(_tracks(n, P, 19))
+    a, b = miss_ref.planar(PC.tracks(n, P, 18)), miss_ref.planar(PC.tracks(n, P, 19))
     plain, want = _check(a, b, n, n, n)                                      # weights_out without weights_in: w = 1
     live = want["rate"] > 0.0
     assert np.array_equal(plain["weights"][live], np.floor(want["rate"][live] / SCALE + 0.5).astype(np.uint32)) and plain["weights"].max() > 1
@@ -207,7 +179,7 @@ def test_weights_that_saturate_and_weights_out_alone():
 # ---- 6. NULL outputs, streams
 def test_each_output_alone_and_each_output_left_out():
     n, P = 257, 3
-    a, b = miss_ref.planar(_tracks(n, P, 20)), miss_ref.planar(_tracks(n, P, 21))
+    a, b = miss_ref.planar(PC.tracks(n, P, 20)), miss_ref.planar(PC.tracks(n, P, 21))
     w = np.random.RandomState(4).randint(0, 1000, n)
     full, _ = _check(a, b, n, n, n, weights_in=w)
     assert not (full["flags"] & L.ENC_SATURATED).any()
@@ -221,7 +193,7 @@ def test_each_output_alone_and_each_output_left_out():
 def test_a_stream_of_its_own_and_the_helpers():
     import torch
     n, P = 300, 6
-    rows_a, rows_b = _tracks(n, P, 22), _tracks(n, P, 23)
+    rows_a, rows_b = PC.tracks(n, P, 22), PC.tracks(n, P, 23)
     a, b = miss_ref.planar(rows_a), miss_ref.planar(rows_b)
     want = R.encounter(a, b, n, n, n, RADIUS, HALF_HEIGHT, 7, rate_scale=SCALE)
     side = torch.cuda.Stream()

@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 
 import miss_ref as R
+import pair_cases as PC
 from em_model_manned_bayes_amd import _lib as L
 from em_model_manned_bayes_amd import em_io, native
 from em_model_manned_bayes_amd import encounter_model as E
@@ -15,24 +16,9 @@ from em_model_manned_bayes_amd import functions as F
 
 pytestmark = pytest.mark.gpu
 
-GUARD, FILL = 64, 0xA5
 OUTS = (("hmd", np.float64), ("vmd", np.float64), ("t_cpa", np.int32), ("flags", np.uint8), ("totals", np.uint64))
 UR = ((1852.0 / 0.3048) / 3600.0, 1.0 / 60.0, 1.0)
 _cache = {}
-
-
-def _tracks(n, P, seed):
-    """n random tracks [n, P, 3] of a few thousand feet extent, drawn once per shape and shared (read-only)"""
-    key = (n, P, seed)
-    if key not in _cache:
-        rs = np.random.RandomState(seed * 7919 + n * 131 + P)
-        start = np.concatenate([rs.uniform(-2500.0, 2500.0, (n, 1, 2)), rs.uniform(1000.0, 1600.0, (n, 1, 1))], axis=2)
-        vel = np.concatenate([rs.uniform(-250.0, 250.0, (n, 1, 2)), rs.uniform(-30.0, 30.0, (n, 1, 1))], axis=2)
-        wob = np.cumsum(rs.uniform(-20.0, 20.0, (n, P, 3)), axis=1)
-        xyz = np.ascontiguousarray(start + vel * np.arange(P)[None, :, None] + wob)
-        xyz.setflags(write=False)
-        _cache[key] = xyz
-    return _cache[key]
 
 
 def _run(a, b, n_a, n_b, n_pairs, idx_a=None, idx_b=None, pose=None, weights=None, want=("hmd", "vmd", "t_cpa", "flags", "totals"),
@@ -44,34 +30,18 @@ def _run(a, b, n_a, n_b, n_pairs, idx_a=None, idx_b=None, pose=None, weights=Non
     d_a, d_b = up(a, np.float64), up(b, np.float64)
     d_ia, d_ib, d_pose = up(idx_a, np.int64), up(idx_b, np.int64), up(pose, np.float64)
     d_w = None if weights is None else torch.from_numpy(np.asarray(weights, dtype=np.uint32).view(np.int32).copy()).to(dev)
-    size = {name: (8 if name == "totals" else n_pairs) * np.dtype(dt).itemsize for name, dt in OUTS}
-    host = {name: np.full(size[name] + 2 * GUARD, FILL, dtype=np.uint8) for name in want}
-    if "totals" in want:
-        host["totals"][GUARD:GUARD + 64] = np.asarray(np.zeros(8) if totals is None else totals, dtype=np.uint64).view(np.uint8)
-    bufs = {name: torch.from_numpy(h).to(dev) for name, h in host.items()}
+    size = {name: (8 if name == "totals" else n_pairs) * np.dtype(dt).itemsize for name, dt in OUTS if name in want}
+    zero = np.asarray(np.zeros(8) if totals is None else totals, dtype=np.uint64).view(np.uint8)
+    bufs = PC.guarded(size, dev, {"totals": zero})
     ptr = lambda t: 0 if t is None else t.data_ptr()          # noqa: E731
     p = native.miss_params(n_pairs, n_a, n_b, a.shape[0], nmac[0], nmac[1], ld_a=a.shape[2], ld_b=b.shape[2])
     native.miss_distance_device(p, ptr(d_a), ptr(d_b), ptr(d_ia), ptr(d_ib), ptr(d_pose), ptr(d_w),
-                                **{name: bufs[name].data_ptr() + GUARD for name in want})
+                                **{name: bufs[name].data_ptr() + PC.GUARD for name in want})
     torch.cuda.synchronize()
-    out = {}
-    for name, dt in OUTS:
-        if name in want:
-            raw = bufs[name].cpu().numpy()
-            assert (raw[:GUARD] == FILL).all() and (raw[GUARD + size[name]:] == FILL).all(), "guard bytes of " + name
-            out[name] = raw[GUARD:GUARD + size[name]].copy().view(dt)
-    return out
+    return {name: raw.view(dict(OUTS)[name]) for name, raw in PC.payloads(bufs, size).items()}
 
 
-def _same(got, want, names=("hmd", "vmd", "t_cpa", "flags", "totals")):
-    for name in names:
-        g, w = got[name], want[name]
-        if g.dtype == np.float64:
-            nan = np.isnan(w)
-            ulps = np.abs(g.view(np.int64)[~nan] - w.view(np.int64)[~nan])
-            assert np.array_equal(np.isnan(g), nan) and not ulps.any(), "%s: largest difference %d ulps" % (name, ulps.max(initial=0))
-        else:
-            assert np.array_equal(g, w), (name, g, w)
+_same = lambda got, want, names=("hmd", "vmd", "t_cpa", "flags", "totals"): PC.same(got, want, names)          # noqa: E731
 
 
 def _check(a, b, n_a, n_b, n_pairs, **kw):
@@ -93,11 +63,11 @@ def _pose(n, seed):
 @pytest.mark.parametrize("P", [1, 2, 5, 64])
 @pytest.mark.parametrize("n", [1, 63, 64, 65, 255, 256, 257, 1000])
 def test_tiles_and_tails(n, P):
-    a, b = R.planar(_tracks(n, P, 1), n + 3), R.planar(_tracks(n, P, 2), n + 9)
+    a, b = R.planar(PC.tracks(n, P, 1), n + 3), R.planar(PC.tracks(n, P, 2), n + 9)
     got, _ = _check(a, b, n, n, n)                                                     # identity
     assert got["totals"][0] == n
     _check(a, b, n, n, n, pose=_pose(n, n + P))
-    own = R.planar(_tracks(1, P, 3), 5)
+    own = R.planar(PC.tracks(1, P, 3), 5)
     _check(own, b, 1, n, n, pose=_pose(n, 5))                                          # one ownship
     _check(a, own, n, 1, n)
     rs = np.random.RandomState(n * 64 + P)
@@ -109,7 +79,7 @@ def test_tiles_and_tails(n, P):
 # ---- 2. two squares that round to one root
 def test_the_minimum_is_over_the_roots_not_the_squares():
     dx, dy = 2607.925961031258, 4757.272111997083
-    a, b = _tracks(256, 2, 4).copy(), _tracks(256, 2, 5).copy()
+    a, b = PC.tracks(256, 2, 4).copy(), PC.tracks(256, 2, 5).copy()
     for lane in (0, 200):
         b[lane] = 0.0
         a[lane, :, 0], a[lane, :, 1], a[lane, :, 2] = [dx, np.nextafter(dx, 0.0)], dy, 0.0
@@ -176,7 +146,7 @@ def test_thresholds_are_strict():
 # ---- 6. bad indices
 def test_bad_indices_load_nothing_and_leave_their_neighbours_alone():
     n, P = 70, 5
-    a, b = R.planar(_tracks(n, P, 6), n + 2), R.planar(_tracks(n, P, 7), n)
+    a, b = R.planar(PC.tracks(n, P, 6), n + 2), R.planar(PC.tracks(n, P, 7), n)
     ia, ib = np.arange(n, dtype=np.int64), np.arange(n, dtype=np.int64)[::-1].copy()
     good, _ = _check(a, b, n, n, n, idx_a=ia, idx_b=ib, pose=_pose(n, 1))
     ia[[0, 64]], ia[33], ib[5], ib[69] = -1, n, 2**62, -2**63
@@ -193,7 +163,7 @@ def test_bad_indices_load_nothing_and_leave_their_neighbours_alone():
 # ---- 7. pose
 def test_a_null_pose_equals_the_identity_pose():
     n, P = 300, 7
-    a, b = R.planar(_tracks(n, P, 8)), R.planar(_tracks(n, P, 9))
+    a, b = R.planar(PC.tracks(n, P, 8)), R.planar(PC.tracks(n, P, 9))
     none, _ = _check(a, b, n, n, n)
     ident, _ = _check(a, b, n, n, n, pose=native.make_pose(np.zeros(n)))
     _same(ident, none)
@@ -202,7 +172,7 @@ def test_a_null_pose_equals_the_identity_pose():
 # ---- 8. weights and accumulation
 def test_weights_enter_the_totals_only_and_a_second_call_accumulates():
     n, P = 513, 4
-    a, b = R.planar(_tracks(n, P, 10)), R.planar(_tracks(n, P, 11))
+    a, b = R.planar(PC.tracks(n, P, 10)), R.planar(PC.tracks(n, P, 11))
     pose = native.make_pose(0.0, np.zeros(n), 0.0, 0.0)
     w = np.array([0, 1, 2**24 - 1, 2**32 - 1], dtype=np.uint64)[np.random.RandomState(3).randint(0, 4, n)]
     plain, _ = _check(a, b, n, n, n, pose=pose)
@@ -221,7 +191,7 @@ def test_weights_enter_the_totals_only_and_a_second_call_accumulates():
 # ---- 9. NULL outputs
 def test_each_output_alone_gives_what_all_together_give():
     n, P = 257, 3
-    a, b = R.planar(_tracks(n, P, 12)), R.planar(_tracks(n, P, 13))
+    a, b = R.planar(PC.tracks(n, P, 12)), R.planar(PC.tracks(n, P, 13))
     w = np.random.RandomState(4).randint(0, 1000, n)
     full, _ = _check(a, b, n, n, n, weights=w)
     for name, _dt in OUTS:
@@ -234,7 +204,7 @@ def test_a_context_hands_its_stream_to_the_context_free_call(gpu_ctx):
     helper then launches on it); either way the answers are the restatement's."""
     import torch
     n, P = 300, 6
-    rows_a, rows_b, pose = _tracks(n, P, 14), _tracks(n, P, 15), _pose(n, 16)
+    rows_a, rows_b, pose = PC.tracks(n, P, 14), PC.tracks(n, P, 15), _pose(n, 16)
     want = R.miss(R.planar(rows_a), R.planar(rows_b), n, n, n, pose_b=pose)
     names = {"hmd_ft": "hmd", "vmd_ft": "vmd", "t_cpa": "t_cpa", "flags": "flags", "totals": "totals"}
     side = torch.cuda.Stream()

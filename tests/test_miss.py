@@ -103,6 +103,29 @@ def test_every_refusal_names_its_argument():
     _refused("nmac_v_ft", ok(nmac_v_ft=float("nan")))
 
 
+def test_both_entry_points_say_the_same_about_a_faulty_pairing():
+    """emgpu_miss_distance_device and emgpu_encounter_pose_device check a pairing in one place: the same fault, the same message; only the
+    outputs named where there is nothing to write and the lower bound of `points` (1 and 2) are each call's own"""
+    def both(xyz_a=True, xyz_b=True, no_p=False, outs=True, **kw):
+        kw = {**dict(n_pairs=4, n_a=4, n_b=4, points=3), **kw}
+        rc, miss = _call(None if no_p else native.miss_params(**kw), xyz_a, xyz_b, outs=(outs,) * 5)
+        buf = np.zeros(64)
+        at = lambda yes: buf.ctypes.data_as(C.c_void_p) if yes else None          # noqa: E731
+        pe = native.encounter_params(radius_ft=1.0, half_height_ft=1.0, seed=0, **kw)
+        rc_e = L.lib().emgpu_encounter_pose_device(None, None if no_p else C.byref(pe), at(xyz_a), at(xyz_b), None, None, None, *(at(outs),) * 4)
+        assert rc == rc_e == L.ERR_ARG
+        return miss, L.lib().emgpu_last_error().decode()
+    for fault in (dict(no_p=True), dict(xyz_a=False), dict(xyz_b=False), dict(n_pairs=-1), dict(n_pairs=2**32 + 1, n_a=1, n_b=1), dict(n_a=0),
+                  dict(n_b=0), dict(ld_a=3), dict(ld_b=3), dict(n_pairs=5, n_b=5), dict(n_pairs=5, n_a=5), dict(n_pairs=5, n_a=1)):
+        miss, enc = both(**fault)
+        assert miss == enc and miss, (fault, miss, enc)
+    for fault in (dict(points=0), dict(points=65538), dict(points=0, n_a=0)):       # (two faults: the first check's message)
+        miss, enc = both(**fault)
+        assert miss == "points outside 1..65537" and enc == "points outside 2..65537"
+    miss, enc = both(outs=False, points=0)
+    assert miss != enc and miss.endswith(": nothing to write") and enc.endswith(": nothing to write")
+
+
 def test_no_pairs_succeed_without_a_launch_and_the_limits_themselves_pass_the_checks():
     assert _call(native.miss_params(0, 4, 4, 3))[0] == L.OK
     assert _call(native.miss_params(0, 1, 1, 65537, nmac_h_ft=0.0, nmac_v_ft=0.0, ld_a=1, ld_b=9))[0] == L.OK

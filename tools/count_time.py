@@ -48,6 +48,7 @@ def build_variant(out_dir, defines, units):
 
 def measure(args):
     sys.path.insert(0, HERE)
+    from _device_timing import timed as timed_on
     from em_model_manned_bayes_amd import _lib as L
     if args.lib:
         L.LIB_PATH = args.lib
@@ -61,16 +62,7 @@ def measure(args):
     launches = args.warmup + args.launches
     mean = lambda v: sum(v) / len(v)   # noqa: E731
 
-    def timed(fn):
-        ms = []
-        for _ in range(launches):
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record(stream)
-            fn()
-            e1.record(stream)
-            ctx.sync()
-            ms.append(round(e0.elapsed_time(e1), 4))
-        return ms[args.warmup:]
+    timed = lambda fn: timed_on(stream, fn, args.warmup, args.launches, ctx.sync)          # noqa: E731
 
     weights = {}
     if args.weighted:

@@ -24,6 +24,7 @@ def main():
     ap.add_argument("--model", default="uncor_1200code_v2p1")
     args = ap.parse_args()
     sys.path.insert(0, HERE)
+    from _device_timing import timed as timed_on
     import torch
     from em_model_manned_bayes_amd import _lib as L
     from em_model_manned_bayes_amd import em_io, native
@@ -34,16 +35,7 @@ def main():
     nm = native.NativeModel.load_txt(em_io.materialize_model(args.model, tempfile.mkdtemp()))
     ni, nd = nm.n_initial, nm.n_dyn
 
-    def timed(fn):
-        ms = []
-        for _ in range(args.warmup + args.launches):
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record(stream)
-            fn()
-            e1.record(stream)
-            ctx.sync()
-            ms.append(round(e0.elapsed_time(e1), 4))
-        return ms[args.warmup:]
+    timed = lambda fn: timed_on(stream, fn, args.warmup, args.launches, ctx.sync)          # noqa: E731
 
     ib = torch.empty((ni, n), dtype=torch.uint8, device=dev)
     db = torch.empty((G4, nd, n), dtype=torch.int32, device=dev)

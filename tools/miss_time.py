@@ -28,21 +28,15 @@ def main():
     import torch
     from em_model_manned_bayes_amd import _lib as L
     from em_model_manned_bayes_amd import native
+    from _device_timing import straight_tracks, timed as timed_on
     dev = torch.device("cuda", 0)
     stream = torch.cuda.current_stream(dev)
+    timed = lambda fn: timed_on(stream, fn, args.warmup, args.launches)          # noqa: E731
     n, P = args.n, args.points
     gen = torch.Generator(device=dev)
     gen.manual_seed(30)
 
-    def tracks():
-        xyz = torch.empty((P, 3, n), dtype=torch.float64, device=dev)
-        start = (torch.rand((3, n), dtype=torch.float64, device=dev, generator=gen) - 0.5) * 6000.0
-        vel = (torch.rand((3, n), dtype=torch.float64, device=dev, generator=gen) - 0.5) * 400.0
-        vel[2] *= 0.1
-        for p in range(P):
-            xyz[p] = start + vel * float(p)
-        return xyz
-    a, b = tracks(), tracks()
+    a, b = straight_tracks(n, P, dev, gen), straight_tracks(n, P, dev, gen)
     own = a[:, :, :1].contiguous()
     rs = np.random.RandomState(30)
     pose = torch.from_numpy(native.make_pose(rs.uniform(-180.0, 180.0, n), rs.uniform(-3000.0, 3000.0, n), rs.uniform(-3000.0, 3000.0, n),
@@ -52,17 +46,6 @@ def main():
     t_cpa, flags = torch.empty(n, dtype=torch.int32, device=dev), torch.empty(n, dtype=torch.uint8, device=dev)
     totals = torch.zeros(8, dtype=torch.int64, device=dev)
     torch.cuda.synchronize()
-
-    def timed(fn):
-        ms = []
-        for _ in range(args.warmup + args.launches):
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record(stream)
-            fn()
-            e1.record(stream)
-            torch.cuda.synchronize()
-            ms.append(round(e0.elapsed_time(e1), 4))
-        return ms[args.warmup:]
 
     def launch(xa, n_a, idx_b=0, with_pose=True):
         totals.zero_()

@@ -22,6 +22,7 @@ def main():
     ap.add_argument("--launches", type=int, default=5)
     args = ap.parse_args()
     sys.path.insert(0, HERE)
+    from _device_timing import timed as timed_on
     import torch
     from em_model_manned_bayes_amd import em_io, native, _lib as L
     dev = torch.device("cuda", 0)
@@ -30,16 +31,7 @@ def main():
     n, T, G4 = args.n, args.T, (args.T + 3) // 4
     out = {"lib": L.lib().emgpu_version().decode(), "device": torch.cuda.get_device_name(0), "n": n, "T": T, "cases": {}}
 
-    def timed(fn):
-        ms = []
-        for _ in range(args.warmup + args.launches):
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record(stream)
-            fn()
-            e1.record(stream)
-            ctx.sync()
-            ms.append(round(e0.elapsed_time(e1), 4))
-        return ms[args.warmup:]
+    timed = lambda fn: timed_on(stream, fn, args.warmup, args.launches, ctx.sync)          # noqa: E731
 
     trace = {}
     for name, mode in CASES:

@@ -23,6 +23,7 @@ def main():
     ap.add_argument("--model", default="uncor_1200code_v2p1")
     args = ap.parse_args()
     sys.path.insert(0, HERE)
+    from _device_timing import timed as timed_on
     import numpy as np
     import torch
     from em_model_manned_bayes_amd import _lib as L
@@ -42,16 +43,7 @@ def main():
     ur = ((1852.0 / 0.3048) / 3600.0, 1.0 / 60.0, 1.0)
     bv = np.asarray(parms["boundaries"][ids[1]], dtype=np.float64)
 
-    def timed(fn):
-        ms = []
-        for _ in range(args.warmup + args.launches):
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record(stream)
-            fn()
-            e1.record(stream)
-            ctx.sync()
-            ms.append(round(e0.elapsed_time(e1), 4))
-        return ms[args.warmup:]
+    timed = lambda fn: timed_on(stream, fn, args.warmup, args.launches, ctx.sync)          # noqa: E731
 
     iv = torch.empty((ni, n), dtype=torch.float32, device=dev)
     dv = torch.empty((G4, nd, n, 4), dtype=torch.float32, device=dev)
