@@ -1,0 +1,236 @@
+"""Paired tracks: the one pairing, and on it the miss distance and the encounter pose.  Torch does the plumbing here."""
+import contextlib
+import types
+
+import numpy as np
+
+from .. import _lib as L
+from .base import _device_call, _weights_array
+
+
+def miss_params(n_pairs, n_a, n_b, points, nmac_h_ft=500.0, nmac_v_ft=100.0, ld_a=0, ld_b=0):
+    """emgpu_miss_params: n_pairs pairs of a column of set A (n_a columns, pitch ld_a, 0 = n_a) and a column of set B, `points` seconds each;
+    the NMAC thresholds of track.m:175 in feet."""
+    p = L.MissParams()
+    p.n_pairs, p.n_a, p.n_b, p.ld_a, p.ld_b, p.points = int(n_pairs), int(n_a), int(n_b), int(ld_a), int(ld_b), int(points)
+    p.nmac_h_ft, p.nmac_v_ft = float(nmac_h_ft), float(nmac_v_ft)
+    return p
+
+
+def _stream_handle(stream):
+    """a raw hipStream_t as a context-free device call takes it: None is torch's current stream, 0 the HIP default stream (NULL)"""
+    if stream is None:
+        import torch
+        stream = torch.cuda.current_stream().cuda_stream
+    return int(stream) or None
+
+
+def miss_distance_device(params, xyz_a, xyz_b, idx_a=0, idx_b=0, pose_b=0, weights=0, hmd=0, vmd=0, t_cpa=0, flags=0, totals=0, stream=None):
+    """emgpu_miss_distance_device: asynchronous, raw device pointers (ints, 0 = none; params: miss_params).  xyz_a / xyz_b f64 PLANAR
+    [P, 3, ld], idx_a / idx_b int64 [n_pairs], pose_b f64 [5, n_pairs] (make_pose), weights uint32 [n_pairs]; hmd / vmd f64, t_cpa int32,
+    flags uint8 [n_pairs] each, totals uint64 [8], ADDED to.  The call takes no context: it runs on the current device and on `stream`, a
+    raw hipStream_t (0: the HIP default stream; None: torch's current stream).  To stay ordered behind a sampler, pass the stream its
+    Context was given (Context.stream)."""
+    _device_call("miss_distance_device", (_stream_handle(stream),), params, xyz_a, xyz_b, idx_a, idx_b, pose_b, weights, hmd, vmd, t_cpa, flags,
+                 totals)
+
+
+def make_pose(heading_deg, ox=0.0, oy=0.0, oz=0.0):
+    """The pose_b of miss_distance: [5, n] float64 on the host, rows cos, sin of heading_deg (counter-clockwise, MATLAB's cosd / sind: the
+    reduction in degrees of CorTerminalModel._sincosd, so that multiples of 90 give exact 0 and +-1), then the offsets ox, oy, oz in feet.
+    Track B is turned about its own origin by the heading, then moved by the offset.  The arguments broadcast against each other."""
+    from ..encounter_model import CorTerminalModel
+    h, ox, oy, oz = np.broadcast_arrays(*(np.atleast_1d(np.asarray(a, dtype=np.float64)) for a in (heading_deg, ox, oy, oz)))
+    s, c = CorTerminalModel._sincosd(h)
+    return np.ascontiguousarray(np.stack([c, s, ox, oy, oz]) + 0.0)   # (+ 0.0: -0.0 becomes 0.0)
+
+
+def _planar_tracks(xyz, layout, dev):
+    """xyz as a contiguous float64 PLANAR [P, 3, n] tensor on dev: numpy [n, P, 3] (layout "rows") or [P, 3, n] ("planar"), or a torch
+    tensor in either layout, uploaded and transposed by torch"""
+    import torch
+    if layout not in ("rows", "planar"):
+        raise ValueError("layout must be 'rows' or 'planar'")
+    if not isinstance(xyz, torch.Tensor):
+        xyz = np.ascontiguousarray(xyz, dtype=np.float64)
+        xyz = xyz if xyz.flags.writeable else xyz.copy()      # (torch takes no read-only array; the tensor is only read)
+    t = xyz if isinstance(xyz, torch.Tensor) else torch.from_numpy(xyz)
+    if t.dim() != 3 or t.shape[2 if layout == "rows" else 1] != 3:
+        raise ValueError("xyz must be [n, points, 3] (layout 'rows') or [points, 3, n] ('planar')")
+    t = t.to(device=dev, dtype=torch.float64)
+    return (t.permute(1, 2, 0) if layout == "rows" else t).contiguous()
+
+
+def _pair_columns(xyz_a, xyz_b, idx_a, idx_b, layout):
+    """(n_a, n_b, [idx_a, idx_b] as int64 vectors or None, n_pairs) of a pairing of two sets of tracks, as miss_distance reads its arguments"""
+    import torch
+    n_of = lambda t: int(t.shape[0 if layout == "rows" else 2])          # noqa: E731
+    for t in (xyz_a, xyz_b):
+        if getattr(t, "ndim", 0) != 3:
+            raise ValueError("xyz must be [n, points, 3] (layout 'rows') or [points, 3, n] ('planar')")
+    n_a, n_b = n_of(xyz_a), n_of(xyz_b)
+    idx = [None if i is None else np.ascontiguousarray(i, dtype=np.int64).reshape(-1) if not isinstance(i, torch.Tensor) else i
+           for i in (idx_a, idx_b)]
+    return n_a, n_b, idx, max([len(i) for i in idx if i is not None] + [n for n, i in zip((n_a, n_b), idx) if i is None])
+
+
+@contextlib.contextmanager
+def _paired(xyz_a, xyz_b, columns, w, pose_b, layout, ctx, stream):
+    """The pairing step of miss_distance, encounter_pose and encounter_miss: what a launch on paired tracks needs, as a namespace of
+    dev, stream (resolved; None: torch's current stream), the PLANAR device tensors a / b, n_a, n_b, n_pairs, and d_ia, d_ib (int64), d_w
+    (uint32 held as int32) and d_pose on the device or None.  columns = _pair_columns(...), w = _weights_array(...) or None: the caller has
+    them before torch.cuda is touched.  The body runs on dev with the uploads complete for its stream; leaving it waits for that stream."""
+    import torch
+    n_a, n_b, idx, n_pairs = columns
+    dev = xyz_a.device if isinstance(xyz_a, torch.Tensor) and xyz_a.is_cuda else torch.device("cuda", torch.cuda.current_device())
+    if ctx is not None and stream is None:
+        stream = ctx.stream
+        if stream is None:
+            ctx.sync()
+    with torch.cuda.device(dev):
+        a, b = _planar_tracks(xyz_a, layout, dev), _planar_tracks(xyz_b, layout, dev)
+        if a.shape[0] != b.shape[0]:
+            raise ValueError("both sets of tracks must hold the same number of points")
+        up = lambda x, dt: None if x is None else (x if isinstance(x, torch.Tensor) else torch.from_numpy(x)).to(device=dev, dtype=dt).contiguous()  # noqa: E731
+        pr = types.SimpleNamespace(dev=dev, stream=stream, a=a, b=b, n_a=n_a, n_b=n_b, n_pairs=n_pairs, d_ia=up(idx[0], torch.int64),
+                                   d_ib=up(idx[1], torch.int64), d_pose=up(pose_b, torch.float64),
+                                   d_w=None if w is None else torch.from_numpy(w.view(np.int32)).to(dev))
+        # torch.cuda.synchronize brackets the launches only when they do not run on torch's stream, where the uploads ran
+        pr.guard = (lambda: None) if stream is None else (lambda: torch.cuda.synchronize(dev))
+        pr.guard()
+        yield pr
+        pr.guard()
+
+
+def _ptr(t):
+    return 0 if t is None else t.data_ptr()
+
+
+def _miss_tensors(pr, d_pose, d_w, nmac_h_ft, nmac_v_ft):
+    """k_miss_distance on the pairing pr with the device tensors d_pose and d_w (or None): the device tensors (hmd, vmd, t_cpa, flags,
+    totals), launched on pr.stream and not waited for"""
+    import torch
+    n, dev = pr.n_pairs, pr.dev
+    hmd, vmd = torch.empty(n, dtype=torch.float64, device=dev), torch.empty(n, dtype=torch.float64, device=dev)
+    t_cpa, flags = torch.empty(n, dtype=torch.int32, device=dev), torch.empty(n, dtype=torch.uint8, device=dev)
+    totals = torch.zeros(8, dtype=torch.int64, device=dev)
+    pr.guard()      # totals was zeroed on torch's stream
+    miss_distance_device(miss_params(n, pr.n_a, pr.n_b, pr.a.shape[0], nmac_h_ft, nmac_v_ft), _ptr(pr.a), _ptr(pr.b), _ptr(pr.d_ia), _ptr(pr.d_ib),
+                         _ptr(d_pose), _ptr(d_w), _ptr(hmd), _ptr(vmd), _ptr(t_cpa), _ptr(flags), _ptr(totals), stream=pr.stream)
+    return hmd, vmd, t_cpa, flags, totals
+
+
+def _miss_dict(hmd, vmd, t_cpa, flags, totals):
+    """miss_distance's dict from _miss_tensors' device tensors"""
+    fl = flags.cpu().numpy()
+    return {"hmd_ft": hmd.cpu().numpy(), "vmd_ft": vmd.cpu().numpy(), "t_cpa": t_cpa.cpu().numpy(), "flags": fl,
+            "nmac": (fl & L.MISS_NMAC_CPA) != 0, "totals": totals.cpu().numpy().view(np.uint64)}
+
+
+def _encounter_pose_tensors(pr, want_weights, radius_ft, half_height_ft, seed, rate_scale, first_index, max_attempts):
+    """k_encounter_pose on the pairing pr: the device tensors (pose [5, n_pairs], rate, flags, weights or None), launched on pr.stream and
+    not waited for"""
+    import torch
+    n, dev = pr.n_pairs, pr.dev
+    pose = torch.empty((5, n), dtype=torch.float64, device=dev)
+    rate = torch.empty(n, dtype=torch.float64, device=dev)
+    flags = torch.empty(n, dtype=torch.uint8, device=dev)
+    w_out = torch.empty(n, dtype=torch.int32, device=dev) if want_weights else None
+    p = encounter_params(n, pr.n_a, pr.n_b, pr.a.shape[0], radius_ft, half_height_ft, seed, first_index, max_attempts,
+                         1.0 if rate_scale is None else rate_scale)
+    encounter_pose_device(p, _ptr(pr.a), _ptr(pr.b), _ptr(pr.d_ia), _ptr(pr.d_ib), _ptr(pr.d_w), _ptr(pose), _ptr(rate), _ptr(flags), _ptr(w_out),
+                          stream=pr.stream)
+    return pose, rate, flags, w_out
+
+
+def _encounter_dict(rate, flags, w_out, flags_key="flags"):
+    """the rate, flags and weights of encounter_pose's dict from _encounter_pose_tensors' device tensors"""
+    return {"rate": rate.cpu().numpy(), flags_key: flags.cpu().numpy(), "weights": None if w_out is None else w_out.cpu().numpy().view(np.uint32)}
+
+
+def _encounter_weights(weights, rate_scale, n_pairs):
+    """(whether weights_out is wanted, weights_in as _weights_array or None) of encounter_pose's `weights`"""
+    want = weights is not None and weights is not False
+    if want and rate_scale is None:
+        raise ValueError("weights need a rate_scale: the rate that leaves a weight as it is")
+    return want, _weights_array(weights, n_pairs) if want and weights is not True else None
+
+
+def miss_distance(xyz_a, xyz_b, idx_a=None, idx_b=None, pose_b=None, weights=None, nmac_h_ft=500.0, nmac_v_ft=100.0, layout="rows", ctx=None,
+                  stream=None):
+    """Horizontal / vertical miss distance, time of closest approach and NMAC flags of paired 1 Hz tracks on the GPU
+    (emgpu_miss_distance_device; the definition is in include/emgpu.h: CorTerminalModel.m:117-133, track.m:175).  xyz_a / xyz_b: numpy
+    arrays [n, P, 3] in feet (layout "rows", what sample2track_host and a track file hold) or [P, 3, n] ("planar"), or torch tensors in
+    that layout, on the device or not; both sets hold the same P points.  Torch does the plumbing: the upload, the transposition to
+    PLANAR on the device, the outputs.  idx_a / idx_b: integer arrays, one column per pair; without idx_x pair i takes column i of set X,
+    or column 0 of a set of one (one ownship against every intruder); the number of pairs is the longest of what is given.  pose_b:
+    [5, n_pairs] float64 from make_pose.  weights: integers [n_pairs] in 0 .. 2**32 - 1 (quantize_weights), ValueError otherwise; they
+    enter totals[5:8] only.
+    Returns {"hmd_ft", "vmd_ft" float64, "t_cpa" int32, "flags" uint8 (L.MISS_*), "nmac" bool: NMAC at the CPA, "totals" uint64 [8]} as
+    numpy arrays; totals[6] / totals[5] is the weighted NMAC rate.
+    The kernel runs on `stream` (a raw hipStream_t) or, without one, on torch's current stream.  ctx: a Context whose earlier device
+    calls produced the inputs -- its stream is used when it was given one (Context.stream), and when it runs on a stream of its own
+    (Context.stream is None) ctx.sync() is called first, so that the inputs are complete."""
+    import torch
+    columns = _pair_columns(xyz_a, xyz_b, idx_a, idx_b, layout)
+    w = None if weights is None else _weights_array(weights, columns[3])
+    if pose_b is not None:
+        pose_b = np.ascontiguousarray(pose_b, dtype=np.float64) if not isinstance(pose_b, torch.Tensor) else pose_b
+        if tuple(pose_b.shape) != (5, columns[3]):
+            raise ValueError("pose_b must be [5, n_pairs] (make_pose)")
+    with _paired(xyz_a, xyz_b, columns, w, pose_b, layout, ctx, stream) as pr:
+        out = _miss_tensors(pr, pr.d_pose, pr.d_w, nmac_h_ft, nmac_v_ft)
+    return _miss_dict(*out)
+
+
+def encounter_params(n_pairs, n_a, n_b, points, radius_ft, half_height_ft, seed, first_index=0, max_attempts=16, rate_scale=1.0, ld_a=0, ld_b=0):
+    """emgpu_encounter_params: n_pairs pairs of a column of set A (the ownship; n_a columns, pitch ld_a, 0 = n_a) and a column of set B (the
+    intruder), an encounter cylinder of radius_ft and half_height_ft around the ownship, the seed and the global index of pair 0;
+    rate_scale divides the rate where it is folded into weights_out."""
+    p = L.EncounterParams()
+    p.n_pairs, p.n_a, p.n_b, p.ld_a, p.ld_b, p.points = int(n_pairs), int(n_a), int(n_b), int(ld_a), int(ld_b), int(points)
+    p.max_attempts, p.seed, p.first_index = int(max_attempts), int(seed) & (2**64 - 1), int(first_index) & (2**64 - 1)
+    p.radius_ft, p.half_height_ft, p.rate_scale = float(radius_ft), float(half_height_ft), float(rate_scale)
+    return p
+
+
+def encounter_pose_device(params, xyz_a, xyz_b, idx_a=0, idx_b=0, weights_in=0, pose=0, rate=0, flags=0, weights_out=0, stream=None):
+    """emgpu_encounter_pose_device: asynchronous, raw device pointers (ints, 0 = none; params: encounter_params).  xyz_a / xyz_b f64 PLANAR
+    [P, 3, ld] (points 0 and 1 are read), idx_a / idx_b int64 [n_pairs], weights_in uint32 [n_pairs]; pose f64 [5, n_pairs] (what
+    miss_distance_device takes as pose_b), rate f64, flags uint8 (L.ENC_*), weights_out uint32 [n_pairs] each.  No context: the current
+    device and `stream`, a raw hipStream_t (0: the HIP default stream; None: torch's current stream)."""
+    _device_call("encounter_pose_device", (_stream_handle(stream),), params, xyz_a, xyz_b, idx_a, idx_b, weights_in, pose, rate, flags, weights_out)
+
+
+def encounter_pose(xyz_a, xyz_b, radius_ft, half_height_ft, seed, idx_a=None, idx_b=None, weights=None, rate_scale=None, first_index=0,
+                   max_attempts=16, layout="rows", ctx=None, stream=None):
+    """Places each intruder (set B) on the encounter cylinder of radius_ft and half_height_ft around its ownship (set A) on the GPU
+    (emgpu_encounter_pose_device; the definition is in include/emgpu.h): a seeded random heading, an entry point where the intruder flies
+    into the cylinder, drawn in proportion to the flux through the side and the ends, and the volume the cylinder sweeps per second
+    relative to the intruder, in cubic feet per second.  xyz_a / xyz_b, idx_a / idx_b, layout, ctx and stream are miss_distance's; only the
+    first two points of each track are read.  Pair i draws from the global index first_index + i, so a call on rows k .. of a set with
+    first_index=k gives rows k .. of the call on the whole set.
+    weights: integers [n_pairs] in 0 .. 2**32 - 1 (quantize_weights) to fold the rate into; True: fold it into weights of 1.  Either needs
+    rate_scale (ValueError without): the weight is floor(w * rate / rate_scale + 0.5), clamped to 2**32 - 1 (L.ENC_SATURATED), so
+    rate_scale is the rate that keeps a weight as it is -- ks times a bound on the relative speed is the caller's to give.
+    Returns {"pose" float64 [5, n_pairs] (miss_distance's pose_b), "rate" float64, "flags" uint8 (L.ENC_*), "weights" uint32 or None}."""
+    columns = _pair_columns(xyz_a, xyz_b, idx_a, idx_b, layout)
+    want_weights, w = _encounter_weights(weights, rate_scale, columns[3])
+    with _paired(xyz_a, xyz_b, columns, w, None, layout, ctx, stream) as pr:
+        pose, *out = _encounter_pose_tensors(pr, want_weights, radius_ft, half_height_ft, seed, rate_scale, first_index, max_attempts)
+    return {"pose": pose.cpu().numpy(), **_encounter_dict(*out)}
+
+
+def encounter_miss(xyz_a, xyz_b, radius_ft, half_height_ft, seed, idx_a=None, idx_b=None, weights=None, rate_scale=None, first_index=0,
+                   max_attempts=16, nmac_h_ft=500.0, nmac_v_ft=100.0, layout="rows", ctx=None, stream=None):
+    """encounter_pose and then miss_distance on one stream, the pose and the rate-folded weights never leaving the device: the intruders
+    placed on the encounter cylinder, then HMD, VMD, CPA time and NMAC flags of the pairs.  The arguments are encounter_pose's and the
+    NMAC thresholds.  With weights (and rate_scale) totals[5:8] are sums of w * rate / rate_scale, so totals[6] / totals[5] is
+    P(NMAC | encounter); without, every pair counts 1 there.
+    Returns miss_distance's dict plus "rate" float64, "encounter_flags" uint8 (L.ENC_*) and "weights" uint32 or None."""
+    columns = _pair_columns(xyz_a, xyz_b, idx_a, idx_b, layout)
+    want_weights, w = _encounter_weights(weights, rate_scale, columns[3])
+    with _paired(xyz_a, xyz_b, columns, w, None, layout, ctx, stream) as pr:
+        pose, rate, eflags, w_out = _encounter_pose_tensors(pr, want_weights, radius_ft, half_height_ft, seed, rate_scale, first_index, max_attempts)
+        out = _miss_tensors(pr, pose, w_out, nmac_h_ft, nmac_v_ft)
+    return dict(_miss_dict(*out), **_encounter_dict(rate, eflags, w_out, "encounter_flags"))
