@@ -26,6 +26,7 @@ TRANSITION_REFERENCE_AUTO, TRANSITION_PER_STEP = 0, 1
 VALUE_F32, VALUE_F64 = 0, 1       # emgpu_discretize_params.value_type
 TRACKS_PLANAR, TRACKS_ROWS = 0, 1 # emgpu_track_values_params.layout
 MISS_NMAC_CPA, MISS_NMAC_ANY, MISS_NO_CPA, MISS_BAD_INDEX = 1, 2, 4, 8   # emgpu_miss_distance_device's flags
+MISS_CPA_BETWEEN, MISS_NMAC_BETWEEN = 16, 32                             # emgpu_miss_segments_device's two more
 ENC_END, ENC_FALLBACK, ENC_NO_ENTRY, ENC_SATURATED, ENC_BAD_INDEX = 1, 2, 4, 8, 16   # emgpu_encounter_pose_device's flags
 FLAG_QUANTIZE500, FLAG_NO_RESAMPLE, FLAG_NO_DEDISC, FLAG_NO_TERMINATOR, FLAG_LOCAL_SMOOTH = 1, 2, 4, 8, 16
 
@@ -209,6 +210,7 @@ SYMBOLS = [
     "emgpu_track_values_device", "emgpu_track_values_host",
     "emgpu_count_dbn_weighted_device", "emgpu_count_dbn_weighted_host",
     "emgpu_miss_distance_device",
+    "emgpu_miss_segments_device",
     "emgpu_encounter_pose_device",
 ]
 
@@ -402,6 +404,7 @@ def lib():
     for f in (L.emgpu_track_values_device, L.emgpu_track_values_host):
         f.argtypes = [C.c_void_p, C.POINTER(TrackValuesParams)] + [C.c_void_p] * 3
     L.emgpu_miss_distance_device.argtypes = [C.c_void_p, C.POINTER(MissParams)] + [C.c_void_p] * 11
+    L.emgpu_miss_segments_device.argtypes = [C.c_void_p, C.POINTER(MissParams)] + [C.c_void_p] * 11
     L.emgpu_encounter_pose_device.argtypes = [C.c_void_p, C.POINTER(EncounterParams)] + [C.c_void_p] * 9
     _lib = L
     return L

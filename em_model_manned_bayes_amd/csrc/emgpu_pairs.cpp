@@ -1,11 +1,13 @@
-// emgpu_pairs.cpp -- the two entry points on paired 1 Hz tracks (the pairing: emgpu_pairs.h), side by side: emgpu_miss_distance_device
-// (k_miss_distance, emgpu_miss.h) and emgpu_encounter_pose_device (k_encounter_pose, emgpu_encounter.h).  They take no context: they need
+// emgpu_pairs.cpp -- the three entry points on paired 1 Hz tracks (the pairing: emgpu_pairs.h), side by side: emgpu_miss_distance_device
+// (k_miss_distance, emgpu_miss.h), emgpu_miss_segments_device (k_miss_segments, emgpu_miss_seg.h) and emgpu_encounter_pose_device
+// (k_encounter_pose, emgpu_encounter.h).  They take no context: they need
 // no model table, no scratch and no status word, so they run on the stream they are given and on the calling thread's current device.
 #include <cmath>
 
 #include "emgpu_internal.hpp"
 #include "emgpu_encounter.h"
 #include "emgpu_miss.h"
+#include "emgpu_miss_seg.h"
 
 namespace {
 // What can be said about a pairing without a device, for either params struct: EMGPU_OK, or the error (recorded).  have_out: the caller
@@ -58,6 +60,29 @@ int emgpu_miss_distance_device(void *hip_stream, const emgpu_miss_params *p, con
     A.P = p->points; A.nmac_h = p->nmac_h_ft; A.nmac_v = p->nmac_v_ft; A.pose = pose_b; A.weights = weights;
     A.hmd = hmd; A.vmd = vmd; A.t_cpa = t_cpa; A.flags = flags; A.totals = (unsigned long long *)totals;
     launch_ok(emgpu::launch_miss_distance(A, (hipStream_t)hip_stream, nullptr));
+    return EMGPU_OK;
+    EMGPU_CATCH
+}
+
+int emgpu_miss_segments_device(void *hip_stream, const emgpu_miss_params *p, const double *xyz_a, const double *xyz_b, const int64_t *idx_a,
+                               const int64_t *idx_b, const double *pose_b, const uint32_t *weights, double *hmd, double *vmd,
+                               double *t_cpa_s, uint8_t *flags, uint64_t *totals) {
+    EMGPU_TRY
+    if (const int rc = check_pairing(p, xyz_a, xyz_b, idx_a, idx_b, hmd || vmd || t_cpa_s || flags || totals,
+                                     "null hmd, vmd, t_cpa_s, flags and totals: nothing to write", 1))
+        return rc;
+    if (!(p->nmac_h_ft >= 0.0)) return fail(EMGPU_ERR_ARG, "nmac_h_ft is negative or NaN");
+    if (!(p->nmac_v_ft >= 0.0)) return fail(EMGPU_ERR_ARG, "nmac_v_ft is negative or NaN");
+    if (((uintptr_t)xyz_a | (uintptr_t)xyz_b | (uintptr_t)idx_a | (uintptr_t)idx_b | (uintptr_t)pose_b | (uintptr_t)hmd | (uintptr_t)vmd |
+         (uintptr_t)t_cpa_s | (uintptr_t)totals) & 7u)
+        return fail(EMGPU_ERR_ARG, "xyz_a, xyz_b, idx_a, idx_b, pose_b, hmd, vmd, t_cpa_s and totals must be 8-byte aligned");
+    if ((uintptr_t)weights & 3u) return fail(EMGPU_ERR_ARG, "weights must be 4-byte aligned");
+    if (p->n_pairs == 0) return EMGPU_OK;
+    EmgpuMissSegRun A{};
+    fill_pairing(p, xyz_a, xyz_b, idx_a, idx_b, A.dim, A.col);
+    A.P = p->points; A.nmac_h = p->nmac_h_ft; A.nmac_v = p->nmac_v_ft; A.pose = pose_b; A.weights = weights;
+    A.hmd = hmd; A.vmd = vmd; A.t_cpa_s = t_cpa_s; A.flags = flags; A.totals = (unsigned long long *)totals;
+    launch_ok(emgpu::launch_miss_segments(A, (hipStream_t)hip_stream, nullptr));
     return EMGPU_OK;
     EMGPU_CATCH
 }

@@ -668,27 +668,32 @@ class UncorEncounterModel(EncounterModel):
         return np.ascontiguousarray(np.stack([np.stack([r["east_ft"], r["north_ft"], r["up_ft"]], axis=1)[::int(stride)] for r in results]))
 
     def pair(self, own_xyz, intruder_xyz, pose=None, weights=None, idx_own=None, idx_intruder=None, nmac_h_ft=500.0, nmac_v_ft=100.0,
-             layout="rows", ctx=None):
+             layout="rows", ctx=None, between=False):
         """Pairs intruder tracks with ownship tracks and returns their miss distances, CPA times and NMAC flags, evaluated on the GPU: a
         thin wrapper over native.miss_distance (set A is the ownship, set B the intruder).  own_xyz / intruder_xyz: 1 Hz positions in
         feet, [n, P, 3] (track_xyz of .track results, sample2track's tracks) or layout="planar" [P, 3, n]; one ownship track serves every
         intruder.  pose: native.make_pose(heading_deg, ox, oy, oz), which turns and places each intruder -- uncor tracks all start at the
         origin heading east, so without one every pair starts as a collision.  weights: integer importance weights
-        (native.quantize_weights) for totals[5:8].  Returns native.miss_distance's dict."""
-        return native.miss_distance(own_xyz, intruder_xyz, idx_a=idx_own, idx_b=idx_intruder, pose_b=pose, weights=weights, nmac_h_ft=nmac_h_ft,
-                                    nmac_v_ft=nmac_v_ft, layout=layout, ctx=ctx)
+        (native.quantize_weights) for totals[5:8].  Returns native.miss_distance's dict.  between=True: the tracks are read as piecewise
+        linear between their seconds (native.miss_segments, whose dict is returned), so an NMAC that no whole second shows is found."""
+        miss = native.miss_segments if between else native.miss_distance
+        return miss(own_xyz, intruder_xyz, idx_a=idx_own, idx_b=idx_intruder, pose_b=pose, weights=weights, nmac_h_ft=nmac_h_ft, nmac_v_ft=nmac_v_ft,
+                    layout=layout, ctx=ctx)
 
     def encounter(self, own_xyz, intruder_xyz, radius_ft, half_height_ft, seed, weights=None, rate_scale=None, idx_own=None,
-                  idx_intruder=None, first_index=0, max_attempts=16, nmac_h_ft=500.0, nmac_v_ft=100.0, layout="rows", ctx=None):
+                  idx_intruder=None, first_index=0, max_attempts=16, nmac_h_ft=500.0, nmac_v_ft=100.0, layout="rows", ctx=None,
+                  between=False):
         """.pair with the pose drawn on the GPU: each intruder gets a seeded random heading and starts on the surface of the encounter
         cylinder of radius_ft and half_height_ft around its ownship, at a point where it flies into it (native.encounter_pose), and the
         pairs are evaluated on the same stream (native.encounter_miss).  "rate" is the volume the cylinder sweeps per second relative to
         the intruder, in cubic feet per second: airspace density times its mean is the encounter rate.  weights (integers, or True for
         1) with rate_scale fold the rate into the weights, so that totals[6] / totals[5] is P(NMAC | encounter).
-        Returns .pair's dict plus "rate", "encounter_flags" (L.ENC_*) and "weights"."""
-        return native.encounter_miss(own_xyz, intruder_xyz, radius_ft, half_height_ft, seed, idx_a=idx_own, idx_b=idx_intruder, weights=weights,
-                                     rate_scale=rate_scale, first_index=first_index, max_attempts=max_attempts, nmac_h_ft=nmac_h_ft,
-                                     nmac_v_ft=nmac_v_ft, layout=layout, ctx=ctx)
+        Returns .pair's dict plus "rate", "encounter_flags" (L.ENC_*) and "weights".  between=True: .pair's
+        (native.encounter_miss_segments)."""
+        miss = native.encounter_miss_segments if between else native.encounter_miss
+        return miss(own_xyz, intruder_xyz, radius_ft, half_height_ft, seed, idx_a=idx_own, idx_b=idx_intruder, weights=weights,
+                    rate_scale=rate_scale, first_index=first_index, max_attempts=max_attempts, nmac_h_ft=nmac_h_ft, nmac_v_ft=nmac_v_ft,
+                    layout=layout, ctx=ctx)
 
     def getDynamicLimits(self, initial, results, idx_G=None, idx_A=None, idx_L=None, idx_V=None, idx_DH=None, is_discretized=None):
         """dynamiclimits = getDynamicLimits(self, initial, results, ...)  (@UncorEncounterModel/getDynamicLimits.m).  The index

@@ -35,6 +35,14 @@ def miss_distance_device(params, xyz_a, xyz_b, idx_a=0, idx_b=0, pose_b=0, weigh
                  totals)
 
 
+def miss_segments_device(params, xyz_a, xyz_b, idx_a=0, idx_b=0, pose_b=0, weights=0, hmd=0, vmd=0, t_cpa_s=0, flags=0, totals=0, stream=None):
+    """emgpu_miss_segments_device: miss_distance_device on the segments between the seconds, the tracks read as piecewise linear.  The
+    arguments are miss_distance_device's but t_cpa_s f64 [n_pairs], the real-valued time of closest approach, and totals uint64 [10],
+    ADDED to; flags may carry L.MISS_CPA_BETWEEN and L.MISS_NMAC_BETWEEN."""
+    _device_call("miss_segments_device", (_stream_handle(stream),), params, xyz_a, xyz_b, idx_a, idx_b, pose_b, weights, hmd, vmd, t_cpa_s, flags,
+                 totals)
+
+
 def make_pose(heading_deg, ox=0.0, oy=0.0, oz=0.0):
     """The pose_b of miss_distance: [5, n] float64 on the host, rows cos, sin of heading_deg (counter-clockwise, MATLAB's cosd / sind: the
     reduction in degrees of CorTerminalModel._sincosd, so that multiples of 90 give exact 0 and +-1), then the offsets ox, oy, oz in feet.
@@ -127,6 +135,28 @@ def _miss_dict(hmd, vmd, t_cpa, flags, totals):
             "nmac": (fl & L.MISS_NMAC_CPA) != 0, "totals": totals.cpu().numpy().view(np.uint64)}
 
 
+def _miss_segments_tensors(pr, d_pose, d_w, nmac_h_ft, nmac_v_ft):
+    """k_miss_segments on the pairing pr, as _miss_tensors: the device tensors (hmd, vmd, t_cpa_s, flags, totals [10]), launched on pr.stream
+    and not waited for"""
+    import torch
+    n, dev = pr.n_pairs, pr.dev
+    hmd, vmd, t_cpa_s = (torch.empty(n, dtype=torch.float64, device=dev) for _ in range(3))
+    flags = torch.empty(n, dtype=torch.uint8, device=dev)
+    totals = torch.zeros(10, dtype=torch.int64, device=dev)
+    pr.guard()      # totals was zeroed on torch's stream
+    miss_segments_device(miss_params(n, pr.n_a, pr.n_b, pr.a.shape[0], nmac_h_ft, nmac_v_ft), _ptr(pr.a), _ptr(pr.b), _ptr(pr.d_ia), _ptr(pr.d_ib),
+                         _ptr(d_pose), _ptr(d_w), _ptr(hmd), _ptr(vmd), _ptr(t_cpa_s), _ptr(flags), _ptr(totals), stream=pr.stream)
+    return hmd, vmd, t_cpa_s, flags, totals
+
+
+def _miss_segments_dict(hmd, vmd, t_cpa_s, flags, totals):
+    """miss_segments' dict from _miss_segments_tensors' device tensors"""
+    fl = flags.cpu().numpy()
+    return {"hmd_ft": hmd.cpu().numpy(), "vmd_ft": vmd.cpu().numpy(), "t_cpa_s": t_cpa_s.cpu().numpy(), "flags": fl,
+            "nmac": (fl & L.MISS_NMAC_CPA) != 0, "nmac_any": (fl & L.MISS_NMAC_ANY) != 0, "between": (fl & L.MISS_NMAC_BETWEEN) != 0,
+            "totals": totals.cpu().numpy().view(np.uint64)}
+
+
 def _encounter_pose_tensors(pr, want_weights, radius_ft, half_height_ft, seed, rate_scale, first_index, max_attempts):
     """k_encounter_pose on the pairing pr: the device tensors (pose [5, n_pairs], rate, flags, weights or None), launched on pr.stream and
     not waited for"""
@@ -156,6 +186,18 @@ def _encounter_weights(weights, rate_scale, n_pairs):
     return want, _weights_array(weights, n_pairs) if want and weights is not True else None
 
 
+def _miss_inputs(xyz_a, xyz_b, idx_a, idx_b, pose_b, weights, layout):
+    """(columns, w, pose_b) of miss_distance's arguments, checked before torch.cuda is touched"""
+    import torch
+    columns = _pair_columns(xyz_a, xyz_b, idx_a, idx_b, layout)
+    w = None if weights is None else _weights_array(weights, columns[3])
+    if pose_b is not None:
+        pose_b = np.ascontiguousarray(pose_b, dtype=np.float64) if not isinstance(pose_b, torch.Tensor) else pose_b
+        if tuple(pose_b.shape) != (5, columns[3]):
+            raise ValueError("pose_b must be [5, n_pairs] (make_pose)")
+    return columns, w, pose_b
+
+
 def miss_distance(xyz_a, xyz_b, idx_a=None, idx_b=None, pose_b=None, weights=None, nmac_h_ft=500.0, nmac_v_ft=100.0, layout="rows", ctx=None,
                   stream=None):
     """Horizontal / vertical miss distance, time of closest approach and NMAC flags of paired 1 Hz tracks on the GPU
@@ -171,16 +213,24 @@ def miss_distance(xyz_a, xyz_b, idx_a=None, idx_b=None, pose_b=None, weights=Non
     The kernel runs on `stream` (a raw hipStream_t) or, without one, on torch's current stream.  ctx: a Context whose earlier device
     calls produced the inputs -- its stream is used when it was given one (Context.stream), and when it runs on a stream of its own
     (Context.stream is None) ctx.sync() is called first, so that the inputs are complete."""
-    import torch
-    columns = _pair_columns(xyz_a, xyz_b, idx_a, idx_b, layout)
-    w = None if weights is None else _weights_array(weights, columns[3])
-    if pose_b is not None:
-        pose_b = np.ascontiguousarray(pose_b, dtype=np.float64) if not isinstance(pose_b, torch.Tensor) else pose_b
-        if tuple(pose_b.shape) != (5, columns[3]):
-            raise ValueError("pose_b must be [5, n_pairs] (make_pose)")
+    columns, w, pose_b = _miss_inputs(xyz_a, xyz_b, idx_a, idx_b, pose_b, weights, layout)
     with _paired(xyz_a, xyz_b, columns, w, pose_b, layout, ctx, stream) as pr:
         out = _miss_tensors(pr, pr.d_pose, pr.d_w, nmac_h_ft, nmac_v_ft)
     return _miss_dict(*out)
+
+
+def miss_segments(xyz_a, xyz_b, idx_a=None, idx_b=None, pose_b=None, weights=None, nmac_h_ft=500.0, nmac_v_ft=100.0, layout="rows", ctx=None,
+                  stream=None):
+    """miss_distance between the seconds (emgpu_miss_segments_device; the definition is in include/emgpu.h): both tracks are read as
+    piecewise linear between their 1 Hz points, so the closest approach may lie inside a second and an NMAC that no sample sees is found.
+    The arguments are miss_distance's.
+    Returns {"hmd_ft", "vmd_ft", "t_cpa_s" float64 (seconds, real-valued), "flags" uint8 (L.MISS_*), "nmac" bool: NMAC at the CPA,
+    "nmac_any" bool: NMAC at some point or inside some segment, "between" bool: an NMAC that no whole second shows
+    (L.MISS_NMAC_BETWEEN), "totals" uint64 [10]: miss_distance's eight, the number of "between" pairs and the sum of their weights}."""
+    columns, w, pose_b = _miss_inputs(xyz_a, xyz_b, idx_a, idx_b, pose_b, weights, layout)
+    with _paired(xyz_a, xyz_b, columns, w, pose_b, layout, ctx, stream) as pr:
+        out = _miss_segments_tensors(pr, pr.d_pose, pr.d_w, nmac_h_ft, nmac_v_ft)
+    return _miss_segments_dict(*out)
 
 
 def encounter_params(n_pairs, n_a, n_b, points, radius_ft, half_height_ft, seed, first_index=0, max_attempts=16, rate_scale=1.0, ld_a=0, ld_b=0):
@@ -221,6 +271,17 @@ def encounter_pose(xyz_a, xyz_b, radius_ft, half_height_ft, seed, idx_a=None, id
     return {"pose": pose.cpu().numpy(), **_encounter_dict(*out)}
 
 
+def _encounter_then(tensors, as_dict, xyz_a, xyz_b, radius_ft, half_height_ft, seed, idx_a, idx_b, weights, rate_scale, first_index,
+                    max_attempts, nmac_h_ft, nmac_v_ft, layout, ctx, stream):
+    """encounter_pose and then `tensors` (_miss_tensors or _miss_segments_tensors) on one stream; the dict of `as_dict` plus the encounter's"""
+    columns = _pair_columns(xyz_a, xyz_b, idx_a, idx_b, layout)
+    want_weights, w = _encounter_weights(weights, rate_scale, columns[3])
+    with _paired(xyz_a, xyz_b, columns, w, None, layout, ctx, stream) as pr:
+        pose, rate, eflags, w_out = _encounter_pose_tensors(pr, want_weights, radius_ft, half_height_ft, seed, rate_scale, first_index, max_attempts)
+        out = tensors(pr, pose, w_out, nmac_h_ft, nmac_v_ft)
+    return dict(as_dict(*out), **_encounter_dict(rate, eflags, w_out, "encounter_flags"))
+
+
 def encounter_miss(xyz_a, xyz_b, radius_ft, half_height_ft, seed, idx_a=None, idx_b=None, weights=None, rate_scale=None, first_index=0,
                    max_attempts=16, nmac_h_ft=500.0, nmac_v_ft=100.0, layout="rows", ctx=None, stream=None):
     """encounter_pose and then miss_distance on one stream, the pose and the rate-folded weights never leaving the device: the intruders
@@ -228,9 +289,14 @@ def encounter_miss(xyz_a, xyz_b, radius_ft, half_height_ft, seed, idx_a=None, id
     NMAC thresholds.  With weights (and rate_scale) totals[5:8] are sums of w * rate / rate_scale, so totals[6] / totals[5] is
     P(NMAC | encounter); without, every pair counts 1 there.
     Returns miss_distance's dict plus "rate" float64, "encounter_flags" uint8 (L.ENC_*) and "weights" uint32 or None."""
-    columns = _pair_columns(xyz_a, xyz_b, idx_a, idx_b, layout)
-    want_weights, w = _encounter_weights(weights, rate_scale, columns[3])
-    with _paired(xyz_a, xyz_b, columns, w, None, layout, ctx, stream) as pr:
-        pose, rate, eflags, w_out = _encounter_pose_tensors(pr, want_weights, radius_ft, half_height_ft, seed, rate_scale, first_index, max_attempts)
-        out = _miss_tensors(pr, pose, w_out, nmac_h_ft, nmac_v_ft)
-    return dict(_miss_dict(*out), **_encounter_dict(rate, eflags, w_out, "encounter_flags"))
+    return _encounter_then(_miss_tensors, _miss_dict, xyz_a, xyz_b, radius_ft, half_height_ft, seed, idx_a, idx_b, weights, rate_scale,
+                           first_index, max_attempts, nmac_h_ft, nmac_v_ft, layout, ctx, stream)
+
+
+def encounter_miss_segments(xyz_a, xyz_b, radius_ft, half_height_ft, seed, idx_a=None, idx_b=None, weights=None, rate_scale=None, first_index=0,
+                            max_attempts=16, nmac_h_ft=500.0, nmac_v_ft=100.0, layout="rows", ctx=None, stream=None):
+    """encounter_miss with miss_segments in the place of miss_distance: the pose and the rate-folded weights stay on the device, and
+    totals[6] / totals[5] is P(NMAC | encounter) with the closest approach found between the seconds.  The arguments are encounter_miss's.
+    Returns miss_segments' dict plus "rate" float64, "encounter_flags" uint8 (L.ENC_*) and "weights" uint32 or None."""
+    return _encounter_then(_miss_segments_tensors, _miss_segments_dict, xyz_a, xyz_b, radius_ft, half_height_ft, seed, idx_a, idx_b, weights,
+                           rate_scale, first_index, max_attempts, nmac_h_ft, nmac_v_ft, layout, ctx, stream)

@@ -7,10 +7,11 @@ heading and an entry point on the cylinder around the ownship, where they fly in
 swept volume per second into the integer weights), and paired with the ownship (emgpu_miss_distance_device).  Nothing of a pair visits
 the host: only the eight totals and the mean rate come back.
 
-    python examples/run_encounter_rate.py [n] [sample_time] [density_per_nm3] [radius_nm] [half_height_ft]
+    python examples/run_encounter_rate.py [n] [sample_time] [density_per_nm3] [radius_nm] [half_height_ft] [--between]
 
 With weights w * rate / rate_scale, totals[6] / totals[5] is P(NMAC | encounter) under the shipped model; airspace density times the mean
-rate is the number of encounters per second of flight.
+rate is the number of encounters per second of flight.  --between: the same pairs once more with the tracks read as piecewise linear
+between their seconds (emgpu_miss_segments_device), which finds the NMACs that fall between two samples; both estimates are printed.
 """
 import os
 import sys
@@ -23,6 +24,8 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from em_model_manned_bayes_amd import _lib as L  # noqa: E402
 from em_model_manned_bayes_amd import em_io, native  # noqa: E402
 
+between = "--between" in sys.argv[1:]
+sys.argv = [a for a in sys.argv if a != "--between"]
 n = int(sys.argv[1]) if len(sys.argv) > 1 else 1_000_000
 T = int(sys.argv[2]) if len(sys.argv) > 2 else 60
 density_nm3 = float(sys.argv[3]) if len(sys.argv) > 3 else 1.0e-3      # aircraft per cubic nautical mile
@@ -77,6 +80,10 @@ native.encounter_pose_device(ep, own.data_ptr(), xyz.data_ptr(), weights_in=d_w.
 totals = torch.zeros(8, dtype=torch.int64, device=dev)
 native.miss_distance_device(native.miss_params(n, 1, n, T + 1), own.data_ptr(), xyz.data_ptr(), pose_b=pose.data_ptr(), weights=w_rate.data_ptr(),
                             totals=totals.data_ptr(), stream=ctx.stream)
+if between:
+    totals_seg = torch.zeros(10, dtype=torch.int64, device=dev)
+    native.miss_segments_device(native.miss_params(n, 1, n, T + 1), own.data_ptr(), xyz.data_ptr(), pose_b=pose.data_ptr(),
+                                weights=w_rate.data_ptr(), totals=totals_seg.data_ptr(), stream=ctx.stream)
 saturated = ((eflags & L.ENC_SATURATED) != 0).sum()
 no_entry = ((eflags & L.ENC_NO_ENTRY) != 0).sum()
 mean_rate = rate.mean()
@@ -94,3 +101,10 @@ ft3_per_nm3 = NM ** 3
 for name, r in (("proposal", float(mean_rate)), ("shipped model", float(mean_rate_model))):
     print("mean rate under the %s: %.4e ft^3/s = %.6f nm^3/s; at %.3g aircraft per nm^3: %.4e encounters per second, %.4f per flight hour"
           % (name, r, r / ft3_per_nm3, density_nm3, density_nm3 * r / ft3_per_nm3, 3600.0 * density_nm3 * r / ft3_per_nm3))
+if between:
+    g = totals_seg.cpu().numpy().view(np.uint64)
+    print("between the seconds: NMAC at CPA %d, NMAC at any time %d, of which no whole second shows %d (%.2f %%)"
+          % (g[1], g[2], g[8], 100.0 * float(g[8]) / max(float(g[2]), 1.0)))
+    print("P(NMAC | encounter) at any time: %.6f with the segments, %.6f at whole seconds only (ratio %.4f); at the CPA: %.6f and %.6f"
+          % (float(g[7]) / float(g[5]), float(t[7]) / float(t[5]), float(g[7]) / max(float(t[7]), 1.0), float(g[6]) / float(g[5]),
+             float(t[6]) / float(t[5])))

@@ -610,6 +610,46 @@ int emgpu_miss_distance_device(void *hip_stream, const emgpu_miss_params *p, con
                                int32_t *t_cpa, uint8_t *flags, uint64_t *totals);
 
 /* ------------------------------------------------------------------------------------------------
+ * Miss distance between the seconds: CPA and NMAC on track segments.  emgpu_miss_distance_device looks at the two aircraft at whole seconds
+ * only; two 250 kt aircraft close at up to 844 ft/s and cross the 1000 ft NMAC disc in 1.2 s, so a pair can pass through an NMAC between
+ * two samples and the per-second HMD is biased high.  This call reads both tracks as PIECEWISE LINEAR between their 1 Hz points and
+ * minimises in closed form per segment.  The params struct, the inputs, the pairing, the pose arithmetic and the bad-index rule are
+ * emgpu_miss_distance_device's; so are "no context, asynchronous, device pointers".
+ * Everything is f64; every product, sum, quotient and root is one IEEE operation in the order written; nothing is contracted; a NaN
+ * compares false.  H = nmac_h_ft, V = nmac_v_ft.
+ * Per point p = 0 .. P-1, as above: dx[p] = xa - xb', dy[p] = ya - yb', dz[p] = zb' - za, d[p] = sqrt(dx * dx + dy * dy).
+ * Per segment p = 1 .. P-1, between points p-1 and p, with (x0, y0, z0) = (dx, dy, dz)[p-1] and z1 = dz[p]:
+ *            ex = dx[p] - x0, ey = dy[p] - y0, ez = z1 - z0;  ee = ex * ex + ey * ey, re = x0 * ex + y0 * ey.
+ *            The segment is VALID iff ee, re, z0 and ez are all finite; an invalid segment contributes nothing.
+ *            ts = ee > 0 ? (-re) / ee : 0.0.
+ *            Interior candidate, iff ts > 0 && ts < 1: px = x0 + ts * ex, py = y0 + ts * ey, ds = sqrt(px * px + py * py),
+ *            zs = z0 + ts * ez, at time (double)(p-1) + ts.
+ *            Between test: near = min(z0, z1) < V && max(z0, z1) > -V.  If ez != 0: t0 = (-V - z0) / ez, t1 = (V - z0) / ez,
+ *            lo = max(min(t0, t1), 0), hi = min(max(t0, t1), 1), as compares and selects (mn = t0 < t1 ? t0 : t1, mx = t0 < t1 ? t1 : t0,
+ *            lo = mn > 0 ? mn : 0, hi = mx < 1 ? mx : 1); otherwise lo = 0, hi = 1.  tc = ts; tc = tc > lo ? tc : lo;
+ *            tc = tc < hi ? tc : hi.  qx = x0 + tc * ex, qy = y0 + tc * ey, dc = sqrt(qx * qx + qy * qy).
+ *            between = near && lo < hi && dc < H.  dc is the horizontal distance minimised over the part of the segment that lies inside
+ *            the vertical band: no discriminant, no cancellation.
+ * CPA        The candidates in time order: point 0, interior of segment 1, point 1, interior of segment 2, ...  A candidate is taken iff
+ *            cand == cand && (none yet || cand < best): the first of equal minima stays.  hmd and vmd are the winner's d and dz (ds and zs
+ *            for an interior winner); t_cpa_s is (double)p for a point and (p-1) + ts for an interior.  No candidate: NaN, NaN, -1.0,
+ *            EMGPU_MISS_NO_CPA.
+ * Flags      uint8 per pair; bits 1, 2, 4 and 8 keep their names.  EMGPU_MISS_NMAC_CPA: from this call's hmd and vmd.  EMGPU_MISS_NMAC_ANY:
+ *            some point has d < H && fabs(dz) < V, or some valid segment has `between`.  EMGPU_MISS_CPA_BETWEEN: the CPA is an interior
+ *            candidate.  EMGPU_MISS_NMAC_BETWEEN: NMAC_ANY is set and no point has it.  A bad index: NaN, NaN, -1.0 and
+ *            EMGPU_MISS_BAD_INDEX alone, no load.
+ * Outputs    hmd, vmd, t_cpa_s f64 [n_pairs], flags uint8 [n_pairs], each may be NULL; totals uint64 [10], ADDED to: [0..7] with the
+ *            meanings above (NMAC_CPA and NMAC_ANY being this call's), [8] pairs with NMAC_BETWEEN, [9] sum of w over those pairs.
+ * EMGPU_ERR_ARG as for emgpu_miss_distance_device, with the same messages for what the two share; t_cpa_s must be 8-byte aligned, and the
+ * nothing-to-write message names this call's outputs.  points >= 1; n_pairs == 0 succeeds and launches nothing.
+ * Out of scope: curved interpolation, slant range, a lag per pair, the ROWS layout, a _host entry point, a mex command. */
+#define EMGPU_MISS_CPA_BETWEEN 16u
+#define EMGPU_MISS_NMAC_BETWEEN 32u
+int emgpu_miss_segments_device(void *hip_stream, const emgpu_miss_params *p, const double *xyz_a, const double *xyz_b, const int64_t *idx_a,
+                               const int64_t *idx_b, const double *pose_b, const uint32_t *weights, double *hmd, double *vmd,
+                               double *t_cpa_s, uint8_t *flags, uint64_t *totals /* [10] */);
+
+/* ------------------------------------------------------------------------------------------------
  * Placing the intruder on the encounter cylinder: per pair a random heading of the intruder, its entry point on the surface of a cylinder
  * of radius R and half height H around the ownship, at a point where it flies INTO the cylinder, and the volume the cylinder sweeps per
  * second relative to it (Kochenderfer et al., "Airspace Encounter Models for Estimating Collision Risk": airspace density x E[rate] is the

@@ -1,4 +1,4 @@
-"""tools/miss_time.py [--n N] [--points P] [--warmup W] [--launches K] -- k_miss_distance on device-resident tracks, on one GPU: 4 M pairs x
+"""tools/miss_time.py [--n N] [--points P] [--warmup W] [--launches K] [--segments] -- k_miss_distance on device-resident tracks, on one GPU: 4 M pairs x
 241 points by default (two PLANAR sets of 24 P n bytes each, seeded straight tracks made by torch).  Three pairings are timed between
 two events on torch's current stream, every launch with a random pose per pair and all five outputs:
   identity    pair i = column i of both sets: a streaming read of both arrays;
@@ -6,7 +6,8 @@ two events on torch's current stream, every launch with a random pose per pair a
   permuted    a random permutation as idx_b: every load of set B is alone in its 64-byte sector.
 In the same process and on the same buffers, torch.sum over the two arrays (and over set B alone, for `ownship`) reads the same bytes.
 Each figure is the median of the launches behind the warm-up; the JSON line holds every launch.  identity_nopose_ms is the identity pairing
-without a pose.  The numbers are a record (HISTORY.md section 30), not a gate."""
+without a pose.  --segments: k_miss_segments[pose] on the same three pairings, in the same process and on the same buffers (t_cpa_s and ten
+totals of its own), as segments_*_ms beside the others.  The numbers are a record (HISTORY.md sections 30 and 36), not a gate."""
 import argparse
 import json
 import os
@@ -22,6 +23,7 @@ def main():
     ap.add_argument("--points", type=int, default=241)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--launches", type=int, default=7)
+    ap.add_argument("--segments", action="store_true")
     args = ap.parse_args()
     sys.path.insert(0, HERE)
     import numpy as np
@@ -57,6 +59,19 @@ def main():
                      ("identity_nopose", lambda: launch(a, n, with_pose=False))):
         ms[name] = timed(fn)
         tot[name] = [int(x) for x in totals.cpu().numpy().view(np.uint64)]
+    if args.segments:
+        t_cpa_s, totals10 = torch.empty(n, dtype=torch.float64, device=dev), torch.zeros(10, dtype=torch.int64, device=dev)
+        torch.cuda.synchronize()
+
+        def launch_segments(xa, n_a, idx_b=0):
+            totals10.zero_()
+            native.miss_segments_device(native.miss_params(n, n_a, n, P), xa.data_ptr(), b.data_ptr(), 0, idx_b, pose.data_ptr(), 0, hmd.data_ptr(),
+                                        vmd.data_ptr(), t_cpa_s.data_ptr(), flags.data_ptr(), totals10.data_ptr(), stream=stream.cuda_stream)
+
+        for name, fn in (("segments_identity", lambda: launch_segments(a, n)), ("segments_ownship", lambda: launch_segments(own, 1)),
+                         ("segments_permuted", lambda: launch_segments(a, n, perm.data_ptr()))):
+            ms[name] = timed(fn)
+            tot[name] = [int(x) for x in totals10.cpu().numpy().view(np.uint64)]
     sum_ab = timed(lambda: (torch.sum(a), torch.sum(b)))
     sum_b = timed(lambda: torch.sum(b))
     med = statistics.median
@@ -71,6 +86,12 @@ def main():
            "ratio_identity_to_sum": round(med(ms["identity"]) / med(sum_ab), 3), "ratio_ownship_to_sum_b": round(med(ms["ownship"]) / med(sum_b), 3),
            "ratio_permuted_to_sum": round(med(ms["permuted"]) / med(sum_ab), 3),
            "ratio_identity_nopose_to_sum": round(med(ms["identity_nopose"]) / med(sum_ab), 3), "totals": tot}
+    if args.segments:
+        out.update({name + "_ms": ms[name] for name in ms if name.startswith("segments_")})
+        out.update({"ratio_segments_identity_to_sum": round(med(ms["segments_identity"]) / med(sum_ab), 3),
+                    "ratio_segments_ownship_to_sum_b": round(med(ms["segments_ownship"]) / med(sum_b), 3),
+                    "ratio_segments_permuted_to_sum": round(med(ms["segments_permuted"]) / med(sum_ab), 3),
+                    "ratio_segments_identity_to_identity": round(med(ms["segments_identity"]) / med(ms["identity"]), 3)})
     print(json.dumps(out))
 
 
