@@ -28,6 +28,7 @@ TRACKS_PLANAR, TRACKS_ROWS = 0, 1 # emgpu_track_values_params.layout
 MISS_NMAC_CPA, MISS_NMAC_ANY, MISS_NO_CPA, MISS_BAD_INDEX = 1, 2, 4, 8   # emgpu_miss_distance_device's flags
 MISS_CPA_BETWEEN, MISS_NMAC_BETWEEN = 16, 32                             # emgpu_miss_segments_device's two more
 ENC_END, ENC_FALLBACK, ENC_NO_ENTRY, ENC_SATURATED, ENC_BAD_INDEX = 1, 2, 4, 8, 16   # emgpu_encounter_pose_device's flags
+CPA_FALLBACK, CPA_NO_PASS, CPA_SATURATED, CPA_BAD_INDEX = 2, 4, 8, 16                # emgpu_cpa_pose_device's flags
 FLAG_QUANTIZE500, FLAG_NO_RESAMPLE, FLAG_NO_DEDISC, FLAG_NO_TERMINATOR, FLAG_LOCAL_SMOOTH = 1, 2, 4, 8, 16
 
 # MATLAB error identifiers the reference raises for the same condition
@@ -176,6 +177,12 @@ class EncounterParams(C.Structure):     # emgpu_encounter_params
                 ("radius_ft", C.c_double), ("half_height_ft", C.c_double), ("rate_scale", C.c_double)]
 
 
+class CpaPoseParams(C.Structure):       # emgpu_cpa_pose_params
+    _fields_ = [("n_pairs", C.c_int64), ("n_a", C.c_int64), ("n_b", C.c_int64), ("ld_a", C.c_int64), ("ld_b", C.c_int64),
+                ("points", C.c_int32), ("max_attempts", C.c_int32), ("seed", C.c_uint64), ("first_index", C.c_uint64),
+                ("t_lo", C.c_int32), ("t_hi", C.c_int32), ("hmd_max_ft", C.c_double), ("vmd_max_ft", C.c_double), ("rate_scale", C.c_double)]
+
+
 class BnParams(C.Structure):
     _fields_ = [("seed", C.c_uint64), ("first_index", C.c_uint64), ("n", C.c_int64), ("flags", C.c_uint32),
                 ("max_attempts", C.c_int32), ("bounds_sample", C.c_void_p),
@@ -212,6 +219,7 @@ SYMBOLS = [
     "emgpu_miss_distance_device",
     "emgpu_miss_segments_device",
     "emgpu_encounter_pose_device",
+    "emgpu_cpa_pose_device",
 ]
 
 _lib = None
@@ -406,6 +414,7 @@ def lib():
     L.emgpu_miss_distance_device.argtypes = [C.c_void_p, C.POINTER(MissParams)] + [C.c_void_p] * 11
     L.emgpu_miss_segments_device.argtypes = [C.c_void_p, C.POINTER(MissParams)] + [C.c_void_p] * 11
     L.emgpu_encounter_pose_device.argtypes = [C.c_void_p, C.POINTER(EncounterParams)] + [C.c_void_p] * 9
+    L.emgpu_cpa_pose_device.argtypes = [C.c_void_p, C.POINTER(CpaPoseParams)] + [C.c_void_p] * 10
     _lib = L
     return L
 

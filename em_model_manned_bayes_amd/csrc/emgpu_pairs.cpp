@@ -1,10 +1,11 @@
-// emgpu_pairs.cpp -- the three entry points on paired 1 Hz tracks (the pairing: emgpu_pairs.h), side by side: emgpu_miss_distance_device
-// (k_miss_distance, emgpu_miss.h), emgpu_miss_segments_device (k_miss_segments, emgpu_miss_seg.h) and emgpu_encounter_pose_device
-// (k_encounter_pose, emgpu_encounter.h).  They take no context: they need
+// emgpu_pairs.cpp -- the four entry points on paired 1 Hz tracks (the pairing: emgpu_pairs.h), side by side: emgpu_miss_distance_device
+// (k_miss_distance, emgpu_miss.h), emgpu_miss_segments_device (k_miss_segments, emgpu_miss_seg.h), emgpu_encounter_pose_device
+// (k_encounter_pose, emgpu_encounter.h) and emgpu_cpa_pose_device (k_cpa_pose, emgpu_cpa.h).  They take no context: they need
 // no model table, no scratch and no status word, so they run on the stream they are given and on the calling thread's current device.
 #include <cmath>
 
 #include "emgpu_internal.hpp"
+#include "emgpu_cpa.h"
 #include "emgpu_encounter.h"
 #include "emgpu_miss.h"
 #include "emgpu_miss_seg.h"
@@ -111,6 +112,38 @@ int emgpu_encounter_pose_device(void *hip_stream, const emgpu_encounter_params *
     A.ke = (3.14159265358979323846 * A.R) * A.R;    // an end's area
     A.weights_in = weights_in; A.pose = pose; A.rate = rate; A.flags = flags; A.weights_out = weights_out;
     launch_ok(emgpu::launch_encounter_pose(A, (hipStream_t)hip_stream, nullptr));
+    return EMGPU_OK;
+    EMGPU_CATCH
+}
+
+int emgpu_cpa_pose_device(void *hip_stream, const emgpu_cpa_pose_params *p, const double *xyz_a, const double *xyz_b, const int64_t *idx_a,
+                          const int64_t *idx_b, const uint32_t *weights_in, double *pose, double *rate, int32_t *t_cpa, uint8_t *flags,
+                          uint32_t *weights_out) {
+    EMGPU_TRY
+    if (const int rc = check_pairing(p, xyz_a, xyz_b, idx_a, idx_b, pose || rate || t_cpa || flags || weights_out,
+                                     "null pose, rate, t_cpa, flags and weights_out: nothing to write", 2))
+        return rc;
+    if (!(std::isfinite(p->hmd_max_ft) && p->hmd_max_ft > 0.0)) return fail(EMGPU_ERR_ARG, "hmd_max_ft is not a finite positive number");
+    if (!(std::isfinite(p->vmd_max_ft) && p->vmd_max_ft > 0.0)) return fail(EMGPU_ERR_ARG, "vmd_max_ft is not a finite positive number");
+    if (!(std::isfinite(p->rate_scale) && p->rate_scale > 0.0)) return fail(EMGPU_ERR_ARG, "rate_scale is not a finite positive number");
+    if (p->max_attempts < 1 || p->max_attempts > 16) return fail(EMGPU_ERR_ARG, "max_attempts outside 1..16");
+    if (p->t_lo < 0) return fail(EMGPU_ERR_ARG, "t_lo is negative");
+    if (p->t_hi < p->t_lo) return fail(EMGPU_ERR_ARG, "t_hi < t_lo");
+    if (p->t_hi > p->points - 2) return fail(EMGPU_ERR_ARG, "t_hi > points - 2: point t_hi + 1 is read");
+    if (weights_in && !weights_out) return fail(EMGPU_ERR_ARG, "weights_in without weights_out");
+    if (((uintptr_t)xyz_a | (uintptr_t)xyz_b | (uintptr_t)idx_a | (uintptr_t)idx_b | (uintptr_t)pose | (uintptr_t)rate) & 7u)
+        return fail(EMGPU_ERR_ARG, "xyz_a, xyz_b, idx_a, idx_b, pose and rate must be 8-byte aligned");
+    if (((uintptr_t)weights_in | (uintptr_t)weights_out | (uintptr_t)t_cpa) & 3u)
+        return fail(EMGPU_ERR_ARG, "weights_in, weights_out and t_cpa must be 4-byte aligned");
+    if (p->n_pairs == 0) return EMGPU_OK;
+    EmgpuCpaRun A{};
+    fill_pairing(p, xyz_a, xyz_b, idx_a, idx_b, A.dim, A.col);
+    A.seed = p->seed; A.first_index = p->first_index; A.max_attempts = p->max_attempts;
+    A.t_lo = p->t_lo; A.span = (uint32_t)(p->t_hi - p->t_lo + 1);
+    A.Hm = p->hmd_max_ft; A.Vm = p->vmd_max_ft; A.rate_scale = p->rate_scale;
+    A.kc = (4.0 * A.Hm) * A.Vm;                     // the miss plane's area per unit of horizontal relative speed: 2 Hm x 2 Vm
+    A.weights_in = weights_in; A.pose = pose; A.rate = rate; A.t_cpa = t_cpa; A.flags = flags; A.weights_out = weights_out;
+    launch_ok(emgpu::launch_cpa_pose(A, (hipStream_t)hip_stream, nullptr));
     return EMGPU_OK;
     EMGPU_CATCH
 }

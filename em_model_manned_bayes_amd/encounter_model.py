@@ -695,6 +695,22 @@ class UncorEncounterModel(EncounterModel):
                     rate_scale=rate_scale, first_index=first_index, max_attempts=max_attempts, nmac_h_ft=nmac_h_ft, nmac_v_ft=nmac_v_ft,
                     layout=layout, ctx=ctx)
 
+    def encounter_cpa(self, own_xyz, intruder_xyz, hmd_max_ft, vmd_max_ft, seed, t_lo, t_hi=None, weights=None, rate_scale=None, between=False,
+                      idx_own=None, idx_intruder=None, first_index=0, max_attempts=16, nmac_h_ft=500.0, nmac_v_ft=100.0, layout="rows",
+                      ctx=None):
+        """.encounter with the intruder placed by its closest approach instead of on a cylinder: each intruder gets a seeded random
+        heading, a second drawn from t_lo .. t_hi (None: t_lo) at which it passes its ownship, and a lateral miss within +-hmd_max_ft
+        and a vertical offset within +-vmd_max_ft there (native.cpa_pose); the pairs are evaluated on the same stream
+        (native.cpa_miss).  "rate" is the flux through that miss plane, (2 hmd_max_ft)(2 vmd_max_ft) times the relative horizontal
+        speed, in cubic feet per second, and takes the cylinder rate's place in every total and weight; every placed pair passes
+        close by, so far fewer pairs are needed for an NMAC rate.  hmd_max_ft and vmd_max_ft must cover the NMAC thresholds.
+        Returns .pair's dict plus "rate", "t_cpa_drawn", "encounter_flags" (L.CPA_*) and "weights".  between=True: .pair's
+        (native.cpa_miss_segments)."""
+        miss = native.cpa_miss_segments if between else native.cpa_miss
+        return miss(own_xyz, intruder_xyz, hmd_max_ft, vmd_max_ft, seed, t_lo, t_hi, idx_a=idx_own, idx_b=idx_intruder, weights=weights,
+                    rate_scale=rate_scale, first_index=first_index, max_attempts=max_attempts, nmac_h_ft=nmac_h_ft, nmac_v_ft=nmac_v_ft,
+                    layout=layout, ctx=ctx)
+
     def getDynamicLimits(self, initial, results, idx_G=None, idx_A=None, idx_L=None, idx_V=None, idx_DH=None, is_discretized=None):
         """dynamiclimits = getDynamicLimits(self, initial, results, ...)  (@UncorEncounterModel/getDynamicLimits.m).  The index
         arguments are accepted for signature compatibility; they are looked up from the labels like .track does."""

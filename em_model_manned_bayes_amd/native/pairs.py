@@ -1,4 +1,5 @@
-"""Paired tracks: the one pairing, and on it the miss distance and the encounter pose.  Torch does the plumbing here."""
+"""Paired tracks: the one pairing, and on it the miss distance and the two placements of the intruder, on the encounter cylinder and at a
+drawn closest approach.  Torch does the plumbing here."""
 import contextlib
 import types
 
@@ -271,15 +272,24 @@ def encounter_pose(xyz_a, xyz_b, radius_ft, half_height_ft, seed, idx_a=None, id
     return {"pose": pose.cpu().numpy(), **_encounter_dict(*out)}
 
 
-def _encounter_then(tensors, as_dict, xyz_a, xyz_b, radius_ft, half_height_ft, seed, idx_a, idx_b, weights, rate_scale, first_index,
-                    max_attempts, nmac_h_ft, nmac_v_ft, layout, ctx, stream):
-    """encounter_pose and then `tensors` (_miss_tensors or _miss_segments_tensors) on one stream; the dict of `as_dict` plus the encounter's"""
+def _placed_then(place, placed_dict, tensors, as_dict, xyz_a, xyz_b, idx_a, idx_b, weights, rate_scale, nmac_h_ft, nmac_v_ft, layout, ctx, stream):
+    """A placement and then `tensors` (_miss_tensors or _miss_segments_tensors) on one stream, the pose and the weights staying on the
+    device.  place(pr, want_weights): the device tensors of _encounter_pose_tensors or _cpa_pose_tensors, the pose first and the weights
+    last; the dict of `as_dict` plus placed_dict of what the placement wrote beside the pose."""
     columns = _pair_columns(xyz_a, xyz_b, idx_a, idx_b, layout)
     want_weights, w = _encounter_weights(weights, rate_scale, columns[3])
     with _paired(xyz_a, xyz_b, columns, w, None, layout, ctx, stream) as pr:
-        pose, rate, eflags, w_out = _encounter_pose_tensors(pr, want_weights, radius_ft, half_height_ft, seed, rate_scale, first_index, max_attempts)
-        out = tensors(pr, pose, w_out, nmac_h_ft, nmac_v_ft)
-    return dict(as_dict(*out), **_encounter_dict(rate, eflags, w_out, "encounter_flags"))
+        pose, *placed = place(pr, want_weights)
+        out = tensors(pr, pose, placed[-1], nmac_h_ft, nmac_v_ft)
+    return dict(as_dict(*out), **placed_dict(*placed))
+
+
+def _encounter_then(tensors, as_dict, xyz_a, xyz_b, radius_ft, half_height_ft, seed, idx_a, idx_b, weights, rate_scale, first_index,
+                    max_attempts, nmac_h_ft, nmac_v_ft, layout, ctx, stream):
+    """encounter_pose and then `tensors` (_miss_tensors or _miss_segments_tensors) on one stream; the dict of `as_dict` plus the encounter's"""
+    return _placed_then(lambda pr, want: _encounter_pose_tensors(pr, want, radius_ft, half_height_ft, seed, rate_scale, first_index, max_attempts),
+                        lambda *placed: _encounter_dict(*placed, "encounter_flags"), tensors, as_dict, xyz_a, xyz_b, idx_a, idx_b, weights,
+                        rate_scale, nmac_h_ft, nmac_v_ft, layout, ctx, stream)
 
 
 def encounter_miss(xyz_a, xyz_b, radius_ft, half_height_ft, seed, idx_a=None, idx_b=None, weights=None, rate_scale=None, first_index=0,
@@ -300,3 +310,90 @@ def encounter_miss_segments(xyz_a, xyz_b, radius_ft, half_height_ft, seed, idx_a
     Returns miss_segments' dict plus "rate" float64, "encounter_flags" uint8 (L.ENC_*) and "weights" uint32 or None."""
     return _encounter_then(_miss_segments_tensors, _miss_segments_dict, xyz_a, xyz_b, radius_ft, half_height_ft, seed, idx_a, idx_b, weights,
                            rate_scale, first_index, max_attempts, nmac_h_ft, nmac_v_ft, layout, ctx, stream)
+
+
+def cpa_pose_params(n_pairs, n_a, n_b, points, hmd_max_ft, vmd_max_ft, seed, t_lo, t_hi=None, first_index=0, max_attempts=16, rate_scale=1.0,
+                    ld_a=0, ld_b=0):
+    """emgpu_cpa_pose_params: n_pairs pairs of a column of set A (the ownship; n_a columns, pitch ld_a, 0 = n_a) and a column of set B (the
+    intruder), a miss plane of +-hmd_max_ft by +-vmd_max_ft, the seconds t_lo .. t_hi (None: t_lo alone) the pass is drawn from, the seed
+    and the global index of pair 0; rate_scale divides the rate where it is folded into weights_out."""
+    p = L.CpaPoseParams()
+    p.n_pairs, p.n_a, p.n_b, p.ld_a, p.ld_b, p.points = int(n_pairs), int(n_a), int(n_b), int(ld_a), int(ld_b), int(points)
+    p.max_attempts, p.seed, p.first_index = int(max_attempts), int(seed) & (2**64 - 1), int(first_index) & (2**64 - 1)
+    p.t_lo, p.t_hi = int(t_lo), int(t_lo if t_hi is None else t_hi)
+    p.hmd_max_ft, p.vmd_max_ft, p.rate_scale = float(hmd_max_ft), float(vmd_max_ft), float(rate_scale)
+    return p
+
+
+def cpa_pose_device(params, xyz_a, xyz_b, idx_a=0, idx_b=0, weights_in=0, pose=0, rate=0, t_cpa=0, flags=0, weights_out=0, stream=None):
+    """emgpu_cpa_pose_device: asynchronous, raw device pointers (ints, 0 = none; params: cpa_pose_params).  xyz_a / xyz_b f64 PLANAR
+    [P, 3, ld] (points tc and tc + 1 are read), idx_a / idx_b int64 [n_pairs], weights_in uint32 [n_pairs]; pose f64 [5, n_pairs] (what
+    miss_distance_device takes as pose_b), rate f64, t_cpa int32 (the drawn second), flags uint8 (L.CPA_*), weights_out uint32 [n_pairs]
+    each.  No context: the current device and `stream`, a raw hipStream_t (0: the HIP default stream; None: torch's current stream)."""
+    _device_call("cpa_pose_device", (_stream_handle(stream),), params, xyz_a, xyz_b, idx_a, idx_b, weights_in, pose, rate, t_cpa, flags, weights_out)
+
+
+def _cpa_pose_tensors(pr, want_weights, hmd_max_ft, vmd_max_ft, seed, t_lo, t_hi, rate_scale, first_index, max_attempts):
+    """k_cpa_pose on the pairing pr: the device tensors (pose [5, n_pairs], rate, t_cpa, flags, weights or None), launched on pr.stream and
+    not waited for"""
+    import torch
+    n, dev = pr.n_pairs, pr.dev
+    pose = torch.empty((5, n), dtype=torch.float64, device=dev)
+    rate = torch.empty(n, dtype=torch.float64, device=dev)
+    t_cpa = torch.empty(n, dtype=torch.int32, device=dev)
+    flags = torch.empty(n, dtype=torch.uint8, device=dev)
+    w_out = torch.empty(n, dtype=torch.int32, device=dev) if want_weights else None
+    p = cpa_pose_params(n, pr.n_a, pr.n_b, pr.a.shape[0], hmd_max_ft, vmd_max_ft, seed, t_lo, t_hi, first_index, max_attempts,
+                        1.0 if rate_scale is None else rate_scale)
+    cpa_pose_device(p, _ptr(pr.a), _ptr(pr.b), _ptr(pr.d_ia), _ptr(pr.d_ib), _ptr(pr.d_w), _ptr(pose), _ptr(rate), _ptr(t_cpa), _ptr(flags),
+                    _ptr(w_out), stream=pr.stream)
+    return pose, rate, t_cpa, flags, w_out
+
+
+def _cpa_dict(rate, t_cpa, flags, w_out, t_key="t_cpa", flags_key="flags"):
+    """the rate, drawn second, flags and weights of cpa_pose's dict from _cpa_pose_tensors' device tensors"""
+    return {t_key: t_cpa.cpu().numpy(), **_encounter_dict(rate, flags, w_out, flags_key)}
+
+
+def cpa_pose(xyz_a, xyz_b, hmd_max_ft, vmd_max_ft, seed, t_lo, t_hi=None, idx_a=None, idx_b=None, weights=None, rate_scale=None, first_index=0,
+             max_attempts=16, layout="rows", ctx=None, stream=None):
+    """Places each intruder (set B) by its closest approach to its ownship (set A) on the GPU (emgpu_cpa_pose_device; the definition is in
+    include/emgpu.h): a seeded random heading, a second drawn from t_lo .. t_hi (t_hi=None: t_lo) at which the two pass, a lateral miss
+    drawn uniformly within +-hmd_max_ft and a vertical offset within +-vmd_max_ft, and the pose with which, both flying on as they do in
+    that second, the pass happens exactly so.  "rate" is the flux through that miss plane, (2 hmd_max_ft)(2 vmd_max_ft) times the relative
+    horizontal speed, in cubic feet per second: it plays the part of encounter_pose's rate, and every placed pair passes close by, which is
+    what a rare-event estimate wants.  xyz_a / xyz_b, idx_a / idx_b, layout, ctx and stream are miss_distance's; t_hi <= P - 2.  weights,
+    rate_scale and first_index are encounter_pose's.
+    Returns {"pose" float64 [5, n_pairs] (miss_distance's pose_b), "rate" float64, "t_cpa" int32 (the drawn second), "flags" uint8
+    (L.CPA_*), "weights" uint32 or None}."""
+    columns = _pair_columns(xyz_a, xyz_b, idx_a, idx_b, layout)
+    want_weights, w = _encounter_weights(weights, rate_scale, columns[3])
+    with _paired(xyz_a, xyz_b, columns, w, None, layout, ctx, stream) as pr:
+        pose, *out = _cpa_pose_tensors(pr, want_weights, hmd_max_ft, vmd_max_ft, seed, t_lo, t_hi, rate_scale, first_index, max_attempts)
+    return {"pose": pose.cpu().numpy(), **_cpa_dict(*out)}
+
+
+def _cpa_then(tensors, as_dict, xyz_a, xyz_b, hmd_max_ft, vmd_max_ft, seed, t_lo, t_hi, idx_a, idx_b, weights, rate_scale, first_index,
+              max_attempts, nmac_h_ft, nmac_v_ft, layout, ctx, stream):
+    """cpa_pose and then `tensors` on one stream; the dict of `as_dict` plus the placement's, the drawn second under "t_cpa_drawn" """
+    return _placed_then(lambda pr, want: _cpa_pose_tensors(pr, want, hmd_max_ft, vmd_max_ft, seed, t_lo, t_hi, rate_scale, first_index, max_attempts),
+                        lambda *placed: _cpa_dict(*placed, "t_cpa_drawn", "encounter_flags"), tensors, as_dict, xyz_a, xyz_b, idx_a, idx_b,
+                        weights, rate_scale, nmac_h_ft, nmac_v_ft, layout, ctx, stream)
+
+
+def cpa_miss(xyz_a, xyz_b, hmd_max_ft, vmd_max_ft, seed, t_lo, t_hi=None, idx_a=None, idx_b=None, weights=None, rate_scale=None, first_index=0,
+             max_attempts=16, nmac_h_ft=500.0, nmac_v_ft=100.0, layout="rows", ctx=None, stream=None):
+    """cpa_pose and then miss_distance on one stream, the pose and the rate-folded weights never leaving the device.  The arguments are
+    cpa_pose's and the NMAC thresholds.  On straight tracks the miss distance found is the one drawn; on tracks that turn it is what the
+    tracks make of that pass.  Returns miss_distance's dict plus "rate" float64, "t_cpa_drawn" int32, "encounter_flags" uint8 (L.CPA_*)
+    and "weights" uint32 or None."""
+    return _cpa_then(_miss_tensors, _miss_dict, xyz_a, xyz_b, hmd_max_ft, vmd_max_ft, seed, t_lo, t_hi, idx_a, idx_b, weights, rate_scale,
+                     first_index, max_attempts, nmac_h_ft, nmac_v_ft, layout, ctx, stream)
+
+
+def cpa_miss_segments(xyz_a, xyz_b, hmd_max_ft, vmd_max_ft, seed, t_lo, t_hi=None, idx_a=None, idx_b=None, weights=None, rate_scale=None,
+                      first_index=0, max_attempts=16, nmac_h_ft=500.0, nmac_v_ft=100.0, layout="rows", ctx=None, stream=None):
+    """cpa_miss with miss_segments in the place of miss_distance.  Returns miss_segments' dict plus "rate", "t_cpa_drawn",
+    "encounter_flags" and "weights"."""
+    return _cpa_then(_miss_segments_tensors, _miss_segments_dict, xyz_a, xyz_b, hmd_max_ft, vmd_max_ft, seed, t_lo, t_hi, idx_a, idx_b, weights,
+                     rate_scale, first_index, max_attempts, nmac_h_ft, nmac_v_ft, layout, ctx, stream)

@@ -687,8 +687,8 @@ int emgpu_miss_segments_device(void *hip_stream, const emgpu_miss_params *p, con
  * EMGPU_ERR_ARG, with a message that names the argument, before any device work: NULL p, xyz_a or xyz_b; every output NULL; points < 2 or
  * > 65537; the n_pairs / n_x / ld_x / idx_x rules of emgpu_miss_distance_device; radius_ft, half_height_ft or rate_scale not finite or
  * <= 0; max_attempts outside 1 .. 16; weights_in without weights_out.  n_pairs == 0 succeeds and launches nothing.
- * Out of scope: a caller-supplied heading, a placement such that the CPA falls at a chosen second, the ROWS layout, a _host entry point,
- * float weights, the terminal model's traj layout. */
+ * Out of scope: a caller-supplied heading, the ROWS layout, a _host entry point, float weights, the terminal model's traj layout.  A
+ * placement such that the CPA falls at a chosen second is emgpu_cpa_pose_device, below. */
 #define EMGPU_ENC_END 1u
 #define EMGPU_ENC_FALLBACK 2u
 #define EMGPU_ENC_NO_ENTRY 4u
@@ -707,6 +707,64 @@ typedef struct {
 int emgpu_encounter_pose_device(void *hip_stream, const emgpu_encounter_params *p, const double *xyz_a, const double *xyz_b, const int64_t *idx_a,
                                 const int64_t *idx_b, const uint32_t *weights_in, double *pose, double *rate, uint8_t *flags,
                                 uint32_t *weights_out);
+
+/* ------------------------------------------------------------------------------------------------
+ * Placing the intruder at a drawn closest approach: per pair a random heading of the intruder, a second tc at which the two aircraft pass,
+ * a signed lateral miss within +-Hm and a vertical offset within +-Vm at that second, and the pose {c, s, ox, oy, oz} such that, both
+ * flying on as they do during second tc, the pass happens exactly so.  The flux of intruders through that "miss plane", 2 Hm wide and
+ * 2 Vm high, perpendicular to the relative horizontal velocity, is uniform in both offsets, so the pair carries a rate as a cylinder
+ * entry does: (2 Hm) (2 Vm) g with g the relative horizontal speed.  Where emgpu_encounter_pose_device spends most pairs on entries that
+ * miss by far, every pair placed here passes within Hm and Vm: the placement for rare events.  Totals and weights downstream keep their
+ * meaning (sum(w rate NMAC) / n estimates E[rate NMAC]) as long as Hm and Vm cover the NMAC thresholds.
+ * Inputs     the two PLANAR sets of emgpu_miss_distance_device (A = ownship, B = intruder), n_a, n_b, ld_a, ld_b, n_pairs, idx_a / idx_b
+ *            with the same column selection, n_x = 1 broadcast and bad-index rule.  points >= 2; only points tc and tc + 1 are read.
+ * Draws      section 13 as above, two streams of their own, so that no existing draw moves: a = 3 is the heading's unit-disc point, taken
+ *            exactly as a = 0 above (none found: (p, q) = (1, 0) and EMGPU_CPA_FALLBACK); a = 4, block 0: word 0 = u1 (lateral), word 1 =
+ *            u2 (vertical), word 2 = x (the second).
+ * Per pair   all in f64, every product, sum, quotient and root one IEEE operation in the order written, nothing contracted, no device
+ *            sin / cos / atan2:
+ *            0. span = t_hi - t_lo + 1, tc = t_lo + ((uint64)x * span >> 32): integer arithmetic, always below t_lo + span; with
+ *               t_lo == t_hi it is that second.
+ *            1. (ax, ay, az) = A[tc+1] - A[tc], (bx, by, bz) = B[tc+1] - B[tc] (az and bz enter nothing below).
+ *            2. r = sqrt(p * p + q * q), c = p / r, s = q / r (a = 3); vx = c * bx - s * by, vy = s * bx + c * by.
+ *            3. rx = vx - ax, ry = vy - ay, g = sqrt(rx * rx + ry * ry).
+ *            4. Q = kc * g, with kc = (4 * Hm) * Vm computed once on the host.  !(Q > 0) or Q infinite: EMGPU_CPA_NO_PASS (no horizontal
+ *               relative motion, or a NaN horizontal coordinate), ox = oy = oz = NaN, rate 0, weight 0; c, s and tc are written as drawn.
+ *            5. ex = rx / g, ey = ry / g; l = Hm * (2 * u1 - 1), relx = (-l) * ey, rely = l * ex: perpendicular to the relative velocity;
+ *               dz = Vm * (2 * u2 - 1).
+ *            6. ox = (Atc_x + relx) - (c * Btc_x - s * Btc_y), oy = (Atc_y + rely) - (s * Btc_x + c * Btc_y), oz = (Atc_z + dz) - Btc_z:
+ *               emgpu_miss_distance_device's convention, applied at point tc.
+ *            7. rate = Q, t_cpa = tc.
+ *            8. weights_out = f <= 2^32 - 1 ? f : 2^32 - 1 with f = floor(w * (Q / rate_scale) + 0.5), w = weights_in[i] (NULL: 1);
+ *               EMGPU_CPA_SATURATED when the clamp acted (a NaN f, 0 * inf, clamps too).  Without weights_out no weight is formed and
+ *               the flag is never set.
+ * Outputs    pose f64 [5][n_pairs], rate f64 [n_pairs], t_cpa int32 [n_pairs], flags uint8 [n_pairs], weights_out uint32 [n_pairs]; each
+ *            may be NULL, not all.  A bad index: pose NaN, rate 0, weight 0, t_cpa -1, EMGPU_CPA_BAD_INDEX alone, no load and no draw.
+ *            No load or store leaves the buffers.  The flags have the values of the EMGPU_ENC_* bits they correspond to.
+ * The call takes no context and no model: hip_stream, the current device, device pointers, asynchronous.
+ * EMGPU_ERR_ARG, with a message that names the argument, before any device work: everything emgpu_encounter_pose_device refuses (points
+ * outside 2 .. 65537); hmd_max_ft, vmd_max_ft or rate_scale not finite or <= 0; t_lo < 0, t_hi < t_lo or t_hi > points - 2; weights_in
+ * without weights_out.  n_pairs == 0 succeeds and launches nothing.
+ * Out of scope: a caller-supplied heading or offsets, a CPA inside a second, the ROWS layout, a _host entry point, float weights, a mex
+ * command, the terminal model's traj layout. */
+#define EMGPU_CPA_FALLBACK 2u
+#define EMGPU_CPA_NO_PASS 4u
+#define EMGPU_CPA_SATURATED 8u
+#define EMGPU_CPA_BAD_INDEX 16u
+typedef struct {
+    int64_t n_pairs;
+    int64_t n_a, n_b;
+    int64_t ld_a, ld_b;    /* 0 = n_a / n_b */
+    int32_t points;        /* P: 2 .. 65537 */
+    int32_t max_attempts;  /* 1 .. 16 */
+    uint64_t seed, first_index;
+    int32_t t_lo, t_hi;    /* the seconds the pass is drawn from: 0 <= t_lo <= t_hi <= points - 2 */
+    double hmd_max_ft, vmd_max_ft;
+    double rate_scale;     /* > 0; enters weights_out only */
+} emgpu_cpa_pose_params;
+int emgpu_cpa_pose_device(void *hip_stream, const emgpu_cpa_pose_params *p, const double *xyz_a, const double *xyz_b, const int64_t *idx_a,
+                          const int64_t *idx_b, const uint32_t *weights_in, double *pose, double *rate, int32_t *t_cpa, uint8_t *flags,
+                          uint32_t *weights_out);
 
 /* Pinned host memory for the outputs of the *_host entry points (hipHostMalloc, kept in a per-ctx pool: pinning gigabytes costs about as
  * much as copying them).  emgpu_sample_dbn_host recognises pinned output arrays and lets the copy engine write straight into them;
