@@ -29,6 +29,7 @@ MISS_NMAC_CPA, MISS_NMAC_ANY, MISS_NO_CPA, MISS_BAD_INDEX = 1, 2, 4, 8   # emgpu
 MISS_CPA_BETWEEN, MISS_NMAC_BETWEEN = 16, 32                             # emgpu_miss_segments_device's two more
 ENC_END, ENC_FALLBACK, ENC_NO_ENTRY, ENC_SATURATED, ENC_BAD_INDEX = 1, 2, 4, 8, 16   # emgpu_encounter_pose_device's flags
 CPA_FALLBACK, CPA_NO_PASS, CPA_SATURATED, CPA_BAD_INDEX = 2, 4, 8, 16                # emgpu_cpa_pose_device's flags
+WC_LOST, WC_AT_START, WC_NO_DATA, WC_BAD_INDEX, WC_INSIDE_DMOD, WC_BY_TAU = 1, 2, 4, 8, 16, 32   # emgpu_well_clear_device's flags
 FLAG_QUANTIZE500, FLAG_NO_RESAMPLE, FLAG_NO_DEDISC, FLAG_NO_TERMINATOR, FLAG_LOCAL_SMOOTH = 1, 2, 4, 8, 16
 
 # MATLAB error identifiers the reference raises for the same condition
@@ -183,6 +184,12 @@ class CpaPoseParams(C.Structure):       # emgpu_cpa_pose_params
                 ("t_lo", C.c_int32), ("t_hi", C.c_int32), ("hmd_max_ft", C.c_double), ("vmd_max_ft", C.c_double), ("rate_scale", C.c_double)]
 
 
+class WellClearParams(C.Structure):     # emgpu_well_clear_params
+    _fields_ = [("n_pairs", C.c_int64), ("n_a", C.c_int64), ("n_b", C.c_int64), ("ld_a", C.c_int64), ("ld_b", C.c_int64),
+                ("points", C.c_int32), ("reserved", C.c_int32), ("tau_s", C.c_double), ("dmod_ft", C.c_double), ("hmd_ft", C.c_double),
+                ("h_ft", C.c_double)]
+
+
 class BnParams(C.Structure):
     _fields_ = [("seed", C.c_uint64), ("first_index", C.c_uint64), ("n", C.c_int64), ("flags", C.c_uint32),
                 ("max_attempts", C.c_int32), ("bounds_sample", C.c_void_p),
@@ -220,6 +227,7 @@ SYMBOLS = [
     "emgpu_miss_segments_device",
     "emgpu_encounter_pose_device",
     "emgpu_cpa_pose_device",
+    "emgpu_well_clear_device",
 ]
 
 _lib = None
@@ -415,6 +423,7 @@ def lib():
     L.emgpu_miss_segments_device.argtypes = [C.c_void_p, C.POINTER(MissParams)] + [C.c_void_p] * 11
     L.emgpu_encounter_pose_device.argtypes = [C.c_void_p, C.POINTER(EncounterParams)] + [C.c_void_p] * 9
     L.emgpu_cpa_pose_device.argtypes = [C.c_void_p, C.POINTER(CpaPoseParams)] + [C.c_void_p] * 10
+    L.emgpu_well_clear_device.argtypes = [C.c_void_p, C.POINTER(WellClearParams)] + [C.c_void_p] * 12
     _lib = L
     return L
 

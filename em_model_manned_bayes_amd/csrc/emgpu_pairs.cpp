@@ -1,7 +1,8 @@
-// emgpu_pairs.cpp -- the four entry points on paired 1 Hz tracks (the pairing: emgpu_pairs.h), side by side: emgpu_miss_distance_device
+// emgpu_pairs.cpp -- the five entry points on paired 1 Hz tracks (the pairing: emgpu_pairs.h), side by side: emgpu_miss_distance_device
 // (k_miss_distance, emgpu_miss.h), emgpu_miss_segments_device (k_miss_segments, emgpu_miss_seg.h), emgpu_encounter_pose_device
-// (k_encounter_pose, emgpu_encounter.h) and emgpu_cpa_pose_device (k_cpa_pose, emgpu_cpa.h).  They take no context: they need
-// no model table, no scratch and no status word, so they run on the stream they are given and on the calling thread's current device.
+// (k_encounter_pose, emgpu_encounter.h), emgpu_cpa_pose_device (k_cpa_pose, emgpu_cpa.h) and emgpu_well_clear_device (k_well_clear,
+// emgpu_well_clear.h).  They take no context: they need no model table, no scratch and no status word, so they run on the stream they are
+// given and on the calling thread's current device.
 #include <cmath>
 
 #include "emgpu_internal.hpp"
@@ -9,6 +10,7 @@
 #include "emgpu_encounter.h"
 #include "emgpu_miss.h"
 #include "emgpu_miss_seg.h"
+#include "emgpu_well_clear.h"
 
 namespace {
 // What can be said about a pairing without a device, for either params struct: EMGPU_OK, or the error (recorded).  have_out: the caller
@@ -144,6 +146,32 @@ int emgpu_cpa_pose_device(void *hip_stream, const emgpu_cpa_pose_params *p, cons
     A.kc = (4.0 * A.Hm) * A.Vm;                     // the miss plane's area per unit of horizontal relative speed: 2 Hm x 2 Vm
     A.weights_in = weights_in; A.pose = pose; A.rate = rate; A.t_cpa = t_cpa; A.flags = flags; A.weights_out = weights_out;
     launch_ok(emgpu::launch_cpa_pose(A, (hipStream_t)hip_stream, nullptr));
+    return EMGPU_OK;
+    EMGPU_CATCH
+}
+
+int emgpu_well_clear_device(void *hip_stream, const emgpu_well_clear_params *p, const double *xyz_a, const double *xyz_b, const int64_t *idx_a,
+                            const int64_t *idx_b, const double *pose_b, const uint32_t *weights, const uint8_t *miss_flags, int32_t *t_first,
+                            int32_t *n_lost, double *tau_min, uint8_t *flags, uint64_t *totals) {
+    EMGPU_TRY
+    if (const int rc = check_pairing(p, xyz_a, xyz_b, idx_a, idx_b, t_first || n_lost || tau_min || flags || totals,
+                                     "null t_first, n_lost, tau_min, flags and totals: nothing to write", 1))
+        return rc;
+    if (!(p->tau_s >= 0.0)) return fail(EMGPU_ERR_ARG, "tau_s is negative or NaN");
+    if (!(p->dmod_ft >= 0.0)) return fail(EMGPU_ERR_ARG, "dmod_ft is negative or NaN");
+    if (!(p->hmd_ft >= 0.0)) return fail(EMGPU_ERR_ARG, "hmd_ft is negative or NaN");
+    if (!(p->h_ft >= 0.0)) return fail(EMGPU_ERR_ARG, "h_ft is negative or NaN");
+    if (((uintptr_t)xyz_a | (uintptr_t)xyz_b | (uintptr_t)idx_a | (uintptr_t)idx_b | (uintptr_t)pose_b | (uintptr_t)tau_min | (uintptr_t)totals) & 7u)
+        return fail(EMGPU_ERR_ARG, "xyz_a, xyz_b, idx_a, idx_b, pose_b, tau_min and totals must be 8-byte aligned");
+    if (((uintptr_t)weights | (uintptr_t)t_first | (uintptr_t)n_lost) & 3u)
+        return fail(EMGPU_ERR_ARG, "weights, t_first and n_lost must be 4-byte aligned");
+    if (p->n_pairs == 0) return EMGPU_OK;
+    EmgpuWellClearRun A{};
+    fill_pairing(p, xyz_a, xyz_b, idx_a, idx_b, A.dim, A.col);
+    A.P = p->points; A.tau_s = p->tau_s; A.D2 = p->dmod_ft * p->dmod_ft; A.H2 = p->hmd_ft * p->hmd_ft; A.h = p->h_ft;
+    A.pose = pose_b; A.weights = weights; A.miss_flags = miss_flags;
+    A.t_first = t_first; A.n_lost = n_lost; A.tau_min = tau_min; A.flags = flags; A.totals = (unsigned long long *)totals;
+    launch_ok(emgpu::launch_well_clear(A, (hipStream_t)hip_stream, nullptr));
     return EMGPU_OK;
     EMGPU_CATCH
 }

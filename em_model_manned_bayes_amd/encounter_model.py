@@ -711,6 +711,16 @@ class UncorEncounterModel(EncounterModel):
                     rate_scale=rate_scale, first_index=first_index, max_attempts=max_attempts, nmac_h_ft=nmac_h_ft, nmac_v_ft=nmac_v_ft,
                     layout=layout, ctx=ctx)
 
+    def well_clear(self, own_xyz, intruder_xyz, pose=None, weights=None, idx_own=None, idx_intruder=None, miss_flags=None, tau_s=35.0,
+                   dmod_ft=4000.0, hmd_ft=4000.0, h_ft=450.0, layout="rows", ctx=None):
+        """.pair's question asked of the other event of a detect-and-avoid evaluation: whether, and from which second, each pair has lost
+        DAA well clear (modified tau tau_s, DMOD dmod_ft, predicted horizontal miss hmd_ft, vertical separation h_ft), evaluated on the
+        GPU: a thin wrapper over native.well_clear.  The tracks, pose, weights, indices, layout and ctx are .pair's; miss_flags: the
+        "flags" .pair returned for the same pairs, so that totals[8:10] count the NMACs among the losses.  Returns native.well_clear's
+        dict; "at_start" names the pairs that begin inside the volume."""
+        return native.well_clear(own_xyz, intruder_xyz, idx_a=idx_own, idx_b=idx_intruder, pose_b=pose, weights=weights, miss_flags=miss_flags,
+                                 tau_s=tau_s, dmod_ft=dmod_ft, hmd_ft=hmd_ft, h_ft=h_ft, layout=layout, ctx=ctx)
+
     def getDynamicLimits(self, initial, results, idx_G=None, idx_A=None, idx_L=None, idx_V=None, idx_DH=None, is_discretized=None):
         """dynamiclimits = getDynamicLimits(self, initial, results, ...)  (@UncorEncounterModel/getDynamicLimits.m).  The index
         arguments are accepted for signature compatibility; they are looked up from the labels like .track does."""

@@ -1,5 +1,5 @@
-"""Paired tracks: the one pairing, and on it the miss distance and the two placements of the intruder, on the encounter cylinder and at a
-drawn closest approach.  Torch does the plumbing here."""
+"""Paired tracks: the one pairing, and on it the miss distance, the loss of well clear and the two placements of the intruder, on the
+encounter cylinder and at a drawn closest approach.  Torch does the plumbing here."""
 import contextlib
 import types
 
@@ -397,3 +397,108 @@ def cpa_miss_segments(xyz_a, xyz_b, hmd_max_ft, vmd_max_ft, seed, t_lo, t_hi=Non
     "encounter_flags" and "weights"."""
     return _cpa_then(_miss_segments_tensors, _miss_segments_dict, xyz_a, xyz_b, hmd_max_ft, vmd_max_ft, seed, t_lo, t_hi, idx_a, idx_b, weights,
                      rate_scale, first_index, max_attempts, nmac_h_ft, nmac_v_ft, layout, ctx, stream)
+
+
+def well_clear_params(n_pairs, n_a, n_b, points, tau_s=35.0, dmod_ft=4000.0, hmd_ft=4000.0, h_ft=450.0, ld_a=0, ld_b=0):
+    """emgpu_well_clear_params: miss_params' pairing and the four thresholds of DAA well clear: modified tau in seconds, DMOD, the predicted
+    horizontal miss and the vertical separation in feet."""
+    p = L.WellClearParams()
+    p.n_pairs, p.n_a, p.n_b, p.ld_a, p.ld_b, p.points = int(n_pairs), int(n_a), int(n_b), int(ld_a), int(ld_b), int(points)
+    p.tau_s, p.dmod_ft, p.hmd_ft, p.h_ft = float(tau_s), float(dmod_ft), float(hmd_ft), float(h_ft)
+    return p
+
+
+def well_clear_device(params, xyz_a, xyz_b, idx_a=0, idx_b=0, pose_b=0, weights=0, miss_flags=0, t_first=0, n_lost=0, tau_min=0, flags=0,
+                      totals=0, stream=None):
+    """emgpu_well_clear_device: asynchronous, raw device pointers (ints, 0 = none; params: well_clear_params).  The inputs are
+    miss_distance_device's and miss_flags uint8 [n_pairs], the flags either miss kernel wrote for the same pairs (L.MISS_NMAC_ANY is
+    read); t_first / n_lost int32, tau_min f64, flags uint8 (L.WC_*) [n_pairs] each, totals uint64 [10], ADDED to.  No context: the
+    current device and `stream`, a raw hipStream_t (0: the HIP default stream; None: torch's current stream)."""
+    _device_call("well_clear_device", (_stream_handle(stream),), params, xyz_a, xyz_b, idx_a, idx_b, pose_b, weights, miss_flags, t_first, n_lost,
+                 tau_min, flags, totals)
+
+
+def _well_clear_tensors(pr, d_pose, d_w, d_miss_flags, tau_s, dmod_ft, hmd_ft, h_ft):
+    """k_well_clear on the pairing pr with the device tensors d_pose, d_w and d_miss_flags (or None): the device tensors (t_first, n_lost,
+    tau_min, flags, totals [10]), launched on pr.stream and not waited for"""
+    import torch
+    n, dev = pr.n_pairs, pr.dev
+    t_first, n_lost = torch.empty(n, dtype=torch.int32, device=dev), torch.empty(n, dtype=torch.int32, device=dev)
+    tau_min, flags = torch.empty(n, dtype=torch.float64, device=dev), torch.empty(n, dtype=torch.uint8, device=dev)
+    totals = torch.zeros(10, dtype=torch.int64, device=dev)
+    pr.guard()      # totals was zeroed on torch's stream
+    well_clear_device(well_clear_params(n, pr.n_a, pr.n_b, pr.a.shape[0], tau_s, dmod_ft, hmd_ft, h_ft), _ptr(pr.a), _ptr(pr.b), _ptr(pr.d_ia),
+                      _ptr(pr.d_ib), _ptr(d_pose), _ptr(d_w), _ptr(d_miss_flags), _ptr(t_first), _ptr(n_lost), _ptr(tau_min), _ptr(flags),
+                      _ptr(totals), stream=pr.stream)
+    return t_first, n_lost, tau_min, flags, totals
+
+
+def _well_clear_dict(t_first, n_lost, tau_min, flags, totals, flags_key="flags", totals_key="totals"):
+    """well_clear's dict from _well_clear_tensors' device tensors"""
+    fl = flags.cpu().numpy()
+    return {"t_first": t_first.cpu().numpy(), "n_lost": n_lost.cpu().numpy(), "tau_min_s": tau_min.cpu().numpy(), flags_key: fl,
+            "lowc": (fl & L.WC_LOST) != 0, "at_start": (fl & L.WC_AT_START) != 0, totals_key: totals.cpu().numpy().view(np.uint64)}
+
+
+def well_clear(xyz_a, xyz_b, idx_a=None, idx_b=None, pose_b=None, weights=None, miss_flags=None, tau_s=35.0, dmod_ft=4000.0, hmd_ft=4000.0,
+               h_ft=450.0, layout="rows", ctx=None, stream=None):
+    """Loss of DAA well clear of paired 1 Hz tracks on the GPU (emgpu_well_clear_device; the definition is in include/emgpu.h): at every
+    whole second the pair has lost well clear when it is within h_ft vertically and horizontally either inside dmod_ft or closing with a
+    modified tau of at most tau_s and a predicted horizontal miss of at most hmd_ft.  xyz_a / xyz_b, idx_a / idx_b, pose_b, weights,
+    layout, ctx and stream are miss_distance's.  miss_flags: the "flags" of miss_distance or miss_segments for the same pairs (uint8
+    [n_pairs], a numpy array or a torch tensor), which lets totals[8:10] count the NMACs among the losses.
+    Returns {"t_first" int32: the first second of the loss, -1 without one, "n_lost" int32: the number of such seconds, "tau_min_s"
+    float64: the smallest modified tau, "flags" uint8 (L.WC_*), "lowc" bool, "at_start" bool: lost at second 0, which a study has to
+    exclude, "totals" uint64 [10]}; totals[6] / totals[5] is the weighted P(LoWC), (totals[6] - totals[7]) / (totals[5] - totals[7])
+    the same over the pairs that did not start inside the volume, totals[9] / totals[6] P(NMAC | LoWC)."""
+    import torch
+    columns, w, pose_b = _miss_inputs(xyz_a, xyz_b, idx_a, idx_b, pose_b, weights, layout)
+    if miss_flags is not None:
+        if not isinstance(miss_flags, torch.Tensor):
+            miss_flags = np.ascontiguousarray(miss_flags)
+        if tuple(miss_flags.shape) != (columns[3],) or miss_flags.dtype != (torch.uint8 if isinstance(miss_flags, torch.Tensor) else np.uint8):
+            raise ValueError("miss_flags must be uint8 [n_pairs]: the flags of miss_distance or miss_segments")
+    with _paired(xyz_a, xyz_b, columns, w, pose_b, layout, ctx, stream) as pr:
+        d_mf = None if miss_flags is None else (miss_flags if isinstance(miss_flags, torch.Tensor) else torch.from_numpy(miss_flags.copy()))
+        d_mf = None if d_mf is None else d_mf.to(pr.dev).contiguous()
+        out = _well_clear_tensors(pr, pr.d_pose, pr.d_w, d_mf, tau_s, dmod_ft, hmd_ft, h_ft)
+    return _well_clear_dict(*out)
+
+
+def _miss_then_well_clear(between, tau_s, dmod_ft, hmd_ft, h_ft):
+    """(tensors, as_dict) for _placed_then: a miss kernel (k_miss_segments where `between`) and then k_well_clear on the same pose and
+    weights, the miss kernel's flags handed over on the device; the miss dict plus well_clear's, its flags under "wc_flags" and its
+    totals under "wc_totals" """
+    miss_tensors, miss_dict = (_miss_segments_tensors, _miss_segments_dict) if between else (_miss_tensors, _miss_dict)
+
+    def tensors(pr, d_pose, d_w, nmac_h_ft, nmac_v_ft):
+        miss = miss_tensors(pr, d_pose, d_w, nmac_h_ft, nmac_v_ft)
+        return tuple(miss) + tuple(_well_clear_tensors(pr, d_pose, d_w, miss[3], tau_s, dmod_ft, hmd_ft, h_ft))
+
+    def as_dict(*out):
+        return dict(miss_dict(*out[:5]), **_well_clear_dict(*out[5:], flags_key="wc_flags", totals_key="wc_totals"))
+    return tensors, as_dict
+
+
+def encounter_well_clear(xyz_a, xyz_b, radius_ft, half_height_ft, seed, idx_a=None, idx_b=None, weights=None, rate_scale=None, first_index=0,
+                         max_attempts=16, nmac_h_ft=500.0, nmac_v_ft=100.0, between=False, tau_s=35.0, dmod_ft=4000.0, hmd_ft=4000.0,
+                         h_ft=450.0, layout="rows", ctx=None, stream=None):
+    """encounter_miss (between=True: encounter_miss_segments) and then well_clear on one stream: the intruders placed on the encounter
+    cylinder, the NMAC and the loss of well clear of the pairs, the pose, the rate-folded weights and the miss kernel's flags never
+    leaving the device.  The arguments are encounter_miss's and well_clear's thresholds.  Returns encounter_miss's dict plus "t_first",
+    "n_lost", "tau_min_s", "wc_flags" (L.WC_*), "lowc", "at_start" and "wc_totals" uint64 [10]: wc_totals[6] / wc_totals[5] is
+    P(LoWC | encounter), wc_totals[9] / wc_totals[6] P(NMAC | LoWC).  A cylinder smaller than the well-clear volume places intruders
+    inside it: "at_start" names them."""
+    tensors, as_dict = _miss_then_well_clear(between, tau_s, dmod_ft, hmd_ft, h_ft)
+    return _encounter_then(tensors, as_dict, xyz_a, xyz_b, radius_ft, half_height_ft, seed, idx_a, idx_b, weights, rate_scale, first_index,
+                           max_attempts, nmac_h_ft, nmac_v_ft, layout, ctx, stream)
+
+
+def cpa_well_clear(xyz_a, xyz_b, hmd_max_ft, vmd_max_ft, seed, t_lo, t_hi=None, idx_a=None, idx_b=None, weights=None, rate_scale=None,
+                   first_index=0, max_attempts=16, nmac_h_ft=500.0, nmac_v_ft=100.0, between=False, tau_s=35.0, dmod_ft=4000.0, hmd_ft=4000.0,
+                   h_ft=450.0, layout="rows", ctx=None, stream=None):
+    """cpa_miss (between=True: cpa_miss_segments) and then well_clear on one stream, as encounter_well_clear.  Returns cpa_miss's dict plus
+    "t_first", "n_lost", "tau_min_s", "wc_flags", "lowc", "at_start" and "wc_totals"."""
+    tensors, as_dict = _miss_then_well_clear(between, tau_s, dmod_ft, hmd_ft, h_ft)
+    return _cpa_then(tensors, as_dict, xyz_a, xyz_b, hmd_max_ft, vmd_max_ft, seed, t_lo, t_hi, idx_a, idx_b, weights, rate_scale, first_index,
+                     max_attempts, nmac_h_ft, nmac_v_ft, layout, ctx, stream)

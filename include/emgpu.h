@@ -766,6 +766,68 @@ int emgpu_cpa_pose_device(void *hip_stream, const emgpu_cpa_pose_params *p, cons
                           const int64_t *idx_b, const uint32_t *weights_in, double *pose, double *rate, int32_t *t_cpa, uint8_t *flags,
                           uint32_t *weights_out);
 
+/* ------------------------------------------------------------------------------------------------
+ * Loss of DAA well clear of paired tracks: the second event beside the NMAC that detect-and-avoid evaluations report.  A pair has lost
+ * well clear at a second when the two aircraft are within h_ft vertically AND horizontally either inside DMOD or closing such that the
+ * modified tau is at most tau_s with a predicted horizontal miss of at most hmd_ft.  The predicate is evaluated at every whole second on
+ * the relative state emgpu_miss_distance_device forms; P(LoWC | encounter) and P(NMAC | LoWC) follow from the weighted totals.
+ * Inputs     emgpu_miss_distance_device's: the two PLANAR sets, n_a, n_b, ld_a, ld_b, n_pairs, idx_a / idx_b with the same column
+ *            selection, n_x = 1 broadcast and bad-index rule; the optional pose_b [5][n_pairs], applied per point exactly as stated there;
+ *            the optional weights uint32 [n_pairs].  One more optional input, miss_flags const uint8 [n_pairs]: the flags output of
+ *            emgpu_miss_distance_device or emgpu_miss_segments_device for the same pairs; only its EMGPU_MISS_NMAC_ANY bit is read.
+ * Thresholds tau_s (35 s), dmod_ft (4000 ft), hmd_ft (4000 ft), h_ft (450 ft) are the usual ones; the struct has no defaults.
+ *            D2 = dmod_ft * dmod_ft, H2 = hmd_ft * hmd_ft, computed once on the host.
+ * Everything is f64; every product, sum and quotient is one IEEE double operation in the order written; nothing is contracted; a NaN
+ * compares false.  No square root enters.
+ * Relative state at point p = 0 .. P-1, as above: dx = xa - xb', dy = ya - yb', dz = zb' - za.  The relative velocity at point p is the
+ *            forward difference of the segment that starts there, the last point taking the last segment's: with q = min(p, P-2),
+ *            ux = dx[q+1] - dx[q], uy = dy[q+1] - dy[q]; for P = 1, ux = uy = 0.
+ * Per point  with (x, y, z) = (dx, dy, dz)[p]:
+ *            rr = x * x + y * y, rv = x * ux + y * uy, vv = ux * ux + uy * uy
+ *            valid   = rr, rv, vv and z all finite
+ *            inside  = rr <= D2;  closing = rv < 0
+ *            tau     = inside ? 0 : (closing ? (D2 - rr) / rv : +inf)
+ *            tc      = vv > 0 ? (-rv) / vv : 0;  tc = tc > 0 ? tc : 0
+ *            px = x + tc * ux, py = y + tc * uy, hp2 = px * px + py * py
+ *            by_tau  = !inside && closing && tau <= tau_s && hp2 <= H2
+ *            lost[p] = valid && fabs(z) <= h_ft && (inside || by_tau)
+ *            The comparisons are <=, as the well-clear standard states them: this DIFFERS from the NMAC test of the miss-distance calls,
+ *            which uses <.
+ * Outputs    per pair, each may be NULL: t_first int32 [n_pairs], the first p with lost[p], -1 if none; n_lost int32 [n_pairs], the number
+ *            of such p; tau_min f64 [n_pairs], the smallest tau over the valid points (+inf if none of them is inside or closing, NaN if
+ *            no point is valid); flags uint8 [n_pairs]: EMGPU_WC_LOST (some lost[p]), EMGPU_WC_AT_START (lost[0]), EMGPU_WC_NO_DATA (no
+ *            valid point), EMGPU_WC_BAD_INDEX (as for the miss-distance calls: nothing loaded; -1, 0, NaN written; no other flag),
+ *            EMGPU_WC_INSIDE_DMOD (some lost point had `inside`), EMGPU_WC_BY_TAU (some lost point had `by_tau`).
+ *            totals uint64 [10], ADDED to, w = weights[i] (NULL: 1): [0] pairs evaluated, [1] LOST, [2] AT_START, [3] NO_DATA,
+ *            [4] BAD_INDEX, [5] sum of w over the evaluated pairs, [6] sum of w * LOST, [7] sum of w * AT_START, [8] pairs with LOST whose
+ *            miss_flags has EMGPU_MISS_NMAC_ANY (0 without miss_flags), [9] sum of w over those.  [9] / [6] is the weighted
+ *            P(NMAC | LoWC); ([6] - [7]) / ([5] - [7]) is P(LoWC) over the pairs that did not start inside the volume.  At least one of
+ *            the per-pair outputs and totals must be given.  No load or store leaves the buffers.
+ * The call takes no context and no model: hip_stream, the current device, device pointers, asynchronous.
+ * EMGPU_ERR_ARG, with a message that names the argument, before any device work: everything emgpu_miss_distance_device refuses about the
+ * pairing (points outside 1 .. 65537), with the same messages; tau_s, dmod_ft, hmd_ft or h_ft negative or NaN; every output NULL; a
+ * pointer that is not aligned to its element (8 bytes for doubles, indices and totals; 4 for weights, t_first and n_lost).  n_pairs == 0
+ * succeeds and launches nothing.
+ * Out of scope: the predicate between the seconds, vertical tau and the terminal / TCAS-RA variants of the volume, the severity metric
+ * (SLoWC), an alerting or avoidance logic, the ROWS layout, a _host entry point, a mex command, a lag per pair. */
+#define EMGPU_WC_LOST 1u
+#define EMGPU_WC_AT_START 2u
+#define EMGPU_WC_NO_DATA 4u
+#define EMGPU_WC_BAD_INDEX 8u
+#define EMGPU_WC_INSIDE_DMOD 16u
+#define EMGPU_WC_BY_TAU 32u
+typedef struct {
+    int64_t n_pairs;
+    int64_t n_a, n_b;
+    int64_t ld_a, ld_b;    /* 0 = n_a / n_b */
+    int32_t points;        /* P: 1 .. 65537 */
+    int32_t reserved;
+    double tau_s, dmod_ft, hmd_ft, h_ft;
+} emgpu_well_clear_params;
+int emgpu_well_clear_device(void *hip_stream, const emgpu_well_clear_params *p, const double *xyz_a, const double *xyz_b, const int64_t *idx_a,
+                            const int64_t *idx_b, const double *pose_b, const uint32_t *weights, const uint8_t *miss_flags, int32_t *t_first,
+                            int32_t *n_lost, double *tau_min, uint8_t *flags, uint64_t *totals /* [10] */);
+
 /* Pinned host memory for the outputs of the *_host entry points (hipHostMalloc, kept in a per-ctx pool: pinning gigabytes costs about as
  * much as copying them).  emgpu_sample_dbn_host recognises pinned output arrays and lets the copy engine write straight into them;
  * pageable arrays go through the library's own pinned staging buffers and a few host threads (below). */
