@@ -228,7 +228,12 @@ SYMBOLS = [
     "emgpu_encounter_pose_device",
     "emgpu_cpa_pose_device",
     "emgpu_well_clear_device",
+    "emgpu_debug_device_math",
 ]
+
+# emgpu_debug_device_math's functions (EMGPU_MATH_*), by number
+MATH_FUNCTIONS = ("sincos_small", "sincos_small_sk", "sincosd_small", "t_sincosd", "f_sincosd", "ut_sincos", "ut_sincos_sk", "ut_atan",
+                  "ut_atan_sk", "ut_asin_small", "ut_asin_small_sk", "ut_rcp", "round500")
 
 _lib = None
 _hip_runtime = None
@@ -424,6 +429,7 @@ def lib():
     L.emgpu_encounter_pose_device.argtypes = [C.c_void_p, C.POINTER(EncounterParams)] + [C.c_void_p] * 9
     L.emgpu_cpa_pose_device.argtypes = [C.c_void_p, C.POINTER(CpaPoseParams)] + [C.c_void_p] * 10
     L.emgpu_well_clear_device.argtypes = [C.c_void_p, C.POINTER(WellClearParams)] + [C.c_void_p] * 12
+    L.emgpu_debug_device_math.argtypes = [C.c_void_p, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]
     _lib = L
     return L
 

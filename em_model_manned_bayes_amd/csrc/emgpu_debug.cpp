@@ -1,10 +1,12 @@
-// emgpu_debug.cpp -- the emgpu_debug_* getters that need no device: what the plan compiler made of a model, read back by the tests.
+// emgpu_debug.cpp -- the emgpu_debug_* getters that need no device: what the plan compiler made of a model, read back by the tests; and
+// emgpu_debug_device_math, which needs one and no context: a probe kernel over the track kernels' device math (emgpu_mathprobe.h).
 #include <hip/hip_runtime.h>
 
 #include <cstring>
 #include <memory>
 
 #include "emgpu_internal.hpp"
+#include "emgpu_mathprobe.h"
 
 // The model's plan for a getter of dynamic variable k, or null after fail(): k must be one (`padded`: one with a padded table; the getter
 // says which in its own words, no_k), and col, where the getter has the helper check it, a column of its transition table.
@@ -99,6 +101,19 @@ int emgpu_debug_pk_column(const emgpu_model *m, int32_t k, int64_t col, uint32_t
     const emgpu::CompiledPlan &cp = *cp_keep;
     const EmgpuPlan &P = cp.plan;
     for (int t = 0; t < 4; t++) words[t] = cp.pthr[P.d_poffpk[k] + (size_t)col * 4 + t];
+    return EMGPU_OK;
+    EMGPU_CATCH
+}
+
+int emgpu_debug_device_math(void *hip_stream, int32_t fn, int64_t n, const double *x, double *out0, double *out1) {
+    EMGPU_TRY
+    if (fn < EMGPU_MATH_SINCOS_SMALL || fn > EMGPU_MATH_ROUND500) return fail(EMGPU_ERR_ARG, "no such function: fn outside 0..12");
+    if (n < 0 || n > ((int64_t)1 << 32)) return fail(EMGPU_ERR_ARG, "n outside 0..2^32");
+    if (!x) return fail(EMGPU_ERR_ARG, "null argument: x");
+    if (!out0) return fail(EMGPU_ERR_ARG, "null argument: out0");
+    if (((uintptr_t)x | (uintptr_t)out0 | (uintptr_t)out1) & 7u) return fail(EMGPU_ERR_ARG, "x, out0 and out1 must be 8-byte aligned");
+    if (n == 0) return EMGPU_OK;
+    launch_ok(emgpu::launch_math_probe(fn, n, x, out0, out1, (hipStream_t)hip_stream));
     return EMGPU_OK;
     EMGPU_CATCH
 }

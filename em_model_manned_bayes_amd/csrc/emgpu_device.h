@@ -76,15 +76,20 @@ __device__ __forceinline__ double dedisc_f64(const double *__restrict__ bnd, int
 }
 
 // sin and cos of |x| <= pi/4 (a reduced angle): Taylor sums to x^19 / x^18 in Horner form on explicit fma -- truncation below
-// 1e-19, about two ulp of rounding.  The library's sin() / cos() spend three times the instructions on a range reduction that
-// such an argument never needs.  Used where outputs are compared at a tolerance (tracks), never on the sampling path.
+// 1e-19; measured against the exact values (tests/test_gpu_device_math.py): the sine within 2 ulp of the exact
+// result (relative: s = x exactly from 2^-27 down), the cosine within 2 units of 2^-53 (absolute); measured worst 0.66 ulp and 1.23 units.  The library's sin() / cos() spend
+// three times the instructions on a range reduction that such an argument never needs.  Used where outputs are compared at a tolerance
+// (tracks), never on the sampling path.  Domain: |x| <= pi/4 and the ulp beyond it that a reduction's rounding leaves.  Outside it the
+// truncated series loses accuracy and, from |x| ~ 1e154 on (x * x overflows), gives infinities: +-inf gives (NaN, -inf).  NaN gives NaN.
+// sincos_small_core is the sum alone: its sine of -0.0 is +0.0 (x * z * ps is +0 there, and -0 + +0 = +0), which is right for the callers
+// whose reduced argument is never -0.0 (sincosd_small, ut_sincos); sincos_small gives a zero sine its argument's sign: sin(+-0) = +-0.
 // A constant held in a SCALAR register pair at its use.  The f64 coefficients of a loop body are loop invariants: left to the compiler they are
 // materialised once, ahead of the loop, and then sit in vector registers for its whole length -- 60 of them in k_terminal_propagate, a third
 // of its budget and a whole wave of occupancy.  As scalar operands (one per VALU instruction) they cost two s_mov each at the use.
 __device__ __forceinline__ double sk64(double c) { asm volatile("" : "+s"(c)); return c; }
 // SK: the coefficients as scalar operands (sk64)
 template <bool SK = false>
-__device__ __forceinline__ void sincos_small(double x, double &s, double &c) {
+__device__ __forceinline__ void sincos_small_core(double x, double &s, double &c) {
     auto K = [](double v) { return SK ? sk64(v) : v; };
     const double z = x * x;
     double ps = K(-1.0 / 121645100408832000.0);          // -1/19!
@@ -107,13 +112,24 @@ __device__ __forceinline__ void sincos_small(double x, double &s, double &c) {
     pc = fma(pc, z, K(1.0 / 24.0));                      //  1/4!
     c = (1.0 - 0.5 * z) + (z * z) * pc;
 }
-// cosd / sind with MATLAB's reduction in degrees: n = round(x/90), x - 90 n in [-45, 45], quadrant m = mod(n, 4)
+template <bool SK = false>
+__device__ __forceinline__ void sincos_small(double x, double &s, double &c) {
+    sincos_small_core<SK>(x, s, c);
+    s = (s == 0.0) ? x : s;   // a zero sine is the sine of a zero (a nonzero x down to the smallest subnormal gives s = x): its sign
+}
+// cosd / sind with MATLAB's reduction in degrees: n = round(x/90), x - 90 n in [-45, 45], quadrant m = mod(n, 4); the quotient is
+// round(deg * (1/90)), which differs from the oracle's round(deg / 90) only for doubles next to a tie k * 90 + 45, where the two remainders
+// (+45 and -45 degrees of neighbouring quadrants) name the same angle.  Domain |deg| < 2^53 (deg - 90 n is exact there): exactly 0 and +-1 at
+// every multiple of 90 with the signs MATLAB's reduction gives the zeros (sind(180) = -0, cosd(90) = -0; the reduced argument is never
+// -0.0, sind(-0.0) = +0), elsewhere within 2 units of 2^-53 of the exact values (absolute; measured worst 1.61).  NaN and +-inf give NaN in both results.
+// |deg| >= 2^53 is outside: n * 90 is no longer exact and, from 90 * 2^63 on, n is outside the integer conversion, so the results are
+// not the sine and cosine of deg (measured: unrelated values in [-1, 1]); nothing traps.
 __device__ __forceinline__ void sincosd_small(double deg, double &s, double &c) {
     const double n = round(deg * (1.0 / 90.0));
     const double x = (3.14159265358979323846 / 180.0) * (deg - n * 90.0);
     const int m = (int)((long long)n & 3ll);
     double sx, cx;
-    sincos_small<false>(x, sx, cx);
+    sincos_small_core<false>(x, sx, cx);
     s = (m == 0) ? sx : ((m == 1) ? cx : ((m == 2) ? -sx : -cx));
     c = (m == 0) ? cx : ((m == 1) ? -sx : ((m == 2) ? -cx : sx));
 }
@@ -146,8 +162,12 @@ __device__ __forceinline__ void put(T (&a)[N], int idx, T v) {
     for (int q = 0; q < N; q++) a[q] = (idx == q) ? v : a[q];
 }
 
-__device__ __forceinline__ double round500(double num) { // UncorEncounterModel.m:196
-    return 500.0 * (floor(num / 500.0) + ((fmod(num, 500.0) > 250.0) ? 1.0 : 0.0));
+// UncorEncounterModel.m:196, 500 * (floor(num / 500) + (mod(num, 500) > 250)), bit for bit for every num.  MATLAB's mod is the floored one:
+// for num < 0 fmod's remainder r stands for r + 500, and r + 500 > 250 exactly when r > -250 (the sum is exact next to 250).  NaN and
+// +-inf give themselves (fmod is NaN, the comparison false).
+__device__ __forceinline__ double round500(double num) {
+    const double r = fmod(num, 500.0);
+    return 500.0 * (floor(num / 500.0) + ((r > 250.0 || (r < 0.0 && r > -250.0)) ? 1.0 : 0.0));
 }
 
 // The presets of one lane (bn_sample.m:44-50): sp[p] = the preset bin (1-based) of the node at position p or 0; a lane's own row of the

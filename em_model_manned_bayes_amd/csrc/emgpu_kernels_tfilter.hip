@@ -13,6 +13,7 @@
 #include <hip/hip_runtime.h>
 
 #include "../../include/emgpu.h"
+#include "emgpu_device_math.h"
 #include "emgpu_launch.h"
 #include "emgpu_plan.h"
 
@@ -35,14 +36,7 @@ __device__ __forceinline__ double f_wrapToPi(double x) {
     }
     return x;
 }
-__device__ __forceinline__ void f_sincosd(double deg, double &s, double &c) { // MATLAB's reduction in degrees (see emgpu_kernels_term.hip)
-    const double n = round(deg / 90.0);
-    const double x = (3.14159265358979323846 / 180.0) * (deg - n * 90.0);
-    const int m = (int)((long long)n & 3ll);
-    const double sx = sin(x), cx = cos(x);
-    s = (m == 0) ? sx : ((m == 1) ? cx : ((m == 2) ? -sx : -cx));
-    c = (m == 0) ? cx : ((m == 1) ? -sx : ((m == 2) ? -cx : sx));
-}
+// f_sincosd: emgpu_device_math.h
 
 __global__ void __launch_bounds__(256) k_terminal_geo(const EmgpuTGeoRun A) {
 #pragma clang fp contract(off)

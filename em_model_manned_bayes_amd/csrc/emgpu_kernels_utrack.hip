@@ -22,81 +22,13 @@
 #include <cstdlib>
 
 #include "emgpu_device.h"
+#include "emgpu_device_math.h"
 #include "emgpu_launch.h"
 #include "emgpu_plan.h"
 
 namespace emgpu {
 
-// sin and cos of an angle of moderate size (|x| < 1e5; pitch, bank, heading in radians): k = rint(x * 2/pi), the remainder
-// x - k * pi/2 taken in two pieces of pi/2 (the first has 33 significant bits: k * hi is exact), Horner sums on the remainder
-// (sincos_small, emgpu_device.h), the quadrant from k.  About 45 instructions for both
-// where the library's sin() + cos() take 180; results within 2 ulp of them (the tracks are compared at 1e-9).
-template <bool SK = false>   // SK: coefficients as scalar operands (sk64): for the variant that evaluates these once per recorded row only
-__device__ __forceinline__ void ut_sincos(double x, double &s, double &c) {
-    if (!(fabs(x) < 1.0e5)) { s = sin(x); c = cos(x); return; }
-    const double k = rint(x * 0.63661977236758134308);                 // 2/pi
-    double r = fma(-k, 1.57079632673412561417, x);                     // pi/2, first 33 bits
-    r = fma(-k, 6.07710050650619224932e-11, r);                        // pi/2 - the above
-    double sr, cr;
-    sincos_small<SK>(r, sr, cr);   // (scalar-operand coefficients in the literal step -- three waves instead of two -- were measured: +4 %, it is issue-bound)
-    const int q = (int)((long long)k & 3ll);
-    s = (q == 0) ? sr : ((q == 1) ? cr : ((q == 2) ? -sr : -cr));
-    c = (q == 0) ? cr : ((q == 1) ? -sr : ((q == 2) ? -cr : sr));
-}
-
-// 1 / d to about one ulp: v_rcp_f64 and two Newton steps (5 instructions; the IEEE-exact division the compiler emits for `/`
-// takes ~35).  The dynamics divide six times per 0.1 s step as written; here they share ONE reciprocal, 1 / (v cos(phi)).
-__device__ __forceinline__ double ut_rcp(double d) {
-    double x = __builtin_amdgcn_rcp(d);
-    double e = fma(-d, x, 1.0);
-    x = fma(x, e, x);
-    e = fma(-d, x, 1.0);
-    return fma(x, e, x);
-}
-// atan on fdlibm's breakpoints (s_atan.c: 7/16, 11/16, 19/16, 39/16) and kernel polynomial, the reduced argument's division through
-// ut_rcp, selects instead of branches; within 2 ulp of the library's (checked against numpy in tests/test_host.py's restatement).
-template <bool SK = false>
-__device__ __forceinline__ double ut_atan(double x) {
-    auto K = [](double v) { return SK ? sk64(v) : v; };
-    const double ax = fabs(x);
-    double num = ax, den = 1.0, c = 0.0;
-    if (ax >= 0.4375) { num = fma(2.0, ax, -1.0); den = 2.0 + ax; c = 4.63647609000806093515e-01; }      // atan(0.5)
-    if (ax >= 0.6875) { num = ax - 1.0; den = ax + 1.0; c = 7.85398163397448278999e-01; }                 // atan(1)
-    if (ax >= 1.1875) { num = ax - 1.5; den = fma(1.5, ax, 1.0); c = 9.82793723247329054082e-01; }        // atan(1.5)
-    if (ax >= 2.4375) { num = -1.0; den = ax; c = 1.57079632679489655800e+00; }                           // atan(inf)
-    const double t = num * ut_rcp(den);
-    const double z = t * t, w = z * z;
-    double s1 = fma(w, K(1.62858201153657823623e-02), K(4.97687799461593236017e-02));
-    s1 = fma(w, s1, K(6.66107313738753120669e-02));
-    s1 = fma(w, s1, K(9.09088713343650656196e-02));
-    s1 = fma(w, s1, K(1.42857142725034663711e-01));
-    s1 = fma(w, s1, K(3.33333333333329318027e-01));
-    s1 = z * s1;
-    double s2 = fma(w, K(-3.65315727442169155270e-02), K(-5.83357013379057348645e-02));
-    s2 = fma(w, s2, K(-7.69187620504482999495e-02));
-    s2 = fma(w, s2, K(-1.11111104054623557880e-01));
-    s2 = fma(w, s2, K(-1.99999999998764832476e-01));
-    s2 = w * s2;
-    const double r = c + (t - t * (s1 + s2));
-    return x < 0 ? -r : r;
-}
-// asin for |x| < 0.5 (a climb angle below 30 degrees): fdlibm's rational kernel (e_asin.c), its division through ut_rcp
-template <bool SK = false>
-__device__ __forceinline__ double ut_asin_small(double x) {
-    auto K = [](double v) { return SK ? sk64(v) : v; };
-    const double t = x * x;
-    double p = fma(t, K(3.47933107596021167570e-05), K(7.91534994289814532176e-04));
-    p = fma(t, p, K(-4.00555345006794114027e-02));
-    p = fma(t, p, K(2.01212532134862925881e-01));
-    p = fma(t, p, K(-3.25565818622400915405e-01));
-    p = fma(t, p, K(1.66666666666666657415e-01));
-    p = t * p;
-    double q = fma(t, K(7.70381505559019352791e-02), K(-6.88283971605453293030e-01));
-    q = fma(t, q, K(2.02094576023350569471e+00));
-    q = fma(t, q, K(-2.40339491173441421878e+00));
-    q = fma(t, q, K(1.0));
-    return fma(x, p * ut_rcp(q), x);
-}
+// ut_sincos, ut_rcp, ut_atan, ut_asin_small: emgpu_device_math.h
 
 __device__ __forceinline__ int ut_discretize(double x, const double *cut, int n) { // discretize_bayes.m:14-22
     if (x >= cut[n - 1]) return n + 1;

@@ -1187,6 +1187,27 @@ int emgpu_debug_pk_column(const emgpu_model *m, int32_t k, int64_t col, uint32_t
 int emgpu_debug_uncor_dynamics_host(emgpu_ctx *ctx, int64_t n, int32_t T, int32_t record_stride, int32_t literal, const double dyn[6],
                                     const float *init, const float *controls, double *tracks);
 
+/* Test hook: one of the track kernels' hand-written device math functions (emgpu_device.h, emgpu_device_math.h) evaluated on x[0..n), one
+ * lane per element: out0[i] (and out1[i]) = fn(x[i]).  The sin/cos pairs (fn <= EMGPU_MATH_UT_SINCOS_SK) write the sine to out0 and the
+ * cosine to out1; out1 may be NULL and is ignored by the one-result functions.  Device pointers, no context: it runs on the stream given
+ * and the calling thread's current device, asynchronously.  EMGPU_ERR_ARG before any device work: an unknown fn, n < 0 or n > 2^32, NULL x
+ * or out0, a pointer that is not 8-byte aligned.  n == 0: EMGPU_OK without a launch.  What each function computes, its domain and what it
+ * does outside: its header comment; the measured errors: DESIGN.md section 39. */
+#define EMGPU_MATH_SINCOS_SMALL 0        /* sincos_small<false>  (radians, |x| <= pi/4)                     */
+#define EMGPU_MATH_SINCOS_SMALL_SK 1     /* sincos_small<true>   (coefficients as scalar operands)          */
+#define EMGPU_MATH_SINCOSD_SMALL 2       /* sincosd_small        (degrees; k_sample2track*)                 */
+#define EMGPU_MATH_T_SINCOSD 3           /* t_sincosd            (degrees; k_terminal_propagate's loop)     */
+#define EMGPU_MATH_F_SINCOSD 4           /* f_sincosd            (degrees; k_terminal_geo)                  */
+#define EMGPU_MATH_UT_SINCOS 5           /* ut_sincos<false>     (radians; k_uncor_track)                   */
+#define EMGPU_MATH_UT_SINCOS_SK 6        /* ut_sincos<true>                                                 */
+#define EMGPU_MATH_UT_ATAN 7             /* ut_atan<false>                                                  */
+#define EMGPU_MATH_UT_ATAN_SK 8          /* ut_atan<true>                                                   */
+#define EMGPU_MATH_UT_ASIN_SMALL 9       /* ut_asin_small<false> (|x| < 0.5)                                */
+#define EMGPU_MATH_UT_ASIN_SMALL_SK 10   /* ut_asin_small<true>                                             */
+#define EMGPU_MATH_UT_RCP 11             /* ut_rcp               (1 / x)                                    */
+#define EMGPU_MATH_ROUND500 12           /* round500             (UncorEncounterModel.m:196)                */
+int emgpu_debug_device_math(void *hip_stream, int32_t fn, int64_t n, const double *x, double *out0, double *out1);
+
 /* Measuring builds of k_terminal_propagate (-DEMGPU_TERM_COUNTERS; tools/term_counters.py): the lanes that took each path of the loop
  * since the last call (24 counters, cleared by the call).  Returns 1, or 0 in a normal build (out untouched). */
 int emgpu_debug_terminal_counters(emgpu_ctx *ctx, uint64_t *out, int32_t n);

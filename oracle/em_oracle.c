@@ -588,8 +588,9 @@ typedef struct {
     int32_t max_attempts, per_step;
 } em_uncor_opts_t;
 
-static double round500(double num) { /* UncorEncounterModel.m:196 */
-    return 500.0 * (floor(num / 500.0) + ((fmod(num, 500.0) > 250.0) ? 1.0 : 0.0));
+static double round500(double num) { /* UncorEncounterModel.m:196; MATLAB's mod is the floored one: fmod's remainder r < 0 stands for r + 500 */
+    const double r = fmod(num, 500.0);
+    return 500.0 * (floor(num / 500.0) + ((r > 250.0 || (r < 0.0 && r > -250.0)) ? 1.0 : 0.0));
 }
 
 int em_uncor_sample_one(const em_model_t *m, em_rng_t *g, int sample_time, const em_uncor_opts_t *o,

@@ -219,6 +219,17 @@ def test_a_null_context_is_refused_when_everything_else_is_valid(name, valid):
     assert observe(name, valid.args(name)) == TABLE[name][1]
 
 
+def test_the_device_math_probe_takes_no_handle_and_refuses_null_pointers_in_its_own_words():
+    """emgpu_debug_device_math has neither a context nor a model among its parameters (device pointers and a stream, like the paired-tracks
+    entry points), so TABLE, which is HANDLES by construction, cannot hold it; every pointer NULL and every integer 0 is function 0 on no
+    input at all: refused, with a message, before any device work (tests/test_device_math.py has every other refusal)."""
+    name = "emgpu_debug_device_math"
+    assert name in L.SYMBOLS and name not in HANDLES and name not in TABLE
+    f = getattr(L.lib(), name)
+    args = [t(0) if t in INTS else None for t in f.argtypes]
+    assert len(args) == 6 and observe(name, args) == (L.ERR_ARG, b"null argument: x")
+
+
 def test_the_sampling_and_track_entry_points_say_null_argument():
     """The entry points that open with CTX_DEVICE refuse a null context together with their other pointers, in those words; CTX_ENTER's
     "null ctx" is for the three emgpu_ctx_* calls and the units that check their arguments first (trace, memory)."""
