@@ -94,6 +94,12 @@ class TTrackParams(C.Structure):  # emgpu_ttrack_params
                 ("bounds_sample", C.c_void_p), ("idx", C.c_int32 * 12)]
 
 
+class TFilterParams(C.Structure):  # emgpu_tfilter_params
+    _fields_ = [("n", C.c_int64), ("cap", C.c_int32), ("cap2", C.c_int32),
+                ("dyn_limits", C.c_double * 10), ("max_cum_turn_deg", C.c_double * 2), ("pitch_deg", C.c_double * 2),
+                ("min_enc_time_s", C.c_double), ("thres_dist_ft", C.c_double), ("thres_alt_low_ft", C.c_double), ("thres_vertrate_ft_s", C.c_double)]
+
+
 class Block(C.Structure):         # emgpu_block
     _fields_ = [("model", C.c_int32), ("_pad", C.c_int32), ("first_index", C.c_uint64), ("n", C.c_int64)]
 
@@ -229,6 +235,7 @@ SYMBOLS = [
     "emgpu_cpa_pose_device",
     "emgpu_well_clear_device",
     "emgpu_debug_device_math",
+    "emgpu_filter_terminal_device", "emgpu_smooth_terminal_device",
 ]
 
 # emgpu_debug_device_math's functions (EMGPU_MATH_*), by number
@@ -430,6 +437,8 @@ def lib():
     L.emgpu_cpa_pose_device.argtypes = [C.c_void_p, C.POINTER(CpaPoseParams)] + [C.c_void_p] * 10
     L.emgpu_well_clear_device.argtypes = [C.c_void_p, C.POINTER(WellClearParams)] + [C.c_void_p] * 12
     L.emgpu_debug_device_math.argtypes = [C.c_void_p, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.emgpu_filter_terminal_device.argtypes = [C.c_void_p, C.POINTER(TFilterParams)] + [C.c_void_p] * 7
+    L.emgpu_smooth_terminal_device.argtypes = [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p]
     _lib = L
     return L
 

@@ -95,6 +95,12 @@ static int terminal_models_ok(const emgpu_model *gm, int32_t n_traj_models, cons
     for (int k = 0; k < 12; k++) if (idx[k] < 1 || idx[k] > gm->m.n_initial) return fail(EMGPU_ERR_ARG, "geometry variable index out of range");
     return EMGPU_OK;
 }
+// the limits and thresholds of the filters (track.m:14-17, getDynamicLimits.m), from either parameter struct that carries them
+template <typename Params> static void filter_thresholds(EmgpuTFilterRun &F, const Params *p) {
+    memcpy(F.dl, p->dyn_limits, sizeof F.dl);
+    for (int a = 0; a < 2; a++) { F.max_cum_turn[a] = p->max_cum_turn_deg[a]; F.pitch[a] = p->pitch_deg[a]; }
+    F.min_enc_time_s = p->min_enc_time_s; F.thres_dist_ft = p->thres_dist_ft; F.thres_alt_low_ft = p->thres_alt_low_ft; F.thres_vertrate_ft_s = p->thres_vertrate_ft_s;
+}
 struct TerminalNames { const char *bn = "", *propagate = "", *smooth = ""; };   // what ran (smooth: " + k_terminal_smooth" or nothing)
 static TerminalNames terminal_chain(emgpu_ctx *ctx, const TerminalChain &c) {
     // k_terminal_smooth keeps a track's block in one workgroup's registers: refused before anything is launched
@@ -235,9 +241,7 @@ int emgpu_track_terminal_host(emgpu_ctx *ctx, const emgpu_model *gm, const emgpu
     EmgpuTFilterRun F;
     memset(&F, 0, sizeof F);
     F.tracks = d_out; F.rows = d_rows; F.cap = cap; F.geo = d_geo; F.val = d_val; F.n_i = (int32_t)ni;
-    memcpy(F.dl, p->dyn_limits, sizeof F.dl);
-    for (int a = 0; a < 2; a++) { F.max_cum_turn[a] = p->max_cum_turn_deg[a]; F.pitch[a] = p->pitch_deg[a]; }
-    F.min_enc_time_s = p->min_enc_time_s; F.thres_dist_ft = p->thres_dist_ft; F.thres_alt_low_ft = p->thres_alt_low_ft; F.thres_vertrate_ft_s = p->thres_vertrate_ft_s;
+    filter_thresholds(F, p);
     F.accepted = rounds.accepted();
     F.sample = d_sample; F.traj = d_traj; F.cap2 = cap2; F.len = d_len; F.meta = d_meta; F.attempts = d_att;
     for (; rounds.more(); rounds.next()) {
@@ -253,6 +257,49 @@ int emgpu_track_terminal_host(emgpu_ctx *ctx, const emgpu_model *gm, const emgpu
         back(sample, d_sample, n * ni * 8); back(traj, d_traj, n * 2 * (size_t)cap2 * 6 * 8); back(len, d_len, n * 2 * 4);
         back(meta, d_meta, n * 4 * 8); back(attempts, d_att, n * 4);
     });
+    EMGPU_CATCH
+}
+
+// The two kernels behind the propagation on tracks of the caller's: no context and no model, like the paired-tracks entry points (they
+// need no table, no scratch and no status word), so they run on the stream given and on the calling thread's current device.
+int emgpu_filter_terminal_device(void *hip_stream, const emgpu_tfilter_params *p, const double *geo, const float *tracks, const int32_t *rows,
+                                 uint8_t *accepted, double *meta, int32_t *len, double *traj) {
+    EMGPU_TRY
+    if (!p) return fail(EMGPU_ERR_ARG, "null argument: p");
+    if (!geo) return fail(EMGPU_ERR_ARG, "null argument: geo");
+    if (!tracks) return fail(EMGPU_ERR_ARG, "null argument: tracks");
+    if (!rows) return fail(EMGPU_ERR_ARG, "null argument: rows");
+    if (!accepted) return fail(EMGPU_ERR_ARG, "null argument: accepted");
+    if (p->n < 0 || p->n >= ((int64_t)1 << 29)) return fail(EMGPU_ERR_ARG, "n outside 0..2^29-1");
+    // CheckCumTurn keeps a joined track's heading differences per lane: rf + rb - 2 <= 2 cap - 2 <= 248 (emgpu_track_terminal_host: tmax_s <= 122)
+    if (p->cap < 2 || p->cap > 125) return fail(EMGPU_ERR_UNSUPPORTED, "cap outside 2..125");
+    if (traj && p->cap2 < 1) return fail(EMGPU_ERR_ARG, "traj with cap2 < 1");
+    if (((uintptr_t)geo | (uintptr_t)meta | (uintptr_t)traj) & 7u) return fail(EMGPU_ERR_ARG, "geo, meta and traj must be 8-byte aligned");
+    if (((uintptr_t)tracks | (uintptr_t)rows | (uintptr_t)len) & 3u) return fail(EMGPU_ERR_ARG, "tracks, rows and len must be 4-byte aligned");
+    if (p->n == 0) return EMGPU_OK;
+    EmgpuTFilterRun F;
+    memset(&F, 0, sizeof F);
+    F.n = p->n; F.tracks = tracks; F.rows = rows; F.cap = p->cap; F.geo = geo;
+    filter_thresholds(F, p);
+    F.accepted = accepted; F.traj = traj; F.cap2 = p->cap2; F.len = len; F.meta = meta;
+    const char *name = "";
+    launch_ok(emgpu::launch_terminal_filter(F, (hipStream_t)hip_stream, &name));
+    return EMGPU_OK;
+    EMGPU_CATCH
+}
+
+int emgpu_smooth_terminal_device(void *hip_stream, int64_t n2, int32_t cap, float *tracks, const int32_t *rows) {
+    EMGPU_TRY
+    if (!tracks) return fail(EMGPU_ERR_ARG, "null argument: tracks");
+    if (!rows) return fail(EMGPU_ERR_ARG, "null argument: rows");
+    if (n2 < 0 || n2 >= ((int64_t)1 << 30)) return fail(EMGPU_ERR_ARG, "n2 outside 0..2^30-1");
+    if (cap < 2) return fail(EMGPU_ERR_ARG, "cap < 2");
+    // k_terminal_smooth keeps a track's block in one workgroup's LDS tile of 256 rows
+    if (EMGPU_TERMINAL_BLOCK_ROWS(cap) > 256) return fail(EMGPU_ERR_UNSUPPORTED, "cap above 128");
+    if (((uintptr_t)tracks | (uintptr_t)rows) & 3u) return fail(EMGPU_ERR_ARG, "tracks and rows must be 4-byte aligned");
+    if (n2 == 0) return EMGPU_OK;
+    launch_ok(emgpu::launch_terminal_smooth(tracks, rows, n2, cap, (hipStream_t)hip_stream));
+    return EMGPU_OK;
     EMGPU_CATCH
 }
 

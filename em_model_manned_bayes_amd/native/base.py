@@ -410,6 +410,14 @@ def _device_call(entry, handles, params, *ptrs):
                                                *(C.c_void_p(int(a or 0) or None) for a in ptrs)))
 
 
+def _stream_handle(stream):
+    """a raw hipStream_t as a context-free device call takes it: None is torch's current stream, 0 the HIP default stream (NULL)"""
+    if stream is None:
+        import torch
+        stream = torch.cuda.current_stream().cuda_stream
+    return int(stream) or None
+
+
 def _array_factory(ctx, pinned, pageable):
     """empty(shape, dtype) of a host-path call's output arrays: the context's pinned pool, or the pageable numpy constructor (np.zeros,
     np.empty) of the caller's choice"""

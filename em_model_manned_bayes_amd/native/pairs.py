@@ -6,7 +6,7 @@ import types
 import numpy as np
 
 from .. import _lib as L
-from .base import _device_call, _weights_array
+from .base import _device_call, _stream_handle, _weights_array
 
 
 def miss_params(n_pairs, n_a, n_b, points, nmac_h_ft=500.0, nmac_v_ft=100.0, ld_a=0, ld_b=0):
@@ -16,14 +16,6 @@ def miss_params(n_pairs, n_a, n_b, points, nmac_h_ft=500.0, nmac_v_ft=100.0, ld_
     p.n_pairs, p.n_a, p.n_b, p.ld_a, p.ld_b, p.points = int(n_pairs), int(n_a), int(n_b), int(ld_a), int(ld_b), int(points)
     p.nmac_h_ft, p.nmac_v_ft = float(nmac_h_ft), float(nmac_v_ft)
     return p
-
-
-def _stream_handle(stream):
-    """a raw hipStream_t as a context-free device call takes it: None is torch's current stream, 0 the HIP default stream (NULL)"""
-    if stream is None:
-        import torch
-        stream = torch.cuda.current_stream().cuda_stream
-    return int(stream) or None
 
 
 def miss_distance_device(params, xyz_a, xyz_b, idx_a=0, idx_b=0, pose_b=0, weights=0, hmd=0, vmd=0, t_cpa=0, flags=0, totals=0, stream=None):

@@ -5,7 +5,7 @@ import ctypes as C
 import numpy as np
 
 from .. import _lib as L
-from .base import _device_call, _event_cap_error, _p
+from .base import _device_call, _event_cap_error, _p, _stream_handle
 from .layout import split_rows
 from .sampling import _fill_terminal
 from .text import _buffer_address, _parse_error
@@ -146,6 +146,35 @@ def track_terminal_host(ctx, geom_model, traj_models, n, seed, dyn_limits, max_c
     if not (allow_cap and rc == L.ERR_REJECT_CAP):   # the outputs of the encounters that were accepted are delivered either way (attempts -1 marks the rest)
         L.check(rc)
     return {"sample": sample, "traj": traj, "len": ln, "meta": meta, "attempts": att, "kernel": ctx.last_kernel()}
+
+
+def terminal_filter_params(n, cap, dyn_limits, max_cum_turn_deg, pitch_deg, cap2=0, min_enc_time_s=30.0, thres_dist_ft=2.5 * 6076,
+                           thres_alt_low_ft=750.0, thres_vertrate_ft_s=300.0 / 60.0):
+    """emgpu_tfilter_params: n encounters in blocks of 2 * terminal_t0_row(cap) rows, the limits and thresholds of track_terminal_host,
+    cap2 rows per track of the traj output."""
+    p = L.TFilterParams()
+    p.n, p.cap, p.cap2 = int(n), int(cap), int(cap2)
+    p.dyn_limits[:] = np.asarray(dyn_limits, dtype=np.float64).reshape(10).tolist()
+    for a in range(2):
+        p.max_cum_turn_deg[a], p.pitch_deg[a] = float(max_cum_turn_deg[a]), float(pitch_deg[a])
+    p.min_enc_time_s, p.thres_dist_ft, p.thres_alt_low_ft, p.thres_vertrate_ft_s = float(min_enc_time_s), float(thres_dist_ft), float(thres_alt_low_ft), float(thres_vertrate_ft_s)
+    return p
+
+
+def filter_terminal_device(params, geo, tracks, rows, accepted, meta=0, len=0, traj=0, stream=None):
+    """emgpu_filter_terminal_device: k_terminal_filter once on the caller's track blocks (raw device pointers, ints, 0 = skip an output;
+    params: terminal_filter_params).  geo [n, 12] f64, tracks [2n, 2 C, 5] f32 and rows [4n] i32 in propagate_terminal_joined_host's
+    layout; accepted [n] u8, meta [n, 4] f64, len [n, 2] i32, traj [n, 2, cap2, 6] f64, the last three written for accepted encounters
+    only.  No context: the current device and `stream` (a raw hipStream_t; 0: the HIP default stream; None: torch's current stream).
+    Asynchronous."""
+    _device_call("filter_terminal_device", (_stream_handle(stream),), params, geo, tracks, rows, accepted, meta, len, traj)
+
+
+def smooth_terminal_device(n2, cap, tracks, rows, stream=None):
+    """emgpu_smooth_terminal_device: k_terminal_smooth on n2 joined tracks [n2, 2 C, 5] f32 (rows [2 n2] i32), speed and altitude smoothed
+    in place.  Raw device pointers; the stream as filter_terminal_device's.  Asynchronous."""
+    L.check(L.lib().emgpu_smooth_terminal_device(_stream_handle(stream), int(n2), int(cap), C.c_void_p(int(tracks or 0) or None),
+                                                 C.c_void_p(int(rows or 0) or None)))
 
 
 def track_params(n, T, ur_speed, ur_vertrate, ur_heading, min_speed, max_speed, nd=0, slot_vertrate=0, slot_acc=0, slot_turnrate=0):

@@ -1146,6 +1146,34 @@ int emgpu_track_terminal_host(emgpu_ctx *ctx, const emgpu_model *geom_model, con
                               const emgpu_ttrack_params *p, double *sample, double *traj, int32_t cap2, int32_t *len,
                               double *meta, int32_t *attempts);
 
+/* The two kernels emgpu_track_terminal_host runs behind the propagation, each on tracks of the caller's: what a test hands a track of its
+ * choosing to.  The calls take no context and no model, like emgpu_miss_distance_device: hip_stream, the current device, DEVICE pointers,
+ * asynchronous.  EMGPU_ERR_ARG / EMGPU_ERR_UNSUPPORTED before any device work; n == 0 (n2 == 0): EMGPU_OK without a launch.
+ *
+ * emgpu_filter_terminal_device -- k_terminal_filter once: the filters of track.m:79-145 on n encounters, one decision each.
+ *   geo      [n][12] f64 as emgpu_propagate_terminal_device's; only the two intents (entries 5 and 11) are read
+ *   tracks   [2n][EMGPU_TERMINAL_BLOCK_ROWS(cap)][5] f32, rows [4n] i32: as emgpu_propagate_terminal_device writes them.  Every rows entry
+ *            must be <= cap (the kernel reads rows C-(rows_bck-1) .. C+(rows_fwd-1) of a block); an entry < 1 voids the attempt
+ *   accepted [n] u8: 1 = every filter passed, else 0
+ *   meta [n][4] f64, len [n][2] i32, traj [n][2][cap2][6] f64 as emgpu_track_terminal_host's (any may be NULL): written for ACCEPTED
+ *            encounters only, a rejected encounter's entries are left as they were; traj holds the first min(len, cap2) rows of a track
+ * cap outside 2..125 is EMGPU_ERR_UNSUPPORTED (CheckCumTurn keeps at most 248 heading differences per lane: emgpu_track_terminal_host's
+ * tmax_s <= 122).
+ *
+ * emgpu_smooth_terminal_device -- k_terminal_smooth: v_ft_s and z_ft of n2 joined tracks ([n2][EMGPU_TERMINAL_BLOCK_ROWS(cap)][5], rows
+ * [2 n2]: forward, backward per track) smoothed in place (EMGPU_FLAG_LOCAL_SMOOTH's stand-in); a track with a rows entry < 1 is left alone.
+ * EMGPU_TERMINAL_BLOCK_ROWS(cap) > 256 is EMGPU_ERR_UNSUPPORTED. */
+typedef struct {
+    int64_t n;                       /* < 2^29 encounters                                                  */
+    int32_t cap, cap2;               /* rows per direction of `tracks` (2..125); rows per track of `traj`  */
+    double dyn_limits[2][5];         /* as emgpu_ttrack_params, and so are the rest                        */
+    double max_cum_turn_deg[2], pitch_deg[2];
+    double min_enc_time_s, thres_dist_ft, thres_alt_low_ft, thres_vertrate_ft_s;
+} emgpu_tfilter_params;
+int emgpu_filter_terminal_device(void *hip_stream, const emgpu_tfilter_params *p, const double *geo, const float *tracks, const int32_t *rows,
+                                 uint8_t *accepted, double *meta, int32_t *len, double *traj);
+int emgpu_smooth_terminal_device(void *hip_stream, int64_t n2, int32_t cap, float *tracks, const int32_t *rows);
+
 /* Introspection for benchmarks/tests: name of the kernel variant the last *_device call used and
  * the algorithmic output bytes per trajectory of that call (5*n_i + 5*T*n_d for dense output). */
 const char *emgpu_last_kernel_name(const emgpu_ctx *ctx);

@@ -1382,7 +1382,7 @@ def test_terminal_track_matches_oracle(actypes, n, cap, cum_override, smooth, te
 
 
 def test_terminal_class_track_and_cum_turn(terminal_dir, gpu_ctx):
-    """The class method (out_results(ii).sample / .traj, reformatTrajFiles) and CheckCumTurn known answers."""
+    """The class method (out_results(ii).sample / .traj, reformatTrajFiles); CheckCumTurn's known answers moved to the device test."""
     t = E.CorTerminalModel(srcData="terminalradar", parameters_directory=terminal_dir)
     out, gen_time, info = t.track(12, initialSeed=3, max_track_attempts=3000, ctx=gpu_ctx, return_info=True)
     assert len(out) == 12 and gen_time.shape == (12,) and np.all(info["attempts"] >= 1)
@@ -1391,11 +1391,9 @@ def test_terminal_class_track_and_cum_turn(terminal_dir, gpu_ctx):
         assert {"own_intent", "int_intent", "id", "tcpa", "hmd_ft", "vmd_ft", "nmac", "own_initSpeed_ftps"} <= set(s)
         assert len(tr) == 2 and tr[0]["t"][0] == 0 and np.array_equal(tr[0]["t"], tr[1]["t"]) and len(tr[0]["t"]) >= 30
         assert s["own_intent"] in (1, 2) and s["nmac"] == (abs(s["hmd_ft"]) < 500 and abs(s["vmd_ft"]) < 100)
-    # CheckCumTurn (CorTerminalModel.m:135-185) on hand-made headings: a steady 3 deg/s turn through 210 deg is rejected at 180,
-    # the same amount split into a left and a right turn is not
-    steady = np.concatenate([np.zeros(5), np.arange(0, 211, 3.0), np.full(5, 210.0)])
-    zigzag = np.concatenate([np.zeros(5), np.arange(0, 106, 3.0), np.arange(105, -1, -3.0), np.zeros(5)])
-    assert O.check_cum_turn(steady, 180.0) and not O.check_cum_turn(zigzag, 180.0) and not O.check_cum_turn(steady, np.inf)
+    # CheckCumTurn's known answers (a steady 3 deg/s turn through 210 deg against the same amount split into a left and a right turn): the
+    # restatements in test_terminal_filter.py::test_check_cum_turn_known_answers, the device code on the same headings in
+    # test_gpu_terminal_filter.py (family cum_turn, cases steady_zigzag and steady_limit_inf_180)
 
 
 def test_edge_cases_and_error_paths(gpu_ctx, model_dir):
