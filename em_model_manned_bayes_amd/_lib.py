@@ -30,6 +30,7 @@ MISS_CPA_BETWEEN, MISS_NMAC_BETWEEN = 16, 32                             # emgpu
 ENC_END, ENC_FALLBACK, ENC_NO_ENTRY, ENC_SATURATED, ENC_BAD_INDEX = 1, 2, 4, 8, 16   # emgpu_encounter_pose_device's flags
 CPA_FALLBACK, CPA_NO_PASS, CPA_SATURATED, CPA_BAD_INDEX = 2, 4, 8, 16                # emgpu_cpa_pose_device's flags
 WC_LOST, WC_AT_START, WC_NO_DATA, WC_BAD_INDEX, WC_INSIDE_DMOD, WC_BY_TAU = 1, 2, 4, 8, 16, 32   # emgpu_well_clear_device's flags
+AVOID_ALERTED, AVOID_CLIMB, AVOID_NMAC_UNMIT, AVOID_NMAC_MIT, AVOID_LATE, AVOID_NO_CPA, AVOID_BAD_INDEX = 1, 2, 4, 8, 16, 32, 64   # emgpu_avoid_device's
 FLAG_QUANTIZE500, FLAG_NO_RESAMPLE, FLAG_NO_DEDISC, FLAG_NO_TERMINATOR, FLAG_LOCAL_SMOOTH = 1, 2, 4, 8, 16
 
 # MATLAB error identifiers the reference raises for the same condition
@@ -196,6 +197,13 @@ class WellClearParams(C.Structure):     # emgpu_well_clear_params
                 ("h_ft", C.c_double)]
 
 
+class AvoidParams(C.Structure):         # emgpu_avoid_params
+    _fields_ = [("n_pairs", C.c_int64), ("n_a", C.c_int64), ("n_b", C.c_int64), ("ld_a", C.c_int64), ("ld_b", C.c_int64),
+                ("points", C.c_int32), ("delay_s", C.c_int32), ("alert_tau_s", C.c_double), ("alert_dmod_ft", C.c_double),
+                ("alert_hmd_ft", C.c_double), ("alert_h_ft", C.c_double), ("nmac_h_ft", C.c_double), ("nmac_v_ft", C.c_double),
+                ("rate_fps", C.c_double), ("accel_fps2", C.c_double), ("dz_max_ft", C.c_double)]
+
+
 class BnParams(C.Structure):
     _fields_ = [("seed", C.c_uint64), ("first_index", C.c_uint64), ("n", C.c_int64), ("flags", C.c_uint32),
                 ("max_attempts", C.c_int32), ("bounds_sample", C.c_void_p),
@@ -234,6 +242,7 @@ SYMBOLS = [
     "emgpu_encounter_pose_device",
     "emgpu_cpa_pose_device",
     "emgpu_well_clear_device",
+    "emgpu_avoid_device",
     "emgpu_debug_device_math",
     "emgpu_filter_terminal_device", "emgpu_smooth_terminal_device",
 ]
@@ -436,6 +445,7 @@ def lib():
     L.emgpu_encounter_pose_device.argtypes = [C.c_void_p, C.POINTER(EncounterParams)] + [C.c_void_p] * 9
     L.emgpu_cpa_pose_device.argtypes = [C.c_void_p, C.POINTER(CpaPoseParams)] + [C.c_void_p] * 10
     L.emgpu_well_clear_device.argtypes = [C.c_void_p, C.POINTER(WellClearParams)] + [C.c_void_p] * 12
+    L.emgpu_avoid_device.argtypes = [C.c_void_p, C.POINTER(AvoidParams)] + [C.c_void_p] * 13
     L.emgpu_debug_device_math.argtypes = [C.c_void_p, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]
     L.emgpu_filter_terminal_device.argtypes = [C.c_void_p, C.POINTER(TFilterParams)] + [C.c_void_p] * 7
     L.emgpu_smooth_terminal_device.argtypes = [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p]

@@ -1,11 +1,12 @@
-// emgpu_pairs.cpp -- the five entry points on paired 1 Hz tracks (the pairing: emgpu_pairs.h), side by side: emgpu_miss_distance_device
+// emgpu_pairs.cpp -- the six entry points on paired 1 Hz tracks (the pairing: emgpu_pairs.h), side by side: emgpu_miss_distance_device
 // (k_miss_distance, emgpu_miss.h), emgpu_miss_segments_device (k_miss_segments, emgpu_miss_seg.h), emgpu_encounter_pose_device
-// (k_encounter_pose, emgpu_encounter.h), emgpu_cpa_pose_device (k_cpa_pose, emgpu_cpa.h) and emgpu_well_clear_device (k_well_clear,
-// emgpu_well_clear.h).  They take no context: they need no model table, no scratch and no status word, so they run on the stream they are
-// given and on the calling thread's current device.
+// (k_encounter_pose, emgpu_encounter.h), emgpu_cpa_pose_device (k_cpa_pose, emgpu_cpa.h), emgpu_well_clear_device (k_well_clear,
+// emgpu_well_clear.h) and emgpu_avoid_device (k_avoid, emgpu_avoid.h).  They take no context: they need no model table, no scratch and
+// no status word, so they run on the stream they are given and on the calling thread's current device.
 #include <cmath>
 
 #include "emgpu_internal.hpp"
+#include "emgpu_avoid.h"
 #include "emgpu_cpa.h"
 #include "emgpu_encounter.h"
 #include "emgpu_miss.h"
@@ -172,6 +173,43 @@ int emgpu_well_clear_device(void *hip_stream, const emgpu_well_clear_params *p, 
     A.pose = pose_b; A.weights = weights; A.miss_flags = miss_flags;
     A.t_first = t_first; A.n_lost = n_lost; A.tau_min = tau_min; A.flags = flags; A.totals = (unsigned long long *)totals;
     launch_ok(emgpu::launch_well_clear(A, (hipStream_t)hip_stream, nullptr));
+    return EMGPU_OK;
+    EMGPU_CATCH
+}
+
+int emgpu_avoid_device(void *hip_stream, const emgpu_avoid_params *p, const double *xyz_a, const double *xyz_b, const int64_t *idx_a,
+                       const int64_t *idx_b, const double *pose_b, const uint32_t *weights, double *hmd, double *vmd, double *vmd_mit,
+                       int32_t *t_cpa, int32_t *t_alert, uint8_t *flags, uint64_t *totals) {
+    EMGPU_TRY
+    if (const int rc = check_pairing(p, xyz_a, xyz_b, idx_a, idx_b, hmd || vmd || vmd_mit || t_cpa || t_alert || flags || totals,
+                                     "null hmd, vmd, vmd_mit, t_cpa, t_alert, flags and totals: nothing to write", 1))
+        return rc;
+    if (!(p->alert_tau_s >= 0.0)) return fail(EMGPU_ERR_ARG, "alert_tau_s is negative or NaN");
+    if (!(p->alert_dmod_ft >= 0.0)) return fail(EMGPU_ERR_ARG, "alert_dmod_ft is negative or NaN");
+    if (!(p->alert_hmd_ft >= 0.0)) return fail(EMGPU_ERR_ARG, "alert_hmd_ft is negative or NaN");
+    if (!(p->alert_h_ft >= 0.0)) return fail(EMGPU_ERR_ARG, "alert_h_ft is negative or NaN");
+    if (!(p->nmac_h_ft >= 0.0)) return fail(EMGPU_ERR_ARG, "nmac_h_ft is negative or NaN");
+    if (!(p->nmac_v_ft >= 0.0)) return fail(EMGPU_ERR_ARG, "nmac_v_ft is negative or NaN");
+    if (p->delay_s < 0) return fail(EMGPU_ERR_ARG, "delay_s is negative");
+    if (!(std::isfinite(p->rate_fps) && p->rate_fps >= 0.0)) return fail(EMGPU_ERR_ARG, "rate_fps is negative, NaN or infinite");
+    if (!(p->accel_fps2 > 0.0)) return fail(EMGPU_ERR_ARG, "accel_fps2 is not positive or NaN");
+    if (!(p->dz_max_ft >= 0.0)) return fail(EMGPU_ERR_ARG, "dz_max_ft is negative or NaN");
+    if (((uintptr_t)xyz_a | (uintptr_t)xyz_b | (uintptr_t)idx_a | (uintptr_t)idx_b | (uintptr_t)pose_b | (uintptr_t)hmd | (uintptr_t)vmd |
+         (uintptr_t)vmd_mit | (uintptr_t)totals) & 7u)
+        return fail(EMGPU_ERR_ARG, "xyz_a, xyz_b, idx_a, idx_b, pose_b, hmd, vmd, vmd_mit and totals must be 8-byte aligned");
+    if (((uintptr_t)weights | (uintptr_t)t_cpa | (uintptr_t)t_alert) & 3u)
+        return fail(EMGPU_ERR_ARG, "weights, t_cpa and t_alert must be 4-byte aligned");
+    if (p->n_pairs == 0) return EMGPU_OK;
+    EmgpuAvoidRun A{};
+    fill_pairing(p, xyz_a, xyz_b, idx_a, idx_b, A.dim, A.col);
+    A.P = p->points; A.delay = std::min(p->delay_s, 65537);   // (a longer delay moves no point either: P <= 65537)
+    A.tau_s = p->alert_tau_s; A.D2 = p->alert_dmod_ft * p->alert_dmod_ft; A.H2 = p->alert_hmd_ft * p->alert_hmd_ft; A.h = p->alert_h_ft;
+    A.nmac_h = p->nmac_h_ft; A.nmac_v = p->nmac_v_ft;
+    A.rate = p->rate_fps; A.tr = p->rate_fps / p->accel_fps2; A.half_tr = 0.5 * A.tr; A.half_a = 0.5 * p->accel_fps2; A.dz_max = p->dz_max_ft;
+    A.pose = pose_b; A.weights = weights;
+    A.hmd = hmd; A.vmd = vmd; A.vmd_mit = vmd_mit; A.t_cpa = t_cpa; A.t_alert = t_alert; A.flags = flags;
+    A.totals = (unsigned long long *)totals;
+    launch_ok(emgpu::launch_avoid(A, (hipStream_t)hip_stream, nullptr));
     return EMGPU_OK;
     EMGPU_CATCH
 }

@@ -721,6 +721,19 @@ class UncorEncounterModel(EncounterModel):
         return native.well_clear(own_xyz, intruder_xyz, idx_a=idx_own, idx_b=idx_intruder, pose_b=pose, weights=weights, miss_flags=miss_flags,
                                  tau_s=tau_s, dmod_ft=dmod_ft, hmd_ft=hmd_ft, h_ft=h_ft, layout=layout, ctx=ctx)
 
+    def avoid(self, own_xyz, intruder_xyz, pose=None, weights=None, idx_own=None, idx_intruder=None, alert_tau_s=60.0, alert_dmod_ft=4000.0,
+              alert_hmd_ft=4000.0, alert_h_ft=700.0, nmac_h_ft=500.0, nmac_v_ft=100.0, delay_s=5, rate_fps=25.0, accel_fps2=8.0,
+              dz_max_ft=float("inf"), layout="rows", ctx=None):
+        """.pair with an ownship that reacts: at the first second inside the alert volume (.well_clear's predicate with the four alert_*
+        thresholds) the ownship picks a vertical sense, and delay_s seconds later accelerates with accel_fps2 to the vertical rate
+        rate_fps, up to dz_max_ft feet, evaluated on the GPU: a thin wrapper over native.avoid.  The tracks, pose, weights, indices,
+        layout and ctx are .pair's.  The defaults are an illustration, not the alerting thresholds of any standard.  Returns
+        native.avoid's dict; "risk_ratio" is the weighted P(NMAC with the manoeuvre) / P(NMAC without)."""
+        return native.avoid(own_xyz, intruder_xyz, idx_a=idx_own, idx_b=idx_intruder, pose_b=pose, weights=weights, alert_tau_s=alert_tau_s,
+                            alert_dmod_ft=alert_dmod_ft, alert_hmd_ft=alert_hmd_ft, alert_h_ft=alert_h_ft, nmac_h_ft=nmac_h_ft,
+                            nmac_v_ft=nmac_v_ft, delay_s=delay_s, rate_fps=rate_fps, accel_fps2=accel_fps2, dz_max_ft=dz_max_ft, layout=layout,
+                            ctx=ctx)
+
     def getDynamicLimits(self, initial, results, idx_G=None, idx_A=None, idx_L=None, idx_V=None, idx_DH=None, is_discretized=None):
         """dynamiclimits = getDynamicLimits(self, initial, results, ...)  (@UncorEncounterModel/getDynamicLimits.m).  The index
         arguments are accepted for signature compatibility; they are looked up from the labels like .track does."""

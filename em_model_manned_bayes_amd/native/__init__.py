@@ -23,9 +23,10 @@ from .trace import (_bin_arrays, _count_bytes, _count_host, _count_scope, _count
 from .tracks import (filter_terminal_device, propagate_terminal_host, propagate_terminal_joined_host, sample2track_device,
                      sample2track_host, smooth_terminal_device, split_joined_tracks, terminal_filter_params, terminal_t0_row, track_params,
                      track_terminal_host, track_uncor_device, track_uncor_host, tracks_text_host, uncor_dynamic_limits, utrack_params)
-from .pairs import (_cpa_dict, _cpa_pose_tensors, _encounter_dict, _encounter_pose_tensors, _encounter_weights, _miss_dict,
-                    _miss_segments_dict, _miss_segments_tensors, _miss_tensors, _miss_then_well_clear, _pair_columns, _paired, _placed_then,
-                    _planar_tracks, _ptr, _well_clear_dict, _well_clear_tensors, cpa_miss, cpa_miss_segments, cpa_pose,
-                    cpa_pose_device, cpa_pose_params, cpa_well_clear, encounter_miss, encounter_miss_segments, encounter_params,
+from .pairs import (_avoid_dict, _avoid_tensors, _cpa_dict, _cpa_pose_tensors, _encounter_dict, _encounter_pose_tensors, _encounter_weights,
+                    _miss_dict, _miss_segments_dict, _miss_segments_tensors, _miss_tensors, _miss_then_well_clear, _pair_columns, _paired,
+                    _placed_then, _planar_tracks, _ptr, _well_clear_dict, _well_clear_tensors, avoid, avoid_device, avoid_params, cpa_avoid,
+                    cpa_miss, cpa_miss_segments, cpa_pose, cpa_pose_device, cpa_pose_params, cpa_well_clear, encounter_avoid,
+                    encounter_miss, encounter_miss_segments, encounter_params,
                     encounter_pose, encounter_pose_device, encounter_well_clear, make_pose, miss_distance, miss_distance_device, miss_params,
                     miss_segments, miss_segments_device, well_clear, well_clear_device, well_clear_params)

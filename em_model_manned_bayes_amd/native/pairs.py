@@ -1,5 +1,5 @@
-"""Paired tracks: the one pairing, and on it the miss distance, the loss of well clear and the two placements of the intruder, on the
-encounter cylinder and at a drawn closest approach.  Torch does the plumbing here."""
+"""Paired tracks: the one pairing, and on it the miss distance, the loss of well clear, the ownship's vertical avoidance manoeuvre and the
+two placements of the intruder, on the encounter cylinder and at a drawn closest approach.  Torch does the plumbing here."""
 import contextlib
 import types
 
@@ -493,4 +493,103 @@ def cpa_well_clear(xyz_a, xyz_b, hmd_max_ft, vmd_max_ft, seed, t_lo, t_hi=None, 
     "t_first", "n_lost", "tau_min_s", "wc_flags", "lowc", "at_start" and "wc_totals"."""
     tensors, as_dict = _miss_then_well_clear(between, tau_s, dmod_ft, hmd_ft, h_ft)
     return _cpa_then(tensors, as_dict, xyz_a, xyz_b, hmd_max_ft, vmd_max_ft, seed, t_lo, t_hi, idx_a, idx_b, weights, rate_scale, first_index,
+                     max_attempts, nmac_h_ft, nmac_v_ft, layout, ctx, stream)
+
+
+def avoid_params(n_pairs, n_a, n_b, points, alert_tau_s=60.0, alert_dmod_ft=4000.0, alert_hmd_ft=4000.0, alert_h_ft=700.0, nmac_h_ft=500.0,
+                 nmac_v_ft=100.0, delay_s=5, rate_fps=25.0, accel_fps2=8.0, dz_max_ft=float("inf"), ld_a=0, ld_b=0):
+    """emgpu_avoid_params: miss_params' pairing; the alert volume (well_clear's four thresholds, with values of their own); the NMAC
+    thresholds; the ownship's response: the whole seconds between the alert and the manoeuvre, the vertical rate it reaches in ft/s, the
+    acceleration towards it in ft/s^2 (inf: at once) and the largest displacement in feet.  The defaults are an illustration (1500 ft/min
+    after 5 s at about 0.25 g), not the alerting thresholds of any standard."""
+    p = L.AvoidParams()
+    p.n_pairs, p.n_a, p.n_b, p.ld_a, p.ld_b, p.points, p.delay_s = int(n_pairs), int(n_a), int(n_b), int(ld_a), int(ld_b), int(points), int(delay_s)
+    p.alert_tau_s, p.alert_dmod_ft, p.alert_hmd_ft, p.alert_h_ft = float(alert_tau_s), float(alert_dmod_ft), float(alert_hmd_ft), float(alert_h_ft)
+    p.nmac_h_ft, p.nmac_v_ft = float(nmac_h_ft), float(nmac_v_ft)
+    p.rate_fps, p.accel_fps2, p.dz_max_ft = float(rate_fps), float(accel_fps2), float(dz_max_ft)
+    return p
+
+
+def avoid_device(params, xyz_a, xyz_b, idx_a=0, idx_b=0, pose_b=0, weights=0, hmd=0, vmd=0, vmd_mit=0, t_cpa=0, t_alert=0, flags=0, totals=0,
+                 stream=None):
+    """emgpu_avoid_device: asynchronous, raw device pointers (ints, 0 = none; params: avoid_params).  The inputs are
+    miss_distance_device's; hmd / vmd / vmd_mit f64, t_cpa / t_alert int32, flags uint8 (L.AVOID_*) [n_pairs] each, totals uint64 [12],
+    ADDED to.  No context: the current device and `stream`, a raw hipStream_t (0: the HIP default stream; None: torch's current stream)."""
+    _device_call("avoid_device", (_stream_handle(stream),), params, xyz_a, xyz_b, idx_a, idx_b, pose_b, weights, hmd, vmd, vmd_mit, t_cpa, t_alert,
+                 flags, totals)
+
+
+def _avoid_tensors(pr, d_pose, d_w, **response):
+    """k_avoid on the pairing pr with the device tensors d_pose and d_w (or None) and avoid_params' thresholds and response: the device
+    tensors (hmd, vmd, vmd_mit, t_cpa, t_alert, flags, totals [12]), launched on pr.stream and not waited for"""
+    import torch
+    n, dev = pr.n_pairs, pr.dev
+    hmd, vmd, vmd_mit = (torch.empty(n, dtype=torch.float64, device=dev) for _ in range(3))
+    t_cpa, t_alert = torch.empty(n, dtype=torch.int32, device=dev), torch.empty(n, dtype=torch.int32, device=dev)
+    flags = torch.empty(n, dtype=torch.uint8, device=dev)
+    totals = torch.zeros(12, dtype=torch.int64, device=dev)
+    pr.guard()      # totals was zeroed on torch's stream
+    avoid_device(avoid_params(n, pr.n_a, pr.n_b, pr.a.shape[0], **response), _ptr(pr.a), _ptr(pr.b), _ptr(pr.d_ia), _ptr(pr.d_ib), _ptr(d_pose),
+                 _ptr(d_w), _ptr(hmd), _ptr(vmd), _ptr(vmd_mit), _ptr(t_cpa), _ptr(t_alert), _ptr(flags), _ptr(totals), stream=pr.stream)
+    return hmd, vmd, vmd_mit, t_cpa, t_alert, flags, totals
+
+
+def _avoid_dict(hmd, vmd, vmd_mit, t_cpa, t_alert, flags, totals):
+    """avoid's dict from _avoid_tensors' device tensors"""
+    fl, tot = flags.cpu().numpy(), totals.cpu().numpy().view(np.uint64)
+    nmac, nmac_mit = (fl & L.AVOID_NMAC_UNMIT) != 0, (fl & L.AVOID_NMAC_MIT) != 0
+    return {"hmd_ft": hmd.cpu().numpy(), "vmd_ft": vmd.cpu().numpy(), "vmd_mit_ft": vmd_mit.cpu().numpy(), "t_cpa": t_cpa.cpu().numpy(),
+            "t_alert": t_alert.cpu().numpy(), "flags": fl, "alerted": (fl & L.AVOID_ALERTED) != 0, "climb": (fl & L.AVOID_CLIMB) != 0,
+            "nmac": nmac, "nmac_mit": nmac_mit, "induced": nmac_mit & ~nmac, "totals": tot,
+            "risk_ratio": float(tot[10]) / float(tot[9]) if tot[9] else float("nan")}
+
+
+def avoid(xyz_a, xyz_b, idx_a=None, idx_b=None, pose_b=None, weights=None, alert_tau_s=60.0, alert_dmod_ft=4000.0, alert_hmd_ft=4000.0,
+          alert_h_ft=700.0, nmac_h_ft=500.0, nmac_v_ft=100.0, delay_s=5, rate_fps=25.0, accel_fps2=8.0, dz_max_ft=float("inf"), layout="rows",
+          ctx=None, stream=None):
+    """The ownship's vertical avoidance manoeuvre on paired 1 Hz tracks on the GPU (emgpu_avoid_device; the definition is in
+    include/emgpu.h): set A is the ownship, set B the intruder.  The first second at which the pair is inside the alert volume
+    (well_clear's predicate with alert_tau_s, alert_dmod_ft, alert_hmd_ft, alert_h_ft) alerts the ownship; it picks the sense that moves it
+    away from where the intruder will be at the horizontal closest approach, and delay_s seconds later accelerates with accel_fps2 (inf: at
+    once) to the vertical rate rate_fps, up to dz_max_ft feet.  The intruder flies on as it did.  The defaults are an illustration, not
+    the alerting thresholds of any standard.  xyz_a / xyz_b, idx_a / idx_b, pose_b, weights, layout, ctx and stream are miss_distance's.
+    Returns {"hmd_ft", "vmd_ft" float64, "t_cpa" int32: miss_distance's, "vmd_mit_ft" float64: the vertical miss at that second with the
+    manoeuvre, "t_alert" int32: the alert's second, -1 without one, "flags" uint8 (L.AVOID_*), "alerted", "climb", "nmac": an NMAC at some
+    second without the manoeuvre, "nmac_mit": with it, "induced": with it only (bool each), "totals" uint64 [12], "risk_ratio":
+    totals[10] / totals[9], the weighted P(NMAC with the manoeuvre) / P(NMAC without), NaN when totals[9] is 0}."""
+    columns, w, pose_b = _miss_inputs(xyz_a, xyz_b, idx_a, idx_b, pose_b, weights, layout)
+    with _paired(xyz_a, xyz_b, columns, w, pose_b, layout, ctx, stream) as pr:
+        out = _avoid_tensors(pr, pr.d_pose, pr.d_w, alert_tau_s=alert_tau_s, alert_dmod_ft=alert_dmod_ft, alert_hmd_ft=alert_hmd_ft,
+                             alert_h_ft=alert_h_ft, nmac_h_ft=nmac_h_ft, nmac_v_ft=nmac_v_ft, delay_s=delay_s, rate_fps=rate_fps,
+                             accel_fps2=accel_fps2, dz_max_ft=dz_max_ft)
+    return _avoid_dict(*out)
+
+
+def _avoid_after(**response):
+    """`tensors` for _placed_then: k_avoid on the placement's pose and weights, with the NMAC thresholds _placed_then hands over"""
+    return lambda pr, d_pose, d_w, nmac_h_ft, nmac_v_ft: _avoid_tensors(pr, d_pose, d_w, nmac_h_ft=nmac_h_ft, nmac_v_ft=nmac_v_ft, **response)
+
+
+def encounter_avoid(xyz_a, xyz_b, radius_ft, half_height_ft, seed, idx_a=None, idx_b=None, weights=None, rate_scale=None, first_index=0,
+                    max_attempts=16, alert_tau_s=60.0, alert_dmod_ft=4000.0, alert_hmd_ft=4000.0, alert_h_ft=700.0, nmac_h_ft=500.0,
+                    nmac_v_ft=100.0, delay_s=5, rate_fps=25.0, accel_fps2=8.0, dz_max_ft=float("inf"), layout="rows", ctx=None, stream=None):
+    """encounter_pose and then avoid on one stream, the pose and the rate-folded weights never leaving the device: the intruders placed on
+    the encounter cylinder, then the ownship's alert and manoeuvre.  The arguments are encounter_pose's and avoid's thresholds and
+    response.  With weights (and rate_scale) totals[7:12] are sums of w * rate / rate_scale, so "risk_ratio" is that of the encounters.
+    Returns avoid's dict plus "rate" float64, "encounter_flags" uint8 (L.ENC_*) and "weights" uint32 or None."""
+    tensors = _avoid_after(alert_tau_s=alert_tau_s, alert_dmod_ft=alert_dmod_ft, alert_hmd_ft=alert_hmd_ft, alert_h_ft=alert_h_ft,
+                           delay_s=delay_s, rate_fps=rate_fps, accel_fps2=accel_fps2, dz_max_ft=dz_max_ft)
+    return _encounter_then(tensors, _avoid_dict, xyz_a, xyz_b, radius_ft, half_height_ft, seed, idx_a, idx_b, weights, rate_scale, first_index,
+                           max_attempts, nmac_h_ft, nmac_v_ft, layout, ctx, stream)
+
+
+def cpa_avoid(xyz_a, xyz_b, hmd_max_ft, vmd_max_ft, seed, t_lo, t_hi=None, idx_a=None, idx_b=None, weights=None, rate_scale=None, first_index=0,
+              max_attempts=16, alert_tau_s=60.0, alert_dmod_ft=4000.0, alert_hmd_ft=4000.0, alert_h_ft=700.0, nmac_h_ft=500.0, nmac_v_ft=100.0,
+              delay_s=5, rate_fps=25.0, accel_fps2=8.0, dz_max_ft=float("inf"), layout="rows", ctx=None, stream=None):
+    """cpa_pose and then avoid on one stream, as encounter_avoid: every placed pair passes close by, which is what a risk ratio wants.  The
+    arguments are cpa_pose's and avoid's thresholds and response.  Returns avoid's dict plus "rate" float64, "t_cpa_drawn" int32,
+    "encounter_flags" uint8 (L.CPA_*) and "weights" uint32 or None."""
+    tensors = _avoid_after(alert_tau_s=alert_tau_s, alert_dmod_ft=alert_dmod_ft, alert_hmd_ft=alert_hmd_ft, alert_h_ft=alert_h_ft,
+                           delay_s=delay_s, rate_fps=rate_fps, accel_fps2=accel_fps2, dz_max_ft=dz_max_ft)
+    return _cpa_then(tensors, _avoid_dict, xyz_a, xyz_b, hmd_max_ft, vmd_max_ft, seed, t_lo, t_hi, idx_a, idx_b, weights, rate_scale, first_index,
                      max_attempts, nmac_h_ft, nmac_v_ft, layout, ctx, stream)

@@ -828,6 +828,72 @@ int emgpu_well_clear_device(void *hip_stream, const emgpu_well_clear_params *p, 
                             const int64_t *idx_b, const double *pose_b, const uint32_t *weights, const uint8_t *miss_flags, int32_t *t_first,
                             int32_t *n_lost, double *tau_min, uint8_t *flags, uint64_t *totals /* [10] */);
 
+/* ------------------------------------------------------------------------------------------------
+ * Ownship vertical avoidance on paired tracks: alert, manoeuvre, risk ratio.  The calls above are UNMITIGATED: both aircraft fly their
+ * tracks blindly.  Here the ownship (set A) answers the first alert with one vertical manoeuvre, and the call reports the NMAC with and
+ * without it: sum(w NMAC_MIT) / sum(w NMAC_UNMIT) is the risk ratio.  The alert is the per-point predicate of emgpu_well_clear_device with
+ * thresholds of its own; the manoeuvre is a closed form of the seconds since the alert, so no mitigated track is written anywhere.
+ * Inputs     emgpu_well_clear_device's, without miss_flags: the two PLANAR sets (A = ownship, B = intruder), n_a, n_b, ld_a, ld_b, n_pairs,
+ *            idx_a / idx_b with the same column selection, n_x = 1 broadcast and bad-index rule; the optional pose_b [5][n_pairs]; the
+ *            optional weights uint32 [n_pairs].
+ * Parameters the struct has no defaults.  The Python binding's (alert_tau_s 60 s, alert_dmod_ft 4000 ft, alert_hmd_ft 4000 ft, alert_h_ft
+ *            700 ft; nmac_h_ft 500 ft, nmac_v_ft 100 ft; delay_s 5 s, rate_fps 25 ft/s = 1500 ft/min, accel_fps2 8 ft/s^2, about 0.25 g,
+ *            dz_max_ft +inf) are an ILLUSTRATION, not the alerting thresholds of any standard.  The host forms once D2 = alert_dmod_ft *
+ *            alert_dmod_ft, H2 = alert_hmd_ft * alert_hmd_ft, tr = rate_fps / accel_fps2, half_tr = 0.5 * tr, half_a = 0.5 * accel_fps2;
+ *            accel_fps2 = +inf is allowed and gives tr = 0: the full rate from the first second.
+ * Everything is f64; every product, sum, quotient and root is one IEEE double operation in the order written; nothing is contracted; a NaN
+ * compares false.
+ * State      dx, dy, dz[p], d[p] = sqrt(dx * dx + dy * dy) as for emgpu_miss_distance_device (dz = zb' - za); the relative velocity
+ *            (ux, uy) at point p as for emgpu_well_clear_device (q = min(p, P-2); P = 1: 0), and wz = dz[q+1] - dz[q] (P = 1: 0).
+ * Alert      alert[p] = lost[p] of emgpu_well_clear_device with tau_s = alert_tau_s, D2, H2 and h_ft = alert_h_ft, on the UNMITIGATED state.
+ *            t_alert = the first p with alert[p], -1 if none.  Only the first alert acts: no reversal, no strengthening.
+ * Sense      fixed at t_alert from the intruder's predicted vertical offset at the horizontal closest approach: with (x, y, z) the state
+ *            there and tc the clamped tc of the predicate, zp = z + tc * wz; descend = zp > 0 || (!(zp < 0) && z > 0); otherwise the
+ *            ownship climbs.  A zero or NaN zp falls back to the sign of z, and z = 0 climbs.
+ * Manoeuvre  t0 = t_alert + delay_s.  For a point p with k = p - t0 >= 1, kd = (double)k:
+ *            g = kd < tr ? half_a * (kd * kd) : rate_fps * (kd - half_tr);  g = g < dz_max_ft ? g : dz_max_ft
+ *            dz'[p] = climb ? dz[p] - g : dz[p] + g
+ *            For k <= 0, or without an alert, dz'[p] = dz[p] exactly (no arithmetic).  The horizontal state is untouched.  The alert of
+ *            point p is known when point p + 1 arrives, so k >= 1 is causal even with delay_s = 0.
+ * Outputs    per pair, each may be NULL: hmd, vmd f64 and t_cpa int32 [n_pairs], bit for bit what emgpu_miss_distance_device writes
+ *            (no second holding a number: NaN, NaN, -1); vmd_mit f64 [n_pairs] = dz'[t_cpa] (NaN without a CPA); t_alert int32 [n_pairs];
+ *            flags uint8 [n_pairs]: EMGPU_AVOID_ALERTED; EMGPU_AVOID_CLIMB (only with ALERTED); EMGPU_AVOID_NMAC_UNMIT (some p with
+ *            d[p] < nmac_h_ft && fabs(dz[p]) < nmac_v_ft: emgpu_miss_distance_device's NMAC_ANY); EMGPU_AVOID_NMAC_MIT (the same test with
+ *            dz'[p]); EMGPU_AVOID_LATE (ALERTED and t0 >= P - 1: no point was moved); EMGPU_AVOID_NO_CPA (no second holds a number);
+ *            EMGPU_AVOID_BAD_INDEX (nothing loaded; NaN, NaN, -1, NaN, -1 written; no other flag).
+ *            totals uint64 [12], ADDED to, w = weights[i] (NULL: 1), "induced" = NMAC_MIT && !NMAC_UNMIT: [0] pairs evaluated,
+ *            [1] ALERTED, [2] NMAC_UNMIT, [3] NMAC_MIT, [4] induced, [5] NO_CPA, [6] BAD_INDEX, [7] sum of w over the evaluated pairs,
+ *            [8] sum of w * ALERTED, [9] sum of w * NMAC_UNMIT, [10] sum of w * NMAC_MIT, [11] sum of w * induced.  [10] / [9] is the
+ *            weighted risk ratio.  No load or store leaves the buffers.
+ * The call takes no context and no model: hip_stream, the current device, device pointers, asynchronous.
+ * EMGPU_ERR_ARG, with a message that names the argument, before any device work: everything emgpu_miss_distance_device refuses about the
+ * pairing (points outside 1 .. 65537), with the same messages; one of the six thresholds negative or NaN; delay_s < 0; rate_fps negative,
+ * NaN or infinite; accel_fps2 <= 0 or NaN; dz_max_ft negative or NaN; every output NULL; a pointer that is not aligned to its element
+ * (8 bytes for doubles, indices and totals; 4 for weights, t_cpa and t_alert).  n_pairs == 0 succeeds and launches nothing.
+ * Out of scope: horizontal manoeuvres, a sense reversal or a second alert, an intruder that reacts, the mitigated loss of well clear (its
+ * ratio needs a second predicate per second and is a call of its own), evaluation between the seconds, the ROWS layout, a _host entry
+ * point, a mex command, a limit on the altitude or on the ownship's total vertical rate. */
+#define EMGPU_AVOID_ALERTED 1u
+#define EMGPU_AVOID_CLIMB 2u
+#define EMGPU_AVOID_NMAC_UNMIT 4u
+#define EMGPU_AVOID_NMAC_MIT 8u
+#define EMGPU_AVOID_LATE 16u
+#define EMGPU_AVOID_NO_CPA 32u
+#define EMGPU_AVOID_BAD_INDEX 64u
+typedef struct {
+    int64_t n_pairs;
+    int64_t n_a, n_b;
+    int64_t ld_a, ld_b;    /* 0 = n_a / n_b */
+    int32_t points;        /* P: 1 .. 65537 */
+    int32_t delay_s;       /* >= 0: whole seconds between the alert and the start of the manoeuvre */
+    double alert_tau_s, alert_dmod_ft, alert_hmd_ft, alert_h_ft;
+    double nmac_h_ft, nmac_v_ft;
+    double rate_fps, accel_fps2, dz_max_ft;
+} emgpu_avoid_params;
+int emgpu_avoid_device(void *hip_stream, const emgpu_avoid_params *p, const double *xyz_a, const double *xyz_b, const int64_t *idx_a,
+                       const int64_t *idx_b, const double *pose_b, const uint32_t *weights, double *hmd, double *vmd, double *vmd_mit,
+                       int32_t *t_cpa, int32_t *t_alert, uint8_t *flags, uint64_t *totals /* [12] */);
+
 /* Pinned host memory for the outputs of the *_host entry points (hipHostMalloc, kept in a per-ctx pool: pinning gigabytes costs about as
  * much as copying them).  emgpu_sample_dbn_host recognises pinned output arrays and lets the copy engine write straight into them;
  * pageable arrays go through the library's own pinned staging buffers and a few host threads (below). */
