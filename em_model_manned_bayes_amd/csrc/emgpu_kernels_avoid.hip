@@ -1,41 +1,30 @@
 // emgpu_kernels_avoid.hip -- k_avoid<POSE>: the ownship's vertical avoidance manoeuvre on paired 1 Hz tracks.  Per pair the second of the
-// first alert (k_well_clear's predicate with the alert thresholds), the sense fixed there, and the NMAC and the vertical miss with and
-// without the manoeuvre that follows.  One lane per pair, 256-lane workgroups, sequential in time: k_well_clear's shape
+// first alert (k_well_clear's predicate, EMGPU_TAU_POINT, with the alert thresholds), the sense fixed there, and the NMAC and the vertical
+// miss with and without the manoeuvre that follows.  One lane per pair, 256-lane workgroups, sequential in time: k_well_clear's shape
 // (emgpu_kernels_well_clear.hip).  The definition is in emgpu_avoid.h.
 //
-// Memory: k_miss_distance's six 8-byte loads per (second, lane), and nothing more.  The manoeuvre is a closed form of the seconds since
-// the alert, so no mitigated track is ever written or read: dz'[p] is formed in a register when point p arrives.  The previous point's
-// dx, dy, dz stay in three registers; when point p arrives the alert of point p-1 is evaluated with the forward difference as its velocity
+// Memory: the walk's six 8-byte loads per (second, lane) (emgpu_pair_walk.h), and nothing more.  The manoeuvre is a closed form of the
+// seconds since the alert, so no mitigated track is ever written or read: dz'[p] is formed in a register when point p arrives.  The previous
+// point's dx, dy, dz stay in three registers; when point p arrives the alert of point p-1 is evaluated with the forward difference as its velocity
 // (if no alert has fired), then dz'[p] is formed, then the two NMAC tests and the CPA see the point.  The last point's alert is evaluated
 // behind the loop; it can only be LATE.  Everything that depends on a coordinate is a select: no lane branches on data.  (A wave-uniform
 // skip of the alert's two divisions once every lane of a wave has alerted was tried and left out: the vote keeps the compiler from
 // unrolling the loop over the seconds, which is what keeps twelve loads in flight per lane.)
-// The totals are reduced in the sibling kernels' three stages, twelve counters wide: u32 / u64 registers per lane, a shuffle reduction per
-// wave into one 64-bit LDS slot per (wave, counter), one relaxed agent-scope 64-bit vector atomic without return per (workgroup, touched
-// counter).  The per-pair outputs are plain vector stores, coalesced.  No float atomic, no scratch.
+// The twelve totals are reduced in the three stages of emgpu_pair_walk.h.  The per-pair outputs are plain vector stores, coalesced.
 // Compiler's figures (hipcc -O3, gfx950, -Rpass-analysis=kernel-resource-usage): <no pose> 81 VGPRs, <pose> 91 VGPRs; 106 SGPRs, 384 bytes
 // of LDS, no scratch, 5 waves per SIMD for both.
 #include <hip/hip_runtime.h>
 
 #include "emgpu_avoid.h"
+#include "emgpu_pair_walk.h"
 
 namespace {
-constexpr int kBlock = 256, kWaves = kBlock / 64, kTotals = 12;
-
-__device__ __forceinline__ bool finite(double x) { return __builtin_fabs(x) < __builtin_inf(); }   // a NaN compares false
+constexpr int kTotals = 12;
 
 // the alert of point p of the pair: (x, y, z) = (dx, dy, dz)[p] and its relative velocity (ux, uy, wz); the first one sets t_alert and the sense
 __device__ __forceinline__ void alert_point(const EmgpuAvoidRun &A, int p, double x, double y, double z, double ux, double uy, double wz,
                                             int32_t &t_alert, bool &climb) {
-    const double rr = x * x + y * y, rv = x * ux + y * uy, vv = ux * ux + uy * uy;
-    const bool valid = finite(rr) && finite(rv) && finite(vv) && finite(z);
-    const bool inside = rr <= A.D2, closing = rv < 0.0;
-    const double tau = inside ? 0.0 : (closing ? (A.D2 - rr) / rv : __builtin_inf());
-    double tc = vv > 0.0 ? (-rv) / vv : 0.0;
-    tc = tc > 0.0 ? tc : 0.0;
-    const double px = x + tc * ux, py = y + tc * uy, hp2 = px * px + py * py;
-    const bool by_tau = !inside && closing && tau <= A.tau_s && hp2 <= A.H2;
-    const bool alert = valid && __builtin_fabs(z) <= A.h && (inside || by_tau);
+    EMGPU_TAU_POINT(A, x, y, z, ux, uy, alert)
     const double zp = z + tc * wz;   // the intruder's vertical offset at the horizontal closest approach
     const bool descend = zp > 0.0 || (!(zp < 0.0) && z > 0.0);
     const bool fire = alert && t_alert < 0;
@@ -60,24 +49,13 @@ __global__ __launch_bounds__(kBlock) void k_avoid(const EmgpuAvoidRun A) {
         int32_t t = -1, t_alert = -1;
         uint32_t fl = EMGPU_AVOID_BAD_INDEX;
         if (!bad) {
-            double c = 1.0, s = 0.0, ox = 0.0, oy = 0.0, oz = 0.0;
-            if (POSE) {
-                const double *q = A.pose + (size_t)i;
-                const size_t np = (size_t)A.dim.n_pairs;
-                c = q[0]; s = q[np]; ox = q[2 * np]; oy = q[3 * np]; oz = q[4 * np];
-            }
+            EMGPU_PAIR_POSE(A.pose, A.dim.n_pairs, i)
             const double *a = A.col.xyz_a + (size_t)ia, *b = A.col.xyz_b + (size_t)ib;
             double x0 = 0.0, y0 = 0.0, z0 = 0.0, ux = 0.0, uy = 0.0, wz = 0.0;
             bool climb = false, unmit = false, mit = false;
 #pragma unroll 2
             for (int p = 0; p < A.P; p++, a += step_a, b += step_b) {
-                const double xa = a[0], ya = a[lda], za = a[2 * lda];
-                double xb = b[0], yb = b[ldb], zb = b[2 * ldb];
-                if (POSE) {
-                    const double xr = (c * xb - s * yb) + ox, yr = (s * xb + c * yb) + oy;
-                    xb = xr; yb = yr; zb = zb + oz;
-                }
-                const double dx = xa - xb, dy = ya - yb, dz = zb - za;
+                EMGPU_PAIR_POINT(a, b, lda, ldb)
                 if (p > 0) {   // (uniform) the alert of the second before, now that its forward difference is known
                     ux = dx - x0; uy = dy - y0; wz = dz - z0;
                     alert_point(A, p - 1, x0, y0, z0, ux, uy, wz, t_alert, climb);
@@ -117,32 +95,12 @@ __global__ __launch_bounds__(kBlock) void k_avoid(const EmgpuAvoidRun A) {
         if (A.flags) A.flags[i] = (uint8_t)fl;
     }
     if (!A.totals) return;   // (uniform: every lane of the workgroup returns or none)
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    unsigned long long v[kTotals] = {n_eval, n_alert, n_unmit, n_mit, n_ind, n_none, n_bad, w_eval, w_alert, w_unmit, w_mit, w_ind};
-#pragma unroll
-    for (int k = 0; k < kTotals; k++) {
-        unsigned long long x = v[k];
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) x += __shfl_xor(x, o, 64);
-        if (lane == 0) part[wave][k] = x;
-    }
-    __syncthreads();
-    if (threadIdx.x < kTotals) {
-        unsigned long long x = 0ull;
-#pragma unroll
-        for (int w = 0; w < kWaves; w++) x += part[w][threadIdx.x];
-        if (x) (void)__hip_atomic_fetch_add(A.totals + threadIdx.x, x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
+    EMGPU_PAIR_TOTALS(kTotals, part, A.totals, n_eval, n_alert, n_unmit, n_mit, n_ind, n_none, n_bad, w_eval, w_alert, w_unmit, w_mit, w_ind);
 }
 } // namespace
 
 namespace emgpu {
 hipError_t launch_avoid(const EmgpuAvoidRun &A, hipStream_t s, const char **name) {
-    if (name) *name = A.pose ? "k_avoid[pose]" : "k_avoid";
-    if (A.dim.n_pairs <= 0) return hipSuccess;
-    const dim3 grid = pair_grid(A.dim.n_pairs, kBlock);   // the atomics of stage 3 are paid 2048 times at most
-    if (A.pose) hipLaunchKernelGGL(k_avoid<true>, grid, dim3(kBlock), 0, s, A);
-    else hipLaunchKernelGGL(k_avoid<false>, grid, dim3(kBlock), 0, s, A);
-    return hipGetLastError();
+    return launch_pair_walk(A, s, name, k_avoid<true>, "k_avoid[pose]", k_avoid<false>, "k_avoid");
 }
 } // namespace emgpu

@@ -2,23 +2,21 @@
 // a real-valued time of closest approach and NMAC flags that see what happens between two seconds.  One lane per pair, 256-lane workgroups,
 // sequential in time: k_miss_distance's shape (emgpu_kernels_miss.hip).  The definition is in emgpu_miss_seg.h.
 //
-// Memory: k_miss_distance's six 8-byte loads per (second, lane), and nothing more: the previous second's dx, dy, dz stay in three registers,
-// so a segment costs no load.  The running minimum, its time and dz there, and the NMAC bits stay in registers; the four per-pair outputs
-// are plain vector stores, coalesced.  The minimum and the flags are selects in the source.  The arithmetic behind `near` (two divisions,
-// a root) sits behind a lane branch: measured against the all-select form the two are within each other's spread,
+// Memory: the walk's six 8-byte loads per (second, lane) (emgpu_pair_walk.h), and nothing more: the previous second's dx, dy, dz stay in
+// three registers, so a segment costs no load.  The running minimum, its time and dz there, and the NMAC bits stay in registers; the four
+// per-pair outputs are plain vector stores, coalesced.  The minimum and the flags are selects in the source.  The arithmetic behind `near`
+// (two divisions, a root) sits behind a lane branch: measured against the all-select form the two are within each other's spread,
 // since the compiler guards the expensive operands of a select with an EXEC branch of its own either way.
-// The totals are reduced in k_miss_distance's three stages, widened to ten counters: u32 / u64 registers per lane, a shuffle reduction per
-// wave into one 64-bit LDS slot per (wave, counter), one 64-bit vector atomic without return per (workgroup, touched counter).
+// The totals are k_miss_distance's eight and two more, reduced in the three stages of emgpu_pair_walk.h.
 // Compiler's figures (hipcc -O3, gfx950): <no pose> 79 VGPRs, 6 waves per SIMD; <pose> 89 VGPRs, 5 waves per SIMD; 106 SGPRs, 320 bytes of
 // LDS, no scratch.
 #include <hip/hip_runtime.h>
 
 #include "emgpu_miss_seg.h"
+#include "emgpu_pair_walk.h"
 
 namespace {
-constexpr int kBlock = 256, kWaves = kBlock / 64, kTotals = 10;
-
-__device__ __forceinline__ bool finite(double x) { return __builtin_fabs(x) < __builtin_inf(); }   // a NaN compares false
+constexpr int kTotals = 10;
 
 template <bool POSE>
 __global__ __launch_bounds__(kBlock) void k_miss_segments(const EmgpuMissSegRun A) {
@@ -37,25 +35,14 @@ __global__ __launch_bounds__(kBlock) void k_miss_segments(const EmgpuMissSegRun 
         double best = nan, vmd = nan, t = -1.0;
         uint32_t fl = EMGPU_MISS_BAD_INDEX;
         if (!bad) {
-            double c = 1.0, s = 0.0, ox = 0.0, oy = 0.0, oz = 0.0;
-            if (POSE) {
-                const double *q = A.pose + (size_t)i;
-                const size_t np = (size_t)A.dim.n_pairs;
-                c = q[0]; s = q[np]; ox = q[2 * np]; oy = q[3 * np]; oz = q[4 * np];
-            }
+            EMGPU_PAIR_POSE(A.pose, A.dim.n_pairs, i)
             const double *a = A.col.xyz_a + (size_t)ia, *b = A.col.xyz_b + (size_t)ib;
             bool at_point = false, on_segment = false, inside = false;   // NMAC at some point; on some segment; the CPA is an interior one
             double x0 = 0.0, y0 = 0.0, z0 = 0.0;
 #pragma unroll 2
             for (int p = 0; p < A.P; p++, a += step_a, b += step_b) {
-                const double xa = a[0], ya = a[lda], za = a[2 * lda];
-                double xb = b[0], yb = b[ldb], zb = b[2 * ldb];
-                if (POSE) {
-                    const double xr = (c * xb - s * yb) + ox, yr = (s * xb + c * yb) + oy;
-                    xb = xr; yb = yr; zb = zb + oz;
-                }
-                const double dx = xa - xb, dy = ya - yb;
-                const double d = __builtin_sqrt(dx * dx + dy * dy), dz = zb - za;
+                EMGPU_PAIR_POINT(a, b, lda, ldb)
+                const double d = __builtin_sqrt(dx * dx + dy * dy);
                 if (p > 0) {   // (uniform) the segment from the second before: its interior comes before this point
                     const double ex = dx - x0, ey = dy - y0, ez = dz - z0;
                     const double ee = ex * ex + ey * ey, re = x0 * ex + y0 * ey;
@@ -104,32 +91,12 @@ __global__ __launch_bounds__(kBlock) void k_miss_segments(const EmgpuMissSegRun 
         if (A.flags) A.flags[i] = (uint8_t)fl;
     }
     if (!A.totals) return;   // (uniform: every lane of the workgroup returns or none)
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    unsigned long long v[kTotals] = {n_eval, n_cpa, n_any, n_none, n_bad, w_eval, w_cpa, w_any, n_btw, w_btw};
-#pragma unroll
-    for (int k = 0; k < kTotals; k++) {
-        unsigned long long x = v[k];
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) x += __shfl_xor(x, o, 64);
-        if (lane == 0) part[wave][k] = x;
-    }
-    __syncthreads();
-    if (threadIdx.x < kTotals) {
-        unsigned long long x = 0ull;
-#pragma unroll
-        for (int w = 0; w < kWaves; w++) x += part[w][threadIdx.x];
-        if (x) (void)__hip_atomic_fetch_add(A.totals + threadIdx.x, x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
+    EMGPU_PAIR_TOTALS(kTotals, part, A.totals, n_eval, n_cpa, n_any, n_none, n_bad, w_eval, w_cpa, w_any, n_btw, w_btw);
 }
 } // namespace
 
 namespace emgpu {
 hipError_t launch_miss_segments(const EmgpuMissSegRun &A, hipStream_t s, const char **name) {
-    if (name) *name = A.pose ? "k_miss_segments[pose]" : "k_miss_segments";
-    if (A.dim.n_pairs <= 0) return hipSuccess;
-    const dim3 grid = pair_grid(A.dim.n_pairs, kBlock);   // the atomics of stage 3 are paid 2048 times at most
-    if (A.pose) hipLaunchKernelGGL(k_miss_segments<true>, grid, dim3(kBlock), 0, s, A);
-    else hipLaunchKernelGGL(k_miss_segments<false>, grid, dim3(kBlock), 0, s, A);
-    return hipGetLastError();
+    return launch_pair_walk(A, s, name, k_miss_segments<true>, "k_miss_segments[pose]", k_miss_segments<false>, "k_miss_segments");
 }
 } // namespace emgpu

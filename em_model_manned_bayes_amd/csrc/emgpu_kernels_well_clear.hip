@@ -2,23 +2,20 @@
 // miss, vertical separation) at every whole second.  One lane per pair, 256-lane workgroups, sequential in time: k_miss_distance's shape
 // (emgpu_kernels_miss.hip).  The definition is in emgpu_well_clear.h.
 //
-// Memory: k_miss_distance's six 8-byte loads per (second, lane), and nothing more: the previous second's dx, dy, dz stay in three registers
-// as in k_miss_segments, and point p-1 is evaluated when point p arrives, with the forward difference as its velocity.  The last point is
-// evaluated behind the loop with the last velocity; both go through wc_point, the per-point text once.  The predicate is selects; its two
-// divisions are the only expensive operands, and no root enters.  The per-pair outputs are plain vector stores, coalesced.
-// The totals are reduced in the sibling kernels' three stages, ten counters wide: u32 / u64 registers per lane, a shuffle reduction per
-// wave into one 64-bit LDS slot per (wave, counter), one relaxed agent-scope 64-bit vector atomic without return per (workgroup, touched
-// counter).  No float atomic, no scratch.
+// Memory: the walk's six 8-byte loads per (second, lane) (emgpu_pair_walk.h), and nothing more: the previous second's dx, dy, dz stay in
+// three registers as in k_miss_segments, and point p-1 is evaluated when point p arrives, with the forward difference as its velocity.  The
+// last point is evaluated behind the loop with the last velocity; both go through wc_point, the per-point text once.  The predicate (EMGPU_TAU_POINT,
+// shared with k_avoid) is selects; its two divisions are the only expensive operands, and no root enters.  The per-pair outputs are plain
+// vector stores, coalesced.  The ten totals are reduced in the three stages of emgpu_pair_walk.h.
 // Compiler's figures (hipcc -O3, gfx950, -Rpass-analysis=kernel-resource-usage): <no pose> 73 VGPRs, 6 waves per SIMD; <pose> 83 VGPRs,
 // 5 waves per SIMD; 106 SGPRs, 320 bytes of LDS, no scratch, for both.
 #include <hip/hip_runtime.h>
 
 #include "emgpu_well_clear.h"
+#include "emgpu_pair_walk.h"
 
 namespace {
-constexpr int kBlock = 256, kWaves = kBlock / 64, kTotals = 10;
-
-__device__ __forceinline__ bool finite(double x) { return __builtin_fabs(x) < __builtin_inf(); }   // a NaN compares false
+constexpr int kTotals = 10;
 
 // what a lane keeps of its pair while it walks the seconds
 struct WcState {
@@ -29,15 +26,7 @@ struct WcState {
 
 // point p of the pair: (x, y, z) = (dx, dy, dz)[p] and its relative velocity (ux, uy), into st
 __device__ __forceinline__ void wc_point(const EmgpuWellClearRun &A, int p, double x, double y, double z, double ux, double uy, WcState &st) {
-    const double rr = x * x + y * y, rv = x * ux + y * uy, vv = ux * ux + uy * uy;
-    const bool valid = finite(rr) && finite(rv) && finite(vv) && finite(z);
-    const bool inside = rr <= A.D2, closing = rv < 0.0;
-    const double tau = inside ? 0.0 : (closing ? (A.D2 - rr) / rv : __builtin_inf());
-    double tc = vv > 0.0 ? (-rv) / vv : 0.0;
-    tc = tc > 0.0 ? tc : 0.0;
-    const double px = x + tc * ux, py = y + tc * uy, hp2 = px * px + py * py;
-    const bool by_tau = !inside && closing && tau <= A.tau_s && hp2 <= A.H2;
-    const bool lost = valid && __builtin_fabs(z) <= A.h && (inside || by_tau);
+    EMGPU_TAU_POINT(A, x, y, z, ux, uy, lost)
     const bool take = valid && (!st.have || tau < st.tau_min);
     st.tau_min = take ? tau : st.tau_min;
     st.have = st.have || valid;
@@ -62,23 +51,12 @@ __global__ __launch_bounds__(kBlock) void k_well_clear(const EmgpuWellClearRun A
         WcState st{__builtin_nan(""), -1, 0, false, false, false};
         uint32_t fl = EMGPU_WC_BAD_INDEX;
         if (!bad) {
-            double c = 1.0, s = 0.0, ox = 0.0, oy = 0.0, oz = 0.0;
-            if (POSE) {
-                const double *q = A.pose + (size_t)i;
-                const size_t np = (size_t)A.dim.n_pairs;
-                c = q[0]; s = q[np]; ox = q[2 * np]; oy = q[3 * np]; oz = q[4 * np];
-            }
+            EMGPU_PAIR_POSE(A.pose, A.dim.n_pairs, i)
             const double *a = A.col.xyz_a + (size_t)ia, *b = A.col.xyz_b + (size_t)ib;
             double x0 = 0.0, y0 = 0.0, z0 = 0.0, ux = 0.0, uy = 0.0;
 #pragma unroll 2
             for (int p = 0; p < A.P; p++, a += step_a, b += step_b) {
-                const double xa = a[0], ya = a[lda], za = a[2 * lda];
-                double xb = b[0], yb = b[ldb], zb = b[2 * ldb];
-                if (POSE) {
-                    const double xr = (c * xb - s * yb) + ox, yr = (s * xb + c * yb) + oy;
-                    xb = xr; yb = yr; zb = zb + oz;
-                }
-                const double dx = xa - xb, dy = ya - yb, dz = zb - za;
+                EMGPU_PAIR_POINT(a, b, lda, ldb)
                 if (p > 0) {   // (uniform) the second before, now that its forward difference is known
                     ux = dx - x0; uy = dy - y0;
                     wc_point(A, p - 1, x0, y0, z0, ux, uy, st);
@@ -102,32 +80,12 @@ __global__ __launch_bounds__(kBlock) void k_well_clear(const EmgpuWellClearRun A
         if (A.flags) A.flags[i] = (uint8_t)fl;
     }
     if (!A.totals) return;   // (uniform: every lane of the workgroup returns or none)
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    unsigned long long v[kTotals] = {n_eval, n_lost, n_start, n_none, n_bad, w_eval, w_lost, w_start, n_nmac, w_nmac};
-#pragma unroll
-    for (int k = 0; k < kTotals; k++) {
-        unsigned long long x = v[k];
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) x += __shfl_xor(x, o, 64);
-        if (lane == 0) part[wave][k] = x;
-    }
-    __syncthreads();
-    if (threadIdx.x < kTotals) {
-        unsigned long long x = 0ull;
-#pragma unroll
-        for (int w = 0; w < kWaves; w++) x += part[w][threadIdx.x];
-        if (x) (void)__hip_atomic_fetch_add(A.totals + threadIdx.x, x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
+    EMGPU_PAIR_TOTALS(kTotals, part, A.totals, n_eval, n_lost, n_start, n_none, n_bad, w_eval, w_lost, w_start, n_nmac, w_nmac);
 }
 } // namespace
 
 namespace emgpu {
 hipError_t launch_well_clear(const EmgpuWellClearRun &A, hipStream_t s, const char **name) {
-    if (name) *name = A.pose ? "k_well_clear[pose]" : "k_well_clear";
-    if (A.dim.n_pairs <= 0) return hipSuccess;
-    const dim3 grid = pair_grid(A.dim.n_pairs, kBlock);   // the atomics of stage 3 are paid 2048 times at most
-    if (A.pose) hipLaunchKernelGGL(k_well_clear<true>, grid, dim3(kBlock), 0, s, A);
-    else hipLaunchKernelGGL(k_well_clear<false>, grid, dim3(kBlock), 0, s, A);
-    return hipGetLastError();
+    return launch_pair_walk(A, s, name, k_well_clear<true>, "k_well_clear[pose]", k_well_clear<false>, "k_well_clear");
 }
 } // namespace emgpu

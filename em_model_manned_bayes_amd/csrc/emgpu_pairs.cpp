@@ -4,6 +4,7 @@
 // emgpu_well_clear.h) and emgpu_avoid_device (k_avoid, emgpu_avoid.h).  They take no context: they need no model table, no scratch and
 // no status word, so they run on the stream they are given and on the calling thread's current device.
 #include <cmath>
+#include <initializer_list>
 
 #include "emgpu_internal.hpp"
 #include "emgpu_avoid.h"
@@ -41,6 +42,31 @@ void fill_pairing(const Params *p, const double *xyz_a, const double *xyz_b, con
     dim = {p->n_pairs, p->n_a, p->n_b, p->ld_a ? p->ld_a : p->n_a, p->ld_b ? p->ld_b : p->n_b};
     col = {xyz_a, xyz_b, idx_a, idx_b};
 }
+// The refusals of a threshold or an address.  They throw: EMGPU_CATCH records the message and returns the code, as for a failed launch.
+void not_negative(double v, const std::string &name) {
+    if (!(v >= 0.0)) throw Error(EMGPU_ERR_ARG, name + " is negative or NaN");
+}
+void finite_positive(double v, const char *name) {
+    if (!(std::isfinite(v) && v > 0.0)) throw Error(EMGPU_ERR_ARG, std::string(name) + " is not a finite positive number");
+}
+template <class Params>
+void nmac_thresholds(const Params *p) {
+    not_negative(p->nmac_h_ft, "nmac_h_ft");
+    not_negative(p->nmac_v_ft, "nmac_v_ft");
+}
+// the four thresholds of the well-clear volume, named <prefix>tau_s ...
+void volume_thresholds(const std::string &prefix, double tau_s, double dmod_ft, double hmd_ft, double h_ft) {
+    not_negative(tau_s, prefix + "tau_s");
+    not_negative(dmod_ft, prefix + "dmod_ft");
+    not_negative(hmd_ft, prefix + "hmd_ft");
+    not_negative(h_ft, prefix + "h_ft");
+}
+// every address of ptrs (null: none given) on a multiple of `bytes`, a power of two; `names` lists them for the message
+void aligned(std::initializer_list<const void *> ptrs, unsigned bytes, const char *names) {
+    uintptr_t bits = 0;
+    for (const void *q : ptrs) bits |= (uintptr_t)q;
+    if (bits & (bytes - 1u)) throw Error(EMGPU_ERR_ARG, std::string(names) + " must be " + std::to_string(bytes) + "-byte aligned");
+}
 } // namespace
 
 extern "C" {
@@ -52,12 +78,9 @@ int emgpu_miss_distance_device(void *hip_stream, const emgpu_miss_params *p, con
     if (const int rc = check_pairing(p, xyz_a, xyz_b, idx_a, idx_b, hmd || vmd || t_cpa || flags || totals,
                                      "null hmd, vmd, t_cpa, flags and totals: nothing to write", 1))
         return rc;
-    if (!(p->nmac_h_ft >= 0.0)) return fail(EMGPU_ERR_ARG, "nmac_h_ft is negative or NaN");
-    if (!(p->nmac_v_ft >= 0.0)) return fail(EMGPU_ERR_ARG, "nmac_v_ft is negative or NaN");
-    if (((uintptr_t)xyz_a | (uintptr_t)xyz_b | (uintptr_t)idx_a | (uintptr_t)idx_b | (uintptr_t)pose_b | (uintptr_t)hmd | (uintptr_t)vmd |
-         (uintptr_t)totals) & 7u)
-        return fail(EMGPU_ERR_ARG, "xyz_a, xyz_b, idx_a, idx_b, pose_b, hmd, vmd and totals must be 8-byte aligned");
-    if (((uintptr_t)weights | (uintptr_t)t_cpa) & 3u) return fail(EMGPU_ERR_ARG, "weights and t_cpa must be 4-byte aligned");
+    nmac_thresholds(p);
+    aligned({xyz_a, xyz_b, idx_a, idx_b, pose_b, hmd, vmd, totals}, 8, "xyz_a, xyz_b, idx_a, idx_b, pose_b, hmd, vmd and totals");
+    aligned({weights, t_cpa}, 4, "weights and t_cpa");
     if (p->n_pairs == 0) return EMGPU_OK;
     EmgpuMissRun A{};
     fill_pairing(p, xyz_a, xyz_b, idx_a, idx_b, A.dim, A.col);
@@ -75,12 +98,9 @@ int emgpu_miss_segments_device(void *hip_stream, const emgpu_miss_params *p, con
     if (const int rc = check_pairing(p, xyz_a, xyz_b, idx_a, idx_b, hmd || vmd || t_cpa_s || flags || totals,
                                      "null hmd, vmd, t_cpa_s, flags and totals: nothing to write", 1))
         return rc;
-    if (!(p->nmac_h_ft >= 0.0)) return fail(EMGPU_ERR_ARG, "nmac_h_ft is negative or NaN");
-    if (!(p->nmac_v_ft >= 0.0)) return fail(EMGPU_ERR_ARG, "nmac_v_ft is negative or NaN");
-    if (((uintptr_t)xyz_a | (uintptr_t)xyz_b | (uintptr_t)idx_a | (uintptr_t)idx_b | (uintptr_t)pose_b | (uintptr_t)hmd | (uintptr_t)vmd |
-         (uintptr_t)t_cpa_s | (uintptr_t)totals) & 7u)
-        return fail(EMGPU_ERR_ARG, "xyz_a, xyz_b, idx_a, idx_b, pose_b, hmd, vmd, t_cpa_s and totals must be 8-byte aligned");
-    if ((uintptr_t)weights & 3u) return fail(EMGPU_ERR_ARG, "weights must be 4-byte aligned");
+    nmac_thresholds(p);
+    aligned({xyz_a, xyz_b, idx_a, idx_b, pose_b, hmd, vmd, t_cpa_s, totals}, 8, "xyz_a, xyz_b, idx_a, idx_b, pose_b, hmd, vmd, t_cpa_s and totals");
+    aligned({weights}, 4, "weights");
     if (p->n_pairs == 0) return EMGPU_OK;
     EmgpuMissSegRun A{};
     fill_pairing(p, xyz_a, xyz_b, idx_a, idx_b, A.dim, A.col);
@@ -98,14 +118,13 @@ int emgpu_encounter_pose_device(void *hip_stream, const emgpu_encounter_params *
     if (const int rc = check_pairing(p, xyz_a, xyz_b, idx_a, idx_b, pose || rate || flags || weights_out,
                                      "null pose, rate, flags and weights_out: nothing to write", 2))
         return rc;
-    if (!(std::isfinite(p->radius_ft) && p->radius_ft > 0.0)) return fail(EMGPU_ERR_ARG, "radius_ft is not a finite positive number");
-    if (!(std::isfinite(p->half_height_ft) && p->half_height_ft > 0.0)) return fail(EMGPU_ERR_ARG, "half_height_ft is not a finite positive number");
-    if (!(std::isfinite(p->rate_scale) && p->rate_scale > 0.0)) return fail(EMGPU_ERR_ARG, "rate_scale is not a finite positive number");
+    finite_positive(p->radius_ft, "radius_ft");
+    finite_positive(p->half_height_ft, "half_height_ft");
+    finite_positive(p->rate_scale, "rate_scale");
     if (p->max_attempts < 1 || p->max_attempts > 16) return fail(EMGPU_ERR_ARG, "max_attempts outside 1..16");
     if (weights_in && !weights_out) return fail(EMGPU_ERR_ARG, "weights_in without weights_out");
-    if (((uintptr_t)xyz_a | (uintptr_t)xyz_b | (uintptr_t)idx_a | (uintptr_t)idx_b | (uintptr_t)pose | (uintptr_t)rate) & 7u)
-        return fail(EMGPU_ERR_ARG, "xyz_a, xyz_b, idx_a, idx_b, pose and rate must be 8-byte aligned");
-    if (((uintptr_t)weights_in | (uintptr_t)weights_out) & 3u) return fail(EMGPU_ERR_ARG, "weights_in and weights_out must be 4-byte aligned");
+    aligned({xyz_a, xyz_b, idx_a, idx_b, pose, rate}, 8, "xyz_a, xyz_b, idx_a, idx_b, pose and rate");
+    aligned({weights_in, weights_out}, 4, "weights_in and weights_out");
     if (p->n_pairs == 0) return EMGPU_OK;
     EmgpuEncounterRun A{};
     fill_pairing(p, xyz_a, xyz_b, idx_a, idx_b, A.dim, A.col);
@@ -126,18 +145,16 @@ int emgpu_cpa_pose_device(void *hip_stream, const emgpu_cpa_pose_params *p, cons
     if (const int rc = check_pairing(p, xyz_a, xyz_b, idx_a, idx_b, pose || rate || t_cpa || flags || weights_out,
                                      "null pose, rate, t_cpa, flags and weights_out: nothing to write", 2))
         return rc;
-    if (!(std::isfinite(p->hmd_max_ft) && p->hmd_max_ft > 0.0)) return fail(EMGPU_ERR_ARG, "hmd_max_ft is not a finite positive number");
-    if (!(std::isfinite(p->vmd_max_ft) && p->vmd_max_ft > 0.0)) return fail(EMGPU_ERR_ARG, "vmd_max_ft is not a finite positive number");
-    if (!(std::isfinite(p->rate_scale) && p->rate_scale > 0.0)) return fail(EMGPU_ERR_ARG, "rate_scale is not a finite positive number");
+    finite_positive(p->hmd_max_ft, "hmd_max_ft");
+    finite_positive(p->vmd_max_ft, "vmd_max_ft");
+    finite_positive(p->rate_scale, "rate_scale");
     if (p->max_attempts < 1 || p->max_attempts > 16) return fail(EMGPU_ERR_ARG, "max_attempts outside 1..16");
     if (p->t_lo < 0) return fail(EMGPU_ERR_ARG, "t_lo is negative");
     if (p->t_hi < p->t_lo) return fail(EMGPU_ERR_ARG, "t_hi < t_lo");
     if (p->t_hi > p->points - 2) return fail(EMGPU_ERR_ARG, "t_hi > points - 2: point t_hi + 1 is read");
     if (weights_in && !weights_out) return fail(EMGPU_ERR_ARG, "weights_in without weights_out");
-    if (((uintptr_t)xyz_a | (uintptr_t)xyz_b | (uintptr_t)idx_a | (uintptr_t)idx_b | (uintptr_t)pose | (uintptr_t)rate) & 7u)
-        return fail(EMGPU_ERR_ARG, "xyz_a, xyz_b, idx_a, idx_b, pose and rate must be 8-byte aligned");
-    if (((uintptr_t)weights_in | (uintptr_t)weights_out | (uintptr_t)t_cpa) & 3u)
-        return fail(EMGPU_ERR_ARG, "weights_in, weights_out and t_cpa must be 4-byte aligned");
+    aligned({xyz_a, xyz_b, idx_a, idx_b, pose, rate}, 8, "xyz_a, xyz_b, idx_a, idx_b, pose and rate");
+    aligned({weights_in, weights_out, t_cpa}, 4, "weights_in, weights_out and t_cpa");
     if (p->n_pairs == 0) return EMGPU_OK;
     EmgpuCpaRun A{};
     fill_pairing(p, xyz_a, xyz_b, idx_a, idx_b, A.dim, A.col);
@@ -158,14 +175,9 @@ int emgpu_well_clear_device(void *hip_stream, const emgpu_well_clear_params *p, 
     if (const int rc = check_pairing(p, xyz_a, xyz_b, idx_a, idx_b, t_first || n_lost || tau_min || flags || totals,
                                      "null t_first, n_lost, tau_min, flags and totals: nothing to write", 1))
         return rc;
-    if (!(p->tau_s >= 0.0)) return fail(EMGPU_ERR_ARG, "tau_s is negative or NaN");
-    if (!(p->dmod_ft >= 0.0)) return fail(EMGPU_ERR_ARG, "dmod_ft is negative or NaN");
-    if (!(p->hmd_ft >= 0.0)) return fail(EMGPU_ERR_ARG, "hmd_ft is negative or NaN");
-    if (!(p->h_ft >= 0.0)) return fail(EMGPU_ERR_ARG, "h_ft is negative or NaN");
-    if (((uintptr_t)xyz_a | (uintptr_t)xyz_b | (uintptr_t)idx_a | (uintptr_t)idx_b | (uintptr_t)pose_b | (uintptr_t)tau_min | (uintptr_t)totals) & 7u)
-        return fail(EMGPU_ERR_ARG, "xyz_a, xyz_b, idx_a, idx_b, pose_b, tau_min and totals must be 8-byte aligned");
-    if (((uintptr_t)weights | (uintptr_t)t_first | (uintptr_t)n_lost) & 3u)
-        return fail(EMGPU_ERR_ARG, "weights, t_first and n_lost must be 4-byte aligned");
+    volume_thresholds("", p->tau_s, p->dmod_ft, p->hmd_ft, p->h_ft);
+    aligned({xyz_a, xyz_b, idx_a, idx_b, pose_b, tau_min, totals}, 8, "xyz_a, xyz_b, idx_a, idx_b, pose_b, tau_min and totals");
+    aligned({weights, t_first, n_lost}, 4, "weights, t_first and n_lost");
     if (p->n_pairs == 0) return EMGPU_OK;
     EmgpuWellClearRun A{};
     fill_pairing(p, xyz_a, xyz_b, idx_a, idx_b, A.dim, A.col);
@@ -184,21 +196,14 @@ int emgpu_avoid_device(void *hip_stream, const emgpu_avoid_params *p, const doub
     if (const int rc = check_pairing(p, xyz_a, xyz_b, idx_a, idx_b, hmd || vmd || vmd_mit || t_cpa || t_alert || flags || totals,
                                      "null hmd, vmd, vmd_mit, t_cpa, t_alert, flags and totals: nothing to write", 1))
         return rc;
-    if (!(p->alert_tau_s >= 0.0)) return fail(EMGPU_ERR_ARG, "alert_tau_s is negative or NaN");
-    if (!(p->alert_dmod_ft >= 0.0)) return fail(EMGPU_ERR_ARG, "alert_dmod_ft is negative or NaN");
-    if (!(p->alert_hmd_ft >= 0.0)) return fail(EMGPU_ERR_ARG, "alert_hmd_ft is negative or NaN");
-    if (!(p->alert_h_ft >= 0.0)) return fail(EMGPU_ERR_ARG, "alert_h_ft is negative or NaN");
-    if (!(p->nmac_h_ft >= 0.0)) return fail(EMGPU_ERR_ARG, "nmac_h_ft is negative or NaN");
-    if (!(p->nmac_v_ft >= 0.0)) return fail(EMGPU_ERR_ARG, "nmac_v_ft is negative or NaN");
+    volume_thresholds("alert_", p->alert_tau_s, p->alert_dmod_ft, p->alert_hmd_ft, p->alert_h_ft);
+    nmac_thresholds(p);
     if (p->delay_s < 0) return fail(EMGPU_ERR_ARG, "delay_s is negative");
     if (!(std::isfinite(p->rate_fps) && p->rate_fps >= 0.0)) return fail(EMGPU_ERR_ARG, "rate_fps is negative, NaN or infinite");
     if (!(p->accel_fps2 > 0.0)) return fail(EMGPU_ERR_ARG, "accel_fps2 is not positive or NaN");
-    if (!(p->dz_max_ft >= 0.0)) return fail(EMGPU_ERR_ARG, "dz_max_ft is negative or NaN");
-    if (((uintptr_t)xyz_a | (uintptr_t)xyz_b | (uintptr_t)idx_a | (uintptr_t)idx_b | (uintptr_t)pose_b | (uintptr_t)hmd | (uintptr_t)vmd |
-         (uintptr_t)vmd_mit | (uintptr_t)totals) & 7u)
-        return fail(EMGPU_ERR_ARG, "xyz_a, xyz_b, idx_a, idx_b, pose_b, hmd, vmd, vmd_mit and totals must be 8-byte aligned");
-    if (((uintptr_t)weights | (uintptr_t)t_cpa | (uintptr_t)t_alert) & 3u)
-        return fail(EMGPU_ERR_ARG, "weights, t_cpa and t_alert must be 4-byte aligned");
+    not_negative(p->dz_max_ft, "dz_max_ft");
+    aligned({xyz_a, xyz_b, idx_a, idx_b, pose_b, hmd, vmd, vmd_mit, totals}, 8, "xyz_a, xyz_b, idx_a, idx_b, pose_b, hmd, vmd, vmd_mit and totals");
+    aligned({weights, t_cpa, t_alert}, 4, "weights, t_cpa and t_alert");
     if (p->n_pairs == 0) return EMGPU_OK;
     EmgpuAvoidRun A{};
     fill_pairing(p, xyz_a, xyz_b, idx_a, idx_b, A.dim, A.col);

@@ -9,11 +9,16 @@ from .. import _lib as L
 from .base import _device_call, _stream_handle, _weights_array
 
 
+def _pairing(p, n_pairs, n_a, n_b, points, ld_a, ld_b):
+    """p, one of L's *Params, with its pairing filled in"""
+    p.n_pairs, p.n_a, p.n_b, p.ld_a, p.ld_b, p.points = int(n_pairs), int(n_a), int(n_b), int(ld_a), int(ld_b), int(points)
+    return p
+
+
 def miss_params(n_pairs, n_a, n_b, points, nmac_h_ft=500.0, nmac_v_ft=100.0, ld_a=0, ld_b=0):
     """emgpu_miss_params: n_pairs pairs of a column of set A (n_a columns, pitch ld_a, 0 = n_a) and a column of set B, `points` seconds each;
     the NMAC thresholds of track.m:175 in feet."""
-    p = L.MissParams()
-    p.n_pairs, p.n_a, p.n_b, p.ld_a, p.ld_b, p.points = int(n_pairs), int(n_a), int(n_b), int(ld_a), int(ld_b), int(points)
+    p = _pairing(L.MissParams(), n_pairs, n_a, n_b, points, ld_a, ld_b)
     p.nmac_h_ft, p.nmac_v_ft = float(nmac_h_ft), float(nmac_v_ft)
     return p
 
@@ -78,9 +83,10 @@ def _pair_columns(xyz_a, xyz_b, idx_a, idx_b, layout):
 @contextlib.contextmanager
 def _paired(xyz_a, xyz_b, columns, w, pose_b, layout, ctx, stream):
     """The pairing step of miss_distance, encounter_pose and encounter_miss: what a launch on paired tracks needs, as a namespace of
-    dev, stream (resolved; None: torch's current stream), the PLANAR device tensors a / b, n_a, n_b, n_pairs, and d_ia, d_ib (int64), d_w
-    (uint32 held as int32) and d_pose on the device or None.  columns = _pair_columns(...), w = _weights_array(...) or None: the caller has
-    them before torch.cuda is touched.  The body runs on dev with the uploads complete for its stream; leaving it waits for that stream."""
+    dev, stream (resolved; None: torch's current stream), the PLANAR device tensors a / b, n_a, n_b, n_pairs, sizes (what every *_params
+    opens with: n_pairs, n_a, n_b, points), and d_ia, d_ib (int64), d_w (uint32 held as int32) and d_pose on the device or None.
+    columns = _pair_columns(...), w = _weights_array(...) or None: the caller has them before torch.cuda is touched.  The body runs on dev
+    with the uploads complete for its stream; leaving it waits for that stream."""
     import torch
     n_a, n_b, idx, n_pairs = columns
     dev = xyz_a.device if isinstance(xyz_a, torch.Tensor) and xyz_a.is_cuda else torch.device("cuda", torch.cuda.current_device())
@@ -93,8 +99,8 @@ def _paired(xyz_a, xyz_b, columns, w, pose_b, layout, ctx, stream):
         if a.shape[0] != b.shape[0]:
             raise ValueError("both sets of tracks must hold the same number of points")
         up = lambda x, dt: None if x is None else (x if isinstance(x, torch.Tensor) else torch.from_numpy(x)).to(device=dev, dtype=dt).contiguous()  # noqa: E731
-        pr = types.SimpleNamespace(dev=dev, stream=stream, a=a, b=b, n_a=n_a, n_b=n_b, n_pairs=n_pairs, d_ia=up(idx[0], torch.int64),
-                                   d_ib=up(idx[1], torch.int64), d_pose=up(pose_b, torch.float64),
+        pr = types.SimpleNamespace(dev=dev, stream=stream, a=a, b=b, n_a=n_a, n_b=n_b, n_pairs=n_pairs, sizes=(n_pairs, n_a, n_b, a.shape[0]),
+                                   d_ia=up(idx[0], torch.int64), d_ib=up(idx[1], torch.int64), d_pose=up(pose_b, torch.float64),
                                    d_w=None if w is None else torch.from_numpy(w.view(np.int32)).to(dev))
         # torch.cuda.synchronize brackets the launches only when they do not run on torch's stream, where the uploads ran
         pr.guard = (lambda: None) if stream is None else (lambda: torch.cuda.synchronize(dev))
@@ -107,68 +113,70 @@ def _ptr(t):
     return 0 if t is None else t.data_ptr()
 
 
+def _launch(pr, device_call, params, inputs, outputs, n_totals=0):
+    """One kernel on the pairing pr: device_call(params, the pairing's four addresses, *inputs, *outputs[, totals]) on pr.stream, not waited
+    for.  inputs: device tensors or None.  outputs: {name: dtype, [n_pairs]; or (dtype, 5), [5, n_pairs]; or None, not wanted} in the
+    entry point's order, allocated here; n_totals: the width of the int64 totals behind them, zeroed, or 0 for none.  Returns the outputs
+    as a tuple of device tensors."""
+    import torch
+    def empty(dtype, *rows):
+        return torch.empty((*rows, pr.n_pairs), dtype=getattr(torch, dtype), device=pr.dev)
+    out = [None if d is None else empty(*d) if isinstance(d, tuple) else empty(d) for d in outputs.values()]
+    if n_totals:
+        out.append(torch.zeros(n_totals, dtype=torch.int64, device=pr.dev))
+        pr.guard()      # totals was zeroed on torch's stream
+    device_call(params, *(_ptr(t) for t in (pr.a, pr.b, pr.d_ia, pr.d_ib, *inputs, *out)), stream=pr.stream)
+    return tuple(out)
+
+
+def _host(*tensors):
+    """device tensors as numpy arrays; None stays None"""
+    return [None if t is None else t.cpu().numpy() for t in tensors]
+
+
 def _miss_tensors(pr, d_pose, d_w, nmac_h_ft, nmac_v_ft):
     """k_miss_distance on the pairing pr with the device tensors d_pose and d_w (or None): the device tensors (hmd, vmd, t_cpa, flags,
     totals), launched on pr.stream and not waited for"""
-    import torch
-    n, dev = pr.n_pairs, pr.dev
-    hmd, vmd = torch.empty(n, dtype=torch.float64, device=dev), torch.empty(n, dtype=torch.float64, device=dev)
-    t_cpa, flags = torch.empty(n, dtype=torch.int32, device=dev), torch.empty(n, dtype=torch.uint8, device=dev)
-    totals = torch.zeros(8, dtype=torch.int64, device=dev)
-    pr.guard()      # totals was zeroed on torch's stream
-    miss_distance_device(miss_params(n, pr.n_a, pr.n_b, pr.a.shape[0], nmac_h_ft, nmac_v_ft), _ptr(pr.a), _ptr(pr.b), _ptr(pr.d_ia), _ptr(pr.d_ib),
-                         _ptr(d_pose), _ptr(d_w), _ptr(hmd), _ptr(vmd), _ptr(t_cpa), _ptr(flags), _ptr(totals), stream=pr.stream)
-    return hmd, vmd, t_cpa, flags, totals
+    return _launch(pr, miss_distance_device, miss_params(*pr.sizes, nmac_h_ft, nmac_v_ft), (d_pose, d_w),
+                   {"hmd": "float64", "vmd": "float64", "t_cpa": "int32", "flags": "uint8"}, 8)
 
 
 def _miss_dict(hmd, vmd, t_cpa, flags, totals):
     """miss_distance's dict from _miss_tensors' device tensors"""
-    fl = flags.cpu().numpy()
-    return {"hmd_ft": hmd.cpu().numpy(), "vmd_ft": vmd.cpu().numpy(), "t_cpa": t_cpa.cpu().numpy(), "flags": fl,
-            "nmac": (fl & L.MISS_NMAC_CPA) != 0, "totals": totals.cpu().numpy().view(np.uint64)}
+    hmd, vmd, t_cpa, fl, tot = _host(hmd, vmd, t_cpa, flags, totals)
+    return {"hmd_ft": hmd, "vmd_ft": vmd, "t_cpa": t_cpa, "flags": fl, "nmac": (fl & L.MISS_NMAC_CPA) != 0, "totals": tot.view(np.uint64)}
 
 
 def _miss_segments_tensors(pr, d_pose, d_w, nmac_h_ft, nmac_v_ft):
     """k_miss_segments on the pairing pr, as _miss_tensors: the device tensors (hmd, vmd, t_cpa_s, flags, totals [10]), launched on pr.stream
     and not waited for"""
-    import torch
-    n, dev = pr.n_pairs, pr.dev
-    hmd, vmd, t_cpa_s = (torch.empty(n, dtype=torch.float64, device=dev) for _ in range(3))
-    flags = torch.empty(n, dtype=torch.uint8, device=dev)
-    totals = torch.zeros(10, dtype=torch.int64, device=dev)
-    pr.guard()      # totals was zeroed on torch's stream
-    miss_segments_device(miss_params(n, pr.n_a, pr.n_b, pr.a.shape[0], nmac_h_ft, nmac_v_ft), _ptr(pr.a), _ptr(pr.b), _ptr(pr.d_ia), _ptr(pr.d_ib),
-                         _ptr(d_pose), _ptr(d_w), _ptr(hmd), _ptr(vmd), _ptr(t_cpa_s), _ptr(flags), _ptr(totals), stream=pr.stream)
-    return hmd, vmd, t_cpa_s, flags, totals
+    return _launch(pr, miss_segments_device, miss_params(*pr.sizes, nmac_h_ft, nmac_v_ft), (d_pose, d_w),
+                   {"hmd": "float64", "vmd": "float64", "t_cpa_s": "float64", "flags": "uint8"}, 10)
 
 
 def _miss_segments_dict(hmd, vmd, t_cpa_s, flags, totals):
     """miss_segments' dict from _miss_segments_tensors' device tensors"""
-    fl = flags.cpu().numpy()
-    return {"hmd_ft": hmd.cpu().numpy(), "vmd_ft": vmd.cpu().numpy(), "t_cpa_s": t_cpa_s.cpu().numpy(), "flags": fl,
-            "nmac": (fl & L.MISS_NMAC_CPA) != 0, "nmac_any": (fl & L.MISS_NMAC_ANY) != 0, "between": (fl & L.MISS_NMAC_BETWEEN) != 0,
-            "totals": totals.cpu().numpy().view(np.uint64)}
+    hmd, vmd, t_cpa_s, fl, tot = _host(hmd, vmd, t_cpa_s, flags, totals)
+    return {"hmd_ft": hmd, "vmd_ft": vmd, "t_cpa_s": t_cpa_s, "flags": fl, "nmac": (fl & L.MISS_NMAC_CPA) != 0,
+            "nmac_any": (fl & L.MISS_NMAC_ANY) != 0, "between": (fl & L.MISS_NMAC_BETWEEN) != 0, "totals": tot.view(np.uint64)}
+
+
+def _placement(want_weights, **between):
+    """the outputs of a placement for _launch: pose and rate, what lies `between` them and the flags, and the weights where wanted"""
+    return {"pose": ("float64", 5), "rate": "float64", **between, "flags": "uint8", "weights_out": "int32" if want_weights else None}
 
 
 def _encounter_pose_tensors(pr, want_weights, radius_ft, half_height_ft, seed, rate_scale, first_index, max_attempts):
     """k_encounter_pose on the pairing pr: the device tensors (pose [5, n_pairs], rate, flags, weights or None), launched on pr.stream and
     not waited for"""
-    import torch
-    n, dev = pr.n_pairs, pr.dev
-    pose = torch.empty((5, n), dtype=torch.float64, device=dev)
-    rate = torch.empty(n, dtype=torch.float64, device=dev)
-    flags = torch.empty(n, dtype=torch.uint8, device=dev)
-    w_out = torch.empty(n, dtype=torch.int32, device=dev) if want_weights else None
-    p = encounter_params(n, pr.n_a, pr.n_b, pr.a.shape[0], radius_ft, half_height_ft, seed, first_index, max_attempts,
-                         1.0 if rate_scale is None else rate_scale)
-    encounter_pose_device(p, _ptr(pr.a), _ptr(pr.b), _ptr(pr.d_ia), _ptr(pr.d_ib), _ptr(pr.d_w), _ptr(pose), _ptr(rate), _ptr(flags), _ptr(w_out),
-                          stream=pr.stream)
-    return pose, rate, flags, w_out
+    p = encounter_params(*pr.sizes, radius_ft, half_height_ft, seed, first_index, max_attempts, 1.0 if rate_scale is None else rate_scale)
+    return _launch(pr, encounter_pose_device, p, (pr.d_w,), _placement(want_weights))
 
 
 def _encounter_dict(rate, flags, w_out, flags_key="flags"):
     """the rate, flags and weights of encounter_pose's dict from _encounter_pose_tensors' device tensors"""
-    return {"rate": rate.cpu().numpy(), flags_key: flags.cpu().numpy(), "weights": None if w_out is None else w_out.cpu().numpy().view(np.uint32)}
+    rate, fl, w = _host(rate, flags, w_out)
+    return {"rate": rate, flags_key: fl, "weights": None if w is None else w.view(np.uint32)}
 
 
 def _encounter_weights(weights, rate_scale, n_pairs):
@@ -230,8 +238,7 @@ def encounter_params(n_pairs, n_a, n_b, points, radius_ft, half_height_ft, seed,
     """emgpu_encounter_params: n_pairs pairs of a column of set A (the ownship; n_a columns, pitch ld_a, 0 = n_a) and a column of set B (the
     intruder), an encounter cylinder of radius_ft and half_height_ft around the ownship, the seed and the global index of pair 0;
     rate_scale divides the rate where it is folded into weights_out."""
-    p = L.EncounterParams()
-    p.n_pairs, p.n_a, p.n_b, p.ld_a, p.ld_b, p.points = int(n_pairs), int(n_a), int(n_b), int(ld_a), int(ld_b), int(points)
+    p = _pairing(L.EncounterParams(), n_pairs, n_a, n_b, points, ld_a, ld_b)
     p.max_attempts, p.seed, p.first_index = int(max_attempts), int(seed) & (2**64 - 1), int(first_index) & (2**64 - 1)
     p.radius_ft, p.half_height_ft, p.rate_scale = float(radius_ft), float(half_height_ft), float(rate_scale)
     return p
@@ -261,7 +268,7 @@ def encounter_pose(xyz_a, xyz_b, radius_ft, half_height_ft, seed, idx_a=None, id
     want_weights, w = _encounter_weights(weights, rate_scale, columns[3])
     with _paired(xyz_a, xyz_b, columns, w, None, layout, ctx, stream) as pr:
         pose, *out = _encounter_pose_tensors(pr, want_weights, radius_ft, half_height_ft, seed, rate_scale, first_index, max_attempts)
-    return {"pose": pose.cpu().numpy(), **_encounter_dict(*out)}
+    return {"pose": _host(pose)[0], **_encounter_dict(*out)}
 
 
 def _placed_then(place, placed_dict, tensors, as_dict, xyz_a, xyz_b, idx_a, idx_b, weights, rate_scale, nmac_h_ft, nmac_v_ft, layout, ctx, stream):
@@ -309,8 +316,7 @@ def cpa_pose_params(n_pairs, n_a, n_b, points, hmd_max_ft, vmd_max_ft, seed, t_l
     """emgpu_cpa_pose_params: n_pairs pairs of a column of set A (the ownship; n_a columns, pitch ld_a, 0 = n_a) and a column of set B (the
     intruder), a miss plane of +-hmd_max_ft by +-vmd_max_ft, the seconds t_lo .. t_hi (None: t_lo alone) the pass is drawn from, the seed
     and the global index of pair 0; rate_scale divides the rate where it is folded into weights_out."""
-    p = L.CpaPoseParams()
-    p.n_pairs, p.n_a, p.n_b, p.ld_a, p.ld_b, p.points = int(n_pairs), int(n_a), int(n_b), int(ld_a), int(ld_b), int(points)
+    p = _pairing(L.CpaPoseParams(), n_pairs, n_a, n_b, points, ld_a, ld_b)
     p.max_attempts, p.seed, p.first_index = int(max_attempts), int(seed) & (2**64 - 1), int(first_index) & (2**64 - 1)
     p.t_lo, p.t_hi = int(t_lo), int(t_lo if t_hi is None else t_hi)
     p.hmd_max_ft, p.vmd_max_ft, p.rate_scale = float(hmd_max_ft), float(vmd_max_ft), float(rate_scale)
@@ -328,23 +334,13 @@ def cpa_pose_device(params, xyz_a, xyz_b, idx_a=0, idx_b=0, weights_in=0, pose=0
 def _cpa_pose_tensors(pr, want_weights, hmd_max_ft, vmd_max_ft, seed, t_lo, t_hi, rate_scale, first_index, max_attempts):
     """k_cpa_pose on the pairing pr: the device tensors (pose [5, n_pairs], rate, t_cpa, flags, weights or None), launched on pr.stream and
     not waited for"""
-    import torch
-    n, dev = pr.n_pairs, pr.dev
-    pose = torch.empty((5, n), dtype=torch.float64, device=dev)
-    rate = torch.empty(n, dtype=torch.float64, device=dev)
-    t_cpa = torch.empty(n, dtype=torch.int32, device=dev)
-    flags = torch.empty(n, dtype=torch.uint8, device=dev)
-    w_out = torch.empty(n, dtype=torch.int32, device=dev) if want_weights else None
-    p = cpa_pose_params(n, pr.n_a, pr.n_b, pr.a.shape[0], hmd_max_ft, vmd_max_ft, seed, t_lo, t_hi, first_index, max_attempts,
-                        1.0 if rate_scale is None else rate_scale)
-    cpa_pose_device(p, _ptr(pr.a), _ptr(pr.b), _ptr(pr.d_ia), _ptr(pr.d_ib), _ptr(pr.d_w), _ptr(pose), _ptr(rate), _ptr(t_cpa), _ptr(flags),
-                    _ptr(w_out), stream=pr.stream)
-    return pose, rate, t_cpa, flags, w_out
+    p = cpa_pose_params(*pr.sizes, hmd_max_ft, vmd_max_ft, seed, t_lo, t_hi, first_index, max_attempts, 1.0 if rate_scale is None else rate_scale)
+    return _launch(pr, cpa_pose_device, p, (pr.d_w,), _placement(want_weights, t_cpa="int32"))
 
 
 def _cpa_dict(rate, t_cpa, flags, w_out, t_key="t_cpa", flags_key="flags"):
     """the rate, drawn second, flags and weights of cpa_pose's dict from _cpa_pose_tensors' device tensors"""
-    return {t_key: t_cpa.cpu().numpy(), **_encounter_dict(rate, flags, w_out, flags_key)}
+    return {t_key: _host(t_cpa)[0], **_encounter_dict(rate, flags, w_out, flags_key)}
 
 
 def cpa_pose(xyz_a, xyz_b, hmd_max_ft, vmd_max_ft, seed, t_lo, t_hi=None, idx_a=None, idx_b=None, weights=None, rate_scale=None, first_index=0,
@@ -362,7 +358,7 @@ def cpa_pose(xyz_a, xyz_b, hmd_max_ft, vmd_max_ft, seed, t_lo, t_hi=None, idx_a=
     want_weights, w = _encounter_weights(weights, rate_scale, columns[3])
     with _paired(xyz_a, xyz_b, columns, w, None, layout, ctx, stream) as pr:
         pose, *out = _cpa_pose_tensors(pr, want_weights, hmd_max_ft, vmd_max_ft, seed, t_lo, t_hi, rate_scale, first_index, max_attempts)
-    return {"pose": pose.cpu().numpy(), **_cpa_dict(*out)}
+    return {"pose": _host(pose)[0], **_cpa_dict(*out)}
 
 
 def _cpa_then(tensors, as_dict, xyz_a, xyz_b, hmd_max_ft, vmd_max_ft, seed, t_lo, t_hi, idx_a, idx_b, weights, rate_scale, first_index,
@@ -394,8 +390,7 @@ def cpa_miss_segments(xyz_a, xyz_b, hmd_max_ft, vmd_max_ft, seed, t_lo, t_hi=Non
 def well_clear_params(n_pairs, n_a, n_b, points, tau_s=35.0, dmod_ft=4000.0, hmd_ft=4000.0, h_ft=450.0, ld_a=0, ld_b=0):
     """emgpu_well_clear_params: miss_params' pairing and the four thresholds of DAA well clear: modified tau in seconds, DMOD, the predicted
     horizontal miss and the vertical separation in feet."""
-    p = L.WellClearParams()
-    p.n_pairs, p.n_a, p.n_b, p.ld_a, p.ld_b, p.points = int(n_pairs), int(n_a), int(n_b), int(ld_a), int(ld_b), int(points)
+    p = _pairing(L.WellClearParams(), n_pairs, n_a, n_b, points, ld_a, ld_b)
     p.tau_s, p.dmod_ft, p.hmd_ft, p.h_ft = float(tau_s), float(dmod_ft), float(hmd_ft), float(h_ft)
     return p
 
@@ -413,23 +408,15 @@ def well_clear_device(params, xyz_a, xyz_b, idx_a=0, idx_b=0, pose_b=0, weights=
 def _well_clear_tensors(pr, d_pose, d_w, d_miss_flags, tau_s, dmod_ft, hmd_ft, h_ft):
     """k_well_clear on the pairing pr with the device tensors d_pose, d_w and d_miss_flags (or None): the device tensors (t_first, n_lost,
     tau_min, flags, totals [10]), launched on pr.stream and not waited for"""
-    import torch
-    n, dev = pr.n_pairs, pr.dev
-    t_first, n_lost = torch.empty(n, dtype=torch.int32, device=dev), torch.empty(n, dtype=torch.int32, device=dev)
-    tau_min, flags = torch.empty(n, dtype=torch.float64, device=dev), torch.empty(n, dtype=torch.uint8, device=dev)
-    totals = torch.zeros(10, dtype=torch.int64, device=dev)
-    pr.guard()      # totals was zeroed on torch's stream
-    well_clear_device(well_clear_params(n, pr.n_a, pr.n_b, pr.a.shape[0], tau_s, dmod_ft, hmd_ft, h_ft), _ptr(pr.a), _ptr(pr.b), _ptr(pr.d_ia),
-                      _ptr(pr.d_ib), _ptr(d_pose), _ptr(d_w), _ptr(d_miss_flags), _ptr(t_first), _ptr(n_lost), _ptr(tau_min), _ptr(flags),
-                      _ptr(totals), stream=pr.stream)
-    return t_first, n_lost, tau_min, flags, totals
+    return _launch(pr, well_clear_device, well_clear_params(*pr.sizes, tau_s, dmod_ft, hmd_ft, h_ft), (d_pose, d_w, d_miss_flags),
+                   {"t_first": "int32", "n_lost": "int32", "tau_min": "float64", "flags": "uint8"}, 10)
 
 
 def _well_clear_dict(t_first, n_lost, tau_min, flags, totals, flags_key="flags", totals_key="totals"):
     """well_clear's dict from _well_clear_tensors' device tensors"""
-    fl = flags.cpu().numpy()
-    return {"t_first": t_first.cpu().numpy(), "n_lost": n_lost.cpu().numpy(), "tau_min_s": tau_min.cpu().numpy(), flags_key: fl,
-            "lowc": (fl & L.WC_LOST) != 0, "at_start": (fl & L.WC_AT_START) != 0, totals_key: totals.cpu().numpy().view(np.uint64)}
+    t_first, n_lost, tau_min, fl, tot = _host(t_first, n_lost, tau_min, flags, totals)
+    return {"t_first": t_first, "n_lost": n_lost, "tau_min_s": tau_min, flags_key: fl, "lowc": (fl & L.WC_LOST) != 0,
+            "at_start": (fl & L.WC_AT_START) != 0, totals_key: tot.view(np.uint64)}
 
 
 def well_clear(xyz_a, xyz_b, idx_a=None, idx_b=None, pose_b=None, weights=None, miss_flags=None, tau_s=35.0, dmod_ft=4000.0, hmd_ft=4000.0,
@@ -502,8 +489,8 @@ def avoid_params(n_pairs, n_a, n_b, points, alert_tau_s=60.0, alert_dmod_ft=4000
     thresholds; the ownship's response: the whole seconds between the alert and the manoeuvre, the vertical rate it reaches in ft/s, the
     acceleration towards it in ft/s^2 (inf: at once) and the largest displacement in feet.  The defaults are an illustration (1500 ft/min
     after 5 s at about 0.25 g), not the alerting thresholds of any standard."""
-    p = L.AvoidParams()
-    p.n_pairs, p.n_a, p.n_b, p.ld_a, p.ld_b, p.points, p.delay_s = int(n_pairs), int(n_a), int(n_b), int(ld_a), int(ld_b), int(points), int(delay_s)
+    p = _pairing(L.AvoidParams(), n_pairs, n_a, n_b, points, ld_a, ld_b)
+    p.delay_s = int(delay_s)
     p.alert_tau_s, p.alert_dmod_ft, p.alert_hmd_ft, p.alert_h_ft = float(alert_tau_s), float(alert_dmod_ft), float(alert_hmd_ft), float(alert_h_ft)
     p.nmac_h_ft, p.nmac_v_ft = float(nmac_h_ft), float(nmac_v_ft)
     p.rate_fps, p.accel_fps2, p.dz_max_ft = float(rate_fps), float(accel_fps2), float(dz_max_ft)
@@ -522,26 +509,17 @@ def avoid_device(params, xyz_a, xyz_b, idx_a=0, idx_b=0, pose_b=0, weights=0, hm
 def _avoid_tensors(pr, d_pose, d_w, **response):
     """k_avoid on the pairing pr with the device tensors d_pose and d_w (or None) and avoid_params' thresholds and response: the device
     tensors (hmd, vmd, vmd_mit, t_cpa, t_alert, flags, totals [12]), launched on pr.stream and not waited for"""
-    import torch
-    n, dev = pr.n_pairs, pr.dev
-    hmd, vmd, vmd_mit = (torch.empty(n, dtype=torch.float64, device=dev) for _ in range(3))
-    t_cpa, t_alert = torch.empty(n, dtype=torch.int32, device=dev), torch.empty(n, dtype=torch.int32, device=dev)
-    flags = torch.empty(n, dtype=torch.uint8, device=dev)
-    totals = torch.zeros(12, dtype=torch.int64, device=dev)
-    pr.guard()      # totals was zeroed on torch's stream
-    avoid_device(avoid_params(n, pr.n_a, pr.n_b, pr.a.shape[0], **response), _ptr(pr.a), _ptr(pr.b), _ptr(pr.d_ia), _ptr(pr.d_ib), _ptr(d_pose),
-                 _ptr(d_w), _ptr(hmd), _ptr(vmd), _ptr(vmd_mit), _ptr(t_cpa), _ptr(t_alert), _ptr(flags), _ptr(totals), stream=pr.stream)
-    return hmd, vmd, vmd_mit, t_cpa, t_alert, flags, totals
+    return _launch(pr, avoid_device, avoid_params(*pr.sizes, **response), (d_pose, d_w),
+                   {"hmd": "float64", "vmd": "float64", "vmd_mit": "float64", "t_cpa": "int32", "t_alert": "int32", "flags": "uint8"}, 12)
 
 
 def _avoid_dict(hmd, vmd, vmd_mit, t_cpa, t_alert, flags, totals):
     """avoid's dict from _avoid_tensors' device tensors"""
-    fl, tot = flags.cpu().numpy(), totals.cpu().numpy().view(np.uint64)
-    nmac, nmac_mit = (fl & L.AVOID_NMAC_UNMIT) != 0, (fl & L.AVOID_NMAC_MIT) != 0
-    return {"hmd_ft": hmd.cpu().numpy(), "vmd_ft": vmd.cpu().numpy(), "vmd_mit_ft": vmd_mit.cpu().numpy(), "t_cpa": t_cpa.cpu().numpy(),
-            "t_alert": t_alert.cpu().numpy(), "flags": fl, "alerted": (fl & L.AVOID_ALERTED) != 0, "climb": (fl & L.AVOID_CLIMB) != 0,
-            "nmac": nmac, "nmac_mit": nmac_mit, "induced": nmac_mit & ~nmac, "totals": tot,
-            "risk_ratio": float(tot[10]) / float(tot[9]) if tot[9] else float("nan")}
+    hmd, vmd, vmd_mit, t_cpa, t_alert, fl, tot = _host(hmd, vmd, vmd_mit, t_cpa, t_alert, flags, totals)
+    tot, nmac, nmac_mit = tot.view(np.uint64), (fl & L.AVOID_NMAC_UNMIT) != 0, (fl & L.AVOID_NMAC_MIT) != 0
+    return {"hmd_ft": hmd, "vmd_ft": vmd, "vmd_mit_ft": vmd_mit, "t_cpa": t_cpa, "t_alert": t_alert, "flags": fl,
+            "alerted": (fl & L.AVOID_ALERTED) != 0, "climb": (fl & L.AVOID_CLIMB) != 0, "nmac": nmac, "nmac_mit": nmac_mit,
+            "induced": nmac_mit & ~nmac, "totals": tot, "risk_ratio": float(tot[10]) / float(tot[9]) if tot[9] else float("nan")}
 
 
 def avoid(xyz_a, xyz_b, idx_a=None, idx_b=None, pose_b=None, weights=None, alert_tau_s=60.0, alert_dmod_ft=4000.0, alert_hmd_ft=4000.0,
